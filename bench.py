@@ -11,6 +11,9 @@ DensityMatrixSolversModule.F90:380-413 does it: trace(X) -> sigma, X2 = X*X (SpG
 X <- 2X - X2 or X2, energy = dot(X, H).  All matrices stay in HBM; only scalars return to the host.
 W warm-up iterations are followed by exactly K timed ones (barrier + device synchronise on both
 sides, max over ranks); the region is repeated --blocks times from X0 and the MEDIAN block is reported.
+The iterations are those of a solve: the solver stops once X has converged (iteration ~45 on the headline operand), and
+iterating past that point only amplifies rounding noise until X fills in without bound.  So the iterate restarts from X0
+after every TRS2_WINDOW iterations (warm-up included), outside the clock; W + K <= TRS2_WINDOW never restarts.
 Rank 0 prints ONE JSON line.
 
 Extra objects in the line:
@@ -27,6 +30,10 @@ Other workloads: --permute SEED (the operand under the load balancer's random re
 operand left AS IT STANDS -- no band recovery, no block order: the north star's LDS-hash SpGEMM, the shape of the
 reference's own UnitTests/bench.f90:58-76), --lattice L (3-D Hamiltonian), --config 3 (BASELINE configs[3]: one A*A at
 N = 1 048 576), --arithmetic fma|unfused, --set OPTION=VALUE.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step (the last block's) as DIR/<name>.npy,
+float64: the scalars the step returned and DUMP_COLUMNS whole columns of the resulting matrix, dense, at column indices
+drawn with a fixed seed -- the same columns for the same arguments, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -43,6 +50,30 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+TRS2_WINDOW = 40          # iterations from X0 before the iterate restarts (the headline converges at ~45, fills in from ~53)
+DUMP_COLUMNS = 16         # --dump-outputs: dense columns of the result (16 x 8 B x N: 32 MB at N = 262 144)
+DUMP_SEED = 20260101
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, M, n, scalars):
+    """--dump-outputs: `scalars` (name -> float) and DUMP_COLUMNS dense columns of the distributed matrix M at seeded
+    column indices, as float64 .npy files under `directory` (one rank: every column is local)"""
+    cols = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_COLUMNS, n), replace=False))
+    while 8 * len(cols) * n > DUMP_LIMIT_BYTES - (1 << 20):
+        cols = cols[::2]
+    col, row, val = M.triplets()            # 1-based, sorted by column then row
+    dense = np.zeros((len(cols), n), dtype=np.float64)
+    lo = np.searchsorted(col, cols + 1, side="left")
+    hi = np.searchsorted(col, cols + 1, side="right")
+    for k in range(len(cols)):
+        dense[k, row[lo[k]:hi[k]] - 1] = np.real(val[lo[k]:hi[k]])
+    del col, row, val
+    out = {"column_index": cols.astype(np.float64), "columns": dense}
+    out.update((k, np.array([v], dtype=np.float64)) for k, v in scalars.items())
+    os.makedirs(directory, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def trs2_step(nt, X, X2, WH, pool, trace_target, thr, trace_x=None):
@@ -86,7 +117,7 @@ def cpu_baseline(n, h, thr, warmup, steps, permute=None, fma=False, lattice=None
     # ONE run of warmup + 3 iterations; the oracle stamps the wall clock at the end of every iteration (otrace.stamp), so
     # the last three differences are three samples of one iteration of the region the GPU line times
     nsamp = 3 if lattice is not None else 5
-    iters = max(1, warmup) + nsamp
+    iters = min(max(1, warmup), TRS2_WINDOW - nsamp) + nsamp     # (inside the window the GPU line iterates in)
     try:
         p = O.params(converge_diff=1e-30, max_iterations=iters, threshold=thr, monitor_convergence=False)
         _, _, _, tro = O.density("trs2", H, I, n / 2.0, p)
@@ -209,6 +240,8 @@ def run_config3(nt, args, rank, world):
             stats = rec
         else:
             blocks.append(rec)
+            if args.dump_outputs is not None and blk + 1 == max(1, args.blocks):
+                dump_outputs(args.dump_outputs, Cm, n, {})     # the last timed product (before the statistics block)
     nnz_c = Cm.GetSize()     # (collective; whole matrix)
     order = sorted(range(len(blocks)), key=lambda k: blocks[k]["elapsed"])
     med = blocks[order[len(order) // 2]]
@@ -369,7 +402,15 @@ def main():
                     help="2: the headline (TRS2 iterations at BASELINE configs[2]); 3: BASELINE configs[3], ONE distributed product "
                          "A*A at N = 1 048 576, halfband 100 (with --permute SEED: under the load balancer's random relabelling), a "
                          "step = one MatrixMultiply_ps_wrp, value = nnz-out/s over all ranks")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     launched = int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ
     if args.gpus > 1 and not launched:
@@ -455,33 +496,56 @@ def main():
     # weak 7).  The same region -- X0 from H, W untimed warm-up steps, barrier + device synchronise, exactly K timed
     # steps, barrier + device synchronise, max over ranks -- is therefore run `--blocks` times (default 5), each time
     # from scratch, and the line reports the MEDIAN block (its time, its kernel timers, its counters); `steps` stays K.
-    blocks = []
-    for blk in range(max(1, args.blocks)):
+    def x0():
         X = nt.Matrix_ps(H)
         X.Scale(-1.0)
         X.Increment(Ident, e_max, 0.0)
         X.Scale(1.0 / (e_max - e_min))
+        return X
+
+    blocks = []
+    for blk in range(max(1, args.blocks)):
+        X = x0()
         X2 = nt.Matrix_ps(n)
         energy, tr_x = 0.0, None
-        for _ in range(args.warmup):
+        for g in range(args.warmup):
+            if g and g % TRS2_WINDOW == 0:
+                X, tr_x = x0(), None
             _, energy, tr_x = trs2_step(nt, X, X2, H, pool, trace_target, thr, tr_x)
         nt.reset_spgemm_accum()
         m0 = nt.malloc_stats()
         fz0 = nt.fusion_counts()
+        m_restart = [0, 0.0]    # hipMalloc calls / ms of the restarts (outside the clock)
+        elapsed = 0.0
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            _, energy, tr_x = trs2_step(nt, X, X2, H, pool, trace_target, thr, tr_x)
+        for g in range(args.warmup, args.warmup + args.steps):
+            if g and g % TRS2_WINDOW == 0:
+                # restart from X0 (TRS2_WINDOW): the clock stops for it
+                fence()
+                elapsed += time.perf_counter() - t0
+                r0 = nt.malloc_stats()
+                X, tr_x = x0(), None
+                r1 = nt.malloc_stats()
+                m_restart = [m_restart[0] + r1[0] - r0[0], m_restart[1] + r1[1] - r0[1]]
+                fence()
+                t0 = time.perf_counter()
+            sigma, energy, tr_x = trs2_step(nt, X, X2, H, pool, trace_target, thr, tr_x)
         fence()
-        elapsed = time.perf_counter() - t0
+        elapsed += time.perf_counter() - t0
         if world > 1:
             elapsed = nt.allreduce_max(elapsed)
         m1 = nt.malloc_stats()
+        m1 = (m1[0] - m_restart[0], m1[1] - m_restart[1])
         fz1 = nt.fusion_counts()
         blocks.append(dict(elapsed=elapsed, energy=energy, m0=m0, m1=m1, fused={k: fz1[k] - fz0[k] for k in fz1}, acc=nt.spgemm_accum(),
                            st=nt.last_spgemm_stats(), gs=nt.last_grouped_stats(), bs=nt.last_block_stats(), nnz_x=X.GetSize()))
         if blk + 1 < max(1, args.blocks):
             del X, X2
+    if args.dump_outputs is not None:
+        # the last timed step of the last block: the new iterate X and the scalars the step returned (deterministic: the
+        # same iteration of the same window for the same arguments)
+        dump_outputs(args.dump_outputs, X, n, {"sigma": sigma, "energy": energy, "trace": tr_x})
     order = sorted(range(len(blocks)), key=lambda k: blocks[k]["elapsed"])
     med = blocks[order[len(order) // 2]]
     elapsed, energy, m0, m1, fused, acc, st, gs, bs, nnz_x = (med[k] for k in ("elapsed", "energy", "m0", "m1", "fused", "acc", "st", "gs", "bs", "nnz_x"))
@@ -504,6 +568,10 @@ def main():
         except Exception:
             traffic = None
         iters_per_s = args.steps / elapsed
+        if args.warmup + args.steps > TRS2_WINDOW:
+            timed_note = " (iterations counted from X0, restarted from X0 outside the clock every %d)" % TRS2_WINDOW
+        else:
+            timed_note = ""
         # nnz-out/s of the SpGEMM alone: local output entries / local numeric+symbolic time; whole job
         # = sum over ranks (ranks hold equal panels of a homogeneous band)
         ms_spgemm = max(acc["ms_total"], 1e-9)
@@ -524,16 +592,16 @@ def main():
             "dtype": "f64",
             "data": "synthetic",
             "config": {"workload": ("TRS2 purification on a 3-D lattice Hamiltonian (no band structure): %d^3 = %d sites, couplings within "
-                                    "distance sqrt(13) (203 nnz/row), threshold=%g, ISQ=I, trace=N/2; timed iterations %d..%d" % (
-                                        args.lattice, n, thr, args.warmup + 1, args.warmup + args.steps))
+                                    "distance sqrt(13) (203 nnz/row), threshold=%g, ISQ=I, trace=N/2; timed iterations %d..%d%s" % (
+                                        args.lattice, n, thr, args.warmup + 1, args.warmup + args.steps, timed_note))
                        if args.lattice is not None else
                        "TRS2 purification (BASELINE configs[2]): banded H N=%d halfband=%d (%d nnz/row)%s, "
-                       "threshold=%g, ISQ=I, trace=N/2; timed iterations %d..%d" % (
+                       "threshold=%g, ISQ=I, trace=N/2; timed iterations %d..%d%s" % (
                            n, h, 2 * h + 1,
                            "" if args.permute is None else " under a random symmetric relabelling (seed %d)%s" % (
                                args.permute, ", taken as it stands (no band recovery, no block order: the LDS-hash SpGEMM)" if args.random is not None else ""),
-                           thr, args.warmup + 1, args.warmup + args.steps),
-                       "lattice": args.lattice,
+                           thr, args.warmup + 1, args.warmup + args.steps, timed_note),
+                       "lattice": args.lattice, "trs2_window": TRS2_WINDOW,
                        "arithmetic": ("fma: every product entry is the chain of fma() over ascending k (one rounding per product), "
                                       "the reference's FP-contracted build bit for bit (tests/golden/ps_gemm_fma.npz); run-like "
                                       "operands on the FP64 matrix cores (v_mfma_f64_16x16x4_f64, spgemm_tile.hip), operands without runs "

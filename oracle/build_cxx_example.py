@@ -10,6 +10,7 @@ travel to the GPU box as built files; tests/test_gpu_extras.py runs them there).
     python oracle/build_cxx_example.py
 """
 import os
+import shutil
 import subprocess
 import sys
 
@@ -44,7 +45,7 @@ def build():
         dst = os.path.join(mpidir, lib)
         if os.path.lexists(dst):
             os.unlink(dst)
-        os.symlink(os.path.join("/opt/conda/lib", lib), dst)
+        shutil.copy2(os.path.join("/opt/conda/lib", lib), dst)   # a copy, not a link: the built tree runs where it is sent
     exe = None
     for name, example in EXAMPLES.items():
         obj = os.path.join(OUT, "cxx_obj", name + "_main.o")

@@ -11,6 +11,7 @@ the image's own mpif.h, because MPICH's mpi.mod was written by gfortran).  Outpu
     python oracle/build_fortran_example.py
 """
 import os
+import shutil
 import subprocess
 import sys
 
@@ -44,7 +45,7 @@ def build():
         dst = os.path.join(mpidir, lib)
         if os.path.lexists(dst):
             os.unlink(dst)
-        os.symlink(os.path.join("/opt/conda/lib", lib), dst)
+        shutil.copy2(os.path.join("/opt/conda/lib", lib), dst)   # a copy, not a link: the built tree runs where it is sent
     exe = None
     for name, example in EXAMPLES.items():
         obj = os.path.join(work, name + "_main.o")

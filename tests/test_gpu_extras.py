@@ -266,12 +266,12 @@ def test_reference_examples_link_and_run(tmp_path, binary):
     for name, t in (("Hamiltonian.mtx", g.tri(i_h, "H")), ("Overlap.mtx", g.tri(i_s, "H"))):
         m = sp.coo_matrix((t[4], (t[3] - 1, t[2] - 1)), shape=(t[0], t[1]))
         scipy.io.mmwrite(str(tmp_path / name), m)
-    out = tmp_path / "Density.mtx"
+    out = tmp_path / "Density.mtx"     # (passed by name, run in tmp_path: the Fortran example holds file names in 80 characters)
     r = subprocess.run([exe, "--process_rows", "1", "--process_columns", "1", "--process_slices", "1",
-                        "--hamiltonian", str(tmp_path / "Hamiltonian.mtx"), "--overlap", str(tmp_path / "Overlap.mtx"),
+                        "--hamiltonian", "Hamiltonian.mtx", "--overlap", "Overlap.mtx",
                         "--number_of_electrons", "5", "--threshold", "1e-6", "--converge_overlap", "1e-3",
-                        "--converge_density", "1e-5", "--density", str(out)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+                        "--converge_density", "1e-5", "--density", out.name],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-3000:]
     assert "Density Matrix Solver" in r.stdout and "TRS2" in r.stdout     # the reference's log format, from our logger
     if binary == "premade_f90":
@@ -308,10 +308,10 @@ def test_reference_examples_under_mpiexec_two_ranks(tmp_path, binary):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([mpiexec, "-n", "2", exe, "--process_rows", "2", "--process_columns", "1", "--process_slices", "1",
-                        "--hamiltonian", str(tmp_path / "Hamiltonian.mtx"), "--overlap", str(tmp_path / "Overlap.mtx"),
+                        "--hamiltonian", "Hamiltonian.mtx", "--overlap", "Overlap.mtx",
                         "--number_of_electrons", "5", "--threshold", "1e-6", "--converge_overlap", "1e-3",
-                        "--converge_density", "1e-5", "--density", str(out)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
+                        "--converge_density", "1e-5", "--density", out.name],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-3000:]
     assert r.stdout.count("Density Matrix Solver") == 1, r.stdout[-3000:]     # only the root logs: the ranks are one job
     D = scipy.io.mmread(str(out)).toarray()
@@ -792,13 +792,13 @@ def test_reference_cxx_examples_run(nt, tmp_path):
     # Fortran module layer; oracle/build_fortran_example.py).  The Fortran graph example draws its extra connections
     # with RANDOM_NUMBER, so it runs without them (a plain chain), which numpy can restate.
     if all(os.path.exists(os.path.join(ref, e)) for e in ("hydrogen_f90", "graph_f90")):  # (built where flang is)
-        out = str(tmp_path / "DensityF.mtx")
-        run("hydrogen_f90", grid + ["--threshold", "1e-6", "--convergence_threshold", "1e-5", "--grid_points", "100", "--density", out])
+        out = str(tmp_path / "DensityF.mtx")   # (passed by name: the Fortran examples hold file names in 80 characters)
+        run("hydrogen_f90", grid + ["--threshold", "1e-6", "--convergence_threshold", "1e-5", "--grid_points", "100", "--density", "DensityF.mtx"])
         D = scipy.io.mmread(out).toarray()
         assert abs(np.trace(D) - 1.0) <= 1e-4 and np.abs(D - D.T).max() <= 1e-6 and np.abs(D @ D - D).max() <= 1e-3
         out = str(tmp_path / "OutputF.mtx")
         run("graph_f90", grid + ["--threshold", "1e-6", "--convergence_threshold", "1e-4", "--number_of_nodes", "400",
-                                 "--extra_connections", "0", "--attenuation", "0.7", "--output_file", out])
+                                 "--extra_connections", "0", "--attenuation", "0.7", "--output_file", "OutputF.mtx"])
         Mc = np.eye(400) + 0.1 * (np.eye(400, k=1) + np.eye(400, k=-1))
         want = np.linalg.inv(np.eye(400) - 0.7 * Mc)
         assert np.abs(scipy.io.mmread(out).toarray() - want).max() <= 1e-3 * np.abs(want).max()
