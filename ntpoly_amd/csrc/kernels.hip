@@ -3259,9 +3259,13 @@ static bool spgemm_striped(const DevMat& A, const DevMat& B, DevMat& C, double a
 namespace {
 // the block path (spgemm_block.hip) with spgemm()'s book-keeping around it
 int g_block_keep = 0;           // > 0: a caller that understands DevMat::blk is waiting for the product (BlockKeepScope)
+// (complex operands: FMA arithmetic with complex_tile and block_complex -- where complex products are a tolerance mode already)
+bool block_complex_ok(const DevMat& A, const DevMat& B) {
+  return A.cplx && B.cplx && options().spgemm_fma == 1 && options().complex_tile != 0 && options().block_complex != 0;
+}
 bool block_eligible(const DevMat& A, const DevMat& B, const ColRange* arange) {
-  return !arange && !A.cplx && !B.cplx && block_arithmetic_ok() && options().block_path != 0 && options().spgemm_variant < 0 &&
-         options().spgemm_force_bin <= 0 && A.rows == A.cols && B.rows == B.cols && A.cols == B.rows;
+  return !arange && ((!A.cplx && !B.cplx) || block_complex_ok(A, B)) && block_arithmetic_ok() && options().block_path != 0 &&
+         options().spgemm_variant < 0 && options().spgemm_force_bin <= 0 && A.rows == A.cols && B.rows == B.cols && A.cols == B.rows;
 }
 bool try_block_path(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule) {
   const bool timing = options().time_kernels != 0;
@@ -3301,7 +3305,7 @@ bool try_block_path(const DevMat& A, const DevMat& B, DevMat& C, double alpha, d
   acc.calls += 1;
   acc.products += st.products;
   acc.nnz_c += C.nnz;
-  acc.alg_bytes += 12.0 * (double)(nnz_a + nnz_b + C.nnz) + 4.0 * ((double)acols + bcols + n + 3);
+  acc.alg_bytes += (C.cplx ? 20.0 : 12.0) * (double)(nnz_a + nnz_b + C.nnz) + 4.0 * ((double)acols + bcols + n + 3);
   return true;
 }
 // the thin-left kernel (spgemm_thin.hip) with spgemm()'s book-keeping around it
@@ -3473,7 +3477,11 @@ void spgemm(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double th
   bool grouped_done = false;
   // (bit 0: the dense branch's order of threshold and alpha; bit 1: FMA accumulation, option spgemm_fma, real operands)
   const int dr = (dense_rule ? 1 : 0) | ((options().spgemm_fma && !A.cplx) ? 2 : 0);
-  if (!loose_in && grouped_first_n[A.cplx ? 1 : 0] == n && sv_opt < 0 && options().spgemm_force_bin <= 0 && m == A.cols && (int64_t)n * 1536 < (1ll << 33)) {
+  // (not for a complex product the block path may take -- forced, or with row windows that can lie beyond the direct-mapped LDS
+  // kernels -- and has not declined at this dimension: the real products of such a dimension never reach the grouped kernel,
+  // complex ones did before block_complex, so this memory may be left from one computed with the option off)
+  const bool cblock_first = A.cplx && block_eligible(A, B, arange) && (options().block_path == 2 || n > 4096) && !block_refused(n, A.nnz);
+  if (!loose_in && !cblock_first && grouped_first_n[A.cplx ? 1 : 0] == n && sv_opt < 0 && options().spgemm_force_bin <= 0 && m == A.cols && (int64_t)n * 1536 < (1ll << 33)) {
     constexpr int64_t kSlot = 1536;   // rows of the largest table class: no column of a finished group holds more
     tmp_total = (int64_t)n * kSlot;
     tmp_inner.alloc((size_t)tmp_total + kIndexSlack);

@@ -23,6 +23,10 @@
 // position -- bit for bit what the reference's FP-contracted build computes on the matrix relabelled by `pos`
 // (tests/test_gpu_block.py runs the CPU restatement of the reference on exactly that matrix), and within roundoff of the chain over ascending
 // labels (the tolerance contract of label-ordered operands).
+//
+// Complex operands (options complex_tile and block_complex, FMA arithmetic): the same order (made from the modulus), complex
+// tiles (a real plane and an imaginary plane), and k_bs_numeric_c -- two FMA chains per part of an entry, the tolerance mode
+// of the complex tile kernel; products only, always returned in compressed columns.
 #include "spgemm_block.hpp"
 
 #include <hip/hip_runtime.h>
@@ -53,6 +57,8 @@ __host__ __device__ inline int phys(int o) { return 4 * (o & 3) + (o >> 2); }
 __host__ __device__ inline int tile_word(int row_t, int col_t) {
   return col_t * 16 + ((((row_t >> 1) ^ (col_t >> 1)) & 7) << 1) + (row_t & 1);
 }
+
+__device__ inline v4d bs_zero4() { const v4d z = {0.0, 0.0, 0.0, 0.0}; return z; }
 
 bool dbg() {
   static const bool d = std::getenv("NTPOLY_AMD_DEBUG_SPGEMM") != nullptr;
@@ -155,6 +161,11 @@ __global__ __launch_bounds__(256) void k_abs_f32(int64_t n, const double* __rest
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < n) w[i] = (float)fabs(v[i]);
 }
+// (complex values: the modulus -- a complex operand gets the order of the real one with the same pattern and |values|)
+__global__ __launch_bounds__(256) void k_abs_c_f32(int64_t n, const double* __restrict__ v, float* __restrict__ w) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < n) w[i] = (float)hypot(v[2 * i], v[2 * i + 1]);
+}
 __global__ __launch_bounds__(256) void k_fill_i32(int64_t n, int32_t* __restrict__ p, int32_t v, int32_t step) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < n) p[i] = v + (int32_t)i * step;
@@ -193,7 +204,8 @@ std::shared_ptr<BlockOrder> build_block_order(const DevMat& M) {
   g.off = M.outer.p;
   g.nbr = M.inner.p;
   g.w_own.alloc((size_t)std::max<int64_t>(1, M.nnz));
-  hipLaunchKernelGGL(k_abs_f32, dim3(grid1(M.nnz)), dim3(256), 0, stream(), M.nnz, M.val.p, g.w_own.p);
+  if (M.cplx) hipLaunchKernelGGL(k_abs_c_f32, dim3(grid1(M.nnz)), dim3(256), 0, stream(), M.nnz, M.val.p, g.w_own.p);
+  else hipLaunchKernelGGL(k_abs_f32, dim3(grid1(M.nnz)), dim3(256), 0, stream(), M.nnz, M.val.p, g.w_own.p);
   g.w = g.w_own.p;
   DevBuf<int32_t> csize((size_t)n), crep((size_t)n);
   hipLaunchKernelGGL(k_fill_i32, dim3(grid1(n)), dim3(256), 0, stream(), (int64_t)n, csize.p, 1, 0);
@@ -362,6 +374,12 @@ std::shared_ptr<BlockOrder> build_block_order(const DevMat& M) {
 // the 16-bit tile mask of the super-tile (I, J) in LDS (two masks to a word) and counts super-tiles and tiles; pass 2
 // (after the scans) rebuilds the masks, lists the super-tiles in ascending I, zero-fills the column's tiles and
 // scatters the values.  Stored zeros are not entries of the block form (a zero factor contributes exact zeros).
+// CPLX: (re, im) pairs in, complex tiles out (BlockForm); a stored zero is one whose two parts are zero.
+template <bool CPLX>
+__device__ inline bool bs_stored(const double* __restrict__ v, int64_t e) {
+  return CPLX ? (v[2 * e] != 0.0 || v[2 * e + 1] != 0.0) : v[e] != 0.0;
+}
+template <bool CPLX>
 __device__ inline void bs_mark_column_masks(const Csc& M, const int32_t* __restrict__ pos, const int32_t* __restrict__ lab, int J,
                                             unsigned* __restrict__ m2) {
   const int wave = threadIdx.x / WAVE, lane = lane_id(), nw = blockDim.x / WAVE;
@@ -370,13 +388,14 @@ __device__ inline void bs_mark_column_masks(const Csc& M, const int32_t* __restr
     if (j < 0) continue;
     const double* __restrict__ v = static_cast<const double*>(M.val);
     for (int64_t e = M.outer[j] + lane; e < M.outer[j + 1]; e += WAVE) {
-      if (v[e] == 0.0) continue;
+      if (!bs_stored<CPLX>(v, e)) continue;
       const int pr = pos[M.inner[e]];
       const int I = pr >> 6, bit = 4 * (c >> 4) + ((pr >> 4) & 3);
       atomicOr(&m2[I >> 1], 1u << (bit + 16 * (I & 1)));
     }
   }
 }
+template <bool CPLX>
 __global__ __launch_bounds__(256) void k_bs_count(Csc M, const int32_t* __restrict__ pos, const int32_t* __restrict__ lab, int ns,
                                                   int32_t* __restrict__ cnt_st, int32_t* __restrict__ cnt_tile) {
   extern __shared__ unsigned m2[];
@@ -385,7 +404,7 @@ __global__ __launch_bounds__(256) void k_bs_count(Csc M, const int32_t* __restri
   for (int i = threadIdx.x; i < (ns + 1) / 2; i += blockDim.x) m2[i] = 0;
   if (threadIdx.x < 2) red[threadIdx.x] = 0;
   __syncthreads();
-  bs_mark_column_masks(M, pos, lab, J, m2);
+  bs_mark_column_masks<CPLX>(M, pos, lab, J, m2);
   __syncthreads();
   int st = 0, tl = 0;
   for (int i = threadIdx.x; i < (ns + 1) / 2; i += blockDim.x) {
@@ -399,6 +418,7 @@ __global__ __launch_bounds__(256) void k_bs_count(Csc M, const int32_t* __restri
   __syncthreads();
   if (threadIdx.x == 0) { cnt_st[J] = red[0]; cnt_tile[J] = red[1]; }
 }
+template <bool CPLX>
 __global__ __launch_bounds__(256) void k_bs_fill(Csc M, const int32_t* __restrict__ pos, const int32_t* __restrict__ lab, int ns,
                                                  const int64_t* __restrict__ soff, const int64_t* __restrict__ tbase,
                                                  int32_t* __restrict__ srow, int32_t* __restrict__ smask, int64_t* __restrict__ sbase,
@@ -409,7 +429,7 @@ __global__ __launch_bounds__(256) void k_bs_fill(Csc M, const int32_t* __restric
   const int nwords = (ns + 1) / 2;
   for (int i = tid; i < nwords; i += blockDim.x) m2[i] = 0;
   __syncthreads();
-  bs_mark_column_masks(M, pos, lab, J, m2);
+  bs_mark_column_masks<CPLX>(M, pos, lab, J, m2);
   __syncthreads();
   // ordered enumeration: thread t owns the words [t * per, (t + 1) * per)
   const int per = (nwords + blockDim.x - 1) / blockDim.x;
@@ -448,9 +468,10 @@ __global__ __launch_bounds__(256) void k_bs_fill(Csc M, const int32_t* __restric
   }
   (void)nw;
   // zero-fill the tiles of this super-column
+  constexpr int TW = CPLX ? 512 : 256;
   const int64_t t1 = tbase[J + 1];
-  v2d* __restrict__ z = reinterpret_cast<v2d*>(tiles + t0 * 256);
-  const int64_t nz2 = (t1 - t0) * 128;
+  v2d* __restrict__ z = reinterpret_cast<v2d*>(tiles + t0 * TW);
+  const int64_t nz2 = (t1 - t0) * (TW / 2);
   const v2d zero = {0.0, 0.0};
   for (int64_t i = tid; i < nz2; i += blockDim.x) z[i] = zero;
   __threadfence();
@@ -462,8 +483,7 @@ __global__ __launch_bounds__(256) void k_bs_fill(Csc M, const int32_t* __restric
     if (j < 0) continue;
     const double* __restrict__ v = static_cast<const double*>(M.val);
     for (int64_t e = M.outer[j] + lane; e < M.outer[j + 1]; e += WAVE) {
-      const double x = v[e];
-      if (x == 0.0) continue;
+      if (!bs_stored<CPLX>(v, e)) continue;
       const int pr = pos[M.inner[e]];
       const int I = pr >> 6, bit = 4 * (c >> 4) + ((pr >> 4) & 3);
       int64_t lo = s0, hi = s1;   // (srow of this super-column was written above by this workgroup)
@@ -473,7 +493,13 @@ __global__ __launch_bounds__(256) void k_bs_fill(Csc M, const int32_t* __restric
       }
       const unsigned mk = (unsigned)smask[lo];
       const int64_t slot = sbase[lo] + __popc(mk & ((1u << bit) - 1u));
-      tiles[slot * 256 + tile_word(phys(pr & 15), phys(c & 15))] = x;
+      const int64_t w = slot * TW + tile_word(phys(pr & 15), phys(c & 15));
+      if (CPLX) {
+        tiles[w] = v[2 * e];
+        tiles[w + 256] = v[2 * e + 1];
+      } else {
+        tiles[w] = v[e];
+      }
     }
   }
 }
@@ -509,12 +535,16 @@ bool to_block(const DevMat& M, const std::shared_ptr<BlockOrder>& bo, BlockForm&
   DevBuf<int64_t> tbase((size_t)ns + 1);
   static bool attr_done = false;
   if (!attr_done) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bs_count), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bs_fill), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bs_count<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bs_fill<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bs_count<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bs_fill<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     attr_done = true;
   }
   const Csc Mv = view(M);
-  hipLaunchKernelGGL(k_bs_count, dim3(ns), dim3(256), bs_count_lds(ns), stream(), Mv, bo->pos.p, bo->lab.p, ns, cnt_st.p, cnt_tile.p);
+  const bool cplx = M.cplx;
+  if (cplx) hipLaunchKernelGGL(k_bs_count<true>, dim3(ns), dim3(256), bs_count_lds(ns), stream(), Mv, bo->pos.p, bo->lab.p, ns, cnt_st.p, cnt_tile.p);
+  else hipLaunchKernelGGL(k_bs_count<false>, dim3(ns), dim3(256), bs_count_lds(ns), stream(), Mv, bo->pos.p, bo->lab.p, ns, cnt_st.p, cnt_tile.p);
   scan_i32_async(cnt_st.p, F.soff.p, (int64_t)ns);
   scan_i32_async(cnt_tile.p, tbase.p, (int64_t)ns);
   int64_t nst = 0, nt = 0;
@@ -528,6 +558,7 @@ bool to_block(const DevMat& M, const std::shared_ptr<BlockOrder>& bo, BlockForm&
   if (fill_out) *fill_out = fill;
   if (nt == 0 || fill < min_fill) return false;
   F.order = bo;
+  F.cplx = cplx;
   F.ns = ns;
   F.nst = nst;
   F.ntiles = nt;
@@ -535,9 +566,13 @@ bool to_block(const DevMat& M, const std::shared_ptr<BlockOrder>& bo, BlockForm&
   F.srow.alloc((size_t)nst);
   F.smask.alloc((size_t)nst);
   F.sbase.alloc((size_t)nst);
-  F.tiles.alloc((size_t)nt * 256 + 512);
-  hipLaunchKernelGGL(k_bs_fill, dim3(ns), dim3(256), bs_fill_lds(ns), stream(), Mv, bo->pos.p, bo->lab.p, ns, F.soff.p, tbase.p, F.srow.p,
-                     F.smask.p, F.sbase.p, F.tiles.p);
+  F.tiles.alloc((size_t)nt * (cplx ? 512 : 256) + 512);
+  if (cplx)
+    hipLaunchKernelGGL(k_bs_fill<true>, dim3(ns), dim3(256), bs_fill_lds(ns), stream(), Mv, bo->pos.p, bo->lab.p, ns, F.soff.p, tbase.p, F.srow.p,
+                       F.smask.p, F.sbase.p, F.tiles.p);
+  else
+    hipLaunchKernelGGL(k_bs_fill<false>, dim3(ns), dim3(256), bs_fill_lds(ns), stream(), Mv, bo->pos.p, bo->lab.p, ns, F.soff.p, tbase.p, F.srow.p,
+                       F.smask.p, F.sbase.p, F.tiles.p);
   F.have_rows = false;
   return true;
 }
@@ -619,7 +654,9 @@ __global__ __launch_bounds__(256) void k_bs_symbolic(int ns, const int64_t* __re
 
 // slice masks of the tiles (BlockForm::quads): a wave per super-tile, lane l looks at the words 4 l .. 4 l + 3 of every tile
 // (statistics, optional: with ccountA = entries per column position of the LEFT operand the same pass counts the
-// intermediate products of the multiply, sum over the entries (k, j) of this matrix of ccountA[k])
+// intermediate products of the multiply, sum over the entries (k, j) of this matrix of ccountA[k]).  CPLX: a word holds an
+// entry when either part is non-zero.
+template <bool CPLX>
 __global__ __launch_bounds__(256) void k_bs_quads(int64_t nst, const int32_t* __restrict__ smask, const int64_t* __restrict__ sbase,
                                                   const double* __restrict__ tiles, unsigned long long* __restrict__ quads,
                                                   const int32_t* __restrict__ srow, const int32_t* __restrict__ ccountA,
@@ -638,17 +675,20 @@ __global__ __launch_bounds__(256) void k_bs_quads(int64_t nst, const int32_t* __
   const int rbase = ccountA ? 64 * srow[s] : 0;
   long long prods = 0;
   const unsigned mk = (unsigned)smask[s];
-  const double* __restrict__ base = tiles + sbase[s] * 256;
+  constexpr int TW = CPLX ? 512 : 256;
+  const double* __restrict__ base = tiles + sbase[s] * TW;
   unsigned long long colq = 0, rowq = 0;
   int rank = 0;
   for (int t = 0; t < 16; ++t) {
     if ((mk & (1u << t)) == 0) continue;
-    const v4d v = *reinterpret_cast<const v4d*>(base + rank * 256 + w0);
+    const v4d v = *reinterpret_cast<const v4d*>(base + rank * TW + w0);
+    v4d vi = bs_zero4();
+    if (CPLX) vi = *reinterpret_cast<const v4d*>(base + rank * TW + 256 + w0);
     rank += 1;
     unsigned c4 = 0, r4 = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (v[e] != 0.0) {
+      if (v[e] != 0.0 || vi[e] != 0.0) {
         c4 |= 1u << cq;
         r4 |= 1u << rq[e];
         if (ccountA) prods += ccountA[rbase + 16 * (t & 3) + rpos[e]];
@@ -667,8 +707,11 @@ __global__ __launch_bounds__(256) void k_bs_quads(int64_t nst, const int32_t* __
 bool block_quads(BlockForm& F, const int32_t* ccountA = nullptr, unsigned long long* prod_out = nullptr) {
   if (F.have_quads) return false;
   F.quads.alloc((size_t)2 * std::max<int64_t>(1, F.nst));
-  if (F.nst > 0)
-    hipLaunchKernelGGL(k_bs_quads, dim3(gridw(F.nst)), dim3(256), 0, stream(), F.nst, F.smask.p, F.sbase.p, F.tiles.p, F.quads.p,
+  if (F.nst > 0 && F.cplx)
+    hipLaunchKernelGGL(k_bs_quads<true>, dim3(gridw(F.nst)), dim3(256), 0, stream(), F.nst, F.smask.p, F.sbase.p, F.tiles.p, F.quads.p,
+                       F.srow.p, ccountA, prod_out);
+  else if (F.nst > 0)
+    hipLaunchKernelGGL(k_bs_quads<false>, dim3(gridw(F.nst)), dim3(256), 0, stream(), F.nst, F.smask.p, F.sbase.p, F.tiles.p, F.quads.p,
                        F.srow.p, ccountA, prod_out);
   F.have_quads = true;
   return ccountA != nullptr;
@@ -745,7 +788,6 @@ __global__ __launch_bounds__(256) void k_bs_match(int64_t ncand, const int32_t* 
   if (lane == 0) mcnt[cand] = cnt;
 }
 
-__device__ inline v4d bs_zero4() { const v4d z = {0.0, 0.0, 0.0, 0.0}; return z; }
 
 // One WORKGROUP of two waves per candidate super-tile (I, J); wave h owns the row blocks 2 h and 2 h + 1: acc[x][b] = tile
 // (row block 2 h + x, column block b), 8 accumulator tiles = 64 VGPRs; no LDS in the loop, no barriers before the
@@ -978,6 +1020,167 @@ __global__ __launch_bounds__(64 * HV) __attribute__((amdgpu_waves_per_eu(UNF ? 3
   if (lane == 0 && nprod) atomicAdd(&a.counters[2], (unsigned long long)nprod);
 }
 
+// COMPLEX tiles (BlockForm::cplx: the real plane, then the imaginary plane, each laid out as a real tile).  The scheme of
+// k_spgemm_tile_c (spgemm_tile_c.hip): with B' = [Re B | Im B] and B'' = [-Im B | Re B] (the planes swapped, the new real
+// one negated -- no cross-lane move: the two planes of a tile are loaded into the same lanes),
+//     [ Re C | Im C ]  =  Re A * B'  +  Im A * B''
+// as TWO chains per part of an entry, each the FMA chain over ascending position of the real kernel, added in the
+// epilogue.  With Im A = Im B = 0 the second chains are exact zeros and the first is the real kernel's chain: the real
+// block path's bits.
+// Geometry: a workgroup of 8 waves per candidate super-tile; wave h owns row block h >> 1 and the column blocks
+// 2 (h & 1), 2 (h & 1) + 1 -- two complex accumulator tiles of four chains each, 8 x v4d = 64 VGPRs, the budget of the real
+// kernel's two-wave geometry (three to four waves per SIMD); no LDS in the loop.  Per match and per block kb: the A tile
+// (h >> 1, kb) of both planes (8 words a lane), the wave's B tiles (kb, b) of both planes (8 words a lane each); per
+// 4-wide slice q with entries on both sides (BlockForm::quads, over both planes) four matrix instructions per tile pair.
+// The matches come from k_bs_match (eight waves would repeat the intersection eight times).
+constexpr int kCW = 8;   // waves per candidate of the complex kernel
+__global__ __launch_bounds__(64 * kCW) void k_bs_numeric_c(const BsArgs a) {
+  __shared__ unsigned wmask[kCW];
+  __shared__ int wcount[kCW];
+  __shared__ long long slot_base;
+  const int wg = xcd_block(a.nwg);
+  if (wg < 0) return;
+  const int lane = lane_id(), h = uni_i32(threadIdx.x / WAVE);
+  const int rb = h >> 1, cb0 = 2 * (h & 1);     // this wave: row block rb, column blocks cb0, cb0 + 1
+  const int64_t cand = uni_i32(a.order[wg]);
+  v4d accr[2], acci[2], accr2[2], acci2[2];     // [column block cb0 + y]: Re A B' (re, im), Im A B'' (re, im)
+#pragma unroll
+  for (int y = 0; y < 2; ++y) { accr[y] = bs_zero4(); acci[y] = bs_zero4(); accr2[y] = bs_zero4(); acci2[y] = bs_zero4(); }
+  const int64_t cb0off = uni_i64(a.soffB[uni_i32(a.cj[cand])]);
+  const int g = lane >> 4, m = lane & 15;
+  int aoffq[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) aoffq[q] = tile_word(phys(m), 4 * g + q);
+  const int blo = m * 16 + (((2 * g) ^ (m >> 1)) & 7) * 2;
+  const int bhi = m * 16 + (((2 * g + 1) ^ (m >> 1)) & 7) * 2;
+  unsigned nprod = 0;
+  const int64_t m0 = uni_i64(a.moff[cand]);
+  const int64_t w1 = (int64_t)uni_i32(a.mcnt[cand]);
+  for (int64_t base = 0; base < w1; base += WAVE) {
+    const int64_t e = base + lane;
+    const bool in = e < w1;
+    const int2 pr = in ? a.mlist[m0 + e] : make_int2(0, 0);
+    const int ia = pr.x, ib = pr.y - (int)cb0off;
+    unsigned long long match = __ballot(in);
+    while (match) {
+      const int l = __ffsll((long long)match) - 1;
+      match &= match - 1;
+      const int ia_s = readlane_i32(ia, l);
+      const int64_t ib_s = cb0off + readlane_i32(ib, l);
+      const unsigned mA = (unsigned)uni_i32(a.smaskA[ia_s]), mB = (unsigned)uni_i32(a.smaskB[ib_s]);
+      if (((mA >> rb) & 0x1111u) == 0 || ((mB >> (4 * cb0)) & 0xFFu) == 0) continue;   // nothing for this wave's tiles
+      const double* __restrict__ tA = a.tilesA + uni_i64(a.sbaseA[ia_s]) * 512;
+      const double* __restrict__ tB = a.tilesB + uni_i64(a.sbaseB[ib_s]) * 512;
+      const unsigned long long cqA = (unsigned long long)uni_i64((int64_t)a.quadsA[2 * (int64_t)ia_s]);
+      const unsigned long long rqB = (unsigned long long)uni_i64((int64_t)a.quadsB[2 * ib_s + 1]);
+#pragma unroll 1
+      for (int kb = 0; kb < 4; ++kb) {
+        const int abit = 4 * kb + rb;
+        const unsigned rowB = (mB >> (4 * cb0 + kb)) & 0x11u;      // bit 4 y: tile B(kb, cb0 + y)
+        if (!(mA & (1u << abit)) || rowB == 0) continue;
+        v2d b01[2], b23[2], c01[2], c23[2];   // real / imaginary plane of B(kb, cb0 + y)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+          if (rowB & (1u << (4 * y))) {
+            const int bbit = 4 * (cb0 + y) + kb;
+            const double* __restrict__ pB = tB + __popc(mB & ((1u << bbit) - 1u)) * 512;
+            b01[y] = *reinterpret_cast<const v2d*>(pB + blo);
+            b23[y] = *reinterpret_cast<const v2d*>(pB + bhi);
+            c01[y] = *reinterpret_cast<const v2d*>(pB + 256 + blo);
+            c23[y] = *reinterpret_cast<const v2d*>(pB + 256 + bhi);
+          }
+        }
+        const double* __restrict__ pA = tA + __popc(mA & ((1u << abit) - 1u)) * 512;
+        double ar[4], ai[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { ar[q] = pA[aoffq[q]]; ai[q] = pA[256 + aoffq[q]]; }
+        const unsigned ca4 = (unsigned)(cqA >> (4 * abit)) & 15u;
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+          if (rowB & (1u << (4 * y))) {
+            const unsigned m4 = ca4 & ((unsigned)(rqB >> (4 * (4 * (cb0 + y) + kb))) & 15u);
+            const double br[4] = {b01[y][0], b01[y][1], b23[y][0], b23[y][1]};
+            const double bi[4] = {c01[y][0], c01[y][1], c23[y][0], c23[y][1]};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              if (m4 & (1u << q)) {
+                accr[y] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[q], br[q], accr[y], 0, 0, 0);
+                acci[y] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[q], bi[q], acci[y], 0, 0, 0);
+                accr2[y] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[q], -bi[q], accr2[y], 0, 0, 0);
+                acci2[y] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[q], br[q], acci2[y], 0, 0, 0);
+              }
+            }
+            nprod += __popc(m4);
+          }
+        }
+      }
+    }
+  }
+  // ---- epilogue: the two chains added, |z| > threshold (PruneList.f90:22, strict >; the dense branch tests before the
+  // scaling) decided without the hypot wherever max(|re|, |im|) or |re| + |im| already tells (as spgemm_tile_c.hip)
+  const double alpha = a.alpha, thr = a.threshold;
+  const bool dense = (a.dense_rule & 1) != 0;
+  unsigned mine = 0;     // bit 4 (cb0 + y) + rb
+  int cnt = 0;
+#pragma unroll
+  for (int y = 0; y < 2; ++y) {
+    bool any = false;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const double re = __dadd_rn(accr[y][r], accr2[y][r]), im = __dadd_rn(acci[y][r], acci2[y][r]);
+      const double sre = __dmul_rn(alpha, re), sim = __dmul_rn(alpha, im);
+      const double ax = fabs(dense ? re : sre), ay = fabs(dense ? im : sim);
+      bool keep = fmax(ax, ay) > thr;
+      if (!keep && __dadd_rn(ax, ay) > thr) keep = hypot(ax, ay) > thr;
+      accr[y][r] = keep ? sre : 0.0;
+      acci[y][r] = keep ? sim : 0.0;
+      any |= keep;
+      cnt += keep ? 1 : 0;
+    }
+    if (__ballot(any) != 0ull) mine |= 1u << (4 * (cb0 + y) + rb);
+  }
+  cnt = (int)wave_sum_i64(cnt);
+  if (lane == 0) { wmask[h] = mine; wcount[h] = cnt; }
+  __syncthreads();
+  unsigned mall = 0;
+  int call = 0;
+#pragma unroll
+  for (int w = 0; w < kCW; ++w) { mall |= wmask[w]; call += wcount[w]; }
+  const unsigned mC = (unsigned)uni_i32((int)mall);
+  const int nt = __popc(mC);
+  if (threadIdx.x == 0) {
+    long long sl = 0;
+    if (nt) sl = (long long)atomicAdd(&a.counters[0], (unsigned long long)nt);
+    slot_base = sl;
+  }
+  __syncthreads();
+  const int64_t slot0 = uni_i64(slot_base);
+  const bool ok = slot0 + nt <= a.pool_tiles;
+  if (nt && ok) {
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+      const int bit = 4 * (cb0 + y) + rb;
+      if (mine & (1u << bit)) {
+        double* __restrict__ pt = a.pool + (slot0 + __popc(mC & ((1u << bit) - 1u))) * 512;
+        v2d lo2, hi2;
+        lo2[0] = accr[y][0]; lo2[1] = accr[y][1]; hi2[0] = accr[y][2]; hi2[1] = accr[y][3];
+        *reinterpret_cast<v2d*>(pt + blo) = lo2;
+        *reinterpret_cast<v2d*>(pt + bhi) = hi2;
+        lo2[0] = acci[y][0]; lo2[1] = acci[y][1]; hi2[0] = acci[y][2]; hi2[1] = acci[y][3];
+        *reinterpret_cast<v2d*>(pt + 256 + blo) = lo2;
+        *reinterpret_cast<v2d*>(pt + 256 + bhi) = hi2;
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    if (nt && !ok) atomicOr(&a.counters[1], 1ull);
+    a.cmask[cand] = ok ? (int32_t)mC : 0;
+    a.cbase[cand] = slot0;
+    a.ccnt[cand] = ok ? call : 0;
+  }
+  if (lane == 0 && nprod) atomicAdd(&a.counters[2], (unsigned long long)nprod);
+}
+
 // Z-order key of a candidate: the bits of its super-row and super-column interleaved
 __device__ inline unsigned bs_spread16(unsigned v) {
   v &= 0xFFFFu;
@@ -1021,8 +1224,8 @@ __global__ __launch_bounds__(256) void k_bs_soff(int ns, const int64_t* __restri
 // =====================================================================================================================
 // A wave per column position: lane (a, i) looks at row i of tile (a, cb) of every super-tile of the super-column.
 // FILL = false counts the entries (cnt[label]); FILL = true writes (row label, value) in position order at outer[label]
-// (the rows are sorted by label afterwards).
-template <bool FILL>
+// (the rows are sorted by label afterwards).  CPLX: complex tiles, (re, im) pairs out.
+template <bool FILL, bool CPLX = false>
 __global__ __launch_bounds__(256) void k_bs_unblock(int ns, const int64_t* __restrict__ soff, const int32_t* __restrict__ srow,
                                                     const int32_t* __restrict__ smask, const int64_t* __restrict__ sbase,
                                                     const double* __restrict__ tiles, const int32_t* __restrict__ lab,
@@ -1035,20 +1238,30 @@ __global__ __launch_bounds__(256) void k_bs_unblock(int ns, const int64_t* __res
   const int lane = lane_id(), J = pc >> 6, cb = (pc >> 4) & 3, a = lane >> 4, i = lane & 15;
   const int bit = 4 * cb + a;
   const int coloff = tile_word(i, phys(pc & 15));   // in-tile row i holds in-block position phys(i)
+  constexpr int TW = CPLX ? 512 : 256;
   int64_t w = FILL ? outer[j] : 0;
   int c = 0;
   for (int64_t t = soff[J]; t < soff[J + 1]; ++t) {
     const unsigned mk = (unsigned)smask[t];
     if (((mk >> (4 * cb)) & 15u) == 0) continue;
-    double v = 0.0;
-    if (mk & (1u << bit)) v = tiles[(sbase[t] + __popc(mk & ((1u << bit) - 1u))) * 256 + coloff];
-    const bool nz = v != 0.0;
+    double v = 0.0, vi = 0.0;
+    if (mk & (1u << bit)) {
+      const int64_t at = (sbase[t] + __popc(mk & ((1u << bit) - 1u))) * TW + coloff;
+      v = tiles[at];
+      if (CPLX) vi = tiles[at + 256];
+    }
+    const bool nz = v != 0.0 || vi != 0.0;
     if (FILL) {
       const unsigned long long bal = __ballot(nz);
       if (nz) {
         const int64_t at = w + __popcll(bal & lanemask_lt());
         inner[at] = lab[64 * srow[t] + 16 * a + phys(i)];
-        val[at] = v;
+        if (CPLX) {
+          val[2 * at] = v;
+          val[2 * at + 1] = vi;
+        } else {
+          val[at] = v;
+        }
       }
       w += __popcll(bal);
     } else {
@@ -1079,7 +1292,9 @@ __global__ __launch_bounds__(256) void k_bs_sum_i32(int64_t n, const int32_t* __
   if (lane_id() == 0 && s) atomicAdd(out, (unsigned long long)s);
 }
 
+void from_block_c(const BlockForm& F, int64_t nnz, DevMat& C);
 void from_block(const BlockForm& F, int64_t nnz, DevMat& C) {
+  if (F.cplx) return from_block_c(F, nnz, C);
   const BlockOrder& bo = *F.order;
   const int n = bo.n, ns = F.ns;
   DevMat R;
@@ -1105,6 +1320,39 @@ void from_block(const BlockForm& F, int64_t nnz, DevMat& C) {
     DevBuf<char> tmp(tb);
     HIP_CHECK(rocprim::segmented_radix_sort_pairs(tmp.p, tb, tin.p, R.inner.p, tval.p, R.val.p, (unsigned)nnz, (unsigned)n, R.outer.p,
                                                   R.outer.p + 1, 0, bits, stream()));
+  }
+  C = std::move(R);
+}
+
+// complex tiles -> compressed columns: as from_block, the (re, im) pairs sorted by label as one 16-byte value
+void from_block_c(const BlockForm& F, int64_t nnz, DevMat& C) {
+  const BlockOrder& bo = *F.order;
+  const int n = bo.n, ns = F.ns;
+  DevMat R;
+  R.rows = n; R.cols = n; R.cplx = true; R.nnz = nnz; R.zero_free = 1;
+  R.outer.alloc((size_t)n + 1);
+  DevBuf<int32_t> cnt((size_t)n);
+  cnt.zero();
+  hipLaunchKernelGGL((k_bs_unblock<false, true>), dim3(gridw((int64_t)64 * ns)), dim3(256), 0, stream(), ns, F.soff.p, F.srow.p, F.smask.p,
+                     F.sbase.p, F.tiles.p, bo.lab.p, cnt.p, (const int64_t*)nullptr, (int32_t*)nullptr, (double*)nullptr);
+  scan_i32_async(cnt.p, R.outer.p, (int64_t)n);
+  R.inner.alloc((size_t)nnz + kIndexSlack);
+  R.val.alloc(2 * ((size_t)nnz + kIndexSlack));
+  if (nnz > 0) {
+    DevBuf<int32_t> tin((size_t)nnz);
+    DevBuf<double> tval(2 * (size_t)nnz);
+    hipLaunchKernelGGL((k_bs_unblock<true, true>), dim3(gridw((int64_t)64 * ns)), dim3(256), 0, stream(), ns, F.soff.p, F.srow.p, F.smask.p,
+                       F.sbase.p, F.tiles.p, bo.lab.p, (int32_t*)nullptr, R.outer.p, tin.p, tval.p);
+    int bits = 1;
+    while ((1ll << bits) < (long long)n) ++bits;
+    const double2* vin = reinterpret_cast<const double2*>(tval.p);
+    double2* vout = reinterpret_cast<double2*>(R.val.p);
+    size_t tb = 0;
+    HIP_CHECK(rocprim::segmented_radix_sort_pairs(nullptr, tb, tin.p, R.inner.p, vin, vout, (unsigned)nnz, (unsigned)n, R.outer.p, R.outer.p + 1,
+                                                  0, bits, stream()));
+    DevBuf<char> tmp(tb);
+    HIP_CHECK(rocprim::segmented_radix_sort_pairs(tmp.p, tb, tin.p, R.inner.p, vin, vout, (unsigned)nnz, (unsigned)n, R.outer.p, R.outer.p + 1,
+                                                  0, bits, stream()));
   }
   C = std::move(R);
 }
@@ -1468,6 +1716,7 @@ struct CachedForm {   // the block form of a matrix in compressed columns, valid
   unsigned long long serial = 0, epoch = 0, order_serial = 0;
   int64_t nnz = -1;
   int32_t cols = 0;
+  bool cplx = false;   // (a real and a complex form of the same buffer are different forms)
   std::shared_ptr<BlockForm> form;
   unsigned long long used = 0;
 };
@@ -1532,8 +1781,13 @@ void drop_block_caches() {
   cache().pool_hint_n = -1;
 }
 
+bool block_refused(int32_t n, int64_t nnz) {
+  const BlockCache& c = cache();
+  return c.refused_n == n && (double)nnz <= 1.5 * (double)c.refused_nnz && (double)nnz >= 0.5 * (double)c.refused_nnz;
+}
+
 bool block_order_for(const DevMat& M, std::vector<int32_t>& pos_host) {
-  if (M.cplx || M.rows != M.cols || M.loose() || M.expanded()) return false;
+  if (M.rows != M.cols || M.loose() || M.expanded()) return false;
   BlockCache& c = cache();
   if (!select_order(c, M.cols)) install_order(c, build_block_order(M));
   pos_host.resize((size_t)M.cols);
@@ -1638,7 +1892,7 @@ void block_product(BlockCache& bc, BlockForm& FA, BlockForm& FB, double alpha, d
   DevBuf<int64_t> moff;
   DevBuf<int32_t> mcnt;
   DevBuf<int2> mlist;
-  if (options().block_match != 0) {
+  if (options().block_match != 0 || FA.cplx) {
     DevBuf<int32_t> bound((size_t)ncand);
     moff.alloc((size_t)ncand + 1);
     mcnt.alloc((size_t)ncand);
@@ -1657,6 +1911,7 @@ void block_product(BlockCache& bc, BlockForm& FA, BlockForm& FB, double alpha, d
   // ---- numeric (the pool is sized from the last product of this dimension; an overflow is repeated with the exact size)
   FC = BlockForm();
   FC.order = bc.order;
+  FC.cplx = FA.cplx;
   FC.ns = ns;
   const bool dense_tiles = (double)FA.nnz > 0.5 * 256.0 * (double)FA.ntiles && (double)FB.nnz > 0.5 * 256.0 * (double)FB.ntiles;
   int64_t pool = std::max<int64_t>(1024, std::max(FA.ntiles, FB.ntiles) * 2);
@@ -1664,7 +1919,7 @@ void block_product(BlockCache& bc, BlockForm& FA, BlockForm& FB, double alpha, d
   pool = std::min<int64_t>(pool, ncand * 16);
   DevBuf<unsigned long long> counters(4);
   for (int attempt = 0; attempt < 2; ++attempt) {
-    FC.tiles.alloc((size_t)pool * 256 + 512);
+    FC.tiles.alloc((size_t)pool * (FC.cplx ? 512 : 256) + 512);
     counters.zero();
     BsArgs a;
     a.roffA = FA.roff.p; a.rcolA = FA.rcol.p; a.ridxA = FA.ridx.p; a.smaskA = FA.smask.p; a.sbaseA = FA.sbase.p; a.tilesA = FA.tiles.p;
@@ -1682,7 +1937,9 @@ void block_product(BlockCache& bc, BlockForm& FA, BlockForm& FB, double alpha, d
     if (ev_begin) HIP_CHECK(hipEventRecord(ev_begin, stream()));
     // (dense tiles: one wave per candidate; sparse tiles: two)
     const bool lst = a.mlist != nullptr;
-    if (options().spgemm_fma == 0) {
+    if (FC.cplx) {
+      hipLaunchKernelGGL(k_bs_numeric_c, dim3(xcd_grid(a.nwg)), dim3(64 * kCW), 0, stream(), a);
+    } else if (options().spgemm_fma == 0) {
       if (lst) hipLaunchKernelGGL((k_bs_numeric<2, true, true>), dim3(xcd_grid(a.nwg)), dim3(128), 0, stream(), a);
       else hipLaunchKernelGGL((k_bs_numeric<2, true>), dim3(xcd_grid(a.nwg)), dim3(128), 0, stream(), a);
     } else if (dense_tiles) {
@@ -1776,7 +2033,7 @@ std::shared_ptr<BlockForm> operand_form(const DevMat& M, BlockCache& bc, double 
   const unsigned long long ser = dev_alloc_serial(M.val.p), ep = matrix_value_epoch();
   for (CachedForm& f : bc.forms)
     if (f.form && f.val == M.val.p && f.serial == ser && ser != 0 && f.epoch == ep && f.nnz == M.nnz && f.cols == M.cols &&
-        f.order_serial == bc.order->serial) {
+        f.cplx == M.cplx && f.order_serial == bc.order->serial) {
       f.used = ++bc.clock;
       *fill = f.form->ntiles > 0 ? (double)M.nnz / (256.0 * (double)f.form->ntiles) : 0.0;
       return f.form;
@@ -1788,6 +2045,7 @@ std::shared_ptr<BlockForm> operand_form(const DevMat& M, BlockCache& bc, double 
   for (CachedForm& f : bc.forms)
     if (!f.form) { slot = &f; break; } else if (f.used < slot->used) slot = &f;
   slot->val = M.val.p; slot->serial = ser; slot->epoch = ep; slot->order_serial = bc.order->serial; slot->nnz = M.nnz; slot->cols = M.cols;
+  slot->cplx = M.cplx;
   slot->form = F;
   slot->used = ++bc.clock;
   return F;
@@ -2153,14 +2411,19 @@ bool block_norm(const DevMat& A, double* out) {
 bool spgemm_block(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule, BlockInfo* info,
                   hipEvent_t ev_begin, hipEvent_t ev_end, bool keep_blocked) {
   if (info) *info = BlockInfo();
-  if (A.cplx || B.cplx || A.rows != A.cols || B.rows != B.cols || A.cols != B.rows) return false;
+  if (A.cplx != B.cplx || A.rows != A.cols || B.rows != B.cols || A.cols != B.rows) return false;
   if (A.loose() || A.expanded() || B.loose() || B.expanded()) return false;
+  // complex operands: only where complex products are a tolerance mode already (FMA arithmetic, complex_tile), always in
+  // compressed columns (the block algebra is real)
+  const bool cplx = A.cplx;
+  if (cplx && (options().spgemm_fma != 1 || options().complex_tile == 0 || options().block_complex == 0 || A.blocked() || B.blocked())) return false;
+  if (cplx) keep_blocked = false;
   const int32_t n = A.cols;
   if (n < 256 || A.nnz == 0 || B.nnz == 0) return false;
   BlockCache& bc = cache();
   const int force = options().block_path;
   const bool any_blocked = A.blocked() || B.blocked();
-  if (!any_blocked && force != 2 && bc.refused_n == n && (double)A.nnz <= 1.5 * (double)bc.refused_nnz && (double)A.nnz >= 0.5 * (double)bc.refused_nnz) return false;
+  if (!any_blocked && force != 2 && block_refused(n, A.nnz)) return false;
   const double min_fill = force == 2 ? 0.0 : kMinFill;
   // The order of a dimension is made ONCE, from the first operand that is dense enough to say something about the index
   // set (8 entries per column), and kept: the same product gives the same bits whenever it is computed.  An operand that
@@ -2227,7 +2490,7 @@ bool spgemm_block(const DevMat& A, const DevMat& B, DevMat& C, double alpha, dou
   block_product(bc, FA, *FB, alpha, threshold, dense_rule, FC, &nnzC, hc, &ncand, ev_begin, ev_end, count_products ? &nprod : nullptr,
                 (!A.blocked() && !B.blocked()) ? &A : nullptr, (!A.blocked() && !B.blocked()) ? &B : nullptr);
   if (ncand == 0) {
-    C.reset_empty(n, n, false);
+    C.reset_empty(n, n, cplx);
     if (info) { info->used = 1; info->fill_a = fa; info->fill_b = fb; }
     return true;
   }

@@ -1,6 +1,7 @@
 // Block-sparse SpGEMM on the FP64 matrix cores for operands WITHOUT run structure (spgemm_block.hip): 3-D Hamiltonians,
 // bands hidden under a relabelling.  Internal interface between spgemm() in kernels.hip, psmatrix.cpp and that
-// translation unit.  FMA arithmetic only (option spgemm_fma = 1), real square operands on one rank.
+// translation unit.  FMA arithmetic only (option spgemm_fma = 1), square operands on one rank; complex ones with options
+// complex_tile = 1 and block_complex = 1 (products only: the block algebra and the TRS2 step in block form are real).
 #pragma once
 #include <memory>
 #include <vector>
@@ -32,15 +33,18 @@ struct BlockOrder {
 // A tile is 256 doubles; element (row o_r, column o_c) of it at phys(o_c) * 16 + phys(o_r), phys(o) = 4 (o & 3) + (o >> 2)
 // (the order in which four lane groups of the matrix instruction hold consecutive words: spgemm_block.hip).
 // Zero = no entry.
+// A COMPLEX tile (cplx) is 512 doubles: the real parts as a real tile, then the imaginary parts in the same layout; an entry
+// is absent only where both parts are zero.
 struct BlockForm {
   std::shared_ptr<BlockOrder> order;
+  bool cplx = false;
   int32_t ns = 0;
   int64_t nst = 0, ntiles = 0, nnz = 0;
   DevBuf<int64_t> soff;        // [ns + 1] super-column J holds the super-tiles soff[J] .. soff[J + 1]
   DevBuf<int32_t> srow;        // [nst]    super-row, ascending inside a super-column
   DevBuf<int32_t> smask;       // [nst]    (low 16 bits)
   DevBuf<int64_t> sbase;       // [nst]    first tile slot
-  DevBuf<double> tiles;        // [256 ntiles (capacity may be larger)]
+  DevBuf<double> tiles;        // [256 ntiles (512 ntiles if cplx; capacity may be larger)]
   // the same super-tiles by super-ROW (what the left operand of a product is walked by): row I holds
   // roff[I] .. roff[I + 1], rcol ascending, ridx = index into srow / smask / sbase.  Built on first use.
   DevBuf<int64_t> roff;
@@ -69,8 +73,9 @@ struct BlockInfo {
   float ms_numeric = 0.f;
 };
 
-// C = alpha A B pruned (PruneList.f90:8-38) through the block path.  false: not taken (operands complex / not square /
-// the clustering finds no blocks worth the matrix cores); C untouched.  ev_begin / ev_end (optional): recorded around the
+// C = alpha A B pruned (PruneList.f90:8-38) through the block path.  false: not taken (operands not square / complex outside
+// FMA arithmetic with complex_tile and block_complex / the clustering finds no blocks worth the matrix cores); C untouched.
+// Complex products are always returned in compressed columns (keep_blocked is ignored).  ev_begin / ev_end (optional): recorded around the
 // numeric kernel.
 // Operands: compressed columns (their block form is cached per matrix: value buffer, its allocation serial, the value
 // epoch) or block form (DevMat::blk).  keep_blocked: C is left in block form (C.blk; pack() converts).
@@ -91,6 +96,9 @@ bool block_order_of_pattern(const DevMat& M, std::vector<int32_t>& pos_host, int
 // order of dimension n: a solve that has redistributed its operands in a block order (band_scope.cpp) multiplies in it
 void install_block_positions(int32_t n, int32_t ns, const std::vector<int32_t>& pos);
 void drop_block_caches();
+// true: the block path has declined operands of dimension n with about nnz entries (no blocks worth the matrix cores) and
+// will decline them again without a look
+bool block_refused(int32_t n, int64_t nnz);
 // Block algebra (one rank, real, FMA arithmetic): the vocabulary of the solver loops on matrices in block form -- the
 // counterpart of the slab algebra (kernels.hpp) for operands without runs.  Operands are in block form or in compressed
 // columns (converted through the per-matrix cache: an identity, the Hamiltonian).  The same element rules as on

@@ -185,6 +185,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "tile_runs_only") options().tile_runs_only = *value;
   else if (n == "tile2") options().tile2 = *value;
   else if (n == "complex_tile") options().complex_tile = *value;
+  else if (n == "block_complex") options().block_complex = *value;
   else if (n == "thin_left") options().thin_left = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
@@ -213,6 +214,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "fused_update") return options().fused_update;
   if (n == "loose_iterates") return options().loose_iterates;
   if (n == "complex_tile") return options().complex_tile;
+  if (n == "block_complex") return options().block_complex;
   if (n == "thin_left") return options().thin_left;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
