@@ -222,6 +222,18 @@ bool blk_any(std::initializer_list<const PSMatrix*> ms) {
     if (m->loc.blocked()) return true;
   return false;
 }
+// complex operands stay in block form (complex products and the complex block algebra, spgemm_block.hpp) inside a session on
+// one rank where complex sessions and the complex block path are both allowed -- a solver's complex session or a one-call
+// session of the C ABI
+bool complex_blocks_on() {
+  return slab_on() && !world().active() && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0 &&
+         options().block_complex != 0 && options().block_path != 0;
+}
+// operands the block algebra may take together: both real, or mixed / complex with a complex one in block form (a real
+// operand in compressed columns joins it as a complex form)
+bool blk_kinds(const PSMatrix& A, const PSMatrix& B) {
+  return (!A.cplx && !B.cplx) || (A.cplx && A.loc.blocked()) || (B.cplx && B.loc.blocked());
+}
 long long g_column_fused[2] = {0, 0};   // in-place identity increments, norms of differences (column_fused.hip)
 long long g_block_counts[2] = {0, 0};   // operations of the block algebra; fallbacks to compressed columns
 // an operation outside the session, or after a refusal: no operand may stay in slab form
@@ -813,7 +825,9 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
   // A one-call session of the C ABI on operands without run structure (or already in block form): the product goes
   // through the block path and STAYS in block form (DevMat::blk) -- the next product of the caller's loop multiplies it
   // as it is, every other entry point packs on access.  Solver loops (sessions of their own) take compressed columns.
-  const bool block_first = slab_on() && !A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308 &&
+  // Complex operands the same way where complex block forms are allowed (complex_blocks_on) -- before a complex session's
+  // attempt on runs, whose refusals would end the session
+  const bool block_first = slab_on() && (!A.cplx || complex_blocks_on()) && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308 &&
                            (A.loc.blocked() || B.loc.blocked() || A.loc.block_hint || B.loc.block_hint) && !A.loc.expanded() && !B.loc.expanded() &&
                            !A.loc.loose() && !B.loc.loose();
   if (block_first) {
@@ -823,7 +837,7 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
     spgemm(A.loc, B.loc, AB, alpha, threshold, dense_rule);
    
     C.grid = A.grid; C.dim = A.dim; C.c0 = B.c0; C.c1 = B.c1;
-    C.cplx = false;
+    C.cplx = A.cplx;
     C.loc = std::move(AB);
     return;
   }
@@ -885,7 +899,7 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
   if (S <= 1) {
     // (a one-call session of the C ABI: should the product turn out to belong to the block path -- decided inside spgemm()
     // once the run-based kernels have declined -- it stays in block form, and the refusal above was not one)
-    const bool keep_block = g_slab_depth > 0 && !g_slab_failed && !A.cplx && std::fabs(beta) < 2.2250738585072014e-308;
+    const bool keep_block = g_slab_depth > 0 && !g_slab_failed && (!A.cplx || complex_blocks_on()) && std::fabs(beta) < 2.2250738585072014e-308;
     if (keep_block) {
       BlockKeepScope keep;
       AB = multiply_panel(A, B, alpha, threshold);
@@ -939,7 +953,7 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
 void ps_increment(const PSMatrix& A, PSMatrix& B, double alpha, double threshold) {
   use_grid_comm(A.grid);
   if (A.dim != B.dim) NTP_FATAL("IncrementMatrix: dimension mismatch");
-  if (blk_any({&A, &B}) && &A != &B && !A.cplx && !B.cplx) {
+  if (blk_any({&A, &B}) && &A != &B && blk_kinds(A, B)) {
     ps_axpby(A, B, alpha, 1.0, threshold);
     return;
   }
@@ -985,8 +999,12 @@ void ps_scale(PSMatrix& A, double c) {
 void ps_axpby(const PSMatrix& A, PSMatrix& B, double alpha, double beta, double threshold) {
   use_grid_comm(A.grid);
   if (A.dim != B.dim) NTP_FATAL("IncrementMatrix: dimension mismatch");
-  if (blk_any({&A, &B}) && !A.cplx && !B.cplx && &A != &B && !A.loc.expanded() && !B.loc.expanded() && !A.loc.loose() && !B.loc.loose()) {
-    if (block_axpby(A.loc, B.loc, alpha, beta, threshold)) { g_block_counts[0] += 1; return; }
+  if (blk_any({&A, &B}) && blk_kinds(A, B) && &A != &B && !A.loc.expanded() && !B.loc.expanded() && !A.loc.loose() && !B.loc.loose()) {
+    if (block_axpby(A.loc, B.loc, alpha, beta, threshold)) {
+      g_block_counts[0] += 1;
+      B.cplx = B.loc.cplx;   // (a real B beside a complex A: up-cast, as IncrementMatrix)
+      return;
+    }
     g_block_counts[1] += 1;
   }
   unblock({&A, &B});
@@ -1106,7 +1124,7 @@ bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatr
 
 void ps_copy_axpby(const PSMatrix& B, const PSMatrix& A, PSMatrix& Out, double alpha, double beta, double threshold) {
   use_grid_comm(B.grid);
-  if (blk_any({&A, &B}) && !A.cplx && !B.cplx && &A != &B && &Out != &A && &Out != &B) {
+  if (blk_any({&A, &B}) && blk_kinds(A, B) && &A != &B && &Out != &A && &Out != &B) {
     ps_copy(B, Out);
     ps_axpby(A, Out, alpha, beta, threshold);
     return;
@@ -1650,11 +1668,17 @@ void ps_pairwise(const PSMatrix& A, const PSMatrix& B, PSMatrix& C) {
 // sum conj(A).B; fused, no Hadamard temporary.
 void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) {
   use_grid_comm(A.grid);
-  if (blk_any({&A, &B}) && !A.cplx && !B.cplx) {
-    double d = 0.0;
-    // (the sum runs over the super-tiles of its first operand: the one in block form)
-    const bool ok = A.loc.blocked() ? block_dot_trace(A.loc, B.loc, &d, nullptr) : block_dot_trace(B.loc, A.loc, &d, nullptr);
-    if (ok) { g_block_counts[0] += 1; out[0] = d; out[1] = 0.0; return; }
+  if (blk_any({&A, &B}) && blk_kinds(A, B)) {
+    double d[2] = {0.0, 0.0};
+    // (the sum runs over the super-tiles of its first operand: the one in block form; sum conj(b) a = conj(sum conj(a) b))
+    const bool swap = !A.loc.blocked();
+    const bool ok = swap ? block_dot_trace(B.loc, A.loc, d, nullptr) : block_dot_trace(A.loc, B.loc, d, nullptr);
+    if (ok) {
+      g_block_counts[0] += 1;
+      out[0] = d[0];
+      out[1] = (swap && (A.cplx || B.cplx)) ? -d[1] : d[1];
+      return;
+    }
     g_block_counts[1] += 1;
   }
   unblock({&A, &B});
@@ -1682,7 +1706,7 @@ void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) {
 
 double ps_trace(const PSMatrix& A) {
   use_grid_comm(A.grid);  // MatrixTrace (distributed_algebra_includes/MatrixTrace.f90)
-  if (blk_any({&A}) && !A.cplx) {
+  if (blk_any({&A})) {
     double t = 0.0;
     if (block_dot_trace(A.loc, A.loc, nullptr, &t)) { g_block_counts[0] += 1; return t; }
     g_block_counts[1] += 1;
@@ -1706,7 +1730,7 @@ double ps_trace(const PSMatrix& A) {
 
 double ps_norm(const PSMatrix& A) {
   use_grid_comm(A.grid);  // MatrixNorm: max column abs-sum; columns are local
-  if (blk_any({&A}) && !A.cplx) {
+  if (blk_any({&A})) {
     double v = 0.0;
     if (block_norm(A.loc, &v)) { g_block_counts[0] += 1; return v; }
     g_block_counts[1] += 1;

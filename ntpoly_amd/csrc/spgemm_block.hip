@@ -26,7 +26,8 @@
 //
 // Complex operands (options complex_tile and block_complex, FMA arithmetic): the same order (made from the modulus), complex
 // tiles (a real plane and an imaginary plane), and k_bs_numeric_c -- two FMA chains per part of an entry, the tolerance mode
-// of the complex tile kernel; products only, always returned in compressed columns.
+// of the complex tile kernel.  Complex results stay in block form where the caller asks (a complex session), and the block
+// algebra's merge, scaling, copy, dot, trace and norm take complex forms (the complex element rules); the TRS2 step is real.
 #include "spgemm_block.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1362,6 +1363,7 @@ void from_block_c(const BlockForm& F, int64_t nnz, DevMat& C) {
 // =====================================================================================================================
 // statistics: intermediate products of A B with both operands in block form = sum over the entries B(k, j) of the
 // entries of column k of A (ccountA by position)
+template <bool CPLX>
 __global__ __launch_bounds__(256) void k_bs_products_blk(int ns, const int64_t* __restrict__ soff, const int32_t* __restrict__ srow,
                                                          const int32_t* __restrict__ smask, const int64_t* __restrict__ sbase,
                                                          const double* __restrict__ tiles, const int32_t* __restrict__ ccountA,
@@ -1372,18 +1374,21 @@ __global__ __launch_bounds__(256) void k_bs_products_blk(int ns, const int64_t* 
   const int bit = 4 * cb + a;
   const int coloff = tile_word(i, phys(pc & 15));
   long long s = 0;
+  constexpr int TW = CPLX ? 512 : 256;
   for (int64_t t = soff[J]; t < soff[J + 1]; ++t) {
     const unsigned mk = (unsigned)smask[t];
     if ((mk & (1u << bit)) == 0) continue;
-    const double v = tiles[(sbase[t] + __popc(mk & ((1u << bit) - 1u))) * 256 + coloff];
-    if (v != 0.0) s += ccountA[64 * srow[t] + 16 * a + phys(i)];
+    const int64_t at = (sbase[t] + __popc(mk & ((1u << bit) - 1u))) * TW + coloff;
+    if (tiles[at] != 0.0 || (CPLX && tiles[at + 256] != 0.0)) s += ccountA[64 * srow[t] + 16 * a + phys(i)];
   }
   s = wave_sum_i64(s);
   if (lane == 0 && s) atomicAdd(&out[(pc >> 2) & 63], (unsigned long long)s);
 }
 // per column position: entries and largest row label.  A wave per SUPER-TILE: every tile is read once, whole (lane l takes the words 4 l .. 4 l + 3, all in
 // in-tile column l / 4), the four lanes of a column are reduced and leave their part with two atomics per column position
-// (a wave per column position walks the super-column with 64 scattered words per step: three times slower)
+// (a wave per column position walks the super-column with 64 scattered words per step: three times slower).  CPLX: an entry
+// where either plane holds a non-zero.
+template <bool CPLX>
 __global__ __launch_bounds__(256) void k_bs_colstat_st(int64_t nst, int ns, const int64_t* __restrict__ soff, const int32_t* __restrict__ srow,
                                                        const int32_t* __restrict__ smask, const int64_t* __restrict__ sbase,
                                                        const double* __restrict__ tiles, const int32_t* __restrict__ lab,
@@ -1402,18 +1407,21 @@ __global__ __launch_bounds__(256) void k_bs_colstat_st(int64_t nst, int ns, cons
 #pragma unroll
   for (int e = 0; e < 4; ++e) rpos[e] = phys(((((ch + (e >> 1)) ^ (col_t >> 1)) & 7) << 1) | (e & 1));
   const unsigned mk = (unsigned)smask[s];
-  const double* __restrict__ base = tiles + sbase[s] * 256;
+  constexpr int TW = CPLX ? 512 : 256;
+  const double* __restrict__ base = tiles + sbase[s] * TW;
   int cnt[4] = {0, 0, 0, 0}, mx[4] = {-1, -1, -1, -1};
   int rank = 0;
 #pragma unroll
   for (int t = 0; t < 16; ++t) {
     if ((mk & (1u << t)) == 0) continue;
-    const v4d v = *reinterpret_cast<const v4d*>(base + rank * 256 + w0);
+    const v4d v = *reinterpret_cast<const v4d*>(base + rank * TW + w0);
+    v4d vi = bs_zero4();
+    if (CPLX) vi = *reinterpret_cast<const v4d*>(base + rank * TW + 256 + w0);
     rank += 1;
     const int rb = t & 3, cb = t >> 2;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (v[e] != 0.0) {
+      if (v[e] != 0.0 || vi[e] != 0.0) {
         cnt[cb] += 1;
         mx[cb] = max(mx[cb], lab[64 * I + 16 * rb + rpos[e]]);
       }
@@ -1438,8 +1446,8 @@ void block_colstat(BlockForm& F) {
   F.ccount.zero();
   HIP_CHECK(hipMemsetAsync(F.plast.p, 0xFF, sizeof(int32_t) * (size_t)64 * ns, stream()));
   if (F.nst > 0)
-    hipLaunchKernelGGL(k_bs_colstat_st, dim3(gridw(F.nst)), dim3(256), 0, stream(), F.nst, ns, F.soff.p, F.srow.p, F.smask.p, F.sbase.p,
-                       F.tiles.p, F.order->lab.p, F.ccount.p, F.plast.p);
+    hipLaunchKernelGGL(F.cplx ? k_bs_colstat_st<true> : k_bs_colstat_st<false>, dim3(gridw(F.nst)), dim3(256), 0, stream(), F.nst, ns, F.soff.p,
+                       F.srow.p, F.smask.p, F.sbase.p, F.tiles.p, F.order->lab.p, F.ccount.p, F.plast.p);
   F.have_stat = true;
 }
 
@@ -1502,7 +1510,7 @@ struct BsMergeArgs {
   int64_t ncand;
   const int32_t *ci, *cj;
   int32_t* cmask; int64_t* cbase; int32_t* ccnt;
-  double* pdot;          // [2 ncand]: (dot, trace) of the candidate
+  double* pdot;          // [2 ncand]: (dot, trace) of the candidate ([3 ncand]: (dot re, dot im, trace) with complex tiles)
   double* pool; int64_t pool_tiles;
   unsigned long long* counters;   // [0] tiles handed out, [1] overflow / kept-zero flags
   int32_t* ccount_out; int32_t* plast_out;   // per column position of the result (atomics)
@@ -1516,14 +1524,25 @@ __device__ inline int64_t bs_find(const int32_t* __restrict__ srow, int64_t lo, 
   }
   return (lo < end && srow[lo] == I) ? lo : -1;
 }
+// |value| of the merge rules: the modulus of a complex value is hypot(re, im), as Sc<double2>::mag of the merges on compressed
+// columns and on runs (kernels.hip inc_decide, k_sa_axpby<double2>)
+template <bool CPLX>
+__device__ inline double bs_mag(double re, double im) { return CPLX ? hypot(re, im) : fabs(re); }
 // One wave per super-tile of the union (MODE 2) or of the product (MODE 1).  Lane l owns the words 4 l .. 4 l + 3 of every
 // tile (32 contiguous bytes).  MODE 2: result = am P + bm X element by element with the AddSparseVectors rules
 // (sparse_includes/AddSparseVectors.f90:21-70; inc_decide of kernels.hip): both present -> kept if |sum| > threshold; one
 // present -> kept if |value| > threshold, or unfiltered when its row LABEL lies beyond the other column's last label;
 // kept tiles go to the pool, the (dot with D, trace, entries) of the super-tile to the candidate's slots, entries and last
 // label per column to the result's column statistics.  MODE 1: the result is P itself: dot, trace only.
-template <int MODE>
+// CPLX: complex tiles (the real plane, then the imaginary plane); the same operations per part as the complex merges on
+// compressed columns and runs (am, bm real): a value is present unless both parts are zero, |value| is the modulus, the dot
+// is sum conj(P) D (Sc<double2>::mul of conj(p) and d, as k_dot) and the trace sums real parts; candidate slots of pdot are
+// (dot re, dot im, trace).  The kept tiles of a complex super-tile would take 256 registers a lane: they are computed
+// again, from the same words by the same operations, once the pool slot is known.
+template <int MODE, bool CPLX>
 __global__ __launch_bounds__(64) void k_bs_merge(const BsMergeArgs a) {
+  constexpr int TW = CPLX ? 512 : 256;
+  constexpr int NP = CPLX ? 3 : 2;
   const int64_t cand = blockIdx.x;
   if (cand >= a.ncand) return;
   const int lane = lane_id();
@@ -1532,9 +1551,9 @@ __global__ __launch_bounds__(64) void k_bs_merge(const BsMergeArgs a) {
   const int64_t tx = MODE == 2 ? bs_find(a.srowX, a.soffX[J], a.soffX[J + 1], I) : -1;
   const int64_t td = bs_find(a.srowD, a.soffD[J], a.soffD[J + 1], I);
   const unsigned mP = tp >= 0 ? (unsigned)a.smaskP[tp] : 0u, mX = tx >= 0 ? (unsigned)a.smaskX[tx] : 0u, mD = td >= 0 ? (unsigned)a.smaskD[td] : 0u;
-  const double* __restrict__ bP = tp >= 0 ? a.tilesP + a.sbaseP[tp] * 256 : a.tilesP;
-  const double* __restrict__ bX = tx >= 0 ? a.tilesX + a.sbaseX[tx] * 256 : a.tilesP;
-  const double* __restrict__ bD = td >= 0 ? a.tilesD + a.sbaseD[td] * 256 : a.tilesP;
+  const double* __restrict__ bP = tp >= 0 ? a.tilesP + a.sbaseP[tp] * TW : a.tilesP;
+  const double* __restrict__ bX = tx >= 0 ? a.tilesX + a.sbaseX[tx] * TW : a.tilesP;
+  const double* __restrict__ bD = td >= 0 ? a.tilesD + a.sbaseD[td] * TW : a.tilesP;
   // this lane's four words of a tile: words 4 l + e -> in-tile (row, column) -> in-block positions
   const int w0 = 4 * lane, col_t = w0 >> 4, ch = (w0 & 15) >> 1;   // (two chunks: ch, ch + 1; e = 0, 1 in the first, 2, 3 in the second)
   int rowpos[4];
@@ -1544,8 +1563,63 @@ __global__ __launch_bounds__(64) void k_bs_merge(const BsMergeArgs a) {
     rowpos[e] = phys(row_t);
   }
   const int colpos = phys(col_t);
-  double dsum = 0.0, tsum = 0.0;
-  v4d outv[16];
+  // tile t of the result in this lane's words: values (o4, oi4), kept words, their largest row label, the kept-zero flag
+  auto tile_result = [&](int t, v4d& o4, v4d& oi4, unsigned& keepw, int& kl, unsigned& fl) {
+    const int rb = t & 3, cb = t >> 2;
+    v4d p4 = bs_zero4(), x4 = bs_zero4(), pi4 = bs_zero4(), xi4 = bs_zero4();
+    if (mP & (1u << t)) {
+      const double* q = bP + __popc(mP & ((1u << t) - 1u)) * TW + w0;
+      p4 = *reinterpret_cast<const v4d*>(q);
+      if (CPLX) pi4 = *reinterpret_cast<const v4d*>(q + 256);
+    }
+    if (MODE == 2 && (mX & (1u << t))) {
+      const double* q = bX + __popc(mX & ((1u << t) - 1u)) * TW + w0;
+      x4 = *reinterpret_cast<const v4d*>(q);
+      if (CPLX) xi4 = *reinterpret_cast<const v4d*>(q + 256);
+    }
+    const int pc = 64 * J + 16 * cb + colpos;
+    int lastP = -1, lastX = -1;
+    if (MODE == 2) { lastP = a.plastP[pc]; lastX = a.plastX[pc]; }
+    o4 = bs_zero4();
+    oi4 = bs_zero4();
+    keepw = 0;
+    kl = -1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      double o = 0.0, oi = 0.0;
+      bool keep;
+      if (MODE == 2) {
+        const double p = p4[e], x = x4[e], pi = pi4[e], xi = xi4[e];
+        const bool ha = p != 0.0 || (CPLX && pi != 0.0), hb = x != 0.0 || (CPLX && xi != 0.0);
+        const double wa = __dmul_rn(a.am, p), bs = __dmul_rn(a.bm, x);
+        const double wai = CPLX ? __dmul_rn(a.am, pi) : 0.0, bsi = CPLX ? __dmul_rn(a.bm, xi) : 0.0;
+        keep = false;
+        const int rl = (ha || hb) ? a.lab[64 * I + 16 * rb + rowpos[e]] : -1;
+        if (ha && hb) {
+          o = __dadd_rn(wa, bs);
+          if (CPLX) oi = __dadd_rn(wai, bsi);
+          keep = bs_mag<CPLX>(o, oi) > a.thr;
+        } else if (ha) {
+          o = wa; oi = wai;
+          keep = (rl > lastX) ? true : (bs_mag<CPLX>(wa, wai) > a.thr);
+        } else if (hb) {
+          o = bs; oi = bsi;
+          keep = (rl > lastP) ? true : (bs_mag<CPLX>(bs, bsi) > a.thr);
+        }
+        if (keep && o == 0.0 && oi == 0.0) fl |= 2u;
+        if (keep) kl = max(kl, rl);
+      } else {
+        o = p4[e];
+        oi = pi4[e];
+        keep = o != 0.0 || oi != 0.0;
+      }
+      o4[e] = keep ? o : 0.0;
+      oi4[e] = keep ? oi : 0.0;
+      keepw |= keep ? 1u << e : 0u;
+    }
+  };
+  double dsum = 0.0, dsum_i = 0.0, tsum = 0.0;
+  v4d outv[CPLX ? 1 : 16];
   unsigned mC = 0;
   int cnt = 0;
   unsigned flags = 0;
@@ -1554,54 +1628,41 @@ __global__ __launch_bounds__(64) void k_bs_merge(const BsMergeArgs a) {
   for (int t = 0; t < 16; ++t) {
     if ((mU & (1u << t)) == 0) continue;
     const int rb = t & 3, cb = t >> 2;
-    v4d p4 = bs_zero4(), x4 = bs_zero4(), d4 = bs_zero4();
-    if (mP & (1u << t)) p4 = *reinterpret_cast<const v4d*>(bP + __popc(mP & ((1u << t) - 1u)) * 256 + w0);
-    if (MODE == 2 && (mX & (1u << t))) x4 = *reinterpret_cast<const v4d*>(bX + __popc(mX & ((1u << t) - 1u)) * 256 + w0);
-    if (mD & (1u << t)) d4 = *reinterpret_cast<const v4d*>(bD + __popc(mD & ((1u << t) - 1u)) * 256 + w0);
+    v4d o4, oi4, d4 = bs_zero4(), di4 = bs_zero4();
+    unsigned keepw;
+    int kl;
+    tile_result(t, o4, oi4, keepw, kl, flags);
+    if (mD & (1u << t)) {
+      const double* q = bD + __popc(mD & ((1u << t) - 1u)) * TW + w0;
+      d4 = *reinterpret_cast<const v4d*>(q);
+      if (CPLX) di4 = *reinterpret_cast<const v4d*>(q + 256);
+    }
     const int pc = 64 * J + 16 * cb + colpos;
-    int lastP = -1, lastX = -1;
-    if (MODE == 2) { lastP = a.plastP[pc]; lastX = a.plastX[pc]; }
-    v4d o4 = bs_zero4();
-    bool any = false;
-    int kc = 0, kl = -1;
+    const int kc = __popc(keepw);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      double o;
-      bool keep;
-      if (MODE == 2) {
-        const double p = p4[e], x = x4[e];
-        const bool ha = p != 0.0, hb = x != 0.0;
-        const double wa = __dmul_rn(a.am, p), bs = __dmul_rn(a.bm, x);
-        o = 0.0;
-        keep = false;
-        const int rl = (ha || hb) ? a.lab[64 * I + 16 * rb + rowpos[e]] : -1;
-        if (ha && hb) { o = __dadd_rn(wa, bs); keep = fabs(o) > a.thr; }
-        else if (ha) { o = wa; keep = (rl > lastX) ? true : (fabs(wa) > a.thr); }
-        else if (hb) { o = bs; keep = (rl > lastP) ? true : (fabs(bs) > a.thr); }
-        if (keep && o == 0.0) flags |= 2u;
-        if (keep) kl = max(kl, rl);
-      } else {
-        o = p4[e];
-        keep = o != 0.0;
-      }
-      o4[e] = keep ? o : 0.0;
-      any |= keep;
-      kc += keep ? 1 : 0;
-      if (keep) {
-        dsum = __dadd_rn(dsum, __dmul_rn(o, d4[e]));
-        if (I == J && rb == cb && rowpos[e] == colpos) tsum = __dadd_rn(tsum, o);
+      if ((keepw >> e) & 1u) {
+        if (CPLX) {   // conj(o) d
+          const double cr = o4[e], ci = -oi4[e];
+          dsum = __dadd_rn(dsum, __dsub_rn(__dmul_rn(cr, d4[e]), __dmul_rn(ci, di4[e])));
+          dsum_i = __dadd_rn(dsum_i, __dadd_rn(__dmul_rn(cr, di4[e]), __dmul_rn(ci, d4[e])));
+        } else {
+          dsum = __dadd_rn(dsum, __dmul_rn(o4[e], d4[e]));
+        }
+        if (I == J && rb == cb && rowpos[e] == colpos) tsum = __dadd_rn(tsum, o4[e]);
       }
     }
     cnt += kc;
     if (MODE == 2) {
-      outv[t] = o4;
-      if (__ballot(any) != 0ull) mC |= 1u << t;
+      if constexpr (!CPLX) outv[t] = o4;
+      if (__ballot(keepw != 0) != 0ull) mC |= 1u << t;
       // column statistics of the result: the 4 words of a lane lie in one column (16 lanes x 4 words... 4 lanes per column)
       if (kc) { atomicAdd(&a.ccount_out[pc], kc); atomicMax(&a.plast_out[pc], kl); }
     }
   }
   cnt = (int)wave_sum_i64(cnt);
   dsum = wave_sum_f64(dsum);
+  if (CPLX) dsum_i = wave_sum_f64(dsum_i);
   tsum = wave_sum_f64(tsum);
   if (MODE == 2) {
     const int nt = __popc(mC);
@@ -1618,7 +1679,17 @@ __global__ __launch_bounds__(64) void k_bs_merge(const BsMergeArgs a) {
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
         if (mC & (1u << t)) {
-          *reinterpret_cast<v4d*>(a.pool + (slot0 + rank) * 256 + w0) = outv[t];
+          double* q = a.pool + (slot0 + rank) * TW + w0;
+          if constexpr (CPLX) {
+            v4d o4, oi4;
+            unsigned keepw, fl = 0;
+            int kl;
+            tile_result(t, o4, oi4, keepw, kl, fl);
+            *reinterpret_cast<v4d*>(q) = o4;
+            *reinterpret_cast<v4d*>(q + 256) = oi4;
+          } else {
+            *reinterpret_cast<v4d*>(q) = outv[t];
+          }
           rank += 1;
         }
       }
@@ -1634,23 +1705,33 @@ __global__ __launch_bounds__(64) void k_bs_merge(const BsMergeArgs a) {
       a.ccnt[cand] = ok ? cnt : 0;
     }
   }
-  if (lane == 0) { a.pdot[2 * cand] = dsum; a.pdot[2 * cand + 1] = tsum; }
+  if (lane == 0) {
+    a.pdot[NP * cand] = dsum;
+    if (CPLX) a.pdot[NP * cand + 1] = dsum_i;
+    a.pdot[NP * cand + NP - 1] = tsum;
+  }
 }
-// (dot, trace) pairs summed in a fixed shape: 256 partial sums, then one block
+// (dot, trace) pairs -- K-tuples: (dot re, dot im, trace) of complex forms -- summed in a fixed shape: 256 partial sums, then one block
+template <int K>
 __global__ __launch_bounds__(256) void k_bs_sum_pairs(int64_t n, const double* __restrict__ x, double* __restrict__ part) {
-  __shared__ double sh[2][4];
-  double s0 = 0.0, s1 = 0.0;
+  __shared__ double sh[K][4];
+  double s[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k] = 0.0;
   const int64_t per = (n + gridDim.x - 1) / gridDim.x;
   const int64_t b0 = blockIdx.x * per, b1 = min(n, b0 + per);
-  for (int64_t i = b0 + threadIdx.x; i < b1; i += blockDim.x) { s0 = __dadd_rn(s0, x[2 * i]); s1 = __dadd_rn(s1, x[2 * i + 1]); }
-  s0 = wave_sum_f64(s0);
-  s1 = wave_sum_f64(s1);
-  if (lane_id() == 0) { sh[0][threadIdx.x / WAVE] = s0; sh[1][threadIdx.x / WAVE] = s1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = __dadd_rn(__dadd_rn(sh[0][0], sh[0][1]), __dadd_rn(sh[0][2], sh[0][3]));
-    part[2 * blockIdx.x + 1] = __dadd_rn(__dadd_rn(sh[1][0], sh[1][1]), __dadd_rn(sh[1][2], sh[1][3]));
+  for (int64_t i = b0 + threadIdx.x; i < b1; i += blockDim.x)
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = __dadd_rn(s[k], x[K * i + k]);
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    s[k] = wave_sum_f64(s[k]);
+    if (lane_id() == 0) sh[k][threadIdx.x / WAVE] = s[k];
   }
+  __syncthreads();
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) part[K * blockIdx.x + k] = __dadd_rn(__dadd_rn(sh[k][0], sh[k][1]), __dadd_rn(sh[k][2], sh[k][3]));
 }
 __global__ __launch_bounds__(256) void k_bs_expand_j(int ns, const int64_t* __restrict__ soff, int32_t* __restrict__ cj) {
   const int J = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE);
@@ -1662,7 +1743,8 @@ __global__ __launch_bounds__(256) void k_bs_scale(int64_t nwords, double* __rest
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < nwords) tiles[i] = __dmul_rn(c, tiles[i]);
 }
-// max over the columns of the sum of |v| (non-negative doubles order like their bit patterns)
+// max over the columns of the sum of |v| (non-negative doubles order like their bit patterns); CPLX: |v| = hypot(re, im)
+template <bool CPLX>
 __global__ __launch_bounds__(256) void k_bs_colabs_max(int ns, const int64_t* __restrict__ soff, const int32_t* __restrict__ smask,
                                                        const int64_t* __restrict__ sbase, const double* __restrict__ tiles,
                                                        unsigned long long* __restrict__ out) {
@@ -1671,11 +1753,13 @@ __global__ __launch_bounds__(256) void k_bs_colabs_max(int ns, const int64_t* __
   const int lane = lane_id(), J = pc >> 6, cb = (pc >> 4) & 3, a = lane >> 4, i = lane & 15;
   const int bit = 4 * cb + a;
   const int coloff = tile_word(i, phys(pc & 15));
+  constexpr int TW = CPLX ? 512 : 256;
   double s = 0.0;
   for (int64_t t = soff[J]; t < soff[J + 1]; ++t) {
     const unsigned mk = (unsigned)smask[t];
     if ((mk & (1u << bit)) == 0) continue;
-    s = __dadd_rn(s, fabs(tiles[(sbase[t] + __popc(mk & ((1u << bit) - 1u))) * 256 + coloff]));
+    const int64_t at = (sbase[t] + __popc(mk & ((1u << bit) - 1u))) * TW + coloff;
+    s = __dadd_rn(s, bs_mag<CPLX>(tiles[at], CPLX ? tiles[at + 256] : 0.0));
   }
   s = wave_sum_f64(s);
   if (lane == 0) atomicMax(out, (unsigned long long)__double_as_longlong(s));
@@ -1972,8 +2056,8 @@ void block_product(BlockCache& bc, BlockForm& FA, BlockForm& FB, double alpha, d
       HIP_CHECK(hipMemcpyAsync(tot.p + 1, prod64.p, 64 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream()));
     } else {   // (B's masks existed already: entries per column of A, then the sum over the entries of B)
       block_colstat(FA);
-      hipLaunchKernelGGL(k_bs_products_blk, dim3(gridw((int64_t)64 * ns)), dim3(256), 0, stream(), ns, FB.soff.p, FB.srow.p, FB.smask.p, FB.sbase.p,
-                         FB.tiles.p, FA.ccount.p, tot.p + 1);
+      hipLaunchKernelGGL(FB.cplx ? k_bs_products_blk<true> : k_bs_products_blk<false>, dim3(gridw((int64_t)64 * ns)), dim3(256), 0, stream(), ns,
+                         FB.soff.p, FB.srow.p, FB.smask.p, FB.sbase.p, FB.tiles.p, FA.ccount.p, tot.p + 1);
     }
   }
   hipLaunchKernelGGL(k_bs_flag, dim3(grid1(ncand)), dim3(256), 0, stream(), ncand, cmask.p, flag.p);
@@ -2015,8 +2099,10 @@ DevMat block_unpack(const DevMat& M) {
 
 namespace {
 // the block form of an operand: its own (DevMat::blk, made in the current order), the cached one, or a fresh conversion
-std::shared_ptr<BlockForm> operand_form(const DevMat& M, BlockCache& bc, double min_fill, double* fill, bool* converted) {
+// (as_cplx: the complex form of a real matrix in compressed columns -- the up-cast of a mixed merge, ps_increment)
+std::shared_ptr<BlockForm> operand_form(const DevMat& M, BlockCache& bc, double min_fill, double* fill, bool* converted, bool as_cplx = false) {
   *converted = false;
+  const bool cplx = M.cplx || as_cplx;
   if (M.blocked()) {
     if (M.blk->order.get() == bc.order.get()) {
       *fill = M.blk->ntiles > 0 ? (double)M.nnz / (256.0 * (double)M.blk->ntiles) : 0.0;
@@ -2033,19 +2119,26 @@ std::shared_ptr<BlockForm> operand_form(const DevMat& M, BlockCache& bc, double 
   const unsigned long long ser = dev_alloc_serial(M.val.p), ep = matrix_value_epoch();
   for (CachedForm& f : bc.forms)
     if (f.form && f.val == M.val.p && f.serial == ser && ser != 0 && f.epoch == ep && f.nnz == M.nnz && f.cols == M.cols &&
-        f.cplx == M.cplx && f.order_serial == bc.order->serial) {
+        f.cplx == cplx && f.order_serial == bc.order->serial) {
       f.used = ++bc.clock;
       *fill = f.form->ntiles > 0 ? (double)M.nnz / (256.0 * (double)f.form->ntiles) : 0.0;
       return f.form;
     }
   std::shared_ptr<BlockForm> F(new BlockForm());
   *converted = true;
-  if (!to_block(M, bc.order, *F, min_fill, fill)) return nullptr;
+  if (cplx && !M.cplx) {
+    const DevMat Mc = to_complex(M);
+    const bool made = to_block(Mc, bc.order, *F, min_fill, fill);
+    sync_stream();   // (Mc is released on return)
+    if (!made) return nullptr;
+  } else if (!to_block(M, bc.order, *F, min_fill, fill)) {
+    return nullptr;
+  }
   CachedForm* slot = &bc.forms[0];
   for (CachedForm& f : bc.forms)
     if (!f.form) { slot = &f; break; } else if (f.used < slot->used) slot = &f;
   slot->val = M.val.p; slot->serial = ser; slot->epoch = ep; slot->order_serial = bc.order->serial; slot->nnz = M.nnz; slot->cols = M.cols;
-  slot->cplx = M.cplx;
+  slot->cplx = cplx;
   slot->form = F;
   slot->used = ++bc.clock;
   return F;
@@ -2109,9 +2202,9 @@ bool block_trs2_step(DevMat& X, int mode, double threshold, bool dense_rule, con
     DevBuf<double> pdot((size_t)2 * nc);
     hipLaunchKernelGGL(k_bs_expand_j, dim3(gridw(ns)), dim3(256), 0, stream(), ns, FP.soff.p, cj.p);
     a.ncand = nc; a.ci = FP.srow.p; a.cj = cj.p; a.pdot = pdot.p;
-    hipLaunchKernelGGL((k_bs_merge<1>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
-    hipLaunchKernelGGL(k_bs_sum_pairs, dim3(256), dim3(256), 0, stream(), nc, pdot.p, part.p);
-    hipLaunchKernelGGL(k_bs_sum_pairs, dim3(1), dim3(256), 0, stream(), (int64_t)256, part.p, res.p);
+    hipLaunchKernelGGL((k_bs_merge<1, false>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
+    hipLaunchKernelGGL(k_bs_sum_pairs<2>, dim3(256), dim3(256), 0, stream(), nc, pdot.p, part.p);
+    hipLaunchKernelGGL(k_bs_sum_pairs<2>, dim3(1), dim3(256), 0, stream(), (int64_t)256, part.p, res.p);
     {
       ScalarFetch f;
       f.add(res.p, 2, hres);
@@ -2155,9 +2248,9 @@ bool block_trs2_step(DevMat& X, int mode, double threshold, bool dense_rule, con
     tot.zero();
     a.ncand = nc; a.ci = ci.p; a.cj = cj.p; a.cmask = cmask.p; a.cbase = cbase.p; a.ccnt = ccnt.p; a.pdot = pdot.p;
     a.pool = FN.tiles.p; a.pool_tiles = pool; a.counters = counters.p; a.ccount_out = FN.ccount.p; a.plast_out = FN.plast.p;
-    hipLaunchKernelGGL((k_bs_merge<2>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
-    hipLaunchKernelGGL(k_bs_sum_pairs, dim3(256), dim3(256), 0, stream(), nc, pdot.p, part.p);
-    hipLaunchKernelGGL(k_bs_sum_pairs, dim3(1), dim3(256), 0, stream(), (int64_t)256, part.p, res.p);
+    hipLaunchKernelGGL((k_bs_merge<2, false>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
+    hipLaunchKernelGGL(k_bs_sum_pairs<2>, dim3(256), dim3(256), 0, stream(), nc, pdot.p, part.p);
+    hipLaunchKernelGGL(k_bs_sum_pairs<2>, dim3(1), dim3(256), 0, stream(), (int64_t)256, part.p, res.p);
     hipLaunchKernelGGL(k_bs_flag, dim3(grid1(nc)), dim3(256), 0, stream(), nc, cmask.p, flag.p);
     scan_i32_async(flag.p, excl.p, nc);
     hipLaunchKernelGGL(k_bs_sum_i32, dim3(std::min(1024, grid1(nc))), dim3(256), 0, stream(), nc, ccnt.p, tot.p);
@@ -2209,22 +2302,29 @@ bool block_trs2_step(DevMat& X, int mode, double threshold, bool dense_rule, con
 // ---------------------------------------------------------------------------------------------------------------------
 // block algebra
 namespace {
+// (complex forms: where the block path multiplies complex operands -- FMA arithmetic, complex_tile, block_complex)
+bool complex_forms_ok() { return options().spgemm_fma == 1 && options().complex_tile != 0 && options().block_complex != 0; }
 bool algebra_ok(const DevMat& M) {
-  return !M.cplx && M.rows == M.cols && !M.loose() && !M.expanded() && block_arithmetic_ok() && options().block_path != 0 &&
+  return (!M.cplx || complex_forms_ok()) && M.rows == M.cols && !M.loose() && !M.expanded() && block_arithmetic_ok() && options().block_path != 0 &&
          options().spgemm_variant < 0 && options().spgemm_force_bin <= 0;
 }
-// the form of an operand of the algebra in the order of its dimension (nullptr: none / other order)
-std::shared_ptr<BlockForm> algebra_form(const DevMat& M, BlockCache& bc) {
+// the form of an operand of the algebra in the order of its dimension (nullptr: none / other order).  as_cplx: a real
+// operand in compressed columns joins a complex one as a complex form (cached beside its real form)
+std::shared_ptr<BlockForm> algebra_form(const DevMat& M, BlockCache& bc, bool as_cplx = false) {
   if (!algebra_ok(M) || M.nnz == 0 || !select_order(bc, M.cols)) return nullptr;
   if (bc.order->ns > kMaxSuperBlocks) return nullptr;
   double fill = 0;
   bool conv = false;
   if (M.blocked() && M.blk->order.get() != bc.order.get()) return nullptr;
+  if (as_cplx && !M.cplx) {
+    if (M.blocked() || !complex_forms_ok()) return nullptr;
+    return operand_form(M, bc, 0.0, &fill, &conv, true);
+  }
   return operand_form(M, bc, 0.0, &fill, &conv);
 }
 DevMat blocked_matrix(int32_t n, int64_t nnz, BlockForm&& F) {
   DevMat R;
-  R.rows = n; R.cols = n; R.cplx = false; R.nnz = nnz; R.zero_free = 1; R.block_hint = 1;
+  R.rows = n; R.cols = n; R.cplx = F.cplx; R.nnz = nnz; R.zero_free = 1; R.block_hint = 1;
   R.blk.reset(new BlockForm(std::move(F)));
   return R;
 }
@@ -2237,10 +2337,12 @@ bool block_axpby(const DevMat& A, DevMat& B, double alpha, double beta, double t
   if (&A == &B || alpha == 0.0 || beta == 0.0 || A.cols != B.cols) return false;
   if (!A.blocked() && !B.blocked()) return false;
   BlockCache& bc = cache();
-  std::shared_ptr<BlockForm> pA = algebra_form(A, bc), pB = algebra_form(B, bc);
+  const bool cplx = A.cplx || B.cplx;   // (a real operand in compressed columns joins as a complex form: B is then up-cast)
+  std::shared_ptr<BlockForm> pA = algebra_form(A, bc, cplx), pB = algebra_form(B, bc, cplx);
   if (!pA || !pB) return false;
   BlockForm &FA = *pA, &FB = *pB;
   const int32_t n = B.cols;
+  const int TW = cplx ? 512 : 256, NP = cplx ? 3 : 2;
   const int ns = bc.order->ns;
   block_colstat(FA);
   block_colstat(FB);
@@ -2266,14 +2368,15 @@ bool block_axpby(const DevMat& A, DevMat& B, double alpha, double beta, double t
   if (nc == 0) return false;
   DevBuf<int32_t> ci((size_t)nc), cj((size_t)nc), cmask((size_t)nc), ccnt((size_t)nc), flag((size_t)nc);
   DevBuf<int64_t> cbase((size_t)nc), excl((size_t)nc + 1);
-  DevBuf<double> pdot((size_t)2 * nc);
+  DevBuf<double> pdot((size_t)NP * nc);
   hipLaunchKernelGGL((k_bs_union<true>), dim3(ns), dim3(256), lds, stream(), ns, FB.soff.p, FB.srow.p, FA.soff.p, FA.srow.p, (int32_t*)nullptr,
                      uoff.p, ci.p, cj.p);
   BlockForm FN;
   FN.order = bc.order;
+  FN.cplx = cplx;
   FN.ns = ns;
   const int64_t pool = FA.ntiles + FB.ntiles;
-  FN.tiles.alloc((size_t)pool * 256 + 512);
+  FN.tiles.alloc((size_t)pool * TW + 512);
   FN.ccount.alloc((size_t)64 * ns);
   FN.plast.alloc((size_t)64 * ns);
   FN.ccount.zero();
@@ -2290,7 +2393,7 @@ bool block_axpby(const DevMat& A, DevMat& B, double alpha, double beta, double t
   a.ncand = nc; a.ci = ci.p; a.cj = cj.p; a.cmask = cmask.p; a.cbase = cbase.p; a.ccnt = ccnt.p; a.pdot = pdot.p;
   a.pool = FN.tiles.p; a.pool_tiles = pool; a.counters = counters.p; a.ccount_out = FN.ccount.p; a.plast_out = FN.plast.p;
   a.am = alpha; a.bm = beta; a.thr = threshold;
-  hipLaunchKernelGGL((k_bs_merge<2>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
+  hipLaunchKernelGGL((cplx ? k_bs_merge<2, true> : k_bs_merge<2, false>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
   hipLaunchKernelGGL(k_bs_flag, dim3(grid1(nc)), dim3(256), 0, stream(), nc, cmask.p, flag.p);
   scan_i32_async(flag.p, excl.p, nc);
   hipLaunchKernelGGL(k_bs_sum_i32, dim3(std::min(1024, grid1(nc))), dim3(256), 0, stream(), nc, ccnt.p, tot.p);
@@ -2323,7 +2426,7 @@ bool block_scale(DevMat& A, double c) {
   if (!A.blocked() || !algebra_ok(A) || c == 0.0) return false;
   // (the tiles may be shared with a copy made by block_clone's cheap path: they are not -- clones are deep)
   BlockForm& F = *A.blk;
-  const int64_t nw = F.ntiles * 256;
+  const int64_t nw = F.ntiles * (F.cplx ? 512 : 256);   // (both planes: a real scalar)
   if (nw > 0) hipLaunchKernelGGL(k_bs_scale, dim3(grid1(nw)), dim3(256), 0, stream(), nw, F.tiles.p, c);
   return true;
 }
@@ -2332,7 +2435,8 @@ bool block_clone(const DevMat& A, DevMat& Out) {
   if (!A.blocked() || !algebra_ok(A)) return false;
   const BlockForm& F = *A.blk;
   BlockForm G;
-  G.order = F.order; G.ns = F.ns; G.nst = F.nst; G.ntiles = F.ntiles; G.nnz = F.nnz;
+  G.order = F.order; G.cplx = F.cplx; G.ns = F.ns; G.nst = F.nst; G.ntiles = F.ntiles; G.nnz = F.nnz;
+  const size_t tw = F.cplx ? 512 : 256;
   auto dup = [](auto& dst, const auto& src, size_t count) {
     using T = std::remove_reference_t<decltype(*src.p)>;
     dst.alloc(std::max<size_t>(1, count));
@@ -2343,8 +2447,8 @@ bool block_clone(const DevMat& A, DevMat& Out) {
   dup(G.smask, F.smask, (size_t)F.nst);
   dup(G.sbase, F.sbase, (size_t)F.nst);
   // (the tiles of the copy are packed: slot s of the copy = slot s of the original's pool, whose used part is contiguous)
-  G.tiles.alloc((size_t)F.ntiles * 256 + 512);
-  if (F.ntiles) HIP_CHECK(hipMemcpyAsync(G.tiles.p, F.tiles.p, sizeof(double) * (size_t)F.ntiles * 256, hipMemcpyDeviceToDevice, stream()));
+  G.tiles.alloc((size_t)F.ntiles * tw + 512);
+  if (F.ntiles) HIP_CHECK(hipMemcpyAsync(G.tiles.p, F.tiles.p, sizeof(double) * (size_t)F.ntiles * tw, hipMemcpyDeviceToDevice, stream()));
   if (F.have_stat) {
     dup(G.ccount, F.ccount, (size_t)64 * F.ns);
     dup(G.plast, F.plast, (size_t)64 * F.ns);
@@ -2361,14 +2465,16 @@ bool block_clone(const DevMat& A, DevMat& Out) {
 bool block_dot_trace(const DevMat& A, const DevMat& B, double* dot, double* trace_a) {
   if (A.cols != B.cols || (!A.blocked() && !B.blocked())) return false;
   BlockCache& bc = cache();
-  std::shared_ptr<BlockForm> pA = algebra_form(A, bc), pB = algebra_form(B, bc);
+  const bool cplx = A.cplx || B.cplx;
+  std::shared_ptr<BlockForm> pA = algebra_form(A, bc, cplx), pB = algebra_form(B, bc, cplx);
   if (!pA || !pB) return false;
   BlockForm &FA = *pA, &FB = *pB;
   const int ns = bc.order->ns;
   const int64_t nc = FA.nst;
-  if (nc == 0) { if (dot) *dot = 0.0; if (trace_a) *trace_a = 0.0; return true; }
+  if (nc == 0) { if (dot) dot[0] = dot[1] = 0.0; if (trace_a) *trace_a = 0.0; return true; }
+  const int NP = cplx ? 3 : 2;
   DevBuf<int32_t> cj((size_t)nc);
-  DevBuf<double> pdot((size_t)2 * nc), part(512), res(2);
+  DevBuf<double> pdot((size_t)NP * nc), part((size_t)NP * 256), res((size_t)NP);
   hipLaunchKernelGGL(k_bs_expand_j, dim3(gridw(ns)), dim3(256), 0, stream(), ns, FA.soff.p, cj.p);
   BsMergeArgs a;
   a.soffP = FA.soff.p; a.srowP = FA.srow.p; a.smaskP = FA.smask.p; a.sbaseP = FA.sbase.p; a.tilesP = FA.tiles.p; a.plastP = nullptr;
@@ -2378,17 +2484,23 @@ bool block_dot_trace(const DevMat& A, const DevMat& B, double* dot, double* trac
   a.ncand = nc; a.ci = FA.srow.p; a.cj = cj.p; a.cmask = nullptr; a.cbase = nullptr; a.ccnt = nullptr; a.pdot = pdot.p;
   a.pool = nullptr; a.pool_tiles = 0; a.counters = nullptr; a.ccount_out = nullptr; a.plast_out = nullptr;
   a.am = 1.0; a.bm = 0.0; a.thr = 0.0;
-  hipLaunchKernelGGL((k_bs_merge<1>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
-  hipLaunchKernelGGL(k_bs_sum_pairs, dim3(256), dim3(256), 0, stream(), nc, pdot.p, part.p);
-  hipLaunchKernelGGL(k_bs_sum_pairs, dim3(1), dim3(256), 0, stream(), (int64_t)256, part.p, res.p);
-  double h[2] = {0, 0};
+  if (cplx) {
+    hipLaunchKernelGGL((k_bs_merge<1, true>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
+    hipLaunchKernelGGL(k_bs_sum_pairs<3>, dim3(256), dim3(256), 0, stream(), nc, pdot.p, part.p);
+    hipLaunchKernelGGL(k_bs_sum_pairs<3>, dim3(1), dim3(256), 0, stream(), (int64_t)256, part.p, res.p);
+  } else {
+    hipLaunchKernelGGL((k_bs_merge<1, false>), dim3((unsigned)nc), dim3(64), 0, stream(), a);
+    hipLaunchKernelGGL(k_bs_sum_pairs<2>, dim3(256), dim3(256), 0, stream(), nc, pdot.p, part.p);
+    hipLaunchKernelGGL(k_bs_sum_pairs<2>, dim3(1), dim3(256), 0, stream(), (int64_t)256, part.p, res.p);
+  }
+  double h[3] = {0, 0, 0};
   {
     ScalarFetch f;
-    f.add(res.p, 2, h);
+    f.add(res.p, NP, h);
     f.run();
   }
-  if (dot) *dot = h[0];
-  if (trace_a) *trace_a = h[1];
+  if (dot) { dot[0] = h[0]; dot[1] = cplx ? h[1] : 0.0; }
+  if (trace_a) *trace_a = h[NP - 1];
   return true;
 }
 
@@ -2397,7 +2509,8 @@ bool block_norm(const DevMat& A, double* out) {
   const BlockForm& F = *A.blk;
   DevBuf<unsigned long long> mx(1);
   mx.zero();
-  hipLaunchKernelGGL(k_bs_colabs_max, dim3(gridw((int64_t)64 * F.ns)), dim3(256), 0, stream(), F.ns, F.soff.p, F.smask.p, F.sbase.p, F.tiles.p, mx.p);
+  hipLaunchKernelGGL(F.cplx ? k_bs_colabs_max<true> : k_bs_colabs_max<false>, dim3(gridw((int64_t)64 * F.ns)), dim3(256), 0, stream(), F.ns, F.soff.p,
+                     F.smask.p, F.sbase.p, F.tiles.p, mx.p);
   unsigned long long h = 0;
   {
     ScalarFetch f;
@@ -2413,11 +2526,9 @@ bool spgemm_block(const DevMat& A, const DevMat& B, DevMat& C, double alpha, dou
   if (info) *info = BlockInfo();
   if (A.cplx != B.cplx || A.rows != A.cols || B.rows != B.cols || A.cols != B.rows) return false;
   if (A.loose() || A.expanded() || B.loose() || B.expanded()) return false;
-  // complex operands: only where complex products are a tolerance mode already (FMA arithmetic, complex_tile), always in
-  // compressed columns (the block algebra is real)
+  // complex operands: only where complex products are a tolerance mode already (FMA arithmetic, complex_tile)
   const bool cplx = A.cplx;
-  if (cplx && (options().spgemm_fma != 1 || options().complex_tile == 0 || options().block_complex == 0 || A.blocked() || B.blocked())) return false;
-  if (cplx) keep_blocked = false;
+  if (cplx && !complex_forms_ok()) return false;
   const int32_t n = A.cols;
   if (n < 256 || A.nnz == 0 || B.nnz == 0) return false;
   BlockCache& bc = cache();
@@ -2496,7 +2607,7 @@ bool spgemm_block(const DevMat& A, const DevMat& B, DevMat& C, double alpha, dou
   }
   if (keep_blocked) {
     DevMat R;
-    R.rows = n; R.cols = n; R.cplx = false; R.nnz = (int64_t)nnzC; R.zero_free = 1;
+    R.rows = n; R.cols = n; R.cplx = cplx; R.nnz = (int64_t)nnzC; R.zero_free = 1;
     R.blk.reset(new BlockForm(std::move(FC)));
     C = std::move(R);
   } else {

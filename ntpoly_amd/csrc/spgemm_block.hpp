@@ -1,7 +1,7 @@
 // Block-sparse SpGEMM on the FP64 matrix cores for operands WITHOUT run structure (spgemm_block.hip): 3-D Hamiltonians,
 // bands hidden under a relabelling.  Internal interface between spgemm() in kernels.hip, psmatrix.cpp and that
 // translation unit.  FMA arithmetic only (option spgemm_fma = 1), square operands on one rank; complex ones with options
-// complex_tile = 1 and block_complex = 1 (products only: the block algebra and the TRS2 step in block form are real).
+// complex_tile = 1 and block_complex = 1 (products and the block algebra; the TRS2 step in block form is real).
 #pragma once
 #include <memory>
 #include <vector>
@@ -75,13 +75,12 @@ struct BlockInfo {
 
 // C = alpha A B pruned (PruneList.f90:8-38) through the block path.  false: not taken (operands not square / complex outside
 // FMA arithmetic with complex_tile and block_complex / the clustering finds no blocks worth the matrix cores); C untouched.
-// Complex products are always returned in compressed columns (keep_blocked is ignored).  ev_begin / ev_end (optional): recorded around the
-// numeric kernel.
+// ev_begin / ev_end (optional): recorded around the numeric kernel.
 // Operands: compressed columns (their block form is cached per matrix: value buffer, its allocation serial, the value
 // epoch) or block form (DevMat::blk).  keep_blocked: C is left in block form (C.blk; pack() converts).
 bool spgemm_block(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule, BlockInfo* info,
                   hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr, bool keep_blocked = false);
-DevMat block_unpack(const DevMat& M);   // block form -> compressed columns under the caller's labels
+DevMat block_unpack(const DevMat& M);   // block form -> compressed columns under the caller's labels (real or complex: the one way out)
 // One TRS2 step on an iterate of a dimension the block path multiplies (DensityMatrixSolversModule.F90:380-404): mode 1:
 // X <- X X; mode 2: X <- 2 X - X X merged by the AddSparseVectors rules -- with out[0] = dot(X_new, D), out[2] = trace.
 // X: compressed columns or block form; it is left in BLOCK form.  false: not taken (X unchanged).
@@ -99,15 +98,19 @@ void drop_block_caches();
 // true: the block path has declined operands of dimension n with about nnz entries (no blocks worth the matrix cores) and
 // will decline them again without a look
 bool block_refused(int32_t n, int64_t nnz);
-// Block algebra (one rank, real, FMA arithmetic): the vocabulary of the solver loops on matrices in block form -- the
+// Block algebra (one rank, FMA arithmetic): the vocabulary of the solver loops on matrices in block form -- the
 // counterpart of the slab algebra (kernels.hpp) for operands without runs.  Operands are in block form or in compressed
 // columns (converted through the per-matrix cache: an identity, the Hamiltonian).  The same element rules as on
 // compressed columns (AddSparseVectors with the tail rule in the caller's labels); dots and traces as fixed-shape sums.
+// Complex forms (with the options of complex products): the complex element rules -- |value| is the modulus, an entry is
+// absent only where both parts are zero, real scalars; a real operand in compressed columns beside a complex one joins as
+// a complex form (the up-cast of IncrementMatrix: B becomes complex), a real one in block form does not.
 // Every function returns false and leaves its operands alone when it cannot take them.
 bool block_axpby(const DevMat& A, DevMat& B, double alpha, double beta, double threshold);   // B <- alpha A + beta B
 bool block_scale(DevMat& A, double c);
 bool block_clone(const DevMat& A, DevMat& Out);
-bool block_dot_trace(const DevMat& A, const DevMat& B, double* dot, double* trace_a);   // sum a b; trace(A)
-bool block_norm(const DevMat& A, double* out);   // max column abs-sum
+// dot[0], dot[1] = sum conj(a) b (real and imaginary part; 0 for real operands); trace_a = trace(A) (complex: of the real parts)
+bool block_dot_trace(const DevMat& A, const DevMat& B, double* dot, double* trace_a);
+bool block_norm(const DevMat& A, double* out);   // max column abs-sum (complex: of the moduli)
 
 }  // namespace ntp

@@ -41,7 +41,8 @@ PSMatrix* get_unpacked(const int* ih) {
   return p;
 }
 // The vocabulary entry points (MatrixMultiply, IncrementMatrix, ScaleMatrix, CopyMatrix, DotMatrix, MatrixNorm) run
-// inside a slab session of their own (engine.hpp SlabSession; FMA arithmetic, one rank, real, option slab_algebra):
+// inside a slab session of their own (engine.hpp SlabSession; FMA arithmetic, one rank, real -- complex ones in block form where
+// complex sessions and the complex block path are allowed, psmatrix.cpp complex_blocks_on; option slab_algebra):
 // a caller's own loop over the C ABI then keeps its matrices in the tile kernel's operand form between its calls --
 // operands are converted where they are on first use, products stay where the kernel wrote them -- and every OTHER
 // entry point still sees compressed columns (get<PSMatrix> packs on access).  Session not open: packed as ever.
@@ -843,7 +844,8 @@ void DotMatrix_psr_wrp(const int* ih_matA, const int* ih_matB, double* product) 
 }
 void DotMatrix_psc_wrp(const int* ih_matA, const int* ih_matB, double* product_real, double* product_imag) {
   double out[2];
-  ps_dot(*get<PSMatrix>(ih_matA), *get<PSMatrix>(ih_matB), out);
+  ApiSession ses;
+  ps_dot(*ses.mat(ih_matA), *ses.mat(ih_matB), out);
   *product_real = out[0];
   *product_imag = out[1];
 }
