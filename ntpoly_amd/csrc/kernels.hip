@@ -2710,6 +2710,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_PLAN_AHEAD")) e->plan_ahead = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_SLAB_ALGEBRA")) e->slab_algebra = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_PANEL_SESSIONS")) e->panel_sessions = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PANELS")) e->complex_panels = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_UNFUSED")) e->block_unfused = std::atoi(v);
     return e;
   }();
@@ -4245,7 +4246,7 @@ __global__ void k_pack_reduce4(const double* __restrict__ tot, const int* __rest
 }
 __global__ void k_slab_runs_addr(const int32_t* __restrict__ first, const int32_t* __restrict__ last,
                                  const unsigned long long* __restrict__ addr, unsigned long long fallback,
-                                 SlabRun* __restrict__ runs, int n) {
+                                 SlabRun* __restrict__ runs, int n, int elem_bytes) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n + 4) return;
   const bool any = k < n && last[k] >= first[k];
@@ -4253,10 +4254,10 @@ __global__ void k_slab_runs_addr(const int32_t* __restrict__ first, const int32_
   const unsigned long long a = any ? addr[k] : fallback;
   r.addr_lo = (uint32_t)a;
   r.addr_hi = (uint32_t)(a >> 32) & 0xffffu;
-  r.nbytes = any ? (uint32_t)(last[k] - first[k] + 1) * 8u : 0u;
+  r.nbytes = any ? (uint32_t)(last[k] - first[k] + 1) * (uint32_t)elem_bytes : 0u;
   r.flags = kBufferFlags;
   r.first = any ? first[k] : (1 << 30);
-  r.first8 = any ? first[k] * 8 : 0;
+  r.first8 = any ? first[k] * elem_bytes : 0;
   r.span62 = any ? (last[k] - first[k] + 1) + 62 : 0;
   r.pad = 0;
   runs[k] = r;
@@ -4324,15 +4325,17 @@ __global__ __launch_bounds__(256) void k_slab_order_steps(const int32_t* __restr
 namespace {
 // the plan of a step X * X from the column extents of X (device arrays of n columns; a panel step: the extents of the
 // columns ka .. of the distributed iterate on the A side); sizes are left on the device in stats[16..18] / blk_toff[snb]
+// (J: output columns per block -- SLAB_CJ for the complex tile kernel)
+template <int J = SLAB_J>
 void launch_slab_plan(SlabPlan& P, int n, const int32_t* first, const int32_t* last, const int32_t* afirst, const int32_t* alast,
                       int align, unsigned long long* stats, DevBuf<int64_t>* tile_offsets = nullptr) {
-  const int snb = cdiv(n, SLAB_J);
+  const int snb = cdiv(n, J);
   P.blk_lo.alloc(snb); P.blk_w.alloc(snb); P.blk_kmin.alloc(snb); P.blk_kn.alloc(snb);
   P.blk_toff.alloc((size_t)snb + 1);
   P.align = align;
   DevBuf<int64_t> bsz(snb), tsz(snb);
   if (tile_offsets) tile_offsets->alloc((size_t)snb + 1);
-  hipLaunchKernelGGL((k_slab_plan<SLAB_J>), dim3(cdiv((int64_t)snb * WAVE, 256)), dim3(256), 0, stream(), n, first, last, afirst,
+  hipLaunchKernelGGL((k_slab_plan<J>), dim3(cdiv((int64_t)snb * WAVE, 256)), dim3(256), 0, stream(), n, first, last, afirst,
                      alast, P.blk_lo.p, P.blk_w.p, P.blk_kmin.p, P.blk_kn.p, bsz.p, tsz.p, snb, align);
   if (options().plan_fused != 0) {
     // maxima and both prefix sums in ONE launch (k_slab_offsets) instead of four to seven
@@ -4429,7 +4432,7 @@ bool slab_step(DevMat& X, SlabFusion& fu, double threshold, bool dense_rule, con
   DevBuf<char> runs(((size_t)nka + 4) * sizeof(SlabRun));
   if (halo)
     hipLaunchKernelGGL(k_slab_runs_addr, dim3(cdiv(nka + 4, 256)), dim3(256), 0, stream(), halo->first, halo->last, halo->addr,
-                       (unsigned long long)reinterpret_cast<uintptr_t>(in.val.p), reinterpret_cast<SlabRun*>(runs.p), nka);
+                       (unsigned long long)reinterpret_cast<uintptr_t>(in.val.p), reinterpret_cast<SlabRun*>(runs.p), nka, 8);
   else
     hipLaunchKernelGGL(k_slab_runs, dim3(cdiv(n + 4, 256)), dim3(256), 0, stream(), in.first.p, in.last.p, in.off.p,
                        reinterpret_cast<const char*>(in.val.p), 8, reinterpret_cast<SlabRun*>(runs.p), n);
@@ -5503,26 +5506,29 @@ __global__ void k_slab_request(const int32_t* __restrict__ first, const int32_t*
 }
 // (al > 1: the runs travel in the aligned zero-padded slots the MFMA tile kernel reads several rows per lane from --
 // span = slot size, SlabForm::row_pad)
+// (ew: doubles per row -- 2 for complex runs of (re, im) pairs: the spans, and so the exchange's counts and offsets, are in doubles)
 __global__ void k_slab_extents(const int32_t* __restrict__ first, const int32_t* __restrict__ last, int n,
-                               long long* __restrict__ ext, int32_t* __restrict__ span, int al) {
+                               long long* __restrict__ ext, int32_t* __restrict__ span, int al, int ew) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const int f = first[j], l = last[j];
   ext[j] = (long long)(unsigned)f | ((long long)l << 32);
-  span[j] = l >= f ? (l / al + 1) * al - f / al * al : 0;
+  span[j] = l >= f ? ((l / al + 1) * al - f / al * al) * ew : 0;
 }
+// (T = double2: complex runs, 16-byte elements; off in elements, pre and dst in doubles)
+template <typename T>
 __global__ __launch_bounds__(256) void k_slab_pack_runs(const int32_t* __restrict__ first, const int32_t* __restrict__ last,
-                                                        const int64_t* __restrict__ off, const double* __restrict__ val,
+                                                        const int64_t* __restrict__ off, const T* __restrict__ val,
                                                         const int64_t* __restrict__ pre, int ja, int jb, double* __restrict__ dst, int al) {
   const int j = ja + (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= jb) return;
   const int lane = lane_id();
   const int f = first[j], l = last[j];
   if (l < f) return;
-  const double* __restrict__ src = val + off[j];
-  double* __restrict__ d = dst + (pre[j] - pre[ja]);
+  const T* __restrict__ src = val + off[j];
+  T* __restrict__ d = reinterpret_cast<T*>(dst + (pre[j] - pre[ja]));   // (pre: prefix of the spans in doubles)
   const int a0 = f / al * al, a1 = (l / al + 1) * al;   // the slot: zeros around the run
-  for (int r = a0 + lane; r < a1; r += WAVE) d[r - a0] = (r >= f && r <= l) ? src[r - f] : 0.0;
+  for (int r = a0 + lane; r < a1; r += WAVE) d[r - a0] = (r >= f && r <= l) ? src[r - f] : Sc<T>::zero();
 }
 // extents and run addresses of the columns ka .. kb a rank needs: its own from its buffers, the others from the
 // receive buffer (source s: its segment [ra_s, rb_s) packed back to back at recv + zoff[s])
@@ -5538,7 +5544,8 @@ __global__ void k_slab_halo_layout(const long long* __restrict__ ext_all, const 
                                    const int64_t* __restrict__ own_off, const double* __restrict__ own_val,
                                    int32_t* __restrict__ first, int32_t* __restrict__ last,
                                    unsigned long long* __restrict__ addr, const long long* __restrict__ cnt_all,
-                                   int32_t* __restrict__ count, int al) {
+                                   int32_t* __restrict__ count, int al, int ew) {
+  // (ew: doubles per row; own_off counts elements, pre_all and zoff count doubles)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= kb - ka) return;
   const int k = ka + i;
@@ -5550,11 +5557,11 @@ __global__ void k_slab_halo_layout(const long long* __restrict__ ext_all, const 
   first[i] = (int)(unsigned)(e & 0xffffffffll);
   last[i] = (int)(e >> 32);
   const double* p;
-  if (s == me) p = own_val + own_off[k - c0];
+  if (s == me) p = own_val + own_off[k - c0] * ew;
   else {
     const int ras = ra_p ? ra_p[s] : segs.ra[s];
     const int64_t zs = zoff_p ? zoff_p[s] : segs.zoff[s];
-    p = recv + zs + (pre_all[(size_t)s * pitch + (k - c0)] - pre_all[(size_t)s * pitch + (ras - c0)]) + (first[i] - first[i] / al * al);
+    p = recv + zs + (pre_all[(size_t)s * pitch + (k - c0)] - pre_all[(size_t)s * pitch + (ras - c0)]) + (first[i] - first[i] / al * al) * ew;
   }
   addr[i] = (unsigned long long)reinterpret_cast<uintptr_t>(p);
   if (count) count[i] = (int32_t)cnt_all[(size_t)s * pitch + (k - c0)];
@@ -5586,6 +5593,10 @@ void slab_plan_panel_async(const DevMat& X, const int64_t* d_ext_all, int pitch,
   glast.alloc((size_t)dim);
   hipLaunchKernelGGL(k_unpack_extents, dim3(cdiv(dim, 256)), dim3(256), 0, stream(), reinterpret_cast<const long long*>(d_ext_all),
                      pitch, dim, P, gfirst.p, glast.p);
+  if (X.cplx) {   // (the complex tile kernel: SLAB_CJ columns per block, windows aligned to its 16-row tiles)
+    launch_slab_plan<SLAB_CJ>(plan, X.cols, X.slab->first.p, X.slab->last.p, gfirst.p, glast.p, 16, stats24);
+    return;
+  }
   const bool tile = options().spgemm_fma == 1;
   launch_slab_plan(plan, X.cols, X.slab->first.p, X.slab->last.p, gfirst.p, glast.p, tile ? 16 * tile_rows() : 0, stats24);
 }
@@ -5645,15 +5656,19 @@ void slab_extents_async(const DevMat& X, int64_t* d_ext, int64_t* d_pre) {
   const int n = X.cols;
   DevBuf<int32_t> span((size_t)n);
   hipLaunchKernelGGL(k_slab_extents, dim3(cdiv(n, 256)), dim3(256), 0, stream(), X.slab->first.p, X.slab->last.p, n,
-                     reinterpret_cast<long long*>(d_ext), span.p, std::max(1, X.slab->row_pad));
+                     reinterpret_cast<long long*>(d_ext), span.p, std::max(1, X.slab->row_pad), X.cplx ? 2 : 1);
   scan_async<int32_t>(span.p, d_pre, (int64_t)n);
 }
 
 void slab_pack_runs_async(const DevMat& X, const int64_t* d_pre, int32_t ja, int32_t jb, double* dst) {
   if (jb <= ja) return;
   const SlabForm& f = *X.slab;
-  hipLaunchKernelGGL(k_slab_pack_runs, dim3(cdiv((int64_t)(jb - ja) * WAVE, 256)), dim3(256), 0, stream(), f.first.p, f.last.p,
-                     f.off.p, f.val.p, d_pre, ja, jb, dst, std::max(1, f.row_pad));
+  if (X.cplx)
+    hipLaunchKernelGGL(k_slab_pack_runs<double2>, dim3(cdiv((int64_t)(jb - ja) * WAVE, 256)), dim3(256), 0, stream(), f.first.p, f.last.p,
+                       f.off.p, reinterpret_cast<const double2*>(f.val.p), d_pre, ja, jb, dst, std::max(1, f.row_pad));
+  else
+    hipLaunchKernelGGL(k_slab_pack_runs<double>, dim3(cdiv((int64_t)(jb - ja) * WAVE, 256)), dim3(256), 0, stream(), f.first.p, f.last.p,
+                       f.off.p, f.val.p, d_pre, ja, jb, dst, std::max(1, f.row_pad));
 }
 
 void slab_halo_layout_async(const int64_t* d_ext_all, const int64_t* d_pre_all, int pitch, int32_t dim, int P, int me,
@@ -5671,7 +5686,7 @@ void slab_halo_layout_async(const int64_t* d_ext_all, const int64_t* d_pre_all, 
   hipLaunchKernelGGL(k_slab_halo_layout, dim3(cdiv(kb - ka, 256)), dim3(256), 0, stream(),
                      reinterpret_cast<const long long*>(d_ext_all), reinterpret_cast<const long long*>(d_pre_all), pitch, dim, P, me,
                      ka, kb, d_ra, d_zoff, segs, d_recv, X.slab->off.p, X.slab->val.p, d_first, d_last, d_addr,
-                     reinterpret_cast<const long long*>(d_cnt_all), d_count, std::max(1, X.slab->row_pad));
+                     reinterpret_cast<const long long*>(d_cnt_all), d_count, std::max(1, X.slab->row_pad), X.cplx ? 2 : 1);
 }
 
 void slab_counts_async(const DevMat& X, int64_t* d_cnt64) {
@@ -6679,7 +6694,7 @@ bool slab_multiply(const DevMat& A, const DevMat& B, DevMat& C, double alpha, do
   DevBuf<char> runs(((size_t)nka + 4) * sizeof(SlabRun));
   if (left)
     hipLaunchKernelGGL(k_slab_runs_addr, dim3(cdiv(nka + 4, 256)), dim3(256), 0, stream(), left->first, left->last, left->addr,
-                       (unsigned long long)reinterpret_cast<uintptr_t>(fa.val.p), reinterpret_cast<SlabRun*>(runs.p), nka);
+                       (unsigned long long)reinterpret_cast<uintptr_t>(fa.val.p), reinterpret_cast<SlabRun*>(runs.p), nka, 8);
   else
     hipLaunchKernelGGL(k_slab_runs, dim3(cdiv(A.cols + 4, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fa.off.p,
                        reinterpret_cast<const char*>(fa.val.p), 8, reinterpret_cast<SlabRun*>(runs.p), A.cols);
@@ -6768,11 +6783,11 @@ __global__ __launch_bounds__(256) void k_count_zero_values_c(Csc A, unsigned lon
 }
 }  // namespace
 bool sa_operand_c(const DevMat& M) {
-  return M.expanded() && M.cplx && !M.slab->labelled() && !M.slab->origin && M.rows == M.cols && M.slab->row_pad % 16 == 0;
+  return M.expanded() && M.cplx && !M.slab->labelled() && !M.slab->origin && (M.rows == M.cols || g_panels_ok) && M.slab->row_pad % 16 == 0;
 }
 bool slab_enter_c(DevMat& M) {
   if (M.expanded()) return sa_operand_c(M);
-  if (!M.cplx || M.blocked() || M.loose() || M.rows != M.cols || M.nnz == 0 || M.slab_hint < 0 || options().spgemm_fma != 1 ||
+  if (!M.cplx || M.blocked() || M.loose() || (M.rows != M.cols && !g_panels_ok) || M.nnz == 0 || M.slab_hint < 0 || options().spgemm_fma != 1 ||
       options().complex_tile == 0)
     return false;
   const int n = M.cols, al = 16;
@@ -6816,10 +6831,24 @@ bool slab_enter_c(DevMat& M) {
   return true;
 }
 
+// Every reason slab_multiply_c has to decline a PANEL product once its plan is known -- the one predicate, used by
+// slab_multiply_c itself and by psmatrix.cpp panel_slab_multiply before the ranks agree on the product's path (as
+// slab_multiply_takes_panel: a rank that says yes there cannot say no later)
+bool slab_multiply_c_takes_panel(const DevMat& A, const DevMat& B, int left_row_pad, int32_t ka, int32_t kb, const SlabPlan* plan) {
+  if (options().spgemm_fma != 1 || options().complex_tile == 0 || kb <= ka) return false;
+  if (!sa_operand_c(A) || !sa_operand_c(B) || options().spgemm_variant >= 0 || options().spgemm_force_bin > 0) return false;
+  if (left_row_pad % 16 != 0) return false;
+  if (!plan || plan->align != 16 || (int64_t)plan->blk_lo.n != cdiv(B.cols, SLAB_CJ)) return false;
+  return plan->max_w > 0 && plan->max_w <= 16384 && spgemm_tile_c_fits(plan->max_kn, plan->max_w);
+}
+
 // C = alpha A B with the threshold rule of the SpGEMM, complex operands and result in slab form (the complex MFMA tile kernel:
-// the tolerance mode of DESIGN.md section 4); false: not taken, C untouched
-bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule) {
-  if (!sa_operand_c(A) || !sa_operand_c(B) || A.cols != B.rows || options().spgemm_fma != 1 || options().complex_tile == 0 ||
+// the tolerance mode of DESIGN.md section 4); false: not taken, C untouched.  left (a panel product, psmatrix.cpp): A and B are
+// column panels, the columns of the left operand named by the rows of B's panel are described by `left` (global column
+// numbers, runs in this rank's buffer or in the receive buffer), the plan comes with it
+bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule, const SlabHalo* left) {
+  if (left && !slab_multiply_c_takes_panel(A, B, left->row_pad, left->ka, left->kb, left->plan)) return false;
+  if (!sa_operand_c(A) || !sa_operand_c(B) || (!left && A.cols != B.rows) || options().spgemm_fma != 1 || options().complex_tile == 0 ||
       options().spgemm_variant >= 0 || options().spgemm_force_bin > 0) {
     if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM")) std::fprintf(stderr, "[slab_multiply_c] refused: operands / options\n");
     return false;
@@ -6829,44 +6858,57 @@ bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, 
   const bool timing = options().time_kernels != 0;
   EventTimer t_all(timing), t_num(timing);
   t_all.start();
-  DevBuf<int32_t> blk_lo(snb), blk_w(snb), blk_kmin(snb), blk_kn(snb);
-  DevBuf<int64_t> bsz(snb), tsz(snb), blk_toff((size_t)snb + 1);
-  DevBuf<unsigned long long> stats(24);
-  stats.zero();
-  hipLaunchKernelGGL((k_slab_plan<SLAB_CJ>), dim3(cdiv((int64_t)snb * WAVE, 256)), dim3(256), 0, stream(), n, fb.first.p, fb.last.p, fa.first.p,
-                     fa.last.p, blk_lo.p, blk_w.p, blk_kmin.p, blk_kn.p, bsz.p, tsz.p, snb, 16);
-  hipLaunchKernelGGL(k_slab_reduce, dim3(64), dim3(256), 0, stream(), blk_w.p, blk_kn.p, snb, (const int32_t*)nullptr, 0, stats.p);
-  scan_async<int64_t>(tsz.p, blk_toff.p, (int64_t)snb);
-  int64_t total = 0;
-  unsigned long long hs[3] = {0, 0, 0};
-  {
-    ScalarFetch f;
-    f.add(blk_toff.p + snb, 1, &total);
-    f.add(stats.p + 16, 3, hs);
-    f.run();
+  SlabPlan own;
+  SlabPlan& P = left ? *left->plan : own;
+  if (!left) {
+    own.blk_lo.alloc(snb); own.blk_w.alloc(snb); own.blk_kmin.alloc(snb); own.blk_kn.alloc(snb); own.blk_toff.alloc((size_t)snb + 1);
+    DevBuf<int64_t> bsz(snb), tsz(snb);
+    DevBuf<unsigned long long> stats(24);
+    stats.zero();
+    hipLaunchKernelGGL((k_slab_plan<SLAB_CJ>), dim3(cdiv((int64_t)snb * WAVE, 256)), dim3(256), 0, stream(), n, fb.first.p, fb.last.p, fa.first.p,
+                       fa.last.p, own.blk_lo.p, own.blk_w.p, own.blk_kmin.p, own.blk_kn.p, bsz.p, tsz.p, snb, 16);
+    hipLaunchKernelGGL(k_slab_reduce, dim3(64), dim3(256), 0, stream(), own.blk_w.p, own.blk_kn.p, snb, (const int32_t*)nullptr, 0, stats.p);
+    scan_async<int64_t>(tsz.p, own.blk_toff.p, (int64_t)snb);
+    unsigned long long hs[3] = {0, 0, 0};
+    {
+      ScalarFetch f;
+      f.add(own.blk_toff.p + snb, 1, &own.total);
+      f.add(stats.p + 16, 3, hs);
+      f.run();
+    }
+    if (hs[0] > 16384) hs[0] = 16385;   // (refused below)
+    own.max_w = (int)hs[0];
+    own.max_kn = (int)hs[1];
+    own.align = 16;
   }
-  const int max_w = (int)hs[0], max_kn = (int)hs[1];
-  if (max_w <= 0 || hs[0] > 16384 || !spgemm_tile_c_fits(max_kn, max_w)) {
-    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM")) std::fprintf(stderr, "[slab_multiply_c] refused: window %llu rows, k range %llu\n", hs[0], hs[1]);
+  const int64_t total = P.total;
+  const int max_w = P.max_w, max_kn = P.max_kn;
+  if (max_w <= 0 || max_w > 16384 || !spgemm_tile_c_fits(max_kn, max_w)) {
+    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM")) std::fprintf(stderr, "[slab_multiply_c] refused: window %d rows, k range %d\n", max_w, max_kn);
     if (timing) {
       event_pool().push_back(t_all.a); event_pool().push_back(t_all.b);
       event_pool().push_back(t_num.a); event_pool().push_back(t_num.b);
     }
     return false;
   }
-  DevBuf<char> runs(((size_t)A.cols + 4) * sizeof(SlabRun));
-  hipLaunchKernelGGL(k_slab_runs, dim3(cdiv(A.cols + 4, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fa.off.p,
-                     reinterpret_cast<const char*>(fa.val.p), 16, reinterpret_cast<SlabRun*>(runs.p), A.cols);
+  const int ka = left ? left->ka : 0, nka = left ? left->kb - left->ka : A.cols;
+  DevBuf<char> runs(((size_t)nka + 4) * sizeof(SlabRun));
+  if (left)
+    hipLaunchKernelGGL(k_slab_runs_addr, dim3(cdiv(nka + 4, 256)), dim3(256), 0, stream(), left->first, left->last, left->addr,
+                       (unsigned long long)reinterpret_cast<uintptr_t>(fa.val.p), reinterpret_cast<SlabRun*>(runs.p), nka, 16);
+  else
+    hipLaunchKernelGGL(k_slab_runs, dim3(cdiv(A.cols + 4, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fa.off.p,
+                       reinterpret_cast<const char*>(fa.val.p), 16, reinterpret_cast<SlabRun*>(runs.p), A.cols);
   std::unique_ptr<SlabForm> fo(new SlabForm());
   fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
   fo->count.zero();
   fo->val.alloc(((size_t)total + kIndexSlack) * 2);
   t_num.start();
   TileLaunch tl;
-  tl.runs = reinterpret_cast<const SlabRun*>(runs.p);
+  tl.runs = reinterpret_cast<const SlabRun*>(runs.p) - ka;   // (indexed by global column numbers)
   tl.bblk = fb.val.p; tl.blk_boff = nullptr;
   tl.brun_first = fb.first.p; tl.brun_last = fb.last.p; tl.brun_off = fb.off.p; tl.brun_val = fb.val.p; tl.bbytes = fb.val.n * sizeof(double); tl.brun_pad = fb.row_pad;
-  tl.blk_kmin = blk_kmin.p; tl.blk_kn = blk_kn.p; tl.blk_lo = blk_lo.p; tl.blk_w = blk_w.p; tl.blk_toff = blk_toff.p;
+  tl.blk_kmin = P.blk_kmin.p; tl.blk_kn = P.blk_kn.p; tl.blk_lo = P.blk_lo.p; tl.blk_w = P.blk_w.p; tl.blk_toff = P.blk_toff.p;
   tl.out_val = fo->val.p; tl.count = fo->count.p; tl.ofirst = fo->first.p; tl.olast = fo->last.p; tl.ooff = fo->off.p;
   tl.alpha = alpha; tl.threshold = threshold; tl.dense_rule = dense_rule ? 1 : 0; tl.ncols = n; tl.nblocks = snb;
   tl.max_kn = max_kn; tl.max_w = max_w; tl.epi = 0;
@@ -6878,6 +6920,7 @@ bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, 
   {
     ScalarFetch f;
     f.add(tot.p, 1, &nnz);
+    if (left && left->on_fetch) left->on_fetch(f);
     f.run();
   }
   t_all.stop();

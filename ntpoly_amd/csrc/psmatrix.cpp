@@ -255,7 +255,10 @@ SlabSession::SlabSession(bool eligible, bool api, bool complex_ok) {
   opened = eligible && options().slab_algebra != 0 && (options().spgemm_fma == 1 || options().spgemm_fma == 0) && options().spgemm_variant < 0 &&
            options().spgemm_force_bin <= 0 && (!multi || (options().panel_sessions != 0 && options().spgemm_fma == 1 && !api));
   if (opened && multi && g_slab_depth == 0) slab_allow_panels(true);
-  if (opened && !multi && complex_ok && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0 && !g_complex_session) {
+  // (complex loops across ranks: complex column panels in slab form, products on the complex tile kernel -- option complex_panels,
+  // on top of what opened the panel session above)
+  if (opened && complex_ok && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0 && !g_complex_session &&
+      (!multi || options().complex_panels != 0)) {
     g_complex_session = true;
     set_complex = true;
   }
@@ -566,8 +569,12 @@ bool panel_slab_multiply(const PSMatrix& A, const PSMatrix& B, DevMat& AB, doubl
   const int P = c.nranks, me = c.rank;
   const int32_t dim = A.dim;
   const long long syncs_before = host_sync_count();
-  const bool mine_ok = slab_on() && A.loc.nnz > 0 && B.loc.nnz > 0 && A.c0 == B.c0 && A.c1 == B.c1 && slab_enter(mut(A)) &&
-                       (&A == &B || slab_enter(mut(B))) && A.loc.slab->row_pad % 16 == 0 && A.loc.slab->row_pad < 4096;
+  // (complex operands, a session that takes them: runs of (re, im) pairs -- twice the doubles per row in the exchange, a plan of
+  // SLAB_CJ columns per block, the complex tile kernel)
+  const bool cplx = A.cplx;
+  auto enter = [cplx](const PSMatrix& M) { return cplx ? slab_enter_c(mut(M)) : slab_enter(mut(M)); };
+  const bool mine_ok = slab_on() && A.loc.nnz > 0 && B.loc.nnz > 0 && A.c0 == B.c0 && A.c1 == B.c1 && enter(A) &&
+                       (&A == &B || enter(B)) && A.loc.slab->row_pad % 16 == 0 && A.loc.slab->row_pad < 4096;
   int wcols = 0;
   const int pitch = panel_pitch(dim, P, false, &wcols);
   DevBuf<int64_t> d_all((size_t)P * pitch), d_req((size_t)4 * P), d_bound((size_t)2 * P), d_cnt((size_t)P * P);
@@ -594,7 +601,7 @@ bool panel_slab_multiply(const PSMatrix& A, const PSMatrix& B, DevMat& AB, doubl
   DevBuf<int32_t> gfirst, glast;
   DevBuf<int64_t> plan_stats(24);
   unsigned long long plan_hs[2] = {0, 0};
-  const int snb = (B.loc.cols + 15) / 16;
+  const int snb = cplx ? (B.loc.cols + 7) / 8 : (B.loc.cols + 15) / 16;   // (blocks of SLAB_J / SLAB_CJ columns)
   if (mine_ok) {
     plan_stats.zero();
     slab_plan_panel_async(B.loc, d_ext_all, pitch, dim, P, plan, gfirst, glast, reinterpret_cast<unsigned long long*>(plan_stats.p));
@@ -662,7 +669,9 @@ bool panel_slab_multiply(const PSMatrix& A, const PSMatrix& B, DevMat& AB, doubl
   // (plan.max_w / max_kn are back: the SAME predicate slab_multiply applies -- a rank that agrees here cannot decline later)
   plan.max_w = (int)plan_hs[0];
   plan.max_kn = (int)plan_hs[1];
-  bool ok = mine_ok && kmax >= kmin && slab_multiply_takes_panel(A.loc, B.loc, row_pad, kmin, kmax + 1, &plan);
+  bool ok = mine_ok && kmax >= kmin &&
+            (cplx ? slab_multiply_c_takes_panel(A.loc, B.loc, row_pad, kmin, kmax + 1, &plan)
+                  : slab_multiply_takes_panel(A.loc, B.loc, row_pad, kmin, kmax + 1, &plan));
   DevBuf<double> d_declined(4);
   double declined[4] = {ok ? 0.0 : 1.0, 0.0, 0.0, 0.0};
   d_declined.upload(declined, 4);
@@ -694,7 +703,8 @@ bool panel_slab_multiply(const PSMatrix& A, const PSMatrix& B, DevMat& AB, doubl
     const double denom = (double)dim * (double)dim;
     const bool dense_rule = denom > 0 && std::min((double)nnz_a / denom, (double)nnz_b / denom) > 0.1;
     // (the buffers above are released on return: the allocator is stream ordered, and slab_multiply ends with a read-back)
-    if (!slab_multiply(A.loc, B.loc, AB, alpha, threshold, dense_rule, &halo))
+    if (!(cplx ? slab_multiply_c(A.loc, B.loc, AB, alpha, threshold, dense_rule, &halo)
+               : slab_multiply(A.loc, B.loc, AB, alpha, threshold, dense_rule, &halo)))
       NTP_FATAL("internal: a panel product was declined after its rank had agreed to it");
   }
   if (!fetched) {
@@ -842,7 +852,20 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
     return;
   }
   unblock({&A, &B});
-  if (slab_on() && g_complex_session && A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308 && A.loc.nnz > 0 && B.loc.nnz > 0) {
+  if (g_slab_depth > 0 && world().active() && g_complex_session && A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308) {
+    // (a complex session across ranks: collective, as the real panel product below -- every rank takes the same branch)
+    if (panel_slab_multiply(A, B, AB, alpha, threshold)) {
+      g_slab_counts[0] += 1;
+      C.grid = A.grid; C.dim = A.dim; C.c0 = B.c0; C.c1 = B.c1;
+      C.cplx = true;
+      C.loc = std::move(AB);
+      return;
+    }
+    g_slab_counts[3] += 1;
+    for (const PSMatrix* m : {&A, &B})
+      if (m->loc.expanded() || m->loc.loose()) pack(mut(*m));
+  } else if (slab_on() && !world().active() && g_complex_session && A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308 && A.loc.nnz > 0 &&
+             B.loc.nnz > 0) {
     // (a session that takes complex operands: the iterates stay in the complex tile kernel's operand form)
     const double denom = (double)A.dim * (double)A.dim;
     const bool dense_rule = denom > 0 && std::min((double)A.loc.nnz / denom, (double)B.loc.nnz / denom) > 0.1;
@@ -854,8 +877,7 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
       return;
     }
     slab_refused({&A, &B});
-  }
-  if (g_slab_depth > 0 && world().active() && !A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308) {
+  } else if (g_slab_depth > 0 && world().active() && !A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308) {
     // (a slab session across ranks: collective -- every rank reports whether its panels are in slab form with the halo request)
     if (panel_slab_multiply(A, B, AB, alpha, threshold)) {
       g_slab_counts[0] += 1;
@@ -1049,11 +1071,12 @@ void ps_increment_identity(const PSMatrix& Identity, PSMatrix& B, double alpha) 
 bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double beta, double* norm) {
   use_grid_comm(A.grid);
   if (blk_any({&A, &B})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
-  if (world().active() && g_slab_depth > 0 && !A.cplx && !B.cplx && A.dim == B.dim && &A != &B) {
+  if (world().active() && g_slab_depth > 0 && A.cplx == B.cplx && (!A.cplx || g_complex_session) && A.dim == B.dim && &A != &B) {
     // (a session across ranks: the decision is collective -- one reduction carries the norm and "some rank declined")
     double v = 0.0;
-    const bool ok = slab_on() && (A.loc.expanded() || B.loc.expanded()) && slab_enter(mut(A)) && slab_enter(mut(B)) &&
-                    slab_norm_axpby(A.loc, B.loc, alpha, beta, &v);
+    const bool ok = slab_on() && (A.loc.expanded() || B.loc.expanded()) &&
+                    (A.cplx ? slab_enter_c(mut(A)) && slab_enter_c(mut(B)) && slab_norm_axpby_c(A.loc, B.loc, alpha, beta, &v)
+                            : slab_enter(mut(A)) && slab_enter(mut(B)) && slab_norm_axpby(A.loc, B.loc, alpha, beta, &v));
     double pair[2] = {ok ? v : 0.0, ok ? 0.0 : 1.0};
     comm_allreduce_max(pair, 2);
     if (pair[1] != 0.0) return false;
@@ -1066,7 +1089,7 @@ bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double be
     g_slab_counts[2] += 1;
     return true;
   }
-  if (slab_on() && g_complex_session && A.cplx && B.cplx && A.dim == B.dim && &A != &B && (A.loc.expanded() || B.loc.expanded())) {
+  if (slab_on() && !world().active() && g_complex_session && A.cplx && B.cplx && A.dim == B.dim && &A != &B && (A.loc.expanded() || B.loc.expanded())) {
     if (!(slab_enter_c(mut(A)) && slab_enter_c(mut(B)) && slab_norm_axpby_c(A.loc, B.loc, alpha, beta, norm))) return false;
     g_slab_counts[2] += 1;
     return true;
@@ -1738,7 +1761,11 @@ double ps_norm(const PSMatrix& A) {
   unblock({&A});
   if (slab_on() && g_complex_session && A.cplx && A.loc.expanded()) {
     double v = 0.0;
-    if (slab_norm_c(A.loc, &v)) { g_slab_counts[2] += 1; return v; }
+    if (slab_norm_c(A.loc, &v)) {
+      g_slab_counts[2] += 1;
+      comm_allreduce_max(&v, 1);   // (columns are local: a rank that declines computes its part below, every rank reduces once)
+      return v;
+    }
   }
   if (slab_on() && A.loc.expanded()) {
     double v = 0.0;

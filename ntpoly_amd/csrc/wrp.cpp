@@ -181,6 +181,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "block_match") options().block_match = *value;
   else if (n == "block_scope") options().block_scope = *value;
   else if (n == "panel_sessions") options().panel_sessions = *value;
+  else if (n == "complex_panels") options().complex_panels = *value;
   else if (n == "label_rowoff") options().label_rowoff = *value;
   else if (n == "block_path") options().block_path = *value;
   else if (n == "tile_runs_only") options().tile_runs_only = *value;
@@ -212,6 +213,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "block_match") return options().block_match;
   if (n == "block_scope") return options().block_scope;
   if (n == "panel_sessions") return options().panel_sessions;
+  if (n == "complex_panels") return options().complex_panels;
   if (n == "fused_update") return options().fused_update;
   if (n == "loose_iterates") return options().loose_iterates;
   if (n == "complex_tile") return options().complex_tile;
