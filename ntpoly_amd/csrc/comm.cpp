@@ -33,14 +33,19 @@ Comm& base_world() {
   return *c;
 }
 namespace {
-Comm* g_current_comm = nullptr;                  // nullptr: the communicator over all processes
-std::vector<Comm*>& split_comms() {              // sub-communicators made by comm_split (kept until comm_finalize)
+Comm* g_scope_comm = nullptr;                    // the innermost CommScope's communicator (nullptr: all processes)
+std::vector<Comm*>& split_comms() {              // sub-communicators made by comm_split (never freed: comm_finalize retires them)
   static std::vector<Comm*>* v = new std::vector<Comm*>();
   return *v;
 }
 }  // namespace
-Comm& world() { return g_current_comm ? *g_current_comm : base_world(); }
-void use_comm(Comm* c) { g_current_comm = (c == &base_world()) ? nullptr : c; }
+Comm& world() { return g_scope_comm ? *g_scope_comm : base_world(); }
+CommScope::CommScope(const ProcessGrid* g) : prev(g_scope_comm) {
+  Comm* c = g ? g->comm : nullptr;
+  if (c && c->retired) NTP_FATAL("matrix on a split grid used after the communicator was finalised");
+  g_scope_comm = c;
+}
+CommScope::~CommScope() { g_scope_comm = prev; }
 ExchangeStats& exchange_stats() {
   static ExchangeStats* e = new ExchangeStats();
   return *e;
@@ -469,15 +474,17 @@ bool comm_bind_mpi(int fcomm) {
 }
 
 void comm_finalize() {
-  use_comm(nullptr);
-  for (Comm* sc : split_comms()) {   // (sub-communicators first: they lean on the transport of all processes)
+  // sub-communicators first: they lean on the transport of all processes.  Their Comm objects are retired, not freed: the
+  // grids split_process_grid made, and copies of them, keep pointing at them, and a CommScope on one is refused.  One small
+  // struct per split stays allocated for the life of the process.
+  for (Comm* sc : split_comms()) {
     if (sc->tr) {
       sync_stream();
       delete sc->tr;
+      sc->tr = nullptr;
     }
-    delete sc;
+    sc->retired = true;
   }
-  split_comms().clear();
   Comm& c = base_world();
   if (c.tr) {
     sync_stream();
@@ -817,7 +824,7 @@ DevMat gather_needed(const PSMatrix& m, const DevMat& Bloc, int64_t nnz_global[2
 }
 
 DevMat ps_gather_full(const PSMatrix& m) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   if (!world().active()) return m.loc.clone();
   const int P = world().nranks;
   std::vector<int32_t> widths((size_t)P);

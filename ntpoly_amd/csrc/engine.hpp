@@ -39,17 +39,17 @@ struct Comm {
   Transport* tr = nullptr;
   bool force = false;    // tests: run the multi-rank code paths even with a single rank
   bool user_init = false;  // ntpoly_amd_init_comm was called (also with one rank): the caller's MPI communicator is not consulted
+  bool retired = false;    // a sub-communicator whose transport comm_finalize tore down (the object itself stays)
   bool active() const { return tr != nullptr && (nranks > 1 || force); }
 };
-// The communicator the engine's collectives run on.  Normally the one over all processes; while matrices hosted on a
-// SUB-grid are worked on (SplitProcessGrid / CommSplitMatrix, ProcessGridModule.F90:430-515) that grid's communicator: the C
-// ABI selects it from the grid of the matrices it is handed (use_grid_comm), so the multiply, the reductions and the solvers
-// of a half of the processes stay inside that half.
+// The communicator the engine's collectives run on: the one of the innermost open CommScope, or the one over all processes
+// when no scope is open.  Every ps_* and solver entry opens a scope on the grid of the matrix it works on, so on a SUB-grid
+// (SplitProcessGrid / CommSplitMatrix, ProcessGridModule.F90:430-515) the multiply, the reductions and the solvers stay inside
+// that half, and nothing a call selected outlives it.
 Comm& world();
 Comm& base_world();                 // the communicator over all processes, whatever is selected
-void use_comm(Comm* c);             // nullptr: the communicator over all processes
 // MPI_Comm_split on the current communicator (collective): the ranks of one colour, ordered by (key, rank); the result is
-// owned by the engine (kept until comm_finalize)
+// owned by the engine (retired, never freed, by comm_finalize)
 Comm* comm_split(int color, int key);
 // halo exchanges of the distributed multiply since the start, and the host synchronisations they needed
 struct ExchangeStats { long long exchanges = 0, host_syncs = 0; };
@@ -75,10 +75,18 @@ struct ProcessGrid {
   int num_rows = 1, num_cols = 1, num_slices = 1;
   int my_row = 0, my_col = 0, my_slice = 0;
   int global_rank = 0, total = 1;
-  Comm* comm = nullptr;   // the communicator the grid lives on (nullptr: all processes); set by split_process_grid
+  Comm* comm = nullptr;   // the communicator the grid lives on (nullptr: all processes); set by construct_grid
   bool is_root() const { return global_rank == 0; }
 };
-void use_grid_comm(const ProcessGrid* g);   // selects the communicator of g (collectives that follow run on it)
+// Selects the communicator of g (all processes for a null grid or a grid on all of them) until the end of the enclosing
+// block, then the one selected before.  A grid whose communicator comm_finalize retired is fatal.
+struct CommScope {
+  explicit CommScope(const ProcessGrid* g);
+  ~CommScope();
+  CommScope(const CommScope&) = delete;
+  CommScope& operator=(const CommScope&) = delete;
+  Comm* prev;
+};
 // SplitProcessGrid (ProcessGridModule.F90:430-515): two grids of about half the size, preferably along the slices, else along
 // the longer of rows / columns; collective over the old grid.  The new grid (owned by the engine) lives on a sub-communicator
 // made of the processes of this process's colour in the order of their old ranks.
@@ -89,8 +97,9 @@ struct PSMatrix;
 void ps_comm_split(const PSMatrix& m, PSMatrix& split, int* my_color, bool* split_slice);
 ProcessGrid& global_grid();
 bool global_grid_constructed();
-void construct_grid(ProcessGrid& g, int rows, int cols, int slices);
-void construct_grid_default(ProcessGrid& g, int slices /* <=0: choose */);
+// a grid over the ranks of c (base_world(): all processes)
+void construct_grid(ProcessGrid& g, int rows, int cols, int slices, Comm& c);
+void construct_grid_default(ProcessGrid& g, int slices /* <=0: choose */, Comm& c);
 void write_grid_info(const ProcessGrid& g);
 
 // ------------------------------------------------------------------ distributed matrix

@@ -67,6 +67,7 @@ void read_matrix_market_file(const std::string& path, HostTriplets& t, int* rows
 }
 
 void ps_read_matrix_market(PSMatrix& m, const std::string& path, const ProcessGrid* g) {
+  CommScope cs(g);
   int rows = 0, cols = 0;
   HostTriplets t;
   // every rank parses the header (cheap), only the root reads and contributes the entries
@@ -76,7 +77,7 @@ void ps_read_matrix_market(PSMatrix& m, const std::string& path, const ProcessGr
 }
 
 void ps_write_matrix_market(const PSMatrix& m, const std::string& path) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   const int64_t total = ps_size(m);
   HostTriplets t;
   if (world().active()) {
@@ -103,7 +104,7 @@ void ps_write_matrix_market(const PSMatrix& m, const std::string& path) {
 // header int32[3] {rows, cols, is_complex}, int64 total, then {int32 col, int32 row, f64 val
 // (| f64 re, f64 im)} in native endianness (WriteMatrixToBinary.f90:43-65)
 void ps_write_binary(const PSMatrix& m, const std::string& path) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   const int64_t total = ps_size(m);
   HostTriplets t;
   if (world().active()) {
@@ -130,6 +131,7 @@ void ps_write_binary(const PSMatrix& m, const std::string& path) {
 }
 
 void ps_read_binary(PSMatrix& m, const std::string& path, const ProcessGrid* g) {
+  CommScope cs(g);
   FILE* f = std::fopen(path.c_str(), "rb");
   if (!f) NTP_FATAL("cannot open binary matrix file " + path);
   int32_t header[3];

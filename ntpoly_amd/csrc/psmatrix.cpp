@@ -42,8 +42,7 @@ bool g_grid_built = false;
 ProcessGrid& global_grid() { return g_grid; }
 bool global_grid_constructed() { return g_grid_built; }
 
-void construct_grid(ProcessGrid& g, int rows, int cols, int slices) {
-  const Comm& c = world();
+void construct_grid(ProcessGrid& g, int rows, int cols, int slices, Comm& c) {
   // grid sanity check (ProcessGridModule.F90:162-176): fatal if the shape does not match
   if (rows * cols * slices != c.nranks && !options().virtual_grid)
     NTP_FATAL("process grid " + std::to_string(rows) + "x" + std::to_string(cols) + "x" + std::to_string(slices) +
@@ -53,6 +52,7 @@ void construct_grid(ProcessGrid& g, int rows, int cols, int slices) {
   g.num_slices = slices;
   g.total = c.nranks;
   g.global_rank = c.rank;
+  g.comm = &c == &base_world() ? nullptr : &c;
   // rank -> (slice, row, column) as ProcessGridModule.F90:180-183
   const int slice_size = rows * cols;
   g.my_slice = c.rank / slice_size;
@@ -62,9 +62,9 @@ void construct_grid(ProcessGrid& g, int rows, int cols, int slices) {
   if (&g == &g_grid) g_grid_built = true;
 }
 
-void construct_grid_default(ProcessGrid& g, int slices) {
+void construct_grid_default(ProcessGrid& g, int slices, Comm& c) {
   // ComputeGridSize (ProcessGridModule.F90:576-601): most square rows x cols for the given slices
-  const int total = world().nranks;
+  const int total = c.nranks;
   if (slices <= 0) slices = 1;
   while (total % slices != 0) --slices;
   const int slice_size = total / slices;
@@ -76,14 +76,12 @@ void construct_grid_default(ProcessGrid& g, int slices) {
       break;
     }
   }
-  construct_grid(g, rows, cols, slices);
+  construct_grid(g, rows, cols, slices, c);
 }
-
-void use_grid_comm(const ProcessGrid* g) { use_comm(g ? g->comm : nullptr); }
 
 ProcessGrid* split_process_grid(const ProcessGrid& old_grid, int* my_color, bool* split_slice) {
   static std::vector<ProcessGrid*>* kept = new std::vector<ProcessGrid*>();   // (grids made here live as long as the library)
-  use_grid_comm(&old_grid);
+  CommScope cs(&old_grid);
   int rows = 1, cols = 1, slices = 1, color = 0;
   *split_slice = false;
   if (old_grid.total == 1) {
@@ -111,16 +109,13 @@ ProcessGrid* split_process_grid(const ProcessGrid& old_grid, int* my_color, bool
   Comm* nc = comm_split(color, old_grid.global_rank);
   auto* g = new ProcessGrid();
   kept->push_back(g);
-  use_comm(nc);
-  construct_grid(*g, rows, cols, slices);
-  g->comm = nc;
-  use_grid_comm(&old_grid);
+  construct_grid(*g, rows, cols, slices, *nc);
   return g;
 }
 
 void ps_comm_split(const PSMatrix& m, PSMatrix& split, int* my_color, bool* split_slice) {
   const ProcessGrid& g = *m.grid;
-  use_grid_comm(&g);
+  CommScope cs(&g);
   if (g.total == 1) {   // (distributed_includes/CommSplitMatrix.f90:11-14)
     ps_copy(m, split);
     *my_color = 0;
@@ -132,11 +127,9 @@ void ps_comm_split(const PSMatrix& m, PSMatrix& split, int* my_color, bool* spli
   // owns on its half
   DevMat full = ps_gather_full(m);
   ProcessGrid* ng = split_process_grid(g, my_color, split_slice);
-  use_grid_comm(ng);
-  ps_construct_empty(split, m.dim, ng, m.cplx);
+  ps_construct_empty(split, m.dim, ng, m.cplx);   // (the half's panel: on the half's communicator)
   split.loc = column_slice(full, split.c0, split.c1);
   sync_stream();
-  use_grid_comm(&g);
 }
 
 void write_grid_info(const ProcessGrid& g) {
@@ -178,7 +171,7 @@ void panel_exchange_layout(int32_t dim, int P, int me, const int64_t* req, const
 void ps_construct_empty(PSMatrix& m, int32_t dim, const ProcessGrid* g, bool cplx) {
   if (!g) NTP_FATAL("matrix constructed without a process grid (construct the global grid first)");
   ensure_init();
-  use_grid_comm(g);   // (the matrix lives on its grid's communicator: what follows on it runs there)
+  CommScope cs(g);   // (the matrix lives on its grid's communicator: its panel is one of that communicator's)
   m.grid = g;
   m.dim = dim;
   m.cplx = cplx;
@@ -186,8 +179,7 @@ void ps_construct_empty(PSMatrix& m, int32_t dim, const ProcessGrid* g, bool cpl
   m.loc.reset_empty(dim, m.c1 - m.c0, cplx);
 }
 
-void ps_construct_like(PSMatrix& m, const PSMatrix& ref) {
-  use_grid_comm(ref.grid); ps_construct_empty(m, ref.dim, ref.grid, ref.cplx); }
+void ps_construct_like(PSMatrix& m, const PSMatrix& ref) { ps_construct_empty(m, ref.dim, ref.grid, ref.cplx); }
 
 namespace {
 int g_slab_depth = 0;
@@ -284,7 +276,7 @@ void ps_slab_leave(PSMatrix& m) {
 }
 
 void ps_copy(const PSMatrix& a, PSMatrix& b) {
-  use_grid_comm(a.grid);
+  CommScope cs(a.grid);
   if (&a == &b) return;
   if (blk_any({&a})) {
     DevMat t;
@@ -326,12 +318,12 @@ void ps_copy(const PSMatrix& a, PSMatrix& b) {
 }
 
 void ps_fill_identity(PSMatrix& m) {
-  use_grid_comm(m.grid);  // FillMatrixIdentity (O(N) here, O(N^2/P) in the reference)
+  CommScope cs(m.grid);  // FillMatrixIdentity (O(N) here, O(N^2/P) in the reference)
   m.loc = identity(m.dim, m.c0, m.c1 - m.c0, m.cplx);
 }
 
 void ps_fill_permutation(PSMatrix& m, const std::vector<int32_t>& lookup, bool rows) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   // distributed_includes/FillMatrixPermutation.f90:1-35
   HostTriplets t;
   t.cplx = m.cplx;
@@ -350,7 +342,7 @@ void ps_fill_permutation(PSMatrix& m, const std::vector<int32_t>& lookup, bool r
 }
 
 void ps_fill_from_triplets(PSMatrix& m, const HostTriplets& t) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   // FillMatrixFromTripletList (distributed_includes/FillMatrixFromTripletList.f90:14-47): any rank
   // may hold any triplet.  Ranks exchange what they hold (setup path, host triplets travel through
   // device buffers because RCCL moves device memory) and keep their own columns.
@@ -397,12 +389,12 @@ void ps_fill_from_triplets(PSMatrix& m, const HostTriplets& t) {
 }
 
 void ps_get_triplets(const PSMatrix& m, HostTriplets& t) {
-  use_grid_comm(m.grid); to_triplets(m.loc, m.c0, t); }
+  CommScope cs(m.grid); to_triplets(m.loc, m.c0, t); }
 
 // FillMatrixDense (PSMatrixModule.F90:958-990, distributed_includes/FillMatrixDense.f90): every element of the
 // local panel is 1; dense by definition, so the O(dim * width) host triplets are what the caller asked for
 void ps_fill_dense(PSMatrix& m) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   HostTriplets t;
   t.cplx = m.cplx;
   const size_t w = m.cplx ? 2 : 1;
@@ -421,7 +413,7 @@ void ps_fill_dense(PSMatrix& m) {
 // MatrixDiagonalScale (PSMatrixAlgebraModule.F90:507-532, ScaleDiagonal.f90, sparse_includes/DiagonalScale.f90):
 // for every triplet whose column is stored here, the values of that column are multiplied by its value
 void ps_diagonal_scale(PSMatrix& m, const HostTriplets& t) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   const int32_t width = m.c1 - m.c0;
   if (width == 0) return;
   const size_t w = m.cplx ? 2 : 1;
@@ -452,7 +444,7 @@ void ps_diagonal_scale(PSMatrix& m, const HostTriplets& t) {
 // [start_row, end_row) x [start_column, end_column) (1-based) and receives its entries with absolute coordinates;
 // an entry goes to the FIRST rank whose block contains it (the EXIT in the reference's routing loop)
 void ps_get_block(const PSMatrix& m, int sr, int er, int sc, int ec, HostTriplets& out) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   const int P = world().active() ? world().nranks : 1, me = world().active() ? world().rank : 0;
   std::vector<int64_t> box((size_t)4 * P);
   const int64_t mine[4] = {sr, er, sc, ec};
@@ -481,7 +473,7 @@ void ps_get_block(const PSMatrix& m, int sr, int er, int sc, int ec, HostTriplet
 // GetMatrixSlice (PSMatrixModule.F90:1153-1225, distributed_includes/SliceMatrix.f90): inclusive bounds, result of
 // dimension max(rows, columns) of the slice on the same grid
 void ps_get_slice(const PSMatrix& m, PSMatrix& sub, int sr, int er, int sc, int ec) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   HostTriplets t, s;
   ps_get_triplets(m, t);
   s.cplx = m.cplx;
@@ -503,7 +495,7 @@ void ps_get_slice(const PSMatrix& m, PSMatrix& sub, int sr, int er, int sc, int 
 // ResizeMatrix (PSMatrixModule.F90:1704-1741, distributed_includes/ResizeMatrix.f90): entries beyond the new size
 // are dropped
 void ps_resize(PSMatrix& m, int new_size) {
-  use_grid_comm(m.grid);
+  CommScope cs(m.grid);
   HostTriplets t, s;
   ps_get_triplets(m, t);
   s.cplx = m.cplx;
@@ -522,21 +514,21 @@ void ps_resize(PSMatrix& m, int new_size) {
 }
 
 int64_t ps_size(const PSMatrix& m) {
-  use_grid_comm(m.grid);  // GetMatrixSize (PSMatrixModule.F90:1360-1389)
+  CommScope cs(m.grid);  // GetMatrixSize (PSMatrixModule.F90:1360-1389)
   int64_t n = m.loc.nnz;
   comm_allreduce_sum_i64(&n, 1);
   return n;
 }
 
 void ps_to_complex(const PSMatrix& a, PSMatrix& out) {
-  use_grid_comm(a.grid);
+  CommScope cs(a.grid);
   DevMat t = to_complex(a.loc);
   out.grid = a.grid; out.dim = a.dim; out.c0 = a.c0; out.c1 = a.c1;
   out.cplx = true;
   out.loc = std::move(t);
 }
 void ps_to_real(const PSMatrix& a, PSMatrix& out) {
-  use_grid_comm(a.grid);
+  CommScope cs(a.grid);
   DevMat t = to_real(a.loc);
   out.grid = a.grid; out.dim = a.dim; out.c0 = a.c0; out.c1 = a.c1;
   out.cplx = false;
@@ -816,7 +808,7 @@ DevMat multiply_panel(const PSMatrix& A, const PSMatrix& B, double alpha, double
 }  // namespace
 
 void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha, double beta, double threshold) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   if (A.dim != B.dim) NTP_FATAL("MatrixMultiply: dimension mismatch");
   // up-casting of mixed real/complex operands (PSMatrixAlgebraModule.F90:171-188)
   if (A.cplx != B.cplx) {
@@ -973,7 +965,7 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
 
 // IncrementMatrix_ps (PSMatrixAlgebraModule.F90:414-460)
 void ps_increment(const PSMatrix& A, PSMatrix& B, double alpha, double threshold) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   if (A.dim != B.dim) NTP_FATAL("IncrementMatrix: dimension mismatch");
   if (blk_any({&A, &B}) && &A != &B && blk_kinds(A, B)) {
     ps_axpby(A, B, alpha, 1.0, threshold);
@@ -1002,7 +994,7 @@ void ps_increment(const PSMatrix& A, PSMatrix& B, double alpha, double threshold
 }
 
 void ps_scale(PSMatrix& A, double c) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   if (blk_any({&A})) {
     if (block_scale(A.loc, c)) { g_block_counts[0] += 1; return; }
     g_block_counts[1] += 1;
@@ -1019,7 +1011,7 @@ void ps_scale(PSMatrix& A, double c) {
 // B <- alpha*A + beta*B: ScaleMatrix(B, beta) followed by IncrementMatrix(A, B, alpha, threshold) in one pass (the
 // merge kernels scale B's values as they read them: the same products, the same rules, bit for bit)
 void ps_axpby(const PSMatrix& A, PSMatrix& B, double alpha, double beta, double threshold) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   if (A.dim != B.dim) NTP_FATAL("IncrementMatrix: dimension mismatch");
   if (blk_any({&A, &B}) && blk_kinds(A, B) && &A != &B && !A.loc.expanded() && !B.loc.expanded() && !A.loc.loose() && !B.loc.loose()) {
     if (block_axpby(A.loc, B.loc, alpha, beta, threshold)) {
@@ -1050,7 +1042,7 @@ void ps_axpby(const PSMatrix& A, PSMatrix& B, double alpha, double beta, double 
 }
 
 void ps_increment_identity(const PSMatrix& Identity, PSMatrix& B, double alpha) {
-  use_grid_comm(Identity.grid);
+  CommScope cs(Identity.grid);
   if (slab_on() && B.loc.expanded() && !B.cplx && !Identity.cplx && Identity.dim == B.dim && slab_add_diagonal(B.loc, alpha, B.c0)) {
     g_slab_counts[1] += 1;
     return;
@@ -1069,7 +1061,7 @@ void ps_increment_identity(const PSMatrix& Identity, PSMatrix& B, double alpha) 
 }
 
 bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double beta, double* norm) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   if (blk_any({&A, &B})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
   if (world().active() && g_slab_depth > 0 && A.cplx == B.cplx && (!A.cplx || g_complex_session) && A.dim == B.dim && &A != &B) {
     // (a session across ranks: the decision is collective -- one reduction carries the norm and "some rank declined")
@@ -1113,7 +1105,7 @@ bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double be
 }
 
 bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx) {
-  use_grid_comm(X.grid);
+  CommScope cs(X.grid);
   if (blk_any({&X, &X2})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
   if (world().active()) {
     // (a session across ranks: the decision is collective -- the sums and "some rank declined" in one reduction)
@@ -1134,7 +1126,7 @@ bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, dou
   return true;
 }
 bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P) {
-  use_grid_comm(X.grid);
+  CommScope cs(X.grid);
   if (blk_any({&X, &X2})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
   if (!slab_on() || !X.loc.expanded() || !X2.loc.expanded() || X.cplx || X2.cplx || sigma == 0.0) return false;
   DevMat R;
@@ -1146,7 +1138,7 @@ bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatr
 }
 
 void ps_copy_axpby(const PSMatrix& B, const PSMatrix& A, PSMatrix& Out, double alpha, double beta, double threshold) {
-  use_grid_comm(B.grid);
+  CommScope cs(B.grid);
   if (blk_any({&A, &B}) && blk_kinds(A, B) && &A != &B && &Out != &A && &Out != &B) {
     ps_copy(B, Out);
     ps_axpby(A, Out, alpha, beta, threshold);
@@ -1180,7 +1172,7 @@ void ps_copy_axpby(const PSMatrix& B, const PSMatrix& A, PSMatrix& Out, double a
 
 void ps_axpby_dot(const PSMatrix& A, PSMatrix& B, double alpha, double beta, double threshold, const PSMatrix& D, double out[4],
                   bool want_trace) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   out[2] = out[3] = 0.0;
   if (A.cplx != B.cplx || A.cplx != D.cplx || &A == &B) {  // mixed types: unfused sequence
     ps_scale(B, beta);
@@ -1489,7 +1481,7 @@ bool trs2_block(PSMatrix& B, int mode, double threshold, const PSMatrix& D, doub
 }  // namespace
 
 void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMatrix& D, double out[4], bool want_trace) {
-  use_grid_comm(D.grid);
+  CommScope cs(D.grid);
   out[2] = out[3] = 0.0;
   if (trs2_block(B, 2, threshold, D, out)) return;
   trs2_iterate_form(B);
@@ -1601,7 +1593,7 @@ void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, cons
 // B <- B * B, out = dot(B_new, D) (+ trace(B_new)): the sigma < 0 step of TRS2.  On one rank with real operands the
 // product stays loose (no compaction pass); otherwise multiply, swap and reduce as before.
 void ps_square_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMatrix& D, double out[4], bool want_trace) {
-  use_grid_comm(D.grid);
+  CommScope cs(D.grid);
   out[2] = out[3] = 0.0;
   if (trs2_block(B, 1, threshold, D, out)) return;
   trs2_iterate_form(B);
@@ -1658,7 +1650,7 @@ void ps_square_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMat
 
 // dot(A, B) and trace(A) from one pass
 void ps_dot_trace(const PSMatrix& A, const PSMatrix& B, double out[4], bool want_trace) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   unblock({&A, &B});
   out[2] = out[3] = 0.0;
   if (A.cplx != B.cplx) {
@@ -1671,7 +1663,7 @@ void ps_dot_trace(const PSMatrix& A, const PSMatrix& B, double out[4], bool want
 }
 
 void ps_pairwise(const PSMatrix& A, const PSMatrix& B, PSMatrix& C) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   unblock({&A, &B});
   if (A.cplx != B.cplx) {
     PSMatrix Ac, Bc;
@@ -1690,7 +1682,7 @@ void ps_pairwise(const PSMatrix& A, const PSMatrix& B, PSMatrix& C) {
 // DotMatrix_psr/psc (PSMatrixAlgebraModule.F90:387-410, distributed_algebra_includes/DotMatrix.f90):
 // sum conj(A).B; fused, no Hadamard temporary.
 void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   if (blk_any({&A, &B}) && blk_kinds(A, B)) {
     double d[2] = {0.0, 0.0};
     // (the sum runs over the super-tiles of its first operand: the one in block form; sum conj(b) a = conj(sum conj(a) b))
@@ -1728,7 +1720,7 @@ void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) {
 }
 
 double ps_trace(const PSMatrix& A) {
-  use_grid_comm(A.grid);  // MatrixTrace (distributed_algebra_includes/MatrixTrace.f90)
+  CommScope cs(A.grid);  // MatrixTrace (distributed_algebra_includes/MatrixTrace.f90)
   if (blk_any({&A})) {
     double t = 0.0;
     if (block_dot_trace(A.loc, A.loc, nullptr, &t)) { g_block_counts[0] += 1; return t; }
@@ -1752,7 +1744,7 @@ double ps_trace(const PSMatrix& A) {
 }
 
 double ps_norm(const PSMatrix& A) {
-  use_grid_comm(A.grid);  // MatrixNorm: max column abs-sum; columns are local
+  CommScope cs(A.grid);  // MatrixNorm: max column abs-sum; columns are local
   if (blk_any({&A})) {
     double v = 0.0;
     if (block_norm(A.loc, &v)) { g_block_counts[0] += 1; return v; }
@@ -1778,21 +1770,21 @@ double ps_norm(const PSMatrix& A) {
   } else {
     slab_pack_if({&A});
   }
-  DevBuf<double> cs;
-  column_abs_sums(A.loc, cs);
-  double n = max_of(cs, (size_t)A.loc.cols);
+  DevBuf<double> sums;
+  column_abs_sums(A.loc, sums);
+  double n = max_of(sums, (size_t)A.loc.cols);
   comm_allreduce_max(&n, 1);
   return n;
 }
 
 double ps_sigma(const PSMatrix& A) {
-  use_grid_comm(A.grid);  // MatrixSigma (distributed_algebra_includes/MatrixSigma.f90)
+  CommScope cs(A.grid);  // MatrixSigma (distributed_algebra_includes/MatrixSigma.f90)
   const double n = ps_norm(A);
   return 1.0 / (n * n);
 }
 
 void ps_gershgorin(const PSMatrix& A, double* e_min, double* e_max) {
-  use_grid_comm(A.grid);  // GershgorinBounds.f90:1-41
+  CommScope cs(A.grid);  // GershgorinBounds.f90:1-41
   unblock({&A});
   double mn, mx;
   if (slab_on() && A.loc.expanded()) {
@@ -1816,7 +1808,7 @@ void ps_gershgorin(const PSMatrix& A, double* e_min, double* e_max) {
 }
 
 void ps_transpose(const PSMatrix& A, PSMatrix& AT) {
-  use_grid_comm(A.grid);  // TransposeMatrix_ps
+  CommScope cs(A.grid);  // TransposeMatrix_ps
   unblock({&A});
   DevMat R;
   if (world().active()) {
@@ -1831,10 +1823,10 @@ void ps_transpose(const PSMatrix& A, PSMatrix& AT) {
 }
 
 void ps_conjugate(PSMatrix& A) {
-  use_grid_comm(A.grid); conjugate(A.loc); }
+  CommScope cs(A.grid); conjugate(A.loc); }
 
 bool ps_is_identity(const PSMatrix& A) {
-  use_grid_comm(A.grid);  // distributed_includes/IsIdentity.f90:7-38
+  CommScope cs(A.grid);  // distributed_includes/IsIdentity.f90:7-38
   int64_t d = identity_check(A.loc, A.c0);
   int64_t v[2] = {d < 0 ? 1 : 0, d < 0 ? 0 : d};
   comm_allreduce_sum_i64(v, 2);
@@ -1842,7 +1834,7 @@ bool ps_is_identity(const PSMatrix& A) {
 }
 
 double ps_measure_asymmetry(const PSMatrix& A) {
-  use_grid_comm(A.grid);  // MeasureAsymmetry: norm(A - A^H)
+  CommScope cs(A.grid);  // MeasureAsymmetry: norm(A - A^H)
   PSMatrix T;
   ps_transpose(A, T);
   ps_conjugate(T);
@@ -1851,7 +1843,7 @@ double ps_measure_asymmetry(const PSMatrix& A) {
 }
 
 void ps_symmetrize(PSMatrix& A) {
-  use_grid_comm(A.grid);  // SymmetrizeMatrix: A <- (A + A^H)/2
+  CommScope cs(A.grid);  // SymmetrizeMatrix: A <- (A + A^H)/2
   PSMatrix T;
   ps_transpose(A, T);
   ps_conjugate(T);
@@ -1860,7 +1852,7 @@ void ps_symmetrize(PSMatrix& A) {
 }
 
 void ps_similarity(const PSMatrix& A, const PSMatrix& P, const PSMatrix& PInv, PSMatrix& Res, double threshold) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   // SimilarityTransform (PSMatrixAlgebraModule.F90:603-654)
   if (ps_is_identity(P)) {
     ps_copy(A, Res);
@@ -1904,7 +1896,7 @@ void permutation_random(Permutation& p, int n) {
 // permutation matrices; out(i,j) = in(perm(i), perm(j)) is computed here by re-indexing and a device
 // sort, with the same result (including the pruning of stored zeros by the threshold-0 products).
 void ps_permute(const PSMatrix& in, PSMatrix& out, const Permutation& perm, bool undo) {
-  use_grid_comm(in.grid);
+  CommScope cs(in.grid);
   const int n = in.dim;
   if ((int)perm.index_lookup.size() != n) NTP_FATAL("permutation size does not match the matrix");
   std::vector<int32_t> map((size_t)n);

@@ -14,7 +14,7 @@ namespace ntp {
 
 // ------------------------------------------------------------------ PowerBounds
 void power_bounds(const PSMatrix& A, double* max_value_out, const SolverParameters& p_in, bool defaults) {
-  use_grid_comm(A.grid);
+  CommScope cs(A.grid);
   SolverParameters p = p_in;
   if (defaults) p.max_iterations = 10;  // :81-86
   Monitor mon;
@@ -88,7 +88,7 @@ void power_bounds(const PSMatrix& A, double* max_value_out, const SolverParamete
 
 // ------------------------------------------------------------------ exponential
 void compute_exponential(const PSMatrix& In, PSMatrix& Out, const SolverParameters& p) {
-  use_grid_comm(In.grid);
+  CommScope cs(In.grid);
   SolverParameters sub = p, psub = p;
   psub.max_iterations = 10;
   if (p.be_verbose) {
@@ -220,10 +220,10 @@ void scale_square_trig(const PSMatrix& In, PSMatrix& Out, const SolverParameters
 }  // namespace
 
 void compute_cosine(const PSMatrix& In, PSMatrix& Out, const SolverParameters& p) {
-  use_grid_comm(In.grid); scale_square_trig(In, Out, p); }
+  CommScope cs(In.grid); scale_square_trig(In, Out, p); }
 
 void compute_sine(const PSMatrix& In, PSMatrix& Out, const SolverParameters& p) {
-  use_grid_comm(In.grid);  // sin(x) = cos(x - pi/2), :30-64
+  CommScope cs(In.grid);  // sin(x) = cos(x - pi/2), :30-64
   const double PI = 4 * std::atan(1.0);
   PSMatrix Shifted, Ident;
   ps_copy(In, Shifted);
@@ -338,7 +338,7 @@ void root_impl(const PSMatrix& In, PSMatrix& Out, int root, const SolverParamete
 }  // namespace
 
 void compute_root(const PSMatrix& In, PSMatrix& Out, int root, const SolverParameters& p) {
-  use_grid_comm(In.grid);  // :31-83
+  CommScope cs(In.grid);  // :31-83
   if (p.be_verbose) {
     log_header("Root Solver");
     log_enter();
@@ -369,7 +369,7 @@ void compute_root(const PSMatrix& In, PSMatrix& Out, int root, const SolverParam
 }
 
 void compute_inverse_root(const PSMatrix& In, PSMatrix& Out, int root, const SolverParameters& p) {
-  use_grid_comm(In.grid);  // :124-174
+  CommScope cs(In.grid);  // :124-174
   if (p.be_verbose) {
     log_header("Inverse Root Solver");
     log_enter();
@@ -402,7 +402,7 @@ void compute_inverse_root(const PSMatrix& In, PSMatrix& Out, int root, const Sol
 
 // ------------------------------------------------------------------ logarithm
 void compute_logarithm(const PSMatrix& In, PSMatrix& Out, const SolverParameters& p) {
-  use_grid_comm(In.grid);
+  CommScope cs(In.grid);
   SolverParameters isub = p, psub = p, fsub = p;
   psub.max_iterations = 16;
   if (p.be_verbose) {

@@ -23,21 +23,17 @@ T* get(const int* ih) {
   if (!p) NTP_FATAL("null handle passed to the C ABI");
   return p;
 }
-// every entry point sees packed matrices; only the TRS2 step below passes its iterate on as it is (kernels.hpp, pack())
-template <>
-PSMatrix* get<PSMatrix>(const int* ih) {
-  PSMatrix* p;
-  std::memcpy(&p, ih, sizeof(p));
-  if (!p) NTP_FATAL("null handle passed to the C ABI");
-  if (p->loc.loose() || p->loc.expanded() || p->loc.blocked()) pack(p->loc);
-  if (p->grid) use_grid_comm(p->grid);   // (a matrix on a sub-grid: the call's collectives run on that grid's communicator)
-  return p;
-}
 PSMatrix* get_unpacked(const int* ih) {
   PSMatrix* p;
   std::memcpy(&p, ih, sizeof(p));
   if (!p) NTP_FATAL("null handle passed to the C ABI");
-  if (p->grid) use_grid_comm(p->grid);
+  return p;
+}
+// every entry point sees packed matrices; only the TRS2 step below passes its iterate on as it is (kernels.hpp, pack())
+template <>
+PSMatrix* get<PSMatrix>(const int* ih) {
+  PSMatrix* p = get_unpacked(ih);
+  if (p->loc.loose() || p->loc.expanded() || p->loc.blocked()) pack(p->loc);
   return p;
 }
 // The vocabulary entry points (MatrixMultiply, IncrementMatrix, ScaleMatrix, CopyMatrix, DotMatrix, MatrixNorm) run
@@ -46,9 +42,12 @@ PSMatrix* get_unpacked(const int* ih) {
 // a caller's own loop over the C ABI then keeps its matrices in the tile kernel's operand form between its calls --
 // operands are converted where they are on first use, products stay where the kernel wrote them -- and every OTHER
 // entry point still sees compressed columns (get<PSMatrix> packs on access).  Session not open: packed as ever.
+// The session is judged on the communicator of the call's first matrix operand: its scope is declared first, so it is
+// open before the session is.
 struct ApiSession {
+  CommScope cs;
   SlabSession s;
-  ApiSession() : s(true, true) {}
+  explicit ApiSession(const int* ih_first) : cs(get_unpacked(ih_first)->grid), s(true, true) {}
   PSMatrix* mat(const int* ih) const { return s.opened ? get_unpacked(ih) : get<PSMatrix>(ih); }
 };
 template <typename T>
@@ -121,11 +120,11 @@ extern "C" {
 void ntpoly_amd_get_unique_id(char* out128) { comm_get_unique_id(out128); }
 void ntpoly_amd_init_comm(const char* id128, const int* rank, const int* nranks) { comm_init(id128, *rank, *nranks); }
 void ntpoly_amd_finalize_comm() { comm_finalize(); }
-int ntpoly_amd_comm_rank() { return world().rank; }
-int ntpoly_amd_comm_size() { return world().nranks; }
-void ntpoly_amd_barrier() { use_comm(nullptr); comm_barrier(); }   // (all processes, whatever grid was worked on last)
+int ntpoly_amd_comm_rank() { return base_world().rank; }
+int ntpoly_amd_comm_size() { return base_world().nranks; }
+void ntpoly_amd_barrier() { comm_barrier(); }   // (all processes: no scope is open here)
 // max over all ranks of n host doubles, in place (timing of a distributed region: the slowest rank counts)
-void ntpoly_amd_allreduce_max(double* values, const int* n) { use_comm(nullptr); comm_allreduce_max(values, *n); }
+void ntpoly_amd_allreduce_max(double* values, const int* n) { comm_allreduce_max(values, *n); }
 void ntpoly_amd_synchronize() {
   ensure_init();
   sync_stream();
@@ -309,7 +308,7 @@ void ntpoly_amd_gather_matrix_to_process(const int* ih_this, int* ih_local, cons
 // CommSplitMatrix (PSMatrixModule.F90:1489-1541, distributed_includes/CommSplitMatrix.f90): a copy of the WHOLE matrix on each
 // half of its process grid (SplitProcessGrid, ProcessGridModule.F90:430-515: along the slices where there are several, else
 // along the longer of rows / columns).  The half lives on a sub-communicator (ncclCommSplit); every later call on the copy --
-// products, reductions, solvers -- runs inside that half (engine.hpp use_grid_comm).  One process: the copy itself, colour 0,
+// products, reductions, solvers -- runs inside that half (engine.hpp CommScope).  One process: the copy itself, colour 0,
 // "split along the slices" (the reference's base case, :11-14).
 void ntpoly_amd_comm_split_matrix(const int* ih_this, int* ih_split, int* my_color, bool* split_slice) {
   const PSMatrix& m = *get<PSMatrix>(ih_this);
@@ -438,15 +437,15 @@ void ntpoly_amd_triplets_get(const int* ih_list, int* col, int* row, double* val
 void ConstructGlobalProcessGrid_wrp(const int* world_comm, const int* process_rows, const int* process_columns,
                                     const int* process_slices) {
   comm_bind_mpi(*world_comm);  // the reference's MPI communicator (ProcessGrid.cc:14): honoured when MPI is initialised
-  construct_grid(global_grid(), *process_rows, *process_columns, *process_slices);
+  construct_grid(global_grid(), *process_rows, *process_columns, *process_slices, base_world());
 }
 void ConstructGlobalProcessGrid_onlyslice_wrp(const int* world_comm, const int* process_slices) {
   comm_bind_mpi(*world_comm);
-  construct_grid_default(global_grid(), *process_slices);
+  construct_grid_default(global_grid(), *process_slices, base_world());
 }
 void ConstructGlobalProcessGrid_default_wrp(const int* world_comm) {
   comm_bind_mpi(*world_comm);
-  construct_grid_default(global_grid(), 1);
+  construct_grid_default(global_grid(), 1, base_world());
 }
 void CopyProcessGrid_wrp(const int* ih_old_grid, int* ih_new_grid) {
   put(ih_new_grid, new ProcessGrid(*get<ProcessGrid>(ih_old_grid)));
@@ -464,19 +463,19 @@ void ConstructProcessGrid_wrp(int* ih_grid, const int* world_comm, const int* pr
                               const int* process_slices) {
   comm_bind_mpi(*world_comm);
   ProcessGrid* g = new ProcessGrid();
-  construct_grid(*g, *process_rows, *process_columns, *process_slices);
+  construct_grid(*g, *process_rows, *process_columns, *process_slices, base_world());
   put(ih_grid, g);
 }
 void ConstructProcessGrid_onlyslice_wrp(int* ih_grid, const int* world_comm, const int* process_slices) {
   comm_bind_mpi(*world_comm);
   ProcessGrid* g = new ProcessGrid();
-  construct_grid_default(*g, *process_slices);
+  construct_grid_default(*g, *process_slices, base_world());
   put(ih_grid, g);
 }
 void ConstructProcessGrid_default_wrp(int* ih_grid, const int* world_comm) {
   comm_bind_mpi(*world_comm);
   ProcessGrid* g = new ProcessGrid();
-  construct_grid_default(*g, 1);
+  construct_grid_default(*g, 1, base_world());
   put(ih_grid, g);
 }
 int GetMySlice_wrp(const int* ih_grid) { return get<ProcessGrid>(ih_grid)->my_slice; }
@@ -692,7 +691,7 @@ void ConstructEmptyMatrixPG_ps_wrp(int* ih_this, const int* matrix_dim, const in
   put(ih_this, m);
 }
 void CopyMatrix_ps_wrp(const int* ih_matA, int* ih_matB) {
-  ApiSession ses;
+  ApiSession ses(ih_matA);
   ps_copy(*ses.mat(ih_matA), *ses.mat(ih_matB));
 }
 void DestructMatrix_ps_wrp(int* ih_this) { delete get_unpacked(ih_this); }
@@ -840,19 +839,19 @@ void ntpoly_amd_matrix_local_columns(const int* ih_this, int* c0, int* c1) {
 
 void DotMatrix_psr_wrp(const int* ih_matA, const int* ih_matB, double* product) {
   double out[2];
-  ApiSession ses;
+  ApiSession ses(ih_matA);
   ps_dot(*ses.mat(ih_matA), *ses.mat(ih_matB), out);
   *product = out[0];
 }
 void DotMatrix_psc_wrp(const int* ih_matA, const int* ih_matB, double* product_real, double* product_imag) {
   double out[2];
-  ApiSession ses;
+  ApiSession ses(ih_matA);
   ps_dot(*ses.mat(ih_matA), *ses.mat(ih_matB), out);
   *product_real = out[0];
   *product_imag = out[1];
 }
 void IncrementMatrix_ps_wrp(const int* ih_matA, int* ih_matB, const double* alpha_in, const double* threshold_in) {
-  ApiSession ses;
+  ApiSession ses(ih_matA);
   ps_increment(*ses.mat(ih_matA), *ses.mat(ih_matB), *alpha_in, *threshold_in);
 }
 void MatrixPairwiseMultiply_ps_wrp(const int* ih_matA, const int* ih_matB, int* ih_matC) {
@@ -861,20 +860,20 @@ void MatrixPairwiseMultiply_ps_wrp(const int* ih_matA, const int* ih_matB, int* 
 void MatrixMultiply_ps_wrp(const int* ih_matA, const int* ih_matB, int* ih_matC, const double* alpha_in,
                            const double* beta_in, const double* threshold_in, int* ih_memory_pool_in) {
   (void)ih_memory_pool_in;
-  ApiSession ses;
+  ApiSession ses(ih_matA);
   ps_multiply(*ses.mat(ih_matA), *ses.mat(ih_matB), *ses.mat(ih_matC), *alpha_in, *beta_in, *threshold_in);
 }
 void ScaleMatrix_ps_wrp(int* ih_this, const double* constant) {
-  ApiSession ses;
+  ApiSession ses(ih_this);
   ps_scale(*ses.mat(ih_this), *constant);
 }
 double MatrixNorm_ps_wrp(const int* ih_this) {
-  ApiSession ses;
+  ApiSession ses(ih_this);
   return ps_norm(*ses.mat(ih_this));
 }
 double MeasureAsymmetry_ps_wrp(const int* ih_this) { return ps_measure_asymmetry(*get<PSMatrix>(ih_this)); }
 void MatrixTrace_ps_wrp(const int* ih_this, double* trace_val) {
-  ApiSession ses;
+  ApiSession ses(ih_this);
   *trace_val = ps_trace(*ses.mat(ih_this));
 }
 int IsIdentity_ps_wrp(const int* ih_this) { return ps_is_identity(*get<PSMatrix>(ih_this)) ? 1 : 0; }

@@ -179,6 +179,27 @@ def main():
     res["split_trs2"] = np.array([e_sub, mu_sub])
     keep("split_K", Ksub)
     res["after_split"] = np.array([A.Trace(), A.Norm()])      # (the grid of all processes again)
+    # ---- nothing a call on the half selects outlives the call: directly after a call on Sp, the rank queries, a grid
+    # constructed then and a product on the grid of all processes (its one-call session judged on A's communicator)
+    # are about all processes
+    import ctypes as C
+    from ntpoly_amd.capi import handle, i, lib
+    AA = nt.Matrix_ps(n)      # (constructed, and its memory pool made, before the call on Sp)
+    pool = nt.PMatrixMemoryPool(A)
+    Sp.Trace()
+    res["after_split_comm"] = np.array([lib.ntpoly_amd_comm_rank(), lib.ntpoly_amd_comm_size()])
+    Sp.Norm()
+    g, info = handle(), (C.c_int * 3)()
+    lib.ConstructProcessGrid_default_wrp(g, i(0))
+    lib.ntpoly_amd_grid_comm_info(g, info)
+    res["after_split_grid"] = np.array(list(info))
+    lib.DestructProcessGrid_wrp(g)
+    Sp.Trace()
+    s0, p0 = nt.slab_algebra_counts(), nt.panel_product_counts()
+    AA.Gemm(A, A, pool, 1.0, 0.0, 0.0)     # (the product kept as "AA" above, before the split)
+    s1, p1 = nt.slab_algebra_counts(), nt.panel_product_counts()
+    res["after_split_counts"] = np.array([s1[k] - s0[k] for k in sorted(s0)] + [p1[k] - p0[k] for k in sorted(p0)])
+    keep("after_split_AA", AA)
     nt.barrier()
 
     np.savez(out + ".%d.npz" % rank, **res)

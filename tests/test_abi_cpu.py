@@ -157,12 +157,35 @@ def test_multi_process_launch_without_communicator_is_refused():
     assert r4.returncode != 0 and "no communicator was given to the engine" in r4.stdout
 
 
+def test_split_grid_after_finalize_is_refused():
+    """A grid made by SplitProcessGrid outlives the communicator it was split from when the communicator is finalised: the
+    engine keeps the retired communicator, and a matrix constructed on that grid afterwards is refused with a message
+    (the binary reader selects the grid's communicator before it opens the file or touches the GPU)."""
+    code = ("import ctypes as C\n"
+            "import ntpoly_amd as nt\n"
+            "from ntpoly_amd.capi import handle, i, lib\n"
+            "nt.init_comm()\n"
+            "g, half, m = handle(), handle(), handle()\n"
+            "lib.ConstructProcessGrid_default_wrp(g, i(0))\n"
+            "lib.ntpoly_amd_split_process_grid(g, half, C.byref(C.c_int()), C.byref(C.c_bool()))\n"
+            "lib.ntpoly_amd_finalize_comm()\n"
+            "print('finalised', flush=True)\n"
+            "name = b'/nonexistent/matrix.bin'\n"
+            "lib.ConstructMatrixFromBinaryPG_ps_wrp(m, name, i(len(name)), half)\n"
+            "print('constructed')\n")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PYTHONPATH=ROOT), stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert "finalised" in r.stdout and "constructed" not in r.stdout, r.stdout
+    assert r.returncode != 0 and "used after the communicator was finalised" in r.stdout, r.stdout
+
+
 def test_host_side_under_address_and_ub_sanitizers(tmp_path):
     """The host side of the library built with -fsanitize=address,undefined (ntpoly_amd._build.build_sanitized, the
     analogue of the reference's -fcheck=all leg, Targets/Linux.cmake:20-22) and driven through the host-only part of the
     C ABI: triplet lists (append / resize / set / get / sort / symmetrize through the Python mirror), permutations,
-    solver parameters, the logger, the single-rank grid, and the fatal path of a multi-process launch without a
-    communicator.  Any sanitizer report fails the test.  (GPU sanitizers are not available on this pool.)"""
+    solver parameters, the logger, the single-rank grid, a split of it and a copy of the half's grid across a finalise and a
+    re-init of the communicator, and the fatal path of a multi-process launch without a communicator.  Any sanitizer report
+    fails the test.  (GPU sanitizers are not available on this pool.)"""
     import glob
     import subprocess
     import sys
@@ -206,6 +229,33 @@ assert nt.GetGlobalIsRoot()
 nt.ActivateLogger(True, r"%s")
 nt.WriteGridInfo()
 nt.DeactivateLogger()
+# SplitProcessGrid of a one-rank grid and a copy of the half's grid; after a finalise and a re-init both still point at
+# live (retired) communicators, and what is constructed then lives on all processes
+import ctypes as C
+from ntpoly_amd.capi import handle, i
+def comm_info(h):
+    out = (C.c_int * 3)()
+    lib.ntpoly_amd_grid_comm_info(h, out)
+    return list(out)
+g, half, copy = handle(), handle(), handle()
+lib.ConstructProcessGrid_default_wrp(g, i(0))
+color, split_slice = C.c_int(-1), C.c_bool(False)
+lib.ntpoly_amd_split_process_grid(g, half, C.byref(color), C.byref(split_slice))
+assert color.value == 0
+lib.CopyProcessGrid_wrp(half, copy)
+assert comm_info(g) == [0, 1, 0] and comm_info(half) == [0, 1, 1] and comm_info(copy) == [0, 1, 1]
+lib.DestructProcessGrid_wrp(copy)
+lib.CopyProcessGrid_wrp(half, copy)
+lib.ntpoly_amd_finalize_comm()
+nt.init_comm()
+assert comm_info(half) == [0, 1, 1] and comm_info(copy) == [0, 1, 1]
+lib.DestructProcessGrid_wrp(copy)
+g2 = handle()
+lib.ConstructProcessGrid_default_wrp(g2, i(0))
+assert comm_info(g2) == [0, 1, 0]
+assert lib.ntpoly_amd_comm_rank() == 0 and lib.ntpoly_amd_comm_size() == 1
+lib.DestructProcessGrid_wrp(g2)
+lib.DestructProcessGrid_wrp(g)
 print("HOST-OK")
 ''' % str(tmp_path / "log.yaml")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -178,3 +178,15 @@ def test_comm_split_matrix_on_several_ranks(world, grid, references, tmp_path):
         else:
             e = [float(p["split_trs2"][0]) for p in half]
             assert max(e) - min(e) <= 1e-11 * abs(e[0])      # (one value inside the half; five iterations, no one-rank twin)
+    # directly after a call on the half: the rank queries and a grid constructed then are about all processes, and a
+    # product on the grid of all processes runs without an API session across ranks (C ABI sessions are one-rank only: no
+    # slab operation, no panel product) and is bit for bit the same product made before the split -- and the one-rank
+    # product where the grid has one slice (slices > 1 sum the reference's K-split partial products)
+    for r in range(world):
+        assert list(parts[r]["after_split_comm"]) == [r, world], (r, parts[r]["after_split_comm"])
+        assert list(parts[r]["after_split_grid"]) == [r, world, 0], (r, parts[r]["after_split_grid"])
+        assert not np.any(parts[r]["after_split_counts"]), (r, parts[r]["after_split_counts"])
+    got = cat(parts, "after_split_AA")
+    assert all(np.array_equal(g, w) for g, w in zip(got, cat(parts, "AA")))
+    if slices == 1:
+        assert all(np.array_equal(g, reference["after_split_AA" + s]) for g, s in zip(got, ("_col", "_row", "_val")))
