@@ -118,10 +118,14 @@ bool band_scope_try(const std::vector<const PSMatrix*>& ins, const std::vector<P
   // No band (a 3-D operand): the solve in the pattern's BLOCK order instead -- the index set clustered into blocks of 16 and
   // super-blocks of 64 (spgemm_block.hip), the operands redistributed so that a rank owns a contiguous range of positions;
   // its panel products then run on the block path (psmatrix.cpp multiply_panel) instead of the LDS hash.  Same contract as the
-  // band order: the reference's solve under its load balancer with this permutation.
+  // band order: the reference's solve under its load balancer with this permutation.  A complex first operand (a complex 3-D
+  // Hamiltonian; option block_scope_complex) takes the same scope where the complex block path multiplies on one rank: the order
+  // made from the moduli, its panel products on the complex tile products of the block path; the caller's real operands beside
+  // it (an identity, ISQ) are relabelled as they are, and up-cast where a product meets them, as on one rank
   bool block_mode = false;
   std::vector<int32_t> perm;   // perm[label] = new label
-  if (!c.found && options().block_scope != 0 && options().block_path != 0 && options().spgemm_fma == 1 && !H.cplx) {
+  const bool block_kind = !H.cplx || (options().block_scope_complex != 0 && complex_forms_ok());
+  if (!c.found && options().block_scope != 0 && options().block_path != 0 && options().spgemm_fma == 1 && block_kind) {
     if (!c.block_tried) {
       c.block_tried = true;
       c.block_found = block_order_of_pattern(full, c.block_pos, &c.block_ns);

@@ -2711,6 +2711,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_SLAB_ALGEBRA")) e->slab_algebra = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_PANEL_SESSIONS")) e->panel_sessions = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PANELS")) e->complex_panels = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_SCOPE_COMPLEX")) e->block_scope_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_UNFUSED")) e->block_unfused = std::atoi(v);
     return e;
   }();

@@ -736,9 +736,13 @@ DevMat multiply_panel(const PSMatrix& A, const PSMatrix& B, double alpha, double
     const ColRange need{hx.kmin, hx.kmax + 1};   // the rows of the B panel name these columns only
     // A solve in a block order (band_scope.cpp: 3-D operands on several ranks): the panel of B as the columns c0 .. c1 of a
     // square matrix whose other columns are empty, the product through the block path -- tiles of the order the scope
-    // installed, candidates in this rank's super-columns only -- and the panel's columns cut out of the result
-    const bool block_route = block_scope_active() && !A.cplx && !B.cplx && options().spgemm_fma == 1 && options().block_path != 0 &&
-                             a_fraction == 1.0;
+    // installed, candidates in this rank's super-columns only -- and the panel's columns cut out of the result.  Complex
+    // operands (a complex first operand's scope, option block_scope_complex) the same way, on the complex tile products of the
+    // block path (k_bs_numeric_c); a real operand beside a complex one arrives here up-cast (ps_multiply), as on one rank.  The
+    // route depends only on what every rank sees alike -- the options, the operands' kinds, the scope -- so no rank declines it
+    // alone (the block path's own refusal is local: that rank's product then goes to the LDS hash, no collective follows)
+    const bool kinds_ok = A.cplx == B.cplx && (!A.cplx || (options().block_scope_complex != 0 && complex_forms_ok()));
+    const bool block_route = block_scope_active() && kinds_ok && options().spgemm_fma == 1 && options().block_path != 0 && a_fraction == 1.0;
     if (block_route) {
       hx.finish();
       DevMat Csq;
@@ -750,6 +754,9 @@ DevMat multiply_panel(const PSMatrix& A, const PSMatrix& B, double alpha, double
         fill_i64(pad_outer.p + B.c1 + 1, (int64_t)B.dim - B.c1, B.loc.nnz);
         Bsq.alias(B.loc, pad_outer.p, B.dim, B.loc.nnz);
         hx.full.block_hint = 1;   // (straight to the block path: no run statistics, no band search on the gathered operand)
+        // (complex: no fill floor -- an iterate that has thinned out, 3 I - X^2 late in a sign loop at fill 0.075, would otherwise
+        // send the whole gathered operand to the general kernels: minutes for one product of a 40^3 lattice, against 0.1 s here)
+        BlockForceScope force(A.cplx);
         spgemm(hx.full, Bsq.m, Csq, alpha, threshold, dense_rule);
         sync_stream();   // (the padded offsets are released on leaving the scope)
       }

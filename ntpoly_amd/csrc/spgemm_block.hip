@@ -1865,6 +1865,12 @@ void drop_block_caches() {
   cache().pool_hint_n = -1;
 }
 
+namespace {
+int g_block_force = 0;
+}  // namespace
+BlockForceScope::BlockForceScope(bool on_) : on(on_) { g_block_force += on ? 1 : 0; }
+BlockForceScope::~BlockForceScope() { g_block_force -= on ? 1 : 0; }
+
 bool block_refused(int32_t n, int64_t nnz) {
   const BlockCache& c = cache();
   return c.refused_n == n && (double)nnz <= 1.5 * (double)c.refused_nnz && (double)nnz >= 0.5 * (double)c.refused_nnz;
@@ -1881,7 +1887,7 @@ bool block_order_for(const DevMat& M, std::vector<int32_t>& pos_host) {
 }
 
 bool block_order_of_pattern(const DevMat& M, std::vector<int32_t>& pos_host, int32_t* ns_out) {
-  if (M.cplx || M.rows != M.cols || M.loose() || M.expanded() || M.blocked() || M.nnz < 8LL * M.cols) return false;
+  if ((M.cplx && !complex_forms_ok()) || M.rows != M.cols || M.loose() || M.expanded() || M.blocked() || M.nnz < 8LL * M.cols) return false;
   BlockCache& c = cache();
   const unsigned long long fp = block_pattern_fp(M);
   if (!select_order_fp(c, M.cols, fp)) install_order(c, build_block_order(M));
@@ -2301,9 +2307,8 @@ bool block_trs2_step(DevMat& X, int mode, double threshold, bool dense_rule, con
 
 // ---------------------------------------------------------------------------------------------------------------------
 // block algebra
-namespace {
-// (complex forms: where the block path multiplies complex operands -- FMA arithmetic, complex_tile, block_complex)
 bool complex_forms_ok() { return options().spgemm_fma == 1 && options().complex_tile != 0 && options().block_complex != 0; }
+namespace {
 bool algebra_ok(const DevMat& M) {
   return (!M.cplx || complex_forms_ok()) && M.rows == M.cols && !M.loose() && !M.expanded() && block_arithmetic_ok() && options().block_path != 0 &&
          options().spgemm_variant < 0 && options().spgemm_force_bin <= 0;
@@ -2532,7 +2537,7 @@ bool spgemm_block(const DevMat& A, const DevMat& B, DevMat& C, double alpha, dou
   const int32_t n = A.cols;
   if (n < 256 || A.nnz == 0 || B.nnz == 0) return false;
   BlockCache& bc = cache();
-  const int force = options().block_path;
+  const int force = g_block_force > 0 ? 2 : options().block_path;
   const bool any_blocked = A.blocked() || B.blocked();
   if (!any_blocked && force != 2 && block_refused(n, A.nnz)) return false;
   const double min_fill = force == 2 ? 0.0 : kMinFill;

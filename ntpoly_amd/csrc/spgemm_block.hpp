@@ -89,12 +89,23 @@ bool block_trs2_step(DevMat& X, int mode, double threshold, bool dense_rule, con
 // the block order the engine holds for matrices of M's dimension, made from M if there is none (tests / tools);
 // pos_host[index] = position
 bool block_order_for(const DevMat& M, std::vector<int32_t>& pos_host);
-// the block order made FOR the pattern of M (kept under its fingerprint; made now if there is none): positions and super-blocks
+// the block order made FOR the pattern of M (kept under its fingerprint; made now if there is none): positions and super-blocks.
+// A complex M (where complex_forms_ok): the order made from the moduli -- the positions of the real matrix with its pattern and |values|
 bool block_order_of_pattern(const DevMat& M, std::vector<int32_t>& pos_host, int32_t* ns_out);
+// where the block path multiplies complex operands: FMA arithmetic, options complex_tile and block_complex
+bool complex_forms_ok();
 // an order given by explicit positions (pos[index] in [0, 64 ns), at most 16 indices per block of 16 positions) becomes the current
 // order of dimension n: a solve that has redistributed its operands in a block order (band_scope.cpp) multiplies in it
 void install_block_positions(int32_t n, int32_t ns, const std::vector<int32_t>& pos);
 void drop_block_caches();
+// while one is alive (on = true): the block path takes every operand it can convert, whatever its fill -- as block_path = 2 does.
+// A complex panel product of a solve in a block order across ranks (psmatrix.cpp multiply_panel): the one-rank complex session
+// multiplies the same iterates in block form with no fill floor, and the alternative here is the general kernels on the whole gathered operand
+struct BlockForceScope {
+  explicit BlockForceScope(bool on);
+  ~BlockForceScope();
+  bool on;
+};
 // true: the block path has declined operands of dimension n with about nnz entries (no blocks worth the matrix cores) and
 // will decline them again without a look
 bool block_refused(int32_t n, int64_t nnz);

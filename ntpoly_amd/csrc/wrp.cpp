@@ -179,6 +179,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "block_unfused") options().block_unfused = *value;
   else if (n == "block_match") options().block_match = *value;
   else if (n == "block_scope") options().block_scope = *value;
+  else if (n == "block_scope_complex") options().block_scope_complex = *value;
   else if (n == "panel_sessions") options().panel_sessions = *value;
   else if (n == "complex_panels") options().complex_panels = *value;
   else if (n == "label_rowoff") options().label_rowoff = *value;
@@ -211,6 +212,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "block_unfused") return options().block_unfused;
   if (n == "block_match") return options().block_match;
   if (n == "block_scope") return options().block_scope;
+  if (n == "block_scope_complex") return options().block_scope_complex;
   if (n == "panel_sessions") return options().panel_sessions;
   if (n == "complex_panels") return options().complex_panels;
   if (n == "fused_update") return options().fused_update;
@@ -260,6 +262,18 @@ int ntpoly_amd_block_order(const int* ih, int* position) {
   return 1;
 }
 void ntpoly_amd_drop_block_caches() { drop_block_caches(); }
+// tests: the block order made FOR this matrix's pattern (spgemm_block.hip block_order_of_pattern -- what a solve in a block order
+// across ranks redistributes its operands in; complex matrices from the moduli): position[index], *ns = super-blocks; 1 on success
+int ntpoly_amd_block_order_of_pattern(const int* ih, int* position, int* ns) {
+  PSMatrix& m = *get<PSMatrix>(ih);
+  DevMat full = ps_gather_full(m);
+  std::vector<int32_t> pos;
+  int32_t s = 0;
+  if (!block_order_of_pattern(full, pos, &s)) return 0;
+  std::memcpy(position, pos.data(), sizeof(int32_t) * pos.size());
+  *ns = s;
+  return 1;
+}
 // out[0] = halo exchanges of distributed multiplies so far, out[1] = host synchronisations inside them (counted where the
 // host waits: sync_stream), out[2] = ALL host synchronisations of the process so far: a caller brackets a call with two
 // reads to learn what the whole call cost (exchange, plan, totals)

@@ -993,6 +993,16 @@ def block_order(M):
     return pos if ok else None
 
 
+def block_order_of_pattern(M):
+    """(positions, super-blocks) of the block order made FOR M's pattern (what a solve in a block order across ranks redistributes
+    its operands in; complex M: made from the moduli), or None where there is none"""
+    pos = np.zeros(M.GetActualDimension(), dtype=np.int32)
+    ns = C.c_int()
+    lib.ntpoly_amd_block_order_of_pattern.restype = C.c_int
+    ok = lib.ntpoly_amd_block_order_of_pattern(M.ih, pos.ctypes.data_as(C.c_void_p), C.byref(ns))
+    return (pos, int(ns.value)) if ok else None
+
+
 def increment_identity(Identity, B, alpha):
     """IncrementMatrix(Identity, B, alpha) as the solver loops call it (in place where every column stores its diagonal)"""
     lib.ntpoly_amd_increment_identity(Identity.ih, B.ih, d(alpha))
