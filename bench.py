@@ -16,15 +16,19 @@ iterating past that point only amplifies rounding noise until X fills in without
 after every TRS2_WINDOW iterations (warm-up included), outside the clock; W + K <= TRS2_WINDOW never restarts.
 Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: setup, warm-up, the timed blocks, --dump-outputs, the line.  --full
+adds the measurements and checks that take runs of their own (cpu_baseline, trs2_wrp_check and, for a relabelled or 3-D
+operand on several ranks, the solver path's rate); --no-cpu-baseline / --no-wrp-check leave one of them out of a --full run.
+
 Extra objects in the line:
   roofline     -- the dominant kernel (SpGEMM numeric phase with the TRS2 update in its epilogue: k_spgemm_tile on the FP64
                   matrix cores in the default FMA arithmetic, k_spgemm_slab in unfused arithmetic, k_bs_numeric / k_spgemm_ghash
                   for operands without runs): algorithmic bytes 12*(nnzA+nnzB+nnzC)+4*(cols...) per launch / its HIP-event
                   time on the engine's stream, vs 8 TB/s HBM; traffic = the committed PMC passes of the same command
   roofline_compute -- the same launches against the FP64 peak of the arithmetic mode
-  cpu_baseline -- the oracle (C restatement with OpenMP, kind "port") on all host cores at the FULL size: ONE solve of
-                  warmup + 5 iterations, the last five timed one by one, median -- reported, not the target
-  trs2_wrp_check -- the same rate measured through the reference's entry point TRS2_wrp ((t(25) - t(5)) / 20)
+  cpu_baseline -- (--full) the oracle (C restatement with OpenMP, kind "port") on all host cores at the FULL size: ONE
+                  solve of warmup + 5 iterations, the last five timed one by one, median -- reported, not the target
+  trs2_wrp_check -- (--full) the same rate measured through the reference's entry point TRS2_wrp ((t(25) - t(5)) / 20)
 
 Other workloads: --permute SEED (the operand under the load balancer's random relabelling), --random SEED (the same
 operand left AS IT STANDS -- no band recovery, no block order: the north star's LDS-hash SpGEMM, the shape of the
@@ -371,11 +375,15 @@ def main():
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--halfband", type=int, default=100)
     ap.add_argument("--threshold", type=float, default=1e-8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the CPU baseline, the TRS2_wrp-differenced "
+                         "cross-check of the value and, for a relabelled or 3-D operand on several ranks, the solver path's rate")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-label-order", action="store_true",
                     help="with --permute: do not look for a band hidden under the labels (option label_order = 0): the "
                          "relabelled operand runs on the grouped LDS-hash SpGEMM as it stands")
-    ap.add_argument("--no-wrp-check", action="store_true", help="skip the TRS2_wrp-differenced cross-check of the value")
+    ap.add_argument("--no-wrp-check", action="store_true",
+                    help="with --full: skip the TRS2_wrp-differenced cross-check of the value (on one rank)")
     ap.add_argument("--permute", type=int, default=None, metavar="SEED",
                     help="run on P^T H P under a seeded random relabelling (SURVEY 8(d): the load-balanced / "
                          "unstructured operand; the SpGEMM leaves the run-based kernels for the LDS hash path)")
@@ -655,7 +663,7 @@ def main():
                                       issued_tflops_last_product=(2.0 * issued / (st["ms_numeric"] * 1e-3) / 1e12 if st.get("ms_numeric") else None))
     check = None
     reordered = args.permute is not None or args.lattice is not None   # (operands the solver redistributes on several ranks)
-    if not args.no_wrp_check or (world > 1 and reordered):
+    if args.full and (not args.no_wrp_check or (world > 1 and reordered)):
         del X, X2
         check = trs2_wrp_check(nt, H, n, thr)       # (collective: every rank takes part)
     if rank == 0 and world > 1 and reordered and check:
@@ -672,7 +680,7 @@ def main():
     if rank == 0:
         if check:
             line["trs2_wrp_check"] = check
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(n, h, thr, args.warmup, args.steps, args.permute, fma=args.arithmetic == "fma",
                                                 lattice=args.lattice)
         print(json.dumps(line), flush=True)
