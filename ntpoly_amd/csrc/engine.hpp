@@ -209,6 +209,8 @@ void ps_dot_trace(const PSMatrix& A, const PSMatrix& B, double out[4], bool want
 void ps_square_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMatrix& D, double out[4], bool want_trace);
 // B <- 2B - B*B (threshold on the product and on the merge, TRS2's sigma > 0 update), out = dot(B_new, D), trace(B_new);
 // the product goes from the numeric kernel's slots straight into the merge when the slab kernel computes it
+// a TRS2 solve starts: complex iterates try the complex slab form again (psmatrix.cpp complex_trs2_step)
+void trs2_complex_reset();
 void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMatrix& D, double out[4], bool want_trace);
 void ps_pairwise(const PSMatrix& A, const PSMatrix& B, PSMatrix& C);
 void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]);

@@ -2711,6 +2711,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_SLAB_ALGEBRA")) e->slab_algebra = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_PANEL_SESSIONS")) e->panel_sessions = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PANELS")) e->complex_panels = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_DENSITY")) e->complex_density = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_SCOPE_COMPLEX")) e->block_scope_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_UNFUSED")) e->block_unfused = std::atoi(v);
     return e;
@@ -2994,6 +2995,10 @@ const DotOperand& dot_operand(const DevMat& D) {
 }  // namespace
 
 long long* fusion_counts() {
+  static long long c[3] = {0, 0, 0};
+  return c;
+}
+long long* complex_fusion_counts() {
   static long long c[3] = {0, 0, 0};
   return c;
 }
@@ -6786,7 +6791,7 @@ __global__ __launch_bounds__(256) void k_count_zero_values_c(Csc A, unsigned lon
 bool sa_operand_c(const DevMat& M) {
   return M.expanded() && M.cplx && !M.slab->labelled() && !M.slab->origin && (M.rows == M.cols || g_panels_ok) && M.slab->row_pad % 16 == 0;
 }
-bool slab_enter_c(DevMat& M) {
+bool slab_enter_c(DevMat& M, bool* not_run_like) {
   if (M.expanded()) return sa_operand_c(M);
   if (!M.cplx || M.blocked() || M.loose() || (M.rows != M.cols && !g_panels_ok) || M.nnz == 0 || M.slab_hint < 0 || options().spgemm_fma != 1 ||
       options().complex_tile == 0)
@@ -6816,6 +6821,7 @@ bool slab_enter_c(DevMat& M) {
     if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
       std::fprintf(stderr, "[slab_enter_c] refused: slots %lld for %lld entries, columns with stored zeros %llu\n", (long long)tot, (long long)M.nnz, hz);
     M.slab_hint = -1;
+    if (not_run_like && hz == 0) *not_run_like = true;
     return false;
   }
   f->val.alloc(((size_t)tot + kIndexSlack) * 2);

@@ -89,6 +89,7 @@ struct EngineOptions {
   int block_unfused = 0;       // the block path (spgemm_block.hip) in UNFUSED arithmetic too: products rounded, then added, on the vector units, in ascending POSITION of the block order -- the reference's default build on the matrix relabelled by that order (what its own load balancer does), 1e-13 of the sums over ascending labels.  0 (default): operands without runs keep the label-ordered kernels in unfused arithmetic, bit for bit the reference on the caller's labels
   int panel_sessions = 1;      // slab sessions (TRS4, sign, inverse, square roots, polynomials ...) on more than one rank: the loops' matrices stay in slab form as column panels, a product exchanges the runs of the left operand's halo (psmatrix.cpp panel_slab_multiply); 0: compressed columns across ranks
   int complex_panels = 1;      // complex loops (sign, inverse, square roots) on more than one rank: the iterates stay complex column panels in slab form, a product exchanges the complex runs of the left operand's halo (psmatrix.cpp panel_slab_multiply, complex tile kernel); needs panel_sessions and complex_sessions; 0: compressed columns across ranks
+  int complex_density = 1;     // complex TRS2 on one rank (FMA arithmetic, complex_tile, complex_sessions): the iterate stays out of compressed columns from step to step -- run-like iterates in complex slab form (X*X on the complex tile kernel, then the merge pass, then one energy / trace pass), iterates without runs in complex block form (block_complex, block_path: X*X on k_bs_numeric_c, the complex block merge, block_dot_trace) (psmatrix.cpp complex_trs2_step); 0: every complex density solve as before
   int ghash_mfma = 1;          // grouped LDS-hash SpGEMM, real operands, FMA arithmetic: the products of a phase (four steps) as ONE v_mfma_f64_16x16x4_f64 per tile of 16 slots x 16 columns instead of 64 vector FMAs -- the same chain of fma() over ascending k, bit for bit; 0: vector units
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
@@ -246,12 +247,15 @@ void slab_allow_panels(bool on);   // a slab session across ranks: the operands 
 // slots aligned to 16 rows -- what the complex MFMA tile kernel reads and writes.  Each returns false when it does not take
 // its operands (nothing changed): the caller packs and the compressed-column path does the work.
 bool sa_operand_c(const DevMat& M);
-bool slab_enter_c(DevMat& M);
+bool slab_enter_c(DevMat& M, bool* not_run_like = nullptr);   // (not_run_like: set when it refused because the columns are not run-like)
 bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule, const SlabHalo* left = nullptr);
 // true: slab_multiply_c with a left halo of these columns, this alignment and this plan will NOT decline (the one predicate it uses itself)
 bool slab_multiply_c_takes_panel(const DevMat& A, const DevMat& B, int left_row_pad, int32_t ka, int32_t kb, const SlabPlan* plan);
 bool slab_add_diagonal_c(DevMat& B, double alpha, int32_t col_offset);                      // slab_extra.hip
 bool slab_norm_axpby_c(const DevMat& A, const DevMat& B, double alpha, double beta, double* out);   // slab_extra.hip
+// slab_extra.hip: dot = (Re, Im) of sum conj(A) B for a complex slab-form A and a complex B in slab form or packed compressed
+// columns (B == nullptr: none), trace = sum of the real parts of A's diagonal (col_offset: A's first column); fixed-shape sums
+bool slab_dot_trace_c(const DevMat& A, const DevMat* B, int32_t col_offset, double dot[2], double* trace);
 bool slab_axpby(const DevMat& A, DevMat& B, double alpha, double beta, double threshold);   // B <- alpha A + beta B
 bool slab_axpby_to(const DevMat& A, const DevMat& B, DevMat& Out, double alpha, double beta, double threshold);   // Out = alpha A + beta B
 bool slab_clone(const DevMat& A, DevMat& Out);
@@ -303,6 +307,9 @@ int64_t column_span_sum(const DevMat& A);
 unsigned long long pattern_fingerprint_of(const DevMat& A);
 // since start: [0] steps computed with SlabFusion mode 1, [1] mode 2, [2] fused steps repeated on the unfused path
 long long* fusion_counts();
+// since start: complex TRS2 steps done in complex slab or block form (product, merge and energy pass; not a fused tile epilogue) --
+// [0] X*X, [1] 2X - X*X, [2] steps that had to be repeated the old way
+long long* complex_fusion_counts();
 // [0] multiplies done in the two-block geometry (spgemm_tile2.hip), [1] launches of it that did not fit and were repeated on k_spgemm_tile
 long long* tile2_counts();
 long long& band_searches();   // searches for a bandwidth-reducing order since start (one per sparsity PATTERN: relabel_enter)

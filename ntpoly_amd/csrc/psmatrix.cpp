@@ -1487,9 +1487,107 @@ bool trs2_block(PSMatrix& B, int mode, double threshold, const PSMatrix& D, doub
 }
 }  // namespace
 
+namespace {
+// Complex TRS2 steps that keep the iterate out of compressed columns (option complex_density; one rank, FMA arithmetic,
+// complex_tile, complex_sessions):
+//  - run-like iterates in complex SLAB form: X*X on the complex tile kernel (slab_multiply_c), 2X - X*X by the complex merge of
+//    the slab algebra (the AddSparseVectors rules with the threshold on the modulus), then ONE pass for the energy Re sum conj(X) D
+//    and the trace Re sum X_ii (slab_extra.hip k_sa_dot_trace_c);
+//  - iterates without runs (a complex lattice) in complex BLOCK form (block_complex, block_path): X*X on k_bs_numeric_c kept in
+//    block form, 2X - X*X by the complex block merge (k_bs_merge on complex tiles), energy and trace by block_dot_trace.
+// An iterate the slab form cannot hold (stored zeros) runs its step the old way and the next step tries again.  A Hamiltonian
+// whose iterates neither form takes is remembered (by identity) and its later steps go the old way at once.
+struct CtrsOff {
+  const DevMat* d = nullptr;
+  const double* val = nullptr;
+  int64_t nnz = -1;
+};
+CtrsOff g_ctrs2_off;
+bool ctrs2_off_for(const PSMatrix& D) { return g_ctrs2_off.d == &D.loc && g_ctrs2_off.val == D.loc.val.p && g_ctrs2_off.nnz == D.loc.nnz; }
+void ctrs2_set_off(const PSMatrix& D) { g_ctrs2_off.d = &D.loc; g_ctrs2_off.val = D.loc.val.p; g_ctrs2_off.nnz = D.loc.nnz; }
+bool complex_trs2_block(PSMatrix& B, int mode, double threshold, bool dense_rule, const PSMatrix& D, double out[4]) {
+  if (!complex_forms_ok() || options().block_path == 0 || options().block_complex == 0 || B.loc.expanded() || D.loc.expanded()) return false;
+  DevMat P;
+  BlockInfo info;
+  if (!spgemm_block(B.loc, B.loc, P, 1.0, threshold, dense_rule, &info, nullptr, nullptr, true)) return false;
+  if (!P.blocked()) {   // (an empty product: no block form to carry on with)
+    if (B.loc.blocked()) pack(B.loc);
+    return false;
+  }
+  if (mode == 2) {
+    if (!block_axpby(P, B.loc, -1.0, 2.0, threshold)) {
+      complex_fusion_counts()[2] += 1;
+      if (B.loc.blocked()) pack(B.loc);
+      return false;
+    }
+  } else {
+    B.loc = std::move(P);
+  }
+  double dot[2] = {0.0, 0.0}, tr = 0.0;
+  if (!block_dot_trace(B.loc, D.loc, dot, &tr)) {   // (B is the new iterate now: the energy on compressed columns)
+    pack(B.loc);
+    dot_trace(B.loc, D.loc, out, &out[2], B.c0);
+    out[1] = 0.0;
+    complex_fusion_counts()[mode == 1 ? 0 : 1] += 1;
+    return true;
+  }
+  complex_fusion_counts()[mode == 1 ? 0 : 1] += 1;
+  out[0] = dot[0];
+  out[1] = 0.0;
+  out[2] = tr;
+  return true;
+}
+bool complex_trs2_step(PSMatrix& B, int mode, double threshold, const PSMatrix& D, double out[4]) {
+  if (!B.cplx || !D.cplx || options().complex_density == 0 || options().complex_sessions == 0 || options().spgemm_fma != 1 ||
+      options().complex_tile == 0 || options().spgemm_variant >= 0 || options().spgemm_force_bin > 0 || world().active() ||
+      (B.grid && B.grid->num_slices > 1) || block_scope_active())
+    return false;
+  if (B.loc.loose() || D.loc.blocked() || D.loc.loose() || B.dim != B.loc.cols || B.loc.nnz == 0 ||
+      D.loc.rows != B.loc.rows || D.loc.cols != B.loc.cols || (D.loc.expanded() && (D.loc.slab->labelled() || D.loc.slab->origin)))
+    return false;
+  if (ctrs2_off_for(D)) return false;
+  const double denom = (double)B.dim * (double)B.dim;
+  const bool dense_rule = denom > 0 && (double)B.loc.nnz / denom > 0.1;
+  if (B.loc.blocked()) return complex_trs2_block(B, mode, threshold, dense_rule, D, out);
+  if (!B.loc.expanded()) {
+    bool not_runs = false;
+    if (!slab_enter_c(B.loc, &not_runs)) {
+      if (!not_runs) return false;   // (stored zeros: this step the old way)
+      if (complex_trs2_block(B, mode, threshold, dense_rule, D, out)) return true;
+      ctrs2_set_off(D);
+      return false;
+    }
+  }
+  if (!sa_operand_c(B.loc) || B.loc.zero_free != 1) {
+    pack(B.loc);
+    return false;
+  }
+  DevMat P;
+  bool ok = slab_multiply_c(B.loc, B.loc, P, 1.0, threshold, dense_rule);
+  if (!ok) ctrs2_set_off(D);   // (the product's geometry does not fit the complex tile kernel: it will not next time either)
+  if (ok && mode == 2) ok = slab_axpby_c(P, B.loc, -1.0, 2.0, threshold);   // (refused: B is the iterate the step started from)
+  if (!ok) {
+    complex_fusion_counts()[2] += 1;
+    pack(B.loc);
+    return false;
+  }
+  if (mode == 1) B.loc = std::move(P);
+  double dot[2] = {0.0, 0.0}, tr = 0.0;
+  slab_dot_trace_c(B.loc, &D.loc, B.c0, dot, &tr);   // (takes every operand admitted above)
+  complex_fusion_counts()[mode == 1 ? 0 : 1] += 1;
+  out[0] = dot[0];
+  out[1] = 0.0;
+  out[2] = tr;
+  return true;
+}
+}  // namespace
+
+void trs2_complex_reset() { g_ctrs2_off = CtrsOff(); }
+
 void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMatrix& D, double out[4], bool want_trace) {
   CommScope cs(D.grid);
   out[2] = out[3] = 0.0;
+  if (complex_trs2_step(B, 2, threshold, D, out)) return;
   if (trs2_block(B, 2, threshold, D, out)) return;
   trs2_iterate_form(B);
   // (process slices: the K-split sums of ps_multiply; a solve in a block order across ranks, band_scope.cpp: the panel product
@@ -1602,6 +1700,7 @@ void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, cons
 void ps_square_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMatrix& D, double out[4], bool want_trace) {
   CommScope cs(D.grid);
   out[2] = out[3] = 0.0;
+  if (complex_trs2_step(B, 1, threshold, D, out)) return;
   if (trs2_block(B, 1, threshold, D, out)) return;
   trs2_iterate_form(B);
   const bool keep_loose = !world().active() && options().loose_iterates != 0 && !B.cplx && !D.cplx &&

@@ -469,6 +469,93 @@ bool slab_trace(const DevMat& A, int32_t col_offset, double* out) {
   return true;
 }
 
+// ------------------------------------------------------------------ complex dot and trace of a slab-form matrix
+// (complex TRS2 steps: DotMatrix = sum conj(a) b, MatrixTrace = sum of the real parts of the diagonal)
+namespace {
+// one wave per column j of the complex slab-form A: (Re, Im) of sum_r conj(A(r, j)) B(r, j) into dpart[2 j], (Re A(j + col_offset,
+// j), 0) into tpart[2 j].  B in complex slab form (BSLAB) or in packed compressed columns (a Hamiltonian that never entered
+// slab form); B == nullptr: the trace only.  Fixed shapes (a wave sum per column, then sum_pairs_async): reproducible sums.
+template <bool BSLAB>
+__global__ __launch_bounds__(256) void k_sa_dot_trace_c(int n, const int32_t* __restrict__ fa, const int32_t* __restrict__ la,
+                                                        const int64_t* __restrict__ offa, const double2* __restrict__ va,
+                                                        const int32_t* __restrict__ fb, const int32_t* __restrict__ lb,
+                                                        const int64_t* __restrict__ offb, const double2* __restrict__ vb, Csc bc,
+                                                        int col_offset, double* __restrict__ dpart, double* __restrict__ tpart) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id();
+  const int f = fa[j], l = la[j];
+  const double2* __restrict__ pa = va + (offa[j] - f);   // (row r of column j at pa[r], r in [f, l])
+  double sr = 0.0, si = 0.0;
+  if (dpart && l >= f) {
+    if constexpr (BSLAB) {
+      const int g0 = max(f, fb[j]), g1 = min(l, lb[j]);
+      if (g1 >= g0) {
+        const double2* __restrict__ pb = vb + (offb[j] - fb[j]);
+        for (int r = g0 + lane; r <= g1; r += WAVE) {
+          const double2 a = pa[r], b = pb[r];
+          sr = __dadd_rn(sr, __dadd_rn(__dmul_rn(a.x, b.x), __dmul_rn(a.y, b.y)));
+          si = __dadd_rn(si, __dsub_rn(__dmul_rn(a.x, b.y), __dmul_rn(a.y, b.x)));
+        }
+      }
+    } else {
+      const double2* __restrict__ bv = reinterpret_cast<const double2*>(bc.val);
+      for (int64_t p = bc.outer[j] + lane, e = bc.outer[j + 1]; p < e; p += WAVE) {
+        const int r = bc.inner[p];
+        if (r < f || r > l) continue;
+        const double2 a = pa[r], b = bv[p];
+        sr = __dadd_rn(sr, __dadd_rn(__dmul_rn(a.x, b.x), __dmul_rn(a.y, b.y)));
+        si = __dadd_rn(si, __dsub_rn(__dmul_rn(a.x, b.y), __dmul_rn(a.y, b.x)));
+      }
+    }
+  }
+  if (dpart) {
+    sr = wave_sum_f64(sr);
+    si = wave_sum_f64(si);
+  }
+  if (lane == 0) {
+    if (dpart) { dpart[2 * (size_t)j] = sr; dpart[2 * (size_t)j + 1] = si; }
+    const int d = j + col_offset;
+    tpart[2 * (size_t)j] = (l >= f && d >= f && d <= l) ? pa[d].x : 0.0;
+    tpart[2 * (size_t)j + 1] = 0.0;
+  }
+}
+}  // namespace
+
+bool slab_dot_trace_c(const DevMat& A, const DevMat* B, int32_t col_offset, double dot[2], double* trace) {
+  if (!A.expanded() || !A.cplx || A.slab->labelled() || A.slab->origin) return false;
+  if (B) {
+    if (!B->cplx || B->cols != A.cols || B->rows != A.rows || B->blocked() || B->loose()) return false;
+    if (B->expanded() && (B->slab->labelled() || B->slab->origin)) return false;
+  }
+  const SlabForm& fa = *A.slab;
+  const int n = A.cols;
+  const bool bslab = B && B->expanded();
+  DevBuf<double> dpart(B ? (size_t)2 * n : 2), tpart((size_t)2 * n), res(4);
+  const SlabForm* fb = bslab ? B->slab.get() : nullptr;
+  const Csc bc = (B && !bslab) ? view(*B) : Csc{0, 0, nullptr, nullptr, nullptr};
+  const double2* va = reinterpret_cast<const double2*>(fa.val.p);
+  auto go = [&](auto slab_tag) {
+    constexpr bool S = decltype(slab_tag)::value;
+    hipLaunchKernelGGL((k_sa_dot_trace_c<S>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p, va,
+                       fb ? fb->first.p : nullptr, fb ? fb->last.p : nullptr, fb ? fb->off.p : nullptr,
+                       fb ? reinterpret_cast<const double2*>(fb->val.p) : nullptr, bc, col_offset, B ? dpart.p : nullptr, tpart.p);
+  };
+  if (bslab) go(std::true_type{});
+  else go(std::false_type{});
+  if (B) sum_pairs_async(dpart.p, n, res.p);
+  sum_pairs_async(tpart.p, n, res.p + 2);
+  unsigned long long h[4] = {0, 0, 0, 0};
+  ScalarFetch ft;
+  ft.add(res.p + (B ? 0 : 2), B ? 4 : 2, B ? h : h + 2);
+  ft.run();
+  double d[4];
+  std::memcpy(d, h, sizeof(d));
+  if (B) { dot[0] = d[0]; dot[1] = d[1]; }
+  if (trace) *trace = d[2];
+  return true;
+}
+
 // ------------------------------------------------------------------ how dense the runs are
 namespace {
 __global__ __launch_bounds__(256) void k_sa_span_sum(const int32_t* __restrict__ first, const int32_t* __restrict__ last, int n,

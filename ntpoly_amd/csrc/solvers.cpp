@@ -283,6 +283,7 @@ void solver_trs2(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
   auto t1 = Clock::now();
   double energy_value = 0.0, energy_old;
   double trace_x = std::nan("");  // trace of the current iterate, handed from step to step
+  trs2_complex_reset();
   int II;
   for (II = 1; II <= p.max_iterations; ++II) {                     // :380-413
     energy_old = energy_value;

@@ -1,7 +1,8 @@
 // Block-sparse SpGEMM on the FP64 matrix cores for operands WITHOUT run structure (spgemm_block.hip): 3-D Hamiltonians,
 // bands hidden under a relabelling.  Internal interface between spgemm() in kernels.hip, psmatrix.cpp and that
 // translation unit.  FMA arithmetic only (option spgemm_fma = 1), square operands on one rank; complex ones with options
-// complex_tile = 1 and block_complex = 1 (products and the block algebra; the TRS2 step in block form is real).
+// complex_tile = 1 and block_complex = 1 (products and the block algebra; block_trs2_step is real -- a complex TRS2 step in block form is composed from
+// spgemm_block, block_axpby and block_dot_trace in psmatrix.cpp complex_trs2_step).
 #pragma once
 #include <memory>
 #include <vector>

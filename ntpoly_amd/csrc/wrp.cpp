@@ -182,6 +182,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "block_scope_complex") options().block_scope_complex = *value;
   else if (n == "panel_sessions") options().panel_sessions = *value;
   else if (n == "complex_panels") options().complex_panels = *value;
+  else if (n == "complex_density") options().complex_density = *value;
   else if (n == "label_rowoff") options().label_rowoff = *value;
   else if (n == "block_path") options().block_path = *value;
   else if (n == "tile_runs_only") options().tile_runs_only = *value;
@@ -215,6 +216,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "block_scope_complex") return options().block_scope_complex;
   if (n == "panel_sessions") return options().panel_sessions;
   if (n == "complex_panels") return options().complex_panels;
+  if (n == "complex_density") return options().complex_density;
   if (n == "fused_update") return options().fused_update;
   if (n == "loose_iterates") return options().loose_iterates;
   if (n == "complex_tile") return options().complex_tile;
@@ -298,6 +300,10 @@ int ntpoly_amd_band_order(const int* ih, int* newpos, long long* bandwidth) {
 // to be repeated on the unfused path, since start
 void ntpoly_amd_fusion_counts(long long* out) {
   for (int q = 0; q < 3; ++q) out[q] = fusion_counts()[q];
+}
+// out[0..2]: complex TRS2 steps done in complex slab or block form (X*X; 2X - X*X) and such steps repeated the old way, since start
+void ntpoly_amd_complex_fusion_counts(long long* out) {
+  for (int q = 0; q < 3; ++q) out[q] = complex_fusion_counts()[q];
 }
 // out[0] = multiplies computed in the two-block geometry of the MFMA kernel (spgemm_tile2.hip) since start, out[1] = launches
 // of it whose geometry did not fit after all and were repeated on k_spgemm_tile

@@ -920,6 +920,14 @@ def fusion_counts():
     return dict(square=out[0], update=out[1], repeated=out[2])
 
 
+def complex_fusion_counts():
+    """complex TRS2 steps X*X and 2X - X*X done in complex slab or block form (product, merge and energy pass -- not a fused
+    tile epilogue), and such steps repeated the old way"""
+    out = (C.c_longlong * 3)()
+    lib.ntpoly_amd_complex_fusion_counts(out)
+    return dict(square=out[0], update=out[1], repeated=out[2])
+
+
 def tile2_counts():
     """(multiplies computed in the two-block geometry of the MFMA kernel, launches of it repeated on k_spgemm_tile)"""
     out = (C.c_longlong * 2)()
