@@ -9,6 +9,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <numeric>
+#include <optional>
 #include <random>
 
 #include "engine.hpp"
@@ -152,18 +153,21 @@ void panel_range(int32_t dim, int nranks, int rank, int32_t* c0, int32_t* c1) {
 // last row of rank q's panel of B, ...), cnt[s P + q] = doubles rank s sends to rank q.  sa / sb [q]: my columns [sa, sb) go to
 // rank q, packed from soff[q] in my send buffer; ra / rb [s]: the columns [ra, rb) of rank s arrive at zoff[s] of my receive
 // buffer (nothing travels from a rank to itself).  Pure host arithmetic (tests/test_distributed_cpu.py drives it over gloo).
+namespace {
+// the rows [kmin, kmax] that rank q's request names (an empty panel: kmax < kmin)
+int32_t req_kmin(const int64_t* req, int q) { const int64_t lo = req[(size_t)4 * q], hi = req[(size_t)4 * q + 1]; return hi < lo ? 0 : (int32_t)lo; }
+int32_t req_kmax(const int64_t* req, int q) { const int64_t lo = req[(size_t)4 * q], hi = req[(size_t)4 * q + 1]; return hi < lo ? -1 : (int32_t)hi; }
+}  // namespace
 void panel_exchange_layout(int32_t dim, int P, int me, const int64_t* req, const int64_t* cnt, int32_t* sa, int32_t* sb, int64_t* soff,
                            int32_t* ra, int32_t* rb, int64_t* zoff) {
-  auto kmin_of = [&](int q) { const int64_t lo = req[(size_t)4 * q], hi = req[(size_t)4 * q + 1]; return hi < lo ? 0 : (int32_t)lo; };
-  auto kmax_of = [&](int q) { const int64_t lo = req[(size_t)4 * q], hi = req[(size_t)4 * q + 1]; return hi < lo ? -1 : (int32_t)hi; };
   soff[0] = 0;
   zoff[0] = 0;
   for (int q = 0; q < P; ++q) {
-    halo_segment(dim, P, me, kmin_of(q), kmax_of(q), &sa[q], &sb[q]);
+    halo_segment(dim, P, me, req_kmin(req, q), req_kmax(req, q), &sa[q], &sb[q]);
     soff[q + 1] = soff[q] + (q == me ? 0 : cnt[(size_t)me * P + q]);
   }
   for (int s = 0; s < P; ++s) {
-    halo_segment(dim, P, s, kmin_of(me), kmax_of(me), &ra[s], &rb[s]);
+    halo_segment(dim, P, s, req_kmin(req, me), req_kmax(req, me), &ra[s], &rb[s]);
     zoff[s + 1] = zoff[s] + (s == me ? 0 : cnt[(size_t)s * P + me]);
   }
 }
@@ -182,6 +186,18 @@ void ps_construct_empty(PSMatrix& m, int32_t dim, const ProcessGrid* g, bool cpl
 void ps_construct_like(PSMatrix& m, const PSMatrix& ref) { ps_construct_empty(m, ref.dim, ref.grid, ref.cplx); }
 
 namespace {
+// the header and the local panel of a result
+void install(PSMatrix& X, const ProcessGrid* grid, int32_t dim, bool cplx, int32_t c0, int32_t c1, DevMat&& loc) {
+  X.grid = grid; X.dim = dim; X.cplx = cplx; X.c0 = c0; X.c1 = c1;
+  X.loc = std::move(loc);
+}
+// dense-branch rule of the local multiply (GemmMatrix.f90:49-61) from the operands' entry counts; a_fraction: the share of the
+// inner dimension A is populated over (multiply_panel)
+bool dense_branch(int32_t dim, int64_t nnz_a, int64_t nnz_b, double a_fraction = 1.0) {
+  const double denom = (double)dim * (double)dim;
+  return denom > 0 && std::min((double)nnz_a / (denom * a_fraction), (double)nnz_b / denom) > 0.1;
+}
+bool beta_is_zero(double beta) { return std::fabs(beta) < 2.2250738585072014e-308; }
 int g_slab_depth = 0;
 bool g_slab_failed = false;
 bool slab_on() { return g_slab_depth > 0 && !g_slab_failed; }
@@ -190,6 +206,29 @@ DevMat& mut(const PSMatrix& m) { return const_cast<DevMat&>(m.loc); }
 int g_slab_refusals = 0;
 bool g_complex_session = false;   // the open session's loop takes complex operands in slab form (SlabSession complex_ok)
 long long g_slab_counts[4] = {0, 0, 0, 0};   // products, merges / copies, other operations in slab form; refusals
+// the slab algebra of one element kind, for the operations that exist for both (kernels.hpp: name, name_c)
+struct SlabKind {
+  bool (*enter)(DevMat&);
+  bool (*multiply)(const DevMat&, const DevMat&, DevMat&, double, double, bool, const SlabHalo*);
+  bool (*takes_panel)(const DevMat&, const DevMat&, int, int32_t, int32_t, const SlabPlan*);
+  bool (*clone)(const DevMat&, DevMat&);
+  bool (*scale)(DevMat&, double);
+  bool (*axpby)(const DevMat&, DevMat&, double, double, double);
+  bool (*axpby_to)(const DevMat&, const DevMat&, DevMat&, double, double, double);
+  bool (*add_diagonal)(DevMat&, double, int32_t);
+  bool (*norm)(const DevMat&, double*);
+  bool (*norm_axpby)(const DevMat&, const DevMat&, double, double, double*);
+};
+const SlabKind& slab_kind(bool cplx) {
+  static const SlabKind kinds[2] = {
+      {slab_enter, slab_multiply, slab_multiply_takes_panel, slab_clone, slab_scale, slab_axpby, slab_axpby_to, slab_add_diagonal, slab_norm,
+       slab_norm_axpby},
+      {[](DevMat& M) { return slab_enter_c(M); }, slab_multiply_c, slab_multiply_c_takes_panel, slab_clone_c, slab_scale_c, slab_axpby_c,
+       slab_axpby_to_c, slab_add_diagonal_c, slab_norm_c, slab_norm_axpby_c}};
+  return kinds[cplx ? 1 : 0];
+}
+// this session takes operands of this kind in slab form
+bool session_takes(bool cplx) { return !cplx || g_complex_session; }
 // an operation that cannot be done in slab form: its operands go back to compressed columns and the general path does
 // it (a Hamiltonian with stored zeros in the first merge of a loop); the session goes on, unless this keeps happening
 void slab_refused(std::initializer_list<const PSMatrix*> ms) {
@@ -282,39 +321,23 @@ void ps_copy(const PSMatrix& a, PSMatrix& b) {
     DevMat t;
     if (block_clone(a.loc, t)) {
       g_block_counts[0] += 1;
-      b.grid = a.grid; b.dim = a.dim; b.cplx = a.cplx; b.c0 = a.c0; b.c1 = a.c1;
-      b.loc = std::move(t);
+      install(b, a.grid, a.dim, a.cplx, a.c0, a.c1, std::move(t));
       return;
     }
     g_block_counts[1] += 1;
   }
   unblock({&a});
-  if (slab_on() && g_complex_session && a.cplx && a.loc.expanded()) {   // (a session that takes complex operands)
-    DevMat t;
-    if (slab_clone_c(a.loc, t)) {
-      g_slab_counts[1] += 1;
-      b.grid = a.grid; b.dim = a.dim; b.cplx = true; b.c0 = a.c0; b.c1 = a.c1;
-      b.loc = std::move(t);
-      return;
-    }
-  }
   if (slab_on() && a.loc.expanded()) {
+    // (a complex operand outside a session that takes them is refused: the real slab_clone declines it untouched)
     DevMat t;
-    if (slab_clone(a.loc, t)) {
+    if (session_takes(a.cplx) && slab_kind(a.cplx).clone(a.loc, t)) {
       g_slab_counts[1] += 1;
-      b.grid = a.grid; b.dim = a.dim; b.cplx = a.cplx; b.c0 = a.c0; b.c1 = a.c1;
-      b.loc = std::move(t);
+      install(b, a.grid, a.dim, a.cplx, a.c0, a.c1, std::move(t));
       return;
     }
     slab_refused({&a});
   }
-  DevMat t = a.loc.clone();
-  b.grid = a.grid;
-  b.dim = a.dim;
-  b.cplx = a.cplx;
-  b.c0 = a.c0;
-  b.c1 = a.c1;
-  b.loc = std::move(t);
+  install(b, a.grid, a.dim, a.cplx, a.c0, a.c1, a.loc.clone());
 }
 
 void ps_fill_identity(PSMatrix& m) {
@@ -522,17 +545,11 @@ int64_t ps_size(const PSMatrix& m) {
 
 void ps_to_complex(const PSMatrix& a, PSMatrix& out) {
   CommScope cs(a.grid);
-  DevMat t = to_complex(a.loc);
-  out.grid = a.grid; out.dim = a.dim; out.c0 = a.c0; out.c1 = a.c1;
-  out.cplx = true;
-  out.loc = std::move(t);
+  install(out, a.grid, a.dim, true, a.c0, a.c1, to_complex(a.loc));
 }
 void ps_to_real(const PSMatrix& a, PSMatrix& out) {
   CommScope cs(a.grid);
-  DevMat t = to_real(a.loc);
-  out.grid = a.grid; out.dim = a.dim; out.c0 = a.c0; out.c1 = a.c1;
-  out.cplx = false;
-  out.loc = std::move(t);
+  install(out, a.grid, a.dim, false, a.c0, a.c1, to_real(a.loc));
 }
 
 // ------------------------------------------------------------------ algebra
@@ -542,84 +559,234 @@ void ps_to_real(const PSMatrix& a, PSMatrix& out) {
 // there is no reduction step (slices == 1 semantics: working_threshold = threshold,
 // distributed_algebra_includes/MatrixMultiply.f90:25-29).
 namespace {
-bool exchange_fits_fetch(int P);
-int panel_pitch(int32_t dim, int P, bool with_counts, int* wcols_out);
 long long g_block_scope_products = 0;   // panel products of block-order solves (band_scope.cpp) that took the block path
 long long g_panel_products[3] = {0, 0, 0};   // products of slab sessions across ranks: done in slab form on every rank; declined; host synchronisations inside the former
+
+int panel_pitch(int32_t dim, int P, bool with_counts, int* wcols_out) {
+  int32_t maxw = 0;
+  for (int q = 0; q < P; ++q) {
+    int32_t a0, a1;
+    panel_range(dim, P, q, &a0, &a1);
+    maxw = std::max(maxw, a1 - a0);
+  }
+  // ONE all-gather per step: every rank contributes a record of `pitch` 8-byte words -- its request (4 words), the
+  // packed extents of its columns, the prefix sums of their spans and, for the statistics (timers on), their entry
+  // counts; the kernels below read the sections through the common stride
+  *wcols_out = maxw + 1;
+  return 4 + (with_counts ? 3 : 2) * (maxw + 1);
+}
+// the all-gather of a step's record by a rank that has nothing to say: the others discard what they gather (collective)
+void owed_allgather(int32_t dim) {
+  const int P = world().nranks;
+  int wcols = 0;
+  const int pitch = panel_pitch(dim, P, options().time_kernels != 0, &wcols);
+  DevBuf<int64_t> dummy((size_t)P * pitch);
+  dummy.zero();
+  world().tr->allgather(dummy.p + (size_t)world().rank * pitch, dummy.p, (size_t)pitch * sizeof(int64_t));
+  sync_stream();
+}
+bool exchange_fits_fetch(int P) { return (size_t)4 * P + (size_t)P * P + 2 * P <= 400; }
+
+// The exchange of the left operand's halo as dense column runs, for a panel product (panel_slab_multiply) and for a panel step
+// (slab_exchange_and_step).  What it must know before the halo can travel -- every rank's request, the column extents of the
+// whole left operand, who sends how much to whom, the kernel's plan -- is a function of column extents alone.  It is PREPARED
+// on the device (one all-gather, three small kernels) and read back in one round trip: at the start of a product or a step,
+// or -- for every step after the first -- by the step BEFORE it, from its result's extents, on that step's own read-back
+// (SlabHalo::before_fetch): a panel step then costs ONE host round trip, as a step on one rank does.  Then: exchange() (layout,
+// packing, one send / recv group), halo() (the layout of the columns this rank multiplies with).  The buffers live as long as
+// the object: until the caller's kernel has returned (the allocator is stream ordered, and the kernels end with a read-back).
+struct PanelExchange {
+  int P = 0, me = 0, pitch = 0, wcols = 0, snb = 0;
+  int32_t dim = 0;
+  bool with_counts = false;
+  bool step = false;      // a step's record (its bound is read back), not a product's
+  bool planned = false;   // this rank's panel is in slab form: its plan was made
+  DevBuf<int64_t> d_all, d_req, d_bound, d_cnt, plan_stats;
+  SlabPlan plan;
+  DevBuf<int32_t> gfirst, glast;
+  std::vector<int64_t> req, bound, cnt;
+  unsigned long long plan_hs[2] = {0, 0};
+  const void* owner = nullptr;   // the value buffer of the iterate (in slab form) it was prepared for ...
+  unsigned long long owner_serial = 0;   // ... and that buffer's allocation serial: an address alone comes back from the caching allocator
+  // exchange(): the rows this rank's request names; what it sends (its columns [sa, sb) inside every requester's range, packed
+  // from soff) and what it receives (the segments [ra, rb) of the other owners tile [kmin, kmax] in rank order, at zoff)
+  int32_t kmin = 0, kmax = -1;
+  std::vector<int32_t> sa, sb, ra, rb;
+  std::vector<int64_t> soff, zoff;
+  DevBuf<double> sendbuf, recvbuf;
+  // halo(): the layout of the columns kmin .. kmax
+  DevBuf<int32_t> d_ra, nfirst, nlast, ncount;
+  DevBuf<int64_t> d_zoff;
+  DevBuf<unsigned long long> naddr;
+  const int64_t* d_ext_all() const { return d_all.p + 4; }
+  const int64_t* d_pre_all() const { return d_all.p + 4 + wcols; }
+  const int64_t* d_cnt_all() const { return with_counts ? d_all.p + 4 + 2 * (size_t)wcols : nullptr; }
+
+  // enqueues the preparation (collective).  A step (left == nullptr): request, extents and counts of the iterate `right` in one
+  // pass (d_nnz: its entry count is still on the device).  A product: the request from the rows of `right`, the extents of
+  // `left`, word 3 = entries of left * 4096 + the alignment of its runs; !can: this rank's panels are not in slab form
+  // (entries -1).  cplx: plan blocks of SLAB_CJ = 8 columns instead of SLAB_J = 16.
+  void prepare(const DevMat& right, const DevMat* left, bool cplx, bool can, int32_t dim_, const long long* d_nnz) {
+    Comm& c = world();
+    P = c.nranks;
+    me = c.rank;
+    dim = dim_;
+    step = left == nullptr;
+    planned = can;
+    with_counts = step && options().time_kernels != 0;
+    pitch = panel_pitch(dim, P, with_counts, &wcols);
+    snb = cplx ? (right.cols + 7) / 8 : (right.cols + 15) / 16;
+    req.assign((size_t)4 * P, 0);
+    bound.assign((size_t)2 * P, 0);
+    cnt.assign((size_t)P * P, 0);
+    d_all.alloc((size_t)P * pitch);
+    d_req.alloc((size_t)4 * P);
+    d_bound.alloc((size_t)2 * P);
+    d_cnt.alloc((size_t)P * P);
+    int64_t* mine = d_all.p + (size_t)me * pitch;
+    if (step) {
+      slab_export_async(right, mine, d_nnz, mine + 4, mine + 4 + wcols, with_counts ? mine + 4 + 2 * (size_t)wcols : nullptr);
+    } else if (can) {
+      slab_request_async(right, mine);
+      slab_extents_async(*left, mine + 4, mine + 4 + wcols);
+      const long long w3 = (long long)left->nnz * 4096 + left->slab->row_pad;
+      HIP_CHECK(hipMemcpyAsync(mine + 3, &w3, sizeof(w3), hipMemcpyHostToDevice, stream()));
+    } else {
+      const long long rec[4] = {INT_MAX, -1, -1, 0};
+      HIP_CHECK(hipMemsetAsync(mine, 0, (size_t)pitch * sizeof(int64_t), stream()));
+      HIP_CHECK(hipMemcpyAsync(mine, rec, sizeof(rec), hipMemcpyHostToDevice, stream()));
+    }
+    c.tr->allgather(mine, d_all.p, (size_t)pitch * sizeof(int64_t));
+    HIP_CHECK(hipMemcpy2DAsync(d_req.p, 4 * sizeof(int64_t), d_all.p, (size_t)pitch * sizeof(int64_t), 4 * sizeof(int64_t), (size_t)P,
+                               hipMemcpyDeviceToDevice, stream()));
+    halo_counts_async(d_req.p, d_pre_all(), pitch, dim, P, me, d_cnt.p, d_bound.p);   // (counts in doubles)
+    // the kernel's plan (block windows and k ranges follow from the extents alone) is made here, from the gathered extents of
+    // the left operand and the extents of this rank's right panel, so that its sizes come back in the same read-back as the
+    // exchange layout -- a product then needs ONE more host round trip (its entry count), as on one rank
+    plan_stats.alloc(24);
+    if (can) {
+      plan_stats.zero();
+      slab_plan_panel_async(right, d_ext_all(), pitch, dim, P, plan, gfirst, glast, reinterpret_cast<unsigned long long*>(plan_stats.p));
+    }
+    if (step) {
+      owner = right.slab->val.p;
+      owner_serial = dev_alloc_serial(right.slab->val.p);
+    }
+  }
+  // what the host needs of the preparation, on a read-back of the caller's
+  void add_to(ScalarFetch& f) {
+    f.add(d_req.p, 4 * P, req.data());
+    if (step) f.add(d_bound.p, 2 * P, bound.data());
+    f.add(d_cnt.p, P * P, cnt.data());
+    if (planned) {
+      f.add(plan.blk_toff.p + snb, 1, &plan.total);
+      f.add(plan_stats.p + 16, 2, plan_hs);
+    }
+  }
+  // ... or on one of its own
+  void fetch() {
+    if (exchange_fits_fetch(P)) {
+      ScalarFetch f;
+      add_to(f);
+      f.run();
+      return;
+    }
+    // (too many ranks for one fetch: plain copies)
+    HIP_CHECK(hipMemcpyAsync(req.data(), d_req.p, (size_t)4 * P * 8, hipMemcpyDeviceToHost, stream()));
+    if (step) HIP_CHECK(hipMemcpyAsync(bound.data(), d_bound.p, (size_t)2 * P * 8, hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipMemcpyAsync(cnt.data(), d_cnt.p, (size_t)P * P * 8, hipMemcpyDeviceToHost, stream()));
+    if (planned) {
+      HIP_CHECK(hipMemcpyAsync(&plan.total, plan.blk_toff.p + snb, 8, hipMemcpyDeviceToHost, stream()));
+      HIP_CHECK(hipMemcpyAsync(plan_hs, plan_stats.p + 16, 16, hipMemcpyDeviceToHost, stream()));
+    }
+    sync_stream();
+  }
+  // the preparation is back: the runs of the requested columns of `left` (this rank's panel of the left operand, first column
+  // c0) packed per requester, one send / recv group (collective)
+  void exchange(const DevMat& left, int32_t c0) {
+    plan.max_w = (int)plan_hs[0];
+    plan.max_kn = (int)plan_hs[1];
+    kmin = req_kmin(req.data(), me);
+    kmax = req_kmax(req.data(), me);
+    // panel_exchange_layout: host arithmetic on the gathered requests and counts
+    sa.resize((size_t)P); sb.resize((size_t)P); ra.resize((size_t)P); rb.resize((size_t)P);
+    soff.assign((size_t)P + 1, 0);
+    zoff.assign((size_t)P + 1, 0);
+    panel_exchange_layout(dim, P, me, req.data(), cnt.data(), sa.data(), sb.data(), soff.data(), ra.data(), rb.data(), zoff.data());
+    sendbuf.alloc((size_t)soff[(size_t)P] + 1);
+    for (int q = 0; q < P; ++q)
+      if (q != me && cnt[(size_t)me * P + q] > 0)
+        slab_pack_runs_async(left, d_pre_all() + (size_t)me * pitch, sa[(size_t)q] - c0, sb[(size_t)q] - c0, sendbuf.p + soff[(size_t)q]);
+    recvbuf.alloc((size_t)zoff[(size_t)P] + kIndexSlack);
+    Transport& tr = *world().tr;
+    tr.group_begin();
+    for (int q = 0; q < P; ++q) {
+      const int64_t m = cnt[(size_t)me * P + q];
+      if (q != me && m > 0) tr.send(sendbuf.p + soff[(size_t)q], (size_t)m * sizeof(double), q);
+    }
+    for (int s = 0; s < P; ++s) {
+      const int64_t m = cnt[(size_t)s * P + me];
+      if (s != me && m > 0) tr.recv(recvbuf.p + zoff[(size_t)s], (size_t)m * sizeof(double), s);
+    }
+    tr.group_end();
+  }
+  // layout of the columns kmin .. kmax this rank multiplies with (kmax >= kmin): extents and run addresses, in `left` or in the
+  // receive buffer, whose runs sit in slots aligned to row_pad rows
+  SlabHalo halo(const DevMat& left, int row_pad) {
+    const int32_t ka = kmin, kb = kmax + 1;
+    d_ra.alloc((size_t)P); nfirst.alloc((size_t)(kb - ka)); nlast.alloc((size_t)(kb - ka));
+    d_zoff.alloc((size_t)P);
+    naddr.alloc((size_t)(kb - ka));
+    if (P > 16) {   // (up to 16 ranks the segments travel as kernel arguments)
+      d_ra.upload(ra.data(), (size_t)P);
+      d_zoff.upload(zoff.data(), (size_t)P);
+    }
+    if (d_cnt_all()) ncount.alloc((size_t)(kb - ka));
+    slab_halo_layout_async(d_ext_all(), d_pre_all(), pitch, dim, P, me, ka, kb, d_ra.p, d_zoff.p, recvbuf.p, left, nfirst.p, nlast.p, naddr.p,
+                           d_cnt_all(), ncount.p, ra.data(), zoff.data());
+    SlabHalo h;
+    h.ka = ka;
+    h.kb = kb;
+    h.first = nfirst.p;
+    h.last = nlast.p;
+    h.addr = naddr.p;
+    h.count = ncount.p;
+    h.row_pad = row_pad;
+    h.plan = &plan;
+    return h;
+  }
+};
+std::unique_ptr<PanelExchange> g_pending_exchange;
+long long g_exchange_prefetched = 0;   // panel steps whose exchange layout came with the step before
+}  // namespace
+// the preparation a step left for a successor that never came (the last step of a solve or of a bench block): P * pitch * 8
+// bytes of device memory and a stale layout -- dropped where a solve begins and ends and with the operand caches
+void drop_pending_exchange() { g_pending_exchange.reset(); }
+namespace {
 
 // C = alpha A B of a slab session on more than one rank: A, B column panels in slab form, the result a column panel in slab
 // form (MatrixMultiply.f90:92-267 gathers blocks of both operands along the grid; here the rows of B's panel name the columns
 // of A that have to travel, as dense runs).  Protocol, all on the engine stream: (1) ONE all-gather of a record per rank --
 // request (first / last row of B's panel, entries of B, entries of A and the alignment of its runs; -1: this rank's panels are
 // not in slab form), packed extents of A's columns, prefix sums of their spans; (2) who sends how many doubles to whom, one
-// read-back; (3) the runs of the requested columns packed per requester, one send / recv group; (4) layout of the columns this
-// rank multiplies with, the tile kernel on them (slab_multiply with a left halo); (5) one reduction: did every rank's kernel
-// take its panel.  Collective; false (every rank alike): nothing done, the caller takes the compressed-column path.
+// read-back (PanelExchange prepare, fetch); (3) the runs of the requested columns packed per requester, one send / recv group
+// (exchange); (4) layout of the columns this rank multiplies with (halo), the tile kernel on them (slab_multiply with a left
+// halo); (5) one reduction: did every rank's kernel take its panel.  Collective; false (every rank alike): nothing done, the
+// caller takes the compressed-column path.
 bool panel_slab_multiply(const PSMatrix& A, const PSMatrix& B, DevMat& AB, double alpha, double threshold) {
-  Comm& c = world();
-  Transport& tr = *c.tr;
-  const int P = c.nranks, me = c.rank;
-  const int32_t dim = A.dim;
+  Transport& tr = *world().tr;
+  const int P = world().nranks;
   const long long syncs_before = host_sync_count();
   // (complex operands, a session that takes them: runs of (re, im) pairs -- twice the doubles per row in the exchange, a plan of
   // SLAB_CJ columns per block, the complex tile kernel)
-  const bool cplx = A.cplx;
-  auto enter = [cplx](const PSMatrix& M) { return cplx ? slab_enter_c(mut(M)) : slab_enter(mut(M)); };
-  const bool mine_ok = slab_on() && A.loc.nnz > 0 && B.loc.nnz > 0 && A.c0 == B.c0 && A.c1 == B.c1 && enter(A) &&
-                       (&A == &B || enter(B)) && A.loc.slab->row_pad % 16 == 0 && A.loc.slab->row_pad < 4096;
-  int wcols = 0;
-  const int pitch = panel_pitch(dim, P, false, &wcols);
-  DevBuf<int64_t> d_all((size_t)P * pitch), d_req((size_t)4 * P), d_bound((size_t)2 * P), d_cnt((size_t)P * P);
-  int64_t* mine = d_all.p + (size_t)me * pitch;
-  if (mine_ok) {
-    slab_request_async(B.loc, mine);
-    slab_extents_async(A.loc, mine + 4, mine + 4 + wcols);
-    const long long w3 = (long long)A.loc.nnz * 4096 + A.loc.slab->row_pad;
-    HIP_CHECK(hipMemcpyAsync(mine + 3, &w3, sizeof(w3), hipMemcpyHostToDevice, stream()));
-  } else {
-    const long long rec[4] = {INT_MAX, -1, -1, 0};
-    HIP_CHECK(hipMemsetAsync(mine, 0, (size_t)pitch * sizeof(int64_t), stream()));
-    HIP_CHECK(hipMemcpyAsync(mine, rec, sizeof(rec), hipMemcpyHostToDevice, stream()));
-  }
-  tr.allgather(mine, d_all.p, (size_t)pitch * sizeof(int64_t));
-  HIP_CHECK(hipMemcpy2DAsync(d_req.p, 4 * sizeof(int64_t), d_all.p, (size_t)pitch * sizeof(int64_t), 4 * sizeof(int64_t), (size_t)P,
-                             hipMemcpyDeviceToDevice, stream()));
-  const int64_t *d_ext_all = d_all.p + 4, *d_pre_all = d_all.p + 4 + wcols;
-  halo_counts_async(d_req.p, d_pre_all, pitch, dim, P, me, d_cnt.p, d_bound.p);   // (counts in doubles)
-  // the product's plan (block windows and k ranges follow from the extents alone) from the gathered extents of A and the
-  // extents of this rank's panel of B: its sizes come back with the exchange layout -- the product itself then needs ONE
-  // more host round trip (its entry count), as on one rank
-  SlabPlan plan;
-  DevBuf<int32_t> gfirst, glast;
-  DevBuf<int64_t> plan_stats(24);
-  unsigned long long plan_hs[2] = {0, 0};
-  const int snb = cplx ? (B.loc.cols + 7) / 8 : (B.loc.cols + 15) / 16;   // (blocks of SLAB_J / SLAB_CJ columns)
-  if (mine_ok) {
-    plan_stats.zero();
-    slab_plan_panel_async(B.loc, d_ext_all, pitch, dim, P, plan, gfirst, glast, reinterpret_cast<unsigned long long*>(plan_stats.p));
-  }
-  std::vector<int64_t> req((size_t)4 * P, 0), cnt((size_t)P * P, 0);
-  if (exchange_fits_fetch(P)) {
-    ScalarFetch f;
-    f.add(d_req.p, 4 * P, req.data());
-    f.add(d_cnt.p, P * P, cnt.data());
-    if (mine_ok) {
-      f.add(plan.blk_toff.p + snb, 1, &plan.total);
-      f.add(plan_stats.p + 16, 2, plan_hs);
-    }
-    f.run();
-  } else {
-    HIP_CHECK(hipMemcpyAsync(req.data(), d_req.p, (size_t)4 * P * 8, hipMemcpyDeviceToHost, stream()));
-    HIP_CHECK(hipMemcpyAsync(cnt.data(), d_cnt.p, (size_t)P * P * 8, hipMemcpyDeviceToHost, stream()));
-    if (mine_ok) {
-      HIP_CHECK(hipMemcpyAsync(&plan.total, plan.blk_toff.p + snb, 8, hipMemcpyDeviceToHost, stream()));
-      HIP_CHECK(hipMemcpyAsync(plan_hs, plan_stats.p + 16, 16, hipMemcpyDeviceToHost, stream()));
-    }
-    sync_stream();
-  }
-  plan.max_w = (int)plan_hs[0];
-  plan.max_kn = (int)plan_hs[1];
+  const SlabKind& k = slab_kind(A.cplx);
+  const bool mine_ok = slab_on() && A.loc.nnz > 0 && B.loc.nnz > 0 && A.c0 == B.c0 && A.c1 == B.c1 && k.enter(mut(A)) &&
+                       (&A == &B || k.enter(mut(B))) && A.loc.slab->row_pad % 16 == 0 && A.loc.slab->row_pad < 4096;
+  PanelExchange pe;
+  pe.prepare(B.loc, &A.loc, A.cplx, mine_ok, A.dim, nullptr);
+  pe.fetch();
   exchange_stats().exchanges += 1;
+  const std::vector<int64_t>& req = pe.req;
   int64_t nnz_a = 0, nnz_b = 0;
   bool all_ok = true;
   for (int q = 0; q < P; ++q) {
@@ -633,70 +800,23 @@ bool panel_slab_multiply(const PSMatrix& A, const PSMatrix& B, DevMat& AB, doubl
     return false;
   }
   const int row_pad = (int)(req[3] % 4096);
-  auto kmin_of = [&](int q) { int64_t lo = req[(size_t)4 * q], hi = req[(size_t)4 * q + 1]; return hi < lo ? 0 : (int32_t)lo; };
-  auto kmax_of = [&](int q) { int64_t lo = req[(size_t)4 * q], hi = req[(size_t)4 * q + 1]; return hi < lo ? -1 : (int32_t)hi; };
-  const int32_t kmin = kmin_of(me), kmax = kmax_of(me);
-  // what I send (my columns inside every requester's range, packed per requester) and what I receive (the segments of the
-  // other owners tile [kmin, kmax] in rank order): panel_exchange_layout, host arithmetic on the gathered requests and counts
-  std::vector<int32_t> sa((size_t)P), sb((size_t)P), ra((size_t)P), rb((size_t)P);
-  std::vector<int64_t> soff((size_t)P + 1, 0), zoff((size_t)P + 1, 0);
-  panel_exchange_layout(dim, P, me, req.data(), cnt.data(), sa.data(), sb.data(), soff.data(), ra.data(), rb.data(), zoff.data());
-  DevBuf<double> sendbuf((size_t)soff[(size_t)P] + 1);
-  for (int q = 0; q < P; ++q)
-    if (q != me && cnt[(size_t)me * P + q] > 0)
-      slab_pack_runs_async(A.loc, d_pre_all + (size_t)me * pitch, sa[(size_t)q] - A.c0, sb[(size_t)q] - A.c0, sendbuf.p + soff[(size_t)q]);
-  DevBuf<double> recvbuf((size_t)zoff[(size_t)P] + kIndexSlack);
-  tr.group_begin();
-  for (int q = 0; q < P; ++q) {
-    const int64_t m = cnt[(size_t)me * P + q];
-    if (q != me && m > 0) tr.send(sendbuf.p + soff[(size_t)q], (size_t)m * sizeof(double), q);
-  }
-  for (int s = 0; s < P; ++s) {
-    const int64_t m = cnt[(size_t)s * P + me];
-    if (s != me && m > 0) tr.recv(recvbuf.p + zoff[(size_t)s], (size_t)m * sizeof(double), s);
-  }
-  tr.group_end();
+  pe.exchange(A.loc, A.c0);
   // "did every rank's kernel take its panel": known to a rank once its plan is back; the sum over the ranks is enqueued
   // here and read back with the product's entry count
-  // (plan.max_w / max_kn are back: the SAME predicate slab_multiply applies -- a rank that agrees here cannot decline later)
-  plan.max_w = (int)plan_hs[0];
-  plan.max_kn = (int)plan_hs[1];
-  bool ok = mine_ok && kmax >= kmin &&
-            (cplx ? slab_multiply_c_takes_panel(A.loc, B.loc, row_pad, kmin, kmax + 1, &plan)
-                  : slab_multiply_takes_panel(A.loc, B.loc, row_pad, kmin, kmax + 1, &plan));
+  // (the SAME predicate slab_multiply applies -- a rank that agrees here cannot decline later)
+  const bool ok = mine_ok && pe.kmax >= pe.kmin && k.takes_panel(A.loc, B.loc, row_pad, pe.kmin, pe.kmax + 1, &pe.plan);
   DevBuf<double> d_declined(4);
   double declined[4] = {ok ? 0.0 : 1.0, 0.0, 0.0, 0.0};
   d_declined.upload(declined, 4);
   tr.allreduce(d_declined.p, 4, true, 0);
   bool fetched = false;
   if (ok) {
-    const int32_t ka = kmin, kb = kmax + 1;
-    DevBuf<int32_t> d_ra((size_t)P), nfirst((size_t)(kb - ka)), nlast((size_t)(kb - ka));
-    DevBuf<int64_t> d_zoff((size_t)P);
-    DevBuf<unsigned long long> naddr((size_t)(kb - ka));
-    if (P > 16) {
-      d_ra.upload(ra.data(), (size_t)P);
-      d_zoff.upload(zoff.data(), (size_t)P);
-    }
-    slab_halo_layout_async(d_ext_all, d_pre_all, pitch, dim, P, me, ka, kb, d_ra.p, d_zoff.p, recvbuf.p, A.loc, nfirst.p, nlast.p, naddr.p,
-                           nullptr, nullptr, ra.data(), zoff.data());
-    SlabHalo halo;
-    halo.ka = ka;
-    halo.kb = kb;
-    halo.first = nfirst.p;
-    halo.last = nlast.p;
-    halo.addr = naddr.p;
-    halo.row_pad = row_pad;
-    halo.plan = &plan;
+    SlabHalo halo = pe.halo(A.loc, row_pad);
     halo.on_fetch = [&](ScalarFetch& f) {
       f.add(d_declined.p, 1, reinterpret_cast<unsigned long long*>(&declined[0]));
       fetched = true;
     };
-    const double denom = (double)dim * (double)dim;
-    const bool dense_rule = denom > 0 && std::min((double)nnz_a / denom, (double)nnz_b / denom) > 0.1;
-    // (the buffers above are released on return: the allocator is stream ordered, and slab_multiply ends with a read-back)
-    if (!(cplx ? slab_multiply_c(A.loc, B.loc, AB, alpha, threshold, dense_rule, &halo)
-               : slab_multiply(A.loc, B.loc, AB, alpha, threshold, dense_rule, &halo)))
+    if (!k.multiply(A.loc, B.loc, AB, alpha, threshold, dense_branch(A.dim, nnz_a, nnz_b), &halo))
       NTP_FATAL("internal: a panel product was declined after its rank had agreed to it");
   }
   if (!fetched) {
@@ -725,14 +845,13 @@ DevMat multiply_panel(const PSMatrix& A, const PSMatrix& B, double alpha, double
   // A is populated over (a process slice's operand: its density is that of the populated part, as in the
   // reference's per-block test)
   int64_t nz[2] = {A.loc.nnz, B.loc.nnz};
-  const double denom = (double)A.dim * (double)A.dim;
   DevMat AB;
   if (world().active()) {
     // only the columns of A named by the rows of the local B panel travel (halo for banded operands); the same
     // exchange returns the global nnz for the dense-branch rule
     HaloExchange hx;
     gather_needed_begin(hx, A, B.loc, nz, true);
-    const bool dense_rule = denom > 0 && std::min((double)nz[0] / (denom * a_fraction), (double)nz[1] / denom) > 0.1;
+    const bool dense_rule = dense_branch(A.dim, nz[0], nz[1], a_fraction);
     const ColRange need{hx.kmin, hx.kmax + 1};   // the rows of the B panel name these columns only
     // A solve in a block order (band_scope.cpp: 3-D operands on several ranks): the panel of B as the columns c0 .. c1 of a
     // square matrix whose other columns are empty, the product through the block path -- tiles of the order the scope
@@ -807,8 +926,7 @@ DevMat multiply_panel(const PSMatrix& A, const PSMatrix& B, double alpha, double
       AB = parts.size() == 1 ? std::move(Cint) : concat_columns(parts);
     }
   } else {
-    const bool dense_rule = denom > 0 && std::min((double)nz[0] / (denom * a_fraction), (double)nz[1] / denom) > 0.1;
-    spgemm(A.loc, B.loc, AB, alpha, threshold, dense_rule);
+    spgemm(A.loc, B.loc, AB, alpha, threshold, dense_branch(A.dim, nz[0], nz[1], a_fraction));
   }
   return AB;
 }
@@ -836,80 +954,48 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
   // as it is, every other entry point packs on access.  Solver loops (sessions of their own) take compressed columns.
   // Complex operands the same way where complex block forms are allowed (complex_blocks_on) -- before a complex session's
   // attempt on runs, whose refusals would end the session
-  const bool block_first = slab_on() && (!A.cplx || complex_blocks_on()) && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308 &&
+  const bool block_first = slab_on() && (!A.cplx || complex_blocks_on()) && S <= 1 && beta_is_zero(beta) &&
                            (A.loc.blocked() || B.loc.blocked() || A.loc.block_hint || B.loc.block_hint) && !A.loc.expanded() && !B.loc.expanded() &&
                            !A.loc.loose() && !B.loc.loose();
   if (block_first) {
     BlockKeepScope keep;
-    const double denom = (double)A.dim * (double)A.dim;
-    const bool dense_rule = denom > 0 && std::min((double)A.loc.nnz / denom, (double)B.loc.nnz / denom) > 0.1;
-    spgemm(A.loc, B.loc, AB, alpha, threshold, dense_rule);
-   
-    C.grid = A.grid; C.dim = A.dim; C.c0 = B.c0; C.c1 = B.c1;
-    C.cplx = A.cplx;
-    C.loc = std::move(AB);
+    spgemm(A.loc, B.loc, AB, alpha, threshold, dense_branch(A.dim, A.loc.nnz, B.loc.nnz));
+    install(C, A.grid, A.dim, A.cplx, B.c0, B.c1, std::move(AB));
     return;
   }
   unblock({&A, &B});
-  if (g_slab_depth > 0 && world().active() && g_complex_session && A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308) {
-    // (a complex session across ranks: collective, as the real panel product below -- every rank takes the same branch)
+  // (real operands, or complex ones in a session that takes them)
+  const bool in_slab_form = session_takes(A.cplx) && S <= 1 && beta_is_zero(beta);
+  const SlabKind& k = slab_kind(A.cplx);
+  if (g_slab_depth > 0 && world().active() && in_slab_form) {
+    // (a slab session across ranks: collective -- every rank reports whether its panels are in slab form with the halo request,
+    // and every rank takes the same branch)
     if (panel_slab_multiply(A, B, AB, alpha, threshold)) {
       g_slab_counts[0] += 1;
-      C.grid = A.grid; C.dim = A.dim; C.c0 = B.c0; C.c1 = B.c1;
-      C.cplx = true;
-      C.loc = std::move(AB);
+      install(C, A.grid, A.dim, A.cplx, B.c0, B.c1, std::move(AB));
       return;
     }
     g_slab_counts[3] += 1;
     for (const PSMatrix* m : {&A, &B})
       if (m->loc.expanded() || m->loc.loose()) pack(mut(*m));
-  } else if (slab_on() && !world().active() && g_complex_session && A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308 && A.loc.nnz > 0 &&
-             B.loc.nnz > 0) {
-    // (a session that takes complex operands: the iterates stay in the complex tile kernel's operand form)
-    const double denom = (double)A.dim * (double)A.dim;
-    const bool dense_rule = denom > 0 && std::min((double)A.loc.nnz / denom, (double)B.loc.nnz / denom) > 0.1;
-    if (slab_enter_c(mut(A)) && (&A == &B || slab_enter_c(mut(B))) && slab_multiply_c(A.loc, B.loc, AB, alpha, threshold, dense_rule)) {
-      g_slab_counts[0] += 1;
-      C.grid = A.grid; C.dim = A.dim; C.c0 = B.c0; C.c1 = B.c1;
-      C.cplx = true;
-      C.loc = std::move(AB);
-      return;
-    }
-    slab_refused({&A, &B});
-  } else if (g_slab_depth > 0 && world().active() && !A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308) {
-    // (a slab session across ranks: collective -- every rank reports whether its panels are in slab form with the halo request)
-    if (panel_slab_multiply(A, B, AB, alpha, threshold)) {
-      g_slab_counts[0] += 1;
-      C.grid = A.grid; C.dim = A.dim; C.c0 = B.c0; C.c1 = B.c1;
-      C.cplx = false;
-      C.loc = std::move(AB);
-      return;
-    }
-    g_slab_counts[3] += 1;
-    for (const PSMatrix* m : {&A, &B})
-      if (m->loc.expanded() || m->loc.loose()) pack(mut(*m));
-  } else if (slab_on() && !world().active() && !A.cplx && S <= 1 && std::fabs(beta) < 2.2250738585072014e-308 && A.loc.nnz > 0 && B.loc.nnz > 0) {
-    // (a slab session: operands are turned into slab form where they are, the product stays in it)
-    const double denom = (double)A.dim * (double)A.dim;
-    const bool dense_rule = denom > 0 && std::min((double)A.loc.nnz / denom, (double)B.loc.nnz / denom) > 0.1;
-    // (unfused arithmetic: the register-slab kernel multiplies whole runs, zeros included -- operands that have become
+  } else if (slab_on() && !world().active() && in_slab_form && A.loc.nnz > 0 && B.loc.nnz > 0) {
+    // (a slab session: operands are turned into slab form where they are, the product stays in it -- complex iterates in the
+    // complex tile kernel's operand form)
+    // (unfused arithmetic, real: the register-slab kernel multiplies whole runs, zeros included -- operands that have become
     // sparse inside wide extents, 3 I - X^2 near the end of a sign iteration, are better served by the general kernels,
     // which the compressed-column path picks per product; the MFMA tile kernel of the FMA mode takes them as they are)
     auto runs_dense = [](const DevMat& M) {
-      return options().spgemm_fma != 0 || !M.expanded() ||
-             (double)slab_span_sum(M) <= 1.5 * (double)M.nnz + 64.0 * (double)M.cols;
+      return options().spgemm_fma != 0 || !M.expanded() || (double)slab_span_sum(M) <= 1.5 * (double)M.nnz + 64.0 * (double)M.cols;
     };
-    if (slab_enter(mut(A)) && (&A == &B || slab_enter(mut(B))) && runs_dense(A.loc) && runs_dense(B.loc) &&
-        slab_multiply(A.loc, B.loc, AB, alpha, threshold, dense_rule)) {
+    if (k.enter(mut(A)) && (&A == &B || k.enter(mut(B))) && (A.cplx || (runs_dense(A.loc) && runs_dense(B.loc))) &&
+        k.multiply(A.loc, B.loc, AB, alpha, threshold, dense_branch(A.dim, A.loc.nnz, B.loc.nnz), nullptr)) {
       g_slab_counts[0] += 1;
-      if (options().time_kernels != 0) {   // (statistics mode: the products a plan over compressed columns would have counted)
+      if (!A.cplx && options().time_kernels != 0) {   // (statistics mode: the products a plan over compressed columns would have counted)
         const long long pr = slab_product_count(A.loc, B.loc);
         last_spgemm_stats().products = pr;
         spgemm_accum().products += pr;
       }
-      C.grid = A.grid; C.dim = A.dim; C.c0 = B.c0; C.c1 = B.c1;
-      C.cplx = false;
-      C.loc = std::move(AB);
+      install(C, A.grid, A.dim, A.cplx, B.c0, B.c1, std::move(AB));
       return;
     }
     slab_refused({&A, &B});
@@ -920,13 +1006,10 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
   if (S <= 1) {
     // (a one-call session of the C ABI: should the product turn out to belong to the block path -- decided inside spgemm()
     // once the run-based kernels have declined -- it stays in block form, and the refusal above was not one)
-    const bool keep_block = g_slab_depth > 0 && !g_slab_failed && (!A.cplx || complex_blocks_on()) && std::fabs(beta) < 2.2250738585072014e-308;
-    if (keep_block) {
-      BlockKeepScope keep;
-      AB = multiply_panel(A, B, alpha, threshold);
-    } else {
-      AB = multiply_panel(A, B, alpha, threshold);
-    }
+    std::optional<BlockKeepScope> keep;
+    if (g_slab_depth > 0 && !g_slab_failed && (!A.cplx || complex_blocks_on()) && beta_is_zero(beta)) keep.emplace();
+    AB = multiply_panel(A, B, alpha, threshold);
+    keep.reset();
     if (AB.blocked() && g_slab_refusals > 0) { g_slab_refusals -= 1; }
   } else {
     // Process slices (the reference's 2.5-D algorithm, MatrixMultiply.f90:25-29, 74-80, 230-267): slice s multiplies
@@ -944,8 +1027,7 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
     AB.reset_empty(A.dim, B.c1 - B.c0, A.cplx);
     for (int s = 0; s < S; ++s) {
       PSMatrix As;
-      As.grid = A.grid; As.dim = A.dim; As.cplx = A.cplx; As.c0 = A.c0; As.c1 = A.c1;
-      As.loc = mask_columns(A.loc, A.c0, block, S, s);
+      install(As, A.grid, A.dim, A.cplx, A.c0, A.c1, mask_columns(A.loc, A.c0, block, S, s));
       int64_t kcount = 0;   // columns of the whole matrix in this slice's share
       for (int64_t k0 = (int64_t)s * block; k0 < A.dim; k0 += (int64_t)S * block) kcount += std::min<int64_t>(block, A.dim - k0);
       DevMat part = multiply_panel(As, B, alpha, working, std::max(1e-300, (double)kcount / (double)A.dim));
@@ -953,10 +1035,8 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
     }
   }
   // beta handling (MatrixMultiply.f90:324-329)
-  if (std::fabs(beta) < 2.2250738585072014e-308 || !C.constructed() || C.dim != A.dim) {
-    C.grid = A.grid; C.dim = A.dim; C.c0 = B.c0; C.c1 = B.c1;
-    C.cplx = A.cplx;
-    C.loc = std::move(AB);
+  if (beta_is_zero(beta) || !C.constructed() || C.dim != A.dim) {
+    install(C, A.grid, A.dim, A.cplx, B.c0, B.c1, std::move(AB));
   } else {
     if (C.cplx != A.cplx) {
       PSMatrix Cc;
@@ -1007,9 +1087,9 @@ void ps_scale(PSMatrix& A, double c) {
     g_block_counts[1] += 1;
   }
   unblock({&A});
-  if (slab_on() && g_complex_session && A.cplx && A.loc.expanded() && slab_scale_c(A.loc, c)) { g_slab_counts[2] += 1; return; }
   if (slab_on() && A.loc.expanded()) {
-    if (slab_scale(A.loc, c)) { g_slab_counts[2] += 1; return; }
+    // (a complex operand outside a session that takes them is refused: the real slab_scale declines it untouched)
+    if (session_takes(A.cplx) && slab_kind(A.cplx).scale(A.loc, c)) { g_slab_counts[2] += 1; return; }
     slab_refused({&A});
   }
   scale(A.loc, c);
@@ -1029,13 +1109,11 @@ void ps_axpby(const PSMatrix& A, PSMatrix& B, double alpha, double beta, double 
     g_block_counts[1] += 1;
   }
   unblock({&A, &B});
-  if (slab_on() && g_complex_session && (A.loc.expanded() || B.loc.expanded()) && A.cplx && B.cplx && &A != &B) {
-    // (a session that takes complex operands: the merge on runs of (re, im) pairs)
-    if (slab_enter_c(mut(A)) && slab_enter_c(B.loc) && slab_axpby_c(A.loc, B.loc, alpha, beta, threshold)) { g_slab_counts[1] += 1; return; }
-    slab_refused({&A, &B});
-  } else if (slab_on() && (A.loc.expanded() || B.loc.expanded()) && !A.cplx && !B.cplx && &A != &B) {
-    // (a slab session: the operand still in compressed columns -- an identity, the Hamiltonian -- is turned into slab form)
-    if (slab_enter(mut(A)) && slab_enter(B.loc) && slab_axpby(A.loc, B.loc, alpha, beta, threshold)) { g_slab_counts[1] += 1; return; }
+  if (slab_on() && (A.loc.expanded() || B.loc.expanded()) && A.cplx == B.cplx && session_takes(A.cplx) && &A != &B) {
+    // (a slab session: the operand still in compressed columns -- an identity, the Hamiltonian -- is turned into slab form;
+    // complex operands in a session that takes them: the merge on runs of (re, im) pairs; mixed kinds: the general path)
+    const SlabKind& k = slab_kind(A.cplx);
+    if (k.enter(mut(A)) && k.enter(B.loc) && k.axpby(A.loc, B.loc, alpha, beta, threshold)) { g_slab_counts[1] += 1; return; }
     slab_refused({&A, &B});
   } else {
     slab_pack_if({&A, &B});
@@ -1050,11 +1128,9 @@ void ps_axpby(const PSMatrix& A, PSMatrix& B, double alpha, double beta, double 
 
 void ps_increment_identity(const PSMatrix& Identity, PSMatrix& B, double alpha) {
   CommScope cs(Identity.grid);
-  if (slab_on() && B.loc.expanded() && !B.cplx && !Identity.cplx && Identity.dim == B.dim && slab_add_diagonal(B.loc, alpha, B.c0)) {
-    g_slab_counts[1] += 1;
-    return;
-  }
-  if (slab_on() && g_complex_session && B.loc.expanded() && B.cplx && Identity.dim == B.dim && slab_add_diagonal_c(B.loc, alpha, B.c0)) {
+  // (a real B takes a real identity only; never counted as a refusal: the paths below take what the slab form declines)
+  if (slab_on() && B.loc.expanded() && session_takes(B.cplx) && (B.cplx || !Identity.cplx) && Identity.dim == B.dim &&
+      slab_kind(B.cplx).add_diagonal(B.loc, alpha, B.c0)) {
     g_slab_counts[1] += 1;
     return;
   }
@@ -1070,26 +1146,22 @@ void ps_increment_identity(const PSMatrix& Identity, PSMatrix& B, double alpha) 
 bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double beta, double* norm) {
   CommScope cs(A.grid);
   if (blk_any({&A, &B})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
-  if (world().active() && g_slab_depth > 0 && A.cplx == B.cplx && (!A.cplx || g_complex_session) && A.dim == B.dim && &A != &B) {
-    // (a session across ranks: the decision is collective -- one reduction carries the norm and "some rank declined")
+  const bool in_slab_form = slab_on() && (A.loc.expanded() || B.loc.expanded());
+  if (A.cplx == B.cplx && session_takes(A.cplx) && A.dim == B.dim && &A != &B && (world().active() ? g_slab_depth > 0 : in_slab_form)) {
+    const SlabKind& k = slab_kind(A.cplx);
     double v = 0.0;
-    const bool ok = slab_on() && (A.loc.expanded() || B.loc.expanded()) &&
-                    (A.cplx ? slab_enter_c(mut(A)) && slab_enter_c(mut(B)) && slab_norm_axpby_c(A.loc, B.loc, alpha, beta, &v)
-                            : slab_enter(mut(A)) && slab_enter(mut(B)) && slab_norm_axpby(A.loc, B.loc, alpha, beta, &v));
-    double pair[2] = {ok ? v : 0.0, ok ? 0.0 : 1.0};
-    comm_allreduce_max(pair, 2);
-    if (pair[1] != 0.0) return false;
-    *norm = pair[0];
-    g_slab_counts[2] += 1;
-    return true;
-  }
-  if (slab_on() && !A.cplx && !B.cplx && A.dim == B.dim && &A != &B && (A.loc.expanded() || B.loc.expanded())) {
-    if (!(slab_enter(mut(A)) && slab_enter(mut(B)) && slab_norm_axpby(A.loc, B.loc, alpha, beta, norm))) return false;
-    g_slab_counts[2] += 1;
-    return true;
-  }
-  if (slab_on() && !world().active() && g_complex_session && A.cplx && B.cplx && A.dim == B.dim && &A != &B && (A.loc.expanded() || B.loc.expanded())) {
-    if (!(slab_enter_c(mut(A)) && slab_enter_c(mut(B)) && slab_norm_axpby_c(A.loc, B.loc, alpha, beta, norm))) return false;
+    const bool ok = in_slab_form && k.enter(mut(A)) && k.enter(mut(B)) && k.norm_axpby(A.loc, B.loc, alpha, beta, &v);
+    if (world().active()) {
+      // (a session across ranks: the decision is collective -- one reduction carries the norm and "some rank declined",
+      // whether or not this rank could)
+      double pair[2] = {ok ? v : 0.0, ok ? 0.0 : 1.0};
+      comm_allreduce_max(pair, 2);
+      if (pair[1] != 0.0) return false;
+      v = pair[0];
+    } else if (!ok) {
+      return false;
+    }
+    *norm = v;
     g_slab_counts[2] += 1;
     return true;
   }
@@ -1138,8 +1210,7 @@ bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatr
   if (!slab_on() || !X.loc.expanded() || !X2.loc.expanded() || X.cplx || X2.cplx || sigma == 0.0) return false;
   DevMat R;
   if (!slab_trs4_operand(X.loc, X2.loc, sigma, X.c0, R)) return false;
-  P.grid = X.grid; P.dim = X.dim; P.cplx = false; P.c0 = X.c0; P.c1 = X.c1;
-  P.loc = std::move(R);
+  install(P, X.grid, X.dim, false, X.c0, X.c1, std::move(R));
   g_slab_counts[1] += 1;
   return true;
 }
@@ -1152,22 +1223,13 @@ void ps_copy_axpby(const PSMatrix& B, const PSMatrix& A, PSMatrix& Out, double a
     return;
   }
   unblock({&A, &B});
-  if (slab_on() && g_complex_session && (A.loc.expanded() || B.loc.expanded()) && A.cplx && B.cplx && &A != &B && &Out != &A && &Out != &B &&
+  if (slab_on() && (A.loc.expanded() || B.loc.expanded()) && A.cplx == B.cplx && session_takes(A.cplx) && &A != &B && &Out != &A && &Out != &B &&
       A.dim == B.dim) {
+    const SlabKind& k = slab_kind(A.cplx);
     DevMat R;
-    if (slab_enter_c(mut(A)) && slab_enter_c(mut(B)) && slab_axpby_to_c(A.loc, B.loc, R, alpha, beta, threshold)) {
+    if (k.enter(mut(A)) && k.enter(mut(B)) && k.axpby_to(A.loc, B.loc, R, alpha, beta, threshold)) {
       g_slab_counts[1] += 1;
-      Out.grid = B.grid; Out.dim = B.dim; Out.cplx = true; Out.c0 = B.c0; Out.c1 = B.c1;
-      Out.loc = std::move(R);
-      return;
-    }
-    slab_refused({&A, &B});
-  } else if (slab_on() && (A.loc.expanded() || B.loc.expanded()) && !A.cplx && !B.cplx && &A != &B && &Out != &A && &Out != &B && A.dim == B.dim) {
-    DevMat R;
-    if (slab_enter(mut(A)) && slab_enter(mut(B)) && slab_axpby_to(A.loc, B.loc, R, alpha, beta, threshold)) {
-      g_slab_counts[1] += 1;
-      Out.grid = B.grid; Out.dim = B.dim; Out.cplx = false; Out.c0 = B.c0; Out.c1 = B.c1;
-      Out.loc = std::move(R);
+      install(Out, B.grid, B.dim, A.cplx, B.c0, B.c1, std::move(R));
       return;
     }
     slab_refused({&A, &B});
@@ -1193,105 +1255,24 @@ void ps_axpby_dot(const PSMatrix& A, PSMatrix& B, double alpha, double beta, dou
 }
 
 namespace {
+void dev_allreduce4(double* d) { world().tr->allreduce(d, 4, true, 0); }
+
 // One TRS2 step of a rank whose panel is in slab form (kernels.hpp SlabForm): the halo travels as dense column runs
 // (8 bytes per row of a column's span, no row ids, no offsets: every rank derives the layout from the all-gathered
 // column extents), the run records of the kernel address the received runs where they land, the multiplier tiles are
 // local.  Protocol, all on the engine stream with ONE host synchronisation: (1) ONE all-gather of a record per rank:
 // request (first / last row of the panel, nnz), packed extents, prefix sums of the spans; (2) a kernel
-// derives who sends how many doubles to whom, one read-back; (3) the runs of the requested columns are packed per
-// requester and exchanged in one send / recv group; (4) layout kernel, then slab_step.  Collective: every rank calls it.
+// derives who sends how many doubles to whom, one read-back (PanelExchange prepare, fetch -- or left by the step before);
+// (3) the runs of the requested columns are packed per requester and exchanged in one send / recv group (exchange);
+// (4) layout kernel (halo), then slab_step.  Collective: every rank calls it.
 // Returns this rank's success; the result is in fu.result (the caller installs it when all ranks succeeded).
-void dev_allreduce4(double* d) { world().tr->allreduce(d, 4, true, 0); }
-
-// What a panel step must know before its halo can travel -- every rank's request, the column extents of the whole iterate,
-// who sends how much to whom, the step's plan -- is a function of the iterate's column extents alone.  It is PREPARED on the
-// device (one all-gather, three small kernels) and read back in one round trip: at the start of a step, or -- for every step
-// after the first -- by the step BEFORE it, from its result's extents, on that step's own read-back (SlabHalo::before_fetch):
-// a panel step then costs ONE host round trip, as a step on one rank does.
-struct PanelExchange {
-  int P = 0, me = 0, pitch = 0, wcols = 0, snb = 0;
-  int32_t dim = 0;
-  bool with_counts = false;
-  DevBuf<int64_t> d_all, d_req, d_bound, d_cnt, plan_stats;
-  SlabPlan plan;
-  DevBuf<int32_t> gfirst, glast;
-  std::vector<int64_t> req, bound, cnt;
-  unsigned long long plan_hs[2] = {0, 0};
-  const void* owner = nullptr;   // the value buffer of the iterate (in slab form) it was prepared for ...
-  unsigned long long owner_serial = 0;   // ... and that buffer's allocation serial: an address alone comes back from the caching allocator
-  const int64_t* d_ext_all() const { return d_all.p + 4; }
-  const int64_t* d_pre_all() const { return d_all.p + 4 + wcols; }
-  const int64_t* d_cnt_all() const { return with_counts ? d_all.p + 4 + 2 * (size_t)wcols : nullptr; }
-};
-std::unique_ptr<PanelExchange> g_pending_exchange;
-long long g_exchange_prefetched = 0;   // panel steps whose exchange layout came with the step before
-}  // namespace
-// the preparation a step left for a successor that never came (the last step of a solve or of a bench block): P * pitch * 8
-// bytes of device memory and a stale layout -- dropped where a solve begins and ends and with the operand caches
-void drop_pending_exchange() { g_pending_exchange.reset(); }
-namespace {
-
-int panel_pitch(int32_t dim, int P, bool with_counts, int* wcols_out) {
-  int32_t maxw = 0;
-  for (int q = 0; q < P; ++q) {
-    int32_t a0, a1;
-    panel_range(dim, P, q, &a0, &a1);
-    maxw = std::max(maxw, a1 - a0);
-  }
-  // ONE all-gather per step: every rank contributes a record of `pitch` 8-byte words -- its request (4 words), the
-  // packed extents of its columns, the prefix sums of their spans and, for the statistics (timers on), their entry
-  // counts; the kernels below read the sections through the common stride
-  *wcols_out = maxw + 1;
-  return 4 + (with_counts ? 3 : 2) * (maxw + 1);
-}
-// enqueues the preparation for the panel Xl (slab form) and adds what the host needs of it to the fetch (collective)
-void exchange_prepare(const DevMat& Xl, int32_t dim, const long long* d_nnz, PanelExchange& pe, ScalarFetch& f) {
-  Comm& c = world();
-  Transport& tr = *c.tr;
-  pe.P = c.nranks;
-  pe.me = c.rank;
-  pe.dim = dim;
-  pe.with_counts = options().time_kernels != 0;
-  pe.pitch = panel_pitch(dim, pe.P, pe.with_counts, &pe.wcols);
-  pe.snb = (Xl.cols + 15) / 16;
-  const int P = pe.P;
-  pe.req.assign((size_t)4 * P, 0);
-  pe.bound.assign((size_t)2 * P, 0);
-  pe.cnt.assign((size_t)P * P, 0);
-  pe.d_all.alloc((size_t)P * pe.pitch);
-  pe.d_req.alloc((size_t)4 * P);
-  pe.d_bound.alloc((size_t)2 * P);
-  pe.d_cnt.alloc((size_t)P * P);
-  int64_t* mine = pe.d_all.p + (size_t)pe.me * pe.pitch;
-  slab_export_async(Xl, mine, d_nnz, mine + 4, mine + 4 + pe.wcols, pe.with_counts ? mine + 4 + 2 * (size_t)pe.wcols : nullptr);
-  tr.allgather(mine, pe.d_all.p, (size_t)pe.pitch * sizeof(int64_t));
-  HIP_CHECK(hipMemcpy2DAsync(pe.d_req.p, 4 * sizeof(int64_t), pe.d_all.p, (size_t)pe.pitch * sizeof(int64_t), 4 * sizeof(int64_t), (size_t)P,
-                             hipMemcpyDeviceToDevice, stream()));
-  halo_counts_async(pe.d_req.p, pe.d_pre_all(), pe.pitch, dim, P, pe.me, pe.d_cnt.p, pe.d_bound.p);   // (counts in doubles here)
-  // the step's plan (block windows and k ranges follow from the extents alone) is made here, from the gathered
-  // extents, so that its sizes come back in the same read-back as the exchange layout
-  pe.plan_stats.alloc(24);
-  pe.plan_stats.zero();
-  slab_plan_panel_async(Xl, pe.d_ext_all(), pe.pitch, dim, P, pe.plan, pe.gfirst, pe.glast, reinterpret_cast<unsigned long long*>(pe.plan_stats.p));
-  f.add(pe.d_req.p, 4 * P, pe.req.data());
-  f.add(pe.d_bound.p, 2 * P, pe.bound.data());
-  f.add(pe.d_cnt.p, P * P, pe.cnt.data());
-  f.add(pe.plan.blk_toff.p + pe.snb, 1, &pe.plan.total);
-  f.add(pe.plan_stats.p + 16, 2, pe.plan_hs);
-  pe.owner = Xl.slab->val.p;
-  pe.owner_serial = dev_alloc_serial(Xl.slab->val.p);
-}
-bool exchange_fits_fetch(int P) { return (size_t)4 * P + (size_t)P * P + 2 * P <= 400; }
-
 bool slab_exchange_and_step(PSMatrix& B, SlabFusion& fu, double threshold, SlabReduce& red, bool* owed_prefetch) {
   static const bool step_times = std::getenv("NTPOLY_AMD_DEBUG_STEPTIME") != nullptr;   // (host clock of a panel step's phases, rank 0)
   const auto st0 = std::chrono::steady_clock::now();
   auto st_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - st0).count(); };
   double st_prep = 0, st_xchg = 0;
   const long long syncs_before = host_sync_count();
-  Comm& c = world();
-  Transport& tr = *c.tr;
-  const int P = c.nranks, me = c.rank;
+  const int P = world().nranks, me = world().rank;
   const int32_t dim = B.dim;
   const bool with_counts = options().time_kernels != 0;
   const bool ahead = options().exchange_ahead != 0 && exchange_fits_fetch(P);
@@ -1309,105 +1290,60 @@ bool slab_exchange_and_step(PSMatrix& B, SlabFusion& fu, double threshold, SlabR
   } else {
     g_pending_exchange.reset();
     pe.reset(new PanelExchange());
-    if (exchange_fits_fetch(P)) {
-      ScalarFetch f;
-      exchange_prepare(B.loc, dim, nullptr, *pe, f);
-      f.run();
-    } else {
-      ScalarFetch f;   // (too many ranks for one fetch: plain copies)
-      exchange_prepare(B.loc, dim, nullptr, *pe, f);
-      f.n = 0;
-      HIP_CHECK(hipMemcpyAsync(pe->req.data(), pe->d_req.p, (size_t)4 * P * 8, hipMemcpyDeviceToHost, stream()));
-      HIP_CHECK(hipMemcpyAsync(pe->bound.data(), pe->d_bound.p, (size_t)2 * P * 8, hipMemcpyDeviceToHost, stream()));
-      HIP_CHECK(hipMemcpyAsync(pe->cnt.data(), pe->d_cnt.p, (size_t)P * P * 8, hipMemcpyDeviceToHost, stream()));
-      HIP_CHECK(hipMemcpyAsync(&pe->plan.total, pe->plan.blk_toff.p + pe->snb, 8, hipMemcpyDeviceToHost, stream()));
-      HIP_CHECK(hipMemcpyAsync(pe->plan_hs, pe->plan_stats.p + 16, 16, hipMemcpyDeviceToHost, stream()));
-      sync_stream();
-    }
+    pe->prepare(B.loc, nullptr, false, true, dim, nullptr);
+    pe->fetch();
   }
   st_prep = st_ms();
-  const int pitch = pe->pitch;
-  std::vector<int64_t>&req = pe->req, &cnt = pe->cnt;
-  const int64_t *d_ext_all = pe->d_ext_all(), *d_pre_all = pe->d_pre_all(), *d_cnt_all = pe->d_cnt_all();
-  SlabPlan& plan = pe->plan;
-  plan.max_w = (int)pe->plan_hs[0];
-  plan.max_kn = (int)pe->plan_hs[1];
   exchange_stats().host_syncs += host_sync_count() - syncs_before;   // (the exchange's own: measured in sync_stream)
   exchange_stats().exchanges += 1;
   int64_t nnz_global = 0;
-  for (int q = 0; q < P; ++q) nnz_global += req[(size_t)4 * q + 2];
-  auto kmin_of = [&](int q) { int64_t lo = req[(size_t)4 * q], hi = req[(size_t)4 * q + 1]; return hi < lo ? 0 : (int32_t)lo; };
-  auto kmax_of = [&](int q) { int64_t lo = req[(size_t)4 * q], hi = req[(size_t)4 * q + 1]; return hi < lo ? -1 : (int32_t)hi; };
-  const int32_t kmin = kmin_of(me), kmax = kmax_of(me);
-  // what I send (my columns inside every requester's range, packed per requester) and what I receive (the segments of the
-  // other owners tile [kmin, kmax] in rank order): panel_exchange_layout, host arithmetic on the gathered requests and counts
-  std::vector<int32_t> sa((size_t)P), sb((size_t)P), ra((size_t)P), rb((size_t)P);
-  std::vector<int64_t> soff((size_t)P + 1, 0), zoff((size_t)P + 1, 0);
-  panel_exchange_layout(dim, P, me, req.data(), cnt.data(), sa.data(), sb.data(), soff.data(), ra.data(), rb.data(), zoff.data());
-  DevBuf<double> sendbuf((size_t)soff[(size_t)P] + 1);
-  for (int q = 0; q < P; ++q)
-    if (q != me && cnt[(size_t)me * P + q] > 0)
-      slab_pack_runs_async(B.loc, d_pre_all + (size_t)me * pitch, sa[(size_t)q] - B.c0, sb[(size_t)q] - B.c0,
-                           sendbuf.p + soff[(size_t)q]);
-  DevBuf<double> recvbuf((size_t)zoff[(size_t)P] + kIndexSlack);
-  tr.group_begin();
-  for (int q = 0; q < P; ++q) {
-    const int64_t m = cnt[(size_t)me * P + q];
-    if (q != me && m > 0) tr.send(sendbuf.p + soff[(size_t)q], (size_t)m * sizeof(double), q);
-  }
-  for (int s = 0; s < P; ++s) {
-    const int64_t m = cnt[(size_t)s * P + me];
-    if (s != me && m > 0) tr.recv(recvbuf.p + zoff[(size_t)s], (size_t)m * sizeof(double), s);
-  }
-  tr.group_end();
+  for (int q = 0; q < P; ++q) nnz_global += pe->req[(size_t)4 * q + 2];
+  pe->exchange(B.loc, B.c0);
   st_xchg = st_ms();
-  if (kmax < kmin) {   // (an empty panel: nothing to multiply; the caller's consensus takes the other path)
+  if (pe->kmax < pe->kmin) {   // (an empty panel: nothing to multiply; the caller's consensus takes the other path)
     if (ahead) *owed_prefetch = true;
     return false;
   }
-  // layout of the columns I need
-  const int32_t ka = kmin, kb = kmax + 1;
-  DevBuf<int32_t> d_ra((size_t)P), nfirst((size_t)(kb - ka)), nlast((size_t)(kb - ka));
-  DevBuf<int64_t> d_zoff((size_t)P);
-  DevBuf<unsigned long long> naddr((size_t)(kb - ka));
-  if (P > 16) {   // (up to 16 ranks the segments travel as kernel arguments)
-    d_ra.upload(ra.data(), (size_t)P);
-    d_zoff.upload(zoff.data(), (size_t)P);
-  }
-  DevBuf<int32_t> ncount;
-  if (d_cnt_all) ncount.alloc((size_t)(kb - ka));
-  slab_halo_layout_async(d_ext_all, d_pre_all, pitch, dim, P, me, ka, kb, d_ra.p, d_zoff.p, recvbuf.p, B.loc, nfirst.p,
-                         nlast.p, naddr.p, d_cnt_all, ncount.p, ra.data(), zoff.data());
-  SlabHalo halo;
-  halo.ka = ka;
-  halo.kb = kb;
-  halo.first = nfirst.p;
-  halo.last = nlast.p;
-  halo.addr = naddr.p;
-  halo.count = ncount.p;
-  halo.row_pad = std::max(1, B.loc.slab->row_pad);   // (every rank packs with the alignment of its panel: the same option everywhere)
-  halo.plan = &plan;
+  // (every rank packs with the alignment of its panel: the same option everywhere)
+  SlabHalo halo = pe->halo(B.loc, std::max(1, B.loc.slab->row_pad));
   red.allreduce = &dev_allreduce4;
   halo.reduce = &red;
-  const double denom = (double)dim * (double)dim;
-  const bool dense_rule = denom > 0 && (double)nnz_global / denom > 0.1;
   // the NEXT step's preparation, from this step's result, on this step's read-back (option exchange_ahead)
   std::unique_ptr<PanelExchange> next;
   if (ahead) {
     halo.before_fetch = [&](const DevMat& R, const long long* d_nnz, ScalarFetch& f) {
       next.reset(new PanelExchange());
-      exchange_prepare(R, dim, d_nnz, *next, f);
+      next->prepare(R, nullptr, false, true, dim, d_nnz);
+      next->add_to(f);
     };
   }
-  // (the buffers above are released on return: the allocator is stream ordered, and slab_step ends with a read-back)
-  const bool ok = slab_step(B.loc, fu, threshold, dense_rule, &halo);
+  const bool ok = slab_step(B.loc, fu, threshold, dense_branch(dim, nnz_global, nnz_global), &halo);
   if (step_times && me == 0)
     std::fprintf(stderr, "[panel step] preparation %.3f ms (%s), halo exchange %.3f ms (%lld doubles out, %lld in), step %.3f ms\n", st_prep,
-                 g_exchange_prefetched ? "left by the step before or made" : "made", st_xchg - st_prep, (long long)soff[(size_t)P],
-                 (long long)zoff[(size_t)P], st_ms() - st_xchg);
+                 g_exchange_prefetched ? "left by the step before or made" : "made", st_xchg - st_prep, (long long)pe->soff[(size_t)P],
+                 (long long)pe->zoff[(size_t)P], st_ms() - st_xchg);
   if (ahead && !next) *owed_prefetch = true;   // (this rank gave up before its kernel: it owes the others the all-gather)
   if (ok && next) g_pending_exchange = std::move(next);
   return ok;
+}
+
+// the fused epilogue of a TRS2 step (kernels.hpp SlabFusion; panel_c0 >= 0: B is a column panel of the iterate)
+SlabFusion trs2_fusion(int mode, double am, double bm, double threshold, const PSMatrix& D, int32_t col_offset, int32_t panel_c0) {
+  SlabFusion fu;
+  fu.mode = mode;
+  fu.am = am;
+  fu.bm = bm;
+  fu.threshold = threshold;
+  fu.D = &D.loc;
+  fu.col_offset = col_offset;
+  fu.panel_c0 = panel_c0;
+  return fu;
+}
+// energy and trace of a step whose fusion is done
+void fusion_scalars(const SlabFusion& fu, double out[4]) {
+  out[0] = fu.dot;
+  out[1] = 0.0;
+  out[2] = fu.trace;
 }
 
 // TRS2 step across ranks with the fused kernel (mode 1: X <- X*X, mode 2: X <- 2X - X*X; energy and trace in out).
@@ -1416,32 +1352,18 @@ bool slab_exchange_and_step(PSMatrix& B, SlabFusion& fu, double threshold, SlabR
 bool dist_fused_step(PSMatrix& B, int mode, double threshold, const PSMatrix& D, double out[4]) {
   if (!B.loc.expanded()) return false;
   const int P = world().nranks;
-  SlabFusion fu;
-  fu.mode = mode;
-  fu.am = -1.0;
-  fu.bm = 2.0;
-  fu.threshold = threshold;
-  fu.D = &D.loc;
-  fu.col_offset = B.c0;
-  fu.panel_c0 = B.c0;
+  SlabFusion fu = trs2_fusion(mode, -1.0, 2.0, threshold, D, B.c0, B.c0);
   SlabReduce red;
   bool owed_prefetch = false;
-  const bool ok = slab_exchange_and_step(B, fu, threshold, red, &owed_prefetch);
+  slab_exchange_and_step(B, fu, threshold, red, &owed_prefetch);   // (this rank's success is in the sums)
   double v[4] = {0.0, 0.0, 0.0, 0.0};
   if (red.done) {   // the sums came back with the step's totals
     for (int q = 0; q < 4; ++q) v[q] = red.reduced[q];
   } else {          // this rank gave up before its kernel: it still owes the other ranks the collective
     comm_allreduce_sum(v, 4);
   }
-  if (owed_prefetch && !red.done) {   // ... and the all-gather of the next step's preparation, which the others will discard
-    int wcols = 0;
-    const int pitch = panel_pitch(B.dim, P, options().time_kernels != 0, &wcols);
-    DevBuf<int64_t> dummy((size_t)P * pitch);
-    dummy.zero();
-    world().tr->allgather(dummy.p + (size_t)world().rank * pitch, dummy.p, (size_t)pitch * sizeof(int64_t));
-    sync_stream();
-  }
-  (void)ok;
+  // ... and the all-gather of the next step's preparation, which the others will discard
+  if (owed_prefetch && !red.done) owed_allgather(B.dim);
   if (v[3] != (double)P) g_pending_exchange.reset();
   if (v[3] == (double)P) {
     B.loc = std::move(fu.result);
@@ -1453,6 +1375,41 @@ bool dist_fused_step(PSMatrix& B, int mode, double threshold, const PSMatrix& D,
   }
   pack(B.loc);   // (some rank could not: every rank repeats the step on the unfused, equally collective path)
   return false;
+}
+
+// fused TRS2 steps across ranks: real operands, no process slices, no block-order solve (band_scope.cpp: its panel products
+// take the block path of multiply_panel)
+bool fused_across_ranks(const PSMatrix& B, const PSMatrix& D) {
+  return world().active() && options().fused_update != 0 && options().loose_iterates != 0 && !B.cplx && !D.cplx &&
+         !(B.grid && B.grid->num_slices > 1) && !block_scope_active();
+}
+// A fused TRS2 step across ranks from compressed panels: the product of the gathered halo with the panel, with the fused
+// epilogue fu (energy, trace, slab form) where the kernel takes it -- otherwise `separate` finishes this rank's step from the
+// product in AB / L (L == nullptr: no loose product wanted).  fu.mode == 0: the product only, false -- the caller's separate
+// passes follow.  true: the step is done on every rank, out holds the sums.  nnz: this panel's entries, for the dense-branch
+// rule.  Collective.
+template <class Separate>
+bool panel_step_from_columns(PSMatrix& B, int64_t nnz, SlabFusion& fu, double threshold, double out[4], DevMat& AB, LooseProduct* L,
+                             Separate separate) {
+  int64_t nz[2] = {nnz, nnz};
+  HaloExchange hx;
+  gather_needed_begin(hx, B, B.loc, nz, false);
+  hx.finish();
+  const ColRange need{hx.kmin, hx.kmax + 1};
+  spgemm(hx.full, B.loc, AB, 1.0, threshold, dense_branch(B.dim, nz[0], nz[1]), L, &need, fu.mode ? &fu : nullptr);
+  if (!fu.mode) return false;
+  // the ranks must agree on the form of the iterate (the next step's exchange depends on it): slab form only if
+  // every rank's kernel produced it
+  if (fu.done) fusion_scalars(fu, out);
+  else separate();
+  out[3] = fu.done ? 1.0 : 0.0;
+  comm_allreduce_sum(out, 4);
+  if (fu.done) {
+    B.loc = std::move(fu.result);
+    if (out[3] != (double)world().nranks) pack(B.loc);
+  }
+  out[3] = 0.0;
+  return true;
 }
 }  // namespace
 
@@ -1479,9 +1436,7 @@ bool trs2_block(PSMatrix& B, int mode, double threshold, const PSMatrix& D, doub
     return false;
   }
   if (!B.loc.blocked() && (B.loc.expanded() || B.loc.loose() || !B.loc.block_hint)) return false;
-  const double denom = (double)B.dim * (double)B.dim;
-  const bool dense_rule = denom > 0 && (double)B.loc.nnz / denom > 0.1;
-  if (trs2_block_step(B.loc, mode, threshold, dense_rule, D.loc, out)) return true;
+  if (trs2_block_step(B.loc, mode, threshold, dense_branch(B.dim, B.loc.nnz, B.loc.nnz), D.loc, out)) return true;
   if (B.loc.blocked()) pack(B.loc);
   return false;
 }
@@ -1546,8 +1501,7 @@ bool complex_trs2_step(PSMatrix& B, int mode, double threshold, const PSMatrix& 
       D.loc.rows != B.loc.rows || D.loc.cols != B.loc.cols || (D.loc.expanded() && (D.loc.slab->labelled() || D.loc.slab->origin)))
     return false;
   if (ctrs2_off_for(D)) return false;
-  const double denom = (double)B.dim * (double)B.dim;
-  const bool dense_rule = denom > 0 && (double)B.loc.nnz / denom > 0.1;
+  const bool dense_rule = dense_branch(B.dim, B.loc.nnz, B.loc.nnz);
   if (B.loc.blocked()) return complex_trs2_block(B, mode, threshold, dense_rule, D, out);
   if (!B.loc.expanded()) {
     bool not_runs = false;
@@ -1598,62 +1552,31 @@ void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, cons
     ps_axpby_dot(scratch, B, -1.0, 2.0, threshold, D, out, want_trace);
     return;
   }
-  const double denom = (double)B.dim * (double)B.dim;
-  int64_t nz[2] = {B.loc.nnz, B.loc.nnz};
+  const int64_t nnz = B.loc.nnz;   // (for the dense-branch rule: the iterate as the step found it)
   LooseProduct L;
   DevMat AB;
+  // the merge of the product in compressed columns (no loose product): scratch holds it
+  auto merge_packed = [&](double* trace) {
+    install(scratch, B.grid, B.dim, B.cplx, B.c0, B.c1, std::move(AB));
+    axpby(scratch.loc, B.loc, -1.0, 2.0, threshold, &D.loc, out, trace, B.c0);
+  };
   // one rank: the iterate may stay loose from step to step (kernels.hpp, axpby keep_loose)
   const bool keep_loose = !world().active() && options().loose_iterates != 0;
-  const bool dist_fused = world().active() && options().fused_update != 0 && options().loose_iterates != 0;
+  const bool dist_fused = fused_across_ranks(B, D);
   if (dist_fused && dist_fused_step(B, 2, threshold, D, out)) return;
   if (!keep_loose) pack(B.loc);
   if (world().active()) {
-    HaloExchange hx;
-    gather_needed_begin(hx, B, B.loc, nz, false);
-    hx.finish();
-    const bool dense_rule = denom > 0 && std::min((double)nz[0] / denom, (double)nz[1] / denom) > 0.1;
-    const ColRange need{hx.kmin, hx.kmax + 1};
-    SlabFusion fu;   // (as on one rank; B is the panel [c0, c1) of the iterate whose needed columns hx.full holds)
-    fu.mode = dist_fused ? 2 : 0;
-    fu.am = -1.0;
-    fu.bm = 2.0;
-    fu.threshold = threshold;
-    fu.D = &D.loc;
-    fu.col_offset = B.c0;
-    fu.panel_c0 = B.c0;
-    spgemm(hx.full, B.loc, AB, 1.0, threshold, dense_rule, &L, &need, fu.mode ? &fu : nullptr);
-    if (dist_fused) {
-      // the ranks must agree on the form of the iterate (the next step's exchange depends on it): slab form only if
-      // every rank's kernel produced it
-      if (fu.done) {
-        out[0] = fu.dot;
-        out[1] = 0.0;
-        out[2] = fu.trace;
-      } else if (L.valid) {
-        axpby(L, B.loc, -1.0, 2.0, threshold, &D.loc, out, &out[2], B.c0, nullptr, false);
-      } else {
-        scratch.grid = B.grid; scratch.dim = B.dim; scratch.c0 = B.c0; scratch.c1 = B.c1; scratch.cplx = B.cplx;
-        scratch.loc = std::move(AB);
-        axpby(scratch.loc, B.loc, -1.0, 2.0, threshold, &D.loc, out, &out[2], B.c0);
-      }
-      out[3] = fu.done ? 1.0 : 0.0;
-      comm_allreduce_sum(out, 4);
-      if (fu.done) {
-        B.loc = std::move(fu.result);
-        if (out[3] != (double)world().nranks) pack(B.loc);
-      }
-      out[3] = 0.0;
-      return;
-    }
+    // (as on one rank; B is the panel [c0, c1) of the iterate whose needed columns the gathered operand holds)
+    SlabFusion fu = trs2_fusion(dist_fused ? 2 : 0, -1.0, 2.0, threshold, D, B.c0, B.c0);
+    const bool done = panel_step_from_columns(B, nnz, fu, threshold, out, AB, &L, [&] {
+      if (L.valid) axpby(L, B.loc, -1.0, 2.0, threshold, &D.loc, out, &out[2], B.c0, nullptr, false);
+      else merge_packed(&out[2]);
+    });
+    if (done) return;
   } else {
-    const bool dense_rule = denom > 0 && std::min((double)nz[0] / denom, (double)nz[1] / denom) > 0.1;
-    SlabFusion fu;   // the whole update inside the multiply's epilogue when the register-slab kernel takes it
-    fu.mode = keep_loose && options().fused_update ? 2 : 0;
-    fu.am = -1.0;
-    fu.bm = 2.0;
-    fu.threshold = threshold;
-    fu.D = &D.loc;
-    fu.col_offset = B.c0;
+    const bool dense_rule = dense_branch(B.dim, nnz, nnz);
+    // the whole update inside the multiply's epilogue when the register-slab kernel takes it
+    SlabFusion fu = trs2_fusion(keep_loose && options().fused_update ? 2 : 0, -1.0, 2.0, threshold, D, B.c0, -1);
     // an operand without run structure may hide a band under its labels (kernels.hpp relabel_enter)
     if (fu.mode && !B.loc.expanded() && !B.loc.loose()) relabel_enter(B.loc, D.loc);
     if (B.loc.expanded() && B.loc.slab->labelled()) {
@@ -1665,9 +1588,7 @@ void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, cons
     }
     if (B.loc.expanded()) {   // the iterate is in the kernel's own form already: no preparation pass at all
       if (fu.mode && slab_step(B.loc, fu, threshold, dense_rule)) {
-        out[0] = fu.dot;
-        out[1] = 0.0;
-        out[2] = fu.trace;
+        fusion_scalars(fu, out);
         return;
       }
       if (B.loc.slab->labelled()) relabel_giveup(D.loc);
@@ -1677,9 +1598,7 @@ void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, cons
     spgemm(B.loc, B.loc, AB, 1.0, threshold, dense_rule, &L, nullptr, fu.mode ? &fu : nullptr);
     if (fu.done) {
       B.loc = std::move(fu.result);
-      out[0] = fu.dot;
-      out[1] = 0.0;
-      out[2] = fu.trace;
+      fusion_scalars(fu, out);
       return;
     }
   }
@@ -1687,9 +1606,7 @@ void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, cons
     axpby(L, B.loc, -1.0, 2.0, threshold, &D.loc, out, want_trace ? &out[2] : nullptr, B.c0, nullptr, keep_loose);
   } else {
     pack(B.loc);
-    scratch.grid = B.grid; scratch.dim = B.dim; scratch.c0 = B.c0; scratch.c1 = B.c1; scratch.cplx = B.cplx;
-    scratch.loc = std::move(AB);
-    axpby(scratch.loc, B.loc, -1.0, 2.0, threshold, &D.loc, out, want_trace ? &out[2] : nullptr, B.c0);
+    merge_packed(want_trace ? &out[2] : nullptr);
   }
   if (last_spgemm_stats().block) B.loc.block_hint = 1;   // (the next step takes the iterate in block form: trs2_block)
   comm_allreduce_sum(out, want_trace ? 3 : 2);
@@ -1705,46 +1622,19 @@ void ps_square_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMat
   trs2_iterate_form(B);
   const bool keep_loose = !world().active() && options().loose_iterates != 0 && !B.cplx && !D.cplx &&
                           !(B.grid && B.grid->num_slices > 1);
-  if (keep_loose) {
-    const double denom = (double)B.dim * (double)B.dim;
-    const bool dense_rule = denom > 0 && (double)B.loc.nnz / denom > 0.1;
-    if (square_keep_loose(B.loc, threshold, dense_rule, D.loc, out, want_trace ? &out[2] : nullptr, B.c0)) return;
-  }
-  const bool dist_fused = world().active() && options().fused_update != 0 && options().loose_iterates != 0 && !B.cplx &&
-                          !D.cplx && !(B.grid && B.grid->num_slices > 1) && !block_scope_active();
-  if (dist_fused) {
+  if (keep_loose &&
+      square_keep_loose(B.loc, threshold, dense_branch(B.dim, B.loc.nnz, B.loc.nnz), D.loc, out, want_trace ? &out[2] : nullptr, B.c0))
+    return;
+  if (fused_across_ranks(B, D)) {
     if (dist_fused_step(B, 1, threshold, D, out)) return;
     // from compressed panels: the product with the fused epilogue (energy, trace, slab form) where the kernel takes it
     pack(B.loc);
-    const double denom = (double)B.dim * (double)B.dim;
-    int64_t nz[2] = {B.loc.nnz, B.loc.nnz};
-    HaloExchange hx;
-    gather_needed_begin(hx, B, B.loc, nz, false);
-    hx.finish();
-    const bool dense_rule = denom > 0 && std::min((double)nz[0] / denom, (double)nz[1] / denom) > 0.1;
-    const ColRange need{hx.kmin, hx.kmax + 1};
-    SlabFusion fu;
-    fu.mode = 1;
-    fu.D = &D.loc;
-    fu.col_offset = B.c0;
-    fu.panel_c0 = B.c0;
+    SlabFusion fu = trs2_fusion(1, 0.0, 0.0, 0.0, D, B.c0, B.c0);
     DevMat AB;
-    spgemm(hx.full, B.loc, AB, 1.0, threshold, dense_rule, nullptr, &need, &fu);
-    if (fu.done) {
-      out[0] = fu.dot;
-      out[1] = 0.0;
-      out[2] = fu.trace;
-    } else {
+    panel_step_from_columns(B, B.loc.nnz, fu, threshold, out, AB, nullptr, [&] {
       B.loc = std::move(AB);
       dot_trace(B.loc, D.loc, out, &out[2], B.c0);
-    }
-    out[3] = fu.done ? 1.0 : 0.0;
-    comm_allreduce_sum(out, 4);
-    if (fu.done) {
-      B.loc = std::move(fu.result);
-      if (out[3] != (double)world().nranks) pack(B.loc);
-    }
-    out[3] = 0.0;
+    });
     return;
   }
   pack(B.loc);
@@ -1780,9 +1670,7 @@ void ps_pairwise(const PSMatrix& A, const PSMatrix& B, PSMatrix& C) {
   }
   DevMat R;
   pairwise(A.loc, B.loc, R, false);
-  C.grid = A.grid; C.dim = A.dim; C.c0 = A.c0; C.c1 = A.c1;
-  C.cplx = A.cplx;
-  C.loc = std::move(R);
+  install(C, A.grid, A.dim, A.cplx, A.c0, A.c1, std::move(R));
 }
 
 // DotMatrix_psr/psc (PSMatrixAlgebraModule.F90:387-410, distributed_algebra_includes/DotMatrix.f90):
@@ -1857,19 +1745,12 @@ double ps_norm(const PSMatrix& A) {
     g_block_counts[1] += 1;
   }
   unblock({&A});
-  if (slab_on() && g_complex_session && A.cplx && A.loc.expanded()) {
+  if (slab_on() && A.loc.expanded()) {
+    // (a complex operand outside a session that takes them is refused: the real slab_norm declines it untouched)
     double v = 0.0;
-    if (slab_norm_c(A.loc, &v)) {
+    if (session_takes(A.cplx) && slab_kind(A.cplx).norm(A.loc, &v)) {
       g_slab_counts[2] += 1;
       comm_allreduce_max(&v, 1);   // (columns are local: a rank that declines computes its part below, every rank reduces once)
-      return v;
-    }
-  }
-  if (slab_on() && A.loc.expanded()) {
-    double v = 0.0;
-    if (slab_norm(A.loc, &v)) {
-      g_slab_counts[2] += 1;
-      comm_allreduce_max(&v, 1);
       return v;
     }
     slab_refused({&A});
@@ -1923,9 +1804,7 @@ void ps_transpose(const PSMatrix& A, PSMatrix& AT) {
   } else {
     R = transpose(A.loc);
   }
-  AT.grid = A.grid; AT.dim = A.dim; AT.c0 = A.c0; AT.c1 = A.c1;
-  AT.cplx = A.cplx;
-  AT.loc = std::move(R);
+  install(AT, A.grid, A.dim, A.cplx, A.c0, A.c1, std::move(R));
 }
 
 void ps_conjugate(PSMatrix& A) {
@@ -2022,11 +1901,7 @@ void ps_permute(const PSMatrix& in, PSMatrix& out, const Permutation& perm, bool
     R = remap_general(in.loc, dmap.p, dmap.p, n, 0, n, true);
   }
   sync_stream();
-  const ProcessGrid* g = in.grid;
-  const bool cplx = in.cplx;
-  const int32_t c0 = in.c0, c1 = in.c1;
-  out.grid = g; out.dim = n; out.cplx = cplx; out.c0 = c0; out.c1 = c1;
-  out.loc = std::move(R);
+  install(out, in.grid, n, in.cplx, in.c0, in.c1, std::move(R));   // (by value: out may be in)
 }
 
 }  // namespace ntp
