@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <string>
 #include <functional>
+#include <initializer_list>
 #include <vector>
 
 #include "common.hpp"
@@ -147,13 +148,13 @@ bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatr
 // MatrixNorm of alpha A + beta B (ScaleMatrix(B, beta); IncrementMatrix(A, B, alpha, 0); MatrixNorm(B)) for the loops
 // that build the sum only for its norm; false: not done (outside a slab session, operands in compressed columns ...)
 bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double beta, double* norm);
-void ps_slab_leave(PSMatrix& m);
+void ps_slab_leave(PSMatrix& m);   // back to compressed columns (no-op for a matrix that is not in slab form)
 const long long* column_fused_counts();   // [2] since start: IncrementMatrix(Identity, .) done in place, norms of differences taken without forming them (column_fused.hip)
 const long long* block_algebra_counts();  // [2] since start: operations done in block form (spgemm_block.hpp block algebra); fallbacks
 long long block_scope_products();   // panel products of block-order solves that took the block path (psmatrix.cpp)
 bool block_scope_active();   // band_scope.cpp: the solve in progress runs on operands redistributed in a block order (several ranks)
 const long long* panel_product_counts();  // [3] products of slab sessions across ranks: in slab form on every rank; declined; host synchronisations inside the former
-const long long* slab_algebra_counts();   // [4] since start: products, merges / copies, other operations done in slab form; refusals   // back to compressed columns (no-op for a matrix that is not in slab form)
+const long long* slab_algebra_counts();   // [4] since start: products, merges / copies, other operations done in slab form; refusals
 void ps_fill_identity(PSMatrix& m);
 void ps_fill_permutation(PSMatrix& m, const std::vector<int32_t>& lookup /*1-based*/, bool rows);
 void ps_fill_from_triplets(PSMatrix& m, const HostTriplets& t);
@@ -207,10 +208,10 @@ void ps_axpby_dot(const PSMatrix& A, PSMatrix& B, double alpha, double beta, dou
                   bool want_trace = false);  // out[2] = trace(B_new) on request
 void ps_dot_trace(const PSMatrix& A, const PSMatrix& B, double out[4], bool want_trace);
 void ps_square_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMatrix& D, double out[4], bool want_trace);
-// B <- 2B - B*B (threshold on the product and on the merge, TRS2's sigma > 0 update), out = dot(B_new, D), trace(B_new);
-// the product goes from the numeric kernel's slots straight into the merge when the slab kernel computes it
 // a TRS2 solve starts: complex iterates try the complex slab form again (psmatrix.cpp complex_trs2_step)
 void trs2_complex_reset();
+// B <- 2B - B*B (threshold on the product and on the merge, TRS2's sigma > 0 update), out = dot(B_new, D), trace(B_new);
+// the product goes from the numeric kernel's slots straight into the merge when the slab kernel computes it
 void ps_square_update_dot(PSMatrix& B, PSMatrix& scratch, double threshold, const PSMatrix& D, double out[4], bool want_trace);
 void ps_pairwise(const PSMatrix& A, const PSMatrix& B, PSMatrix& C);
 void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]);
@@ -276,6 +277,15 @@ struct SolverParameters {  // SolverParametersModule.F90:14-33, defaults :48-50
 };
 void print_parameters(const SolverParameters& p);
 void print_matrix_information(const PSMatrix& m);
+// what the solvers share around their loops (solvers.cpp).  solver_header, when p is verbose: the title, one level in, the
+// Method if there is one, the "Citations" block and the parameters; the caller's last log_exit closes it.  The balance_*
+// calls act under p.do_load_balancing only: m under p's permutation, in place; out = `in` under it (a plain copy
+// without load balancing); m back under the caller's labels
+void log_citations(std::initializer_list<const char*> keys);
+void solver_header(const char* title, const char* citation, const SolverParameters& p, const char* method = nullptr);
+void balance_permute(PSMatrix& m, const SolverParameters& p);
+void balance_copy(const PSMatrix& in, PSMatrix& out, const SolverParameters& p);
+void balance_undo(PSMatrix& m, const SolverParameters& p);
 
 // per-iteration record of the last solver call (tests/bench read it through the C ABI extension)
 struct SolverTrace {
@@ -285,7 +295,6 @@ struct SolverTrace {
   double setup_ms = 0, loop_ms = 0;
 };
 SolverTrace& last_trace();
-// one TRS2 iteration (DensityMatrixSolversModule.F90:380-404): returns the energy, sets sigma
 // matrix polynomials (solvers_poly.cpp): coefficient i of the vector multiplies x^i / T_i(x) / H_i(x)
 void polynomial_horner(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p);
 void polynomial_paterson_stockmeyer(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p);
@@ -305,6 +314,7 @@ void solver_scale_and_fold(const PSMatrix& H, const PSMatrix& ISQ, double trace,
                            double* energy_out, const SolverParameters& p);
 void energy_density_matrix(const PSMatrix& H, const PSMatrix& D, PSMatrix& ED, double threshold);
 void mcweeny_step(const PSMatrix& D, PSMatrix& DOut, const PSMatrix* S, double threshold);
+// one TRS2 iteration (DensityMatrixSolversModule.F90:380-404): returns the energy, sets sigma
 double trs2_step(PSMatrix& X, PSMatrix& X2, const PSMatrix& WH, double trace_target, double threshold, double* sigma,
                  double* trace_io = nullptr);
 

@@ -177,6 +177,32 @@ SolverTrace& last_trace() {
   return *t;
 }
 
+// ------------------------------------------------------------------ what the solvers share around their loops
+void log_citations(std::initializer_list<const char*> keys) {
+  log_header("Citations");
+  log_enter();
+  for (const char* k : keys) log_list_element(k);
+  log_exit();
+}
+void solver_header(const char* title, const char* citation, const SolverParameters& p, const char* method) {
+  if (!p.be_verbose) return;
+  log_header(title);
+  log_enter();
+  if (method) log_element("Method", method);
+  log_citations({citation});
+  print_parameters(p);
+}
+void balance_permute(PSMatrix& m, const SolverParameters& p) {
+  if (p.do_load_balancing) ps_permute(m, m, p.balance_permutation, false);
+}
+void balance_copy(const PSMatrix& in, PSMatrix& out, const SolverParameters& p) {
+  if (p.do_load_balancing) ps_permute(in, out, p.balance_permutation, false);
+  else ps_copy(in, out);
+}
+void balance_undo(PSMatrix& m, const SolverParameters& p) {
+  if (p.do_load_balancing) ps_permute(m, m, p.balance_permutation, true);
+}
+
 namespace {
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) {
@@ -200,36 +226,100 @@ double real_dot(const PSMatrix& A, const PSMatrix& B) {
   ps_dot(A, B, out);
   return out[0];
 }
-void density_header(const char* method, const char* citation, const SolverParameters& p) {
+// "this loop may take complex operands in slab form": FMA arithmetic and the complex tile kernel (sign, inverse, square roots)
+bool complex_slab_loop(const PSMatrix& m) {
+  return m.cplx && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0;
+}
+void log_iterations_header(const SolverParameters& p) {
   if (!p.be_verbose) return;
-  log_header("Density Matrix Solver");
+  log_header("Iterations");
   log_enter();
-  log_element("Method", method);
-  log_header("Citations");
-  log_enter();
-  log_list_element(citation);
-  log_exit();
-  print_parameters(p);
 }
-// common prologue of the density solvers: WH = ISQ H ISQ^T, optional permutation, Gershgorin
-void density_setup(const PSMatrix& H, const PSMatrix& ISQ, const SolverParameters& p, PSMatrix& IMat, PSMatrix& ISQT,
-                   PSMatrix& WH, double* e_min, double* e_max) {
-  ps_construct_like(IMat, H);
-  ps_fill_identity(IMat);
-  ps_transpose(ISQ, ISQT);
-  ps_similarity(H, ISQ, ISQT, WH, p.threshold);
-  if (p.do_load_balancing) {
-    ps_permute(WH, WH, p.balance_permutation, false);
-    ps_permute(IMat, IMat, p.balance_permutation, false);
+
+// What the density solvers share around their loops.  The loop body -- the part that differs, and the part read against
+// the Fortran -- stays written out in each solver; so do the communicator scope, the band scope and the slab session,
+// which differ per solver.
+struct DensityFrame {
+  const SolverParameters& p;
+  Clock::time_point t0, t1;
+  Monitor mon;
+  PSMatrix WH, IMat, ISQT;
+  double e_min = 0.0, e_max = 0.0;
+  double energy_value = 0.0;
+
+  // prologue: header, WH = ISQ H ISQ^T, optional permutation, Gershgorin bounds
+  DensityFrame(const char* method, const char* citation, const PSMatrix& H, const PSMatrix& ISQ, const SolverParameters& p_)
+      : p(p_) {
+    trace_reset();
+    t0 = Clock::now();
+    monitor_construct(mon, p.monitor_convergence, p.converge_diff);
+    solver_header("Density Matrix Solver", citation, p, method);
+    ps_construct_like(IMat, H);
+    ps_fill_identity(IMat);
+    ps_transpose(ISQ, ISQT);
+    ps_similarity(H, ISQ, ISQT, WH, p.threshold);
+    balance_permute(WH, p);
+    balance_permute(IMat, p);
+    ps_gershgorin(WH, &e_min, &e_max);
   }
-  ps_gershgorin(WH, e_min, e_max);
-}
-void density_finish(PSMatrix& X, const PSMatrix& ISQT, const PSMatrix& ISQ, PSMatrix& K, const SolverParameters& p) {
-  if (p.do_load_balancing) ps_permute(X, X, p.balance_permutation, true);
-  ps_similarity(X, ISQT, ISQ, K, p.threshold);
-  // what the fused / relabelled steps keep for the NEXT solve on the same operand (the expanded WH, WH in the recovered
-  // band order: about 8 (nnz + 32 columns) + 12 nnz + 8 n bytes, 1.3 GB at N = 262 144) goes now when the caller said so
-  if (!options().operand_cache) drop_operand_caches();
+  // X0 = (e_max I - WH) / (e_max - e_min): the spectrum mapped into [0, 1], reversed
+  void start_iterate(PSMatrix& X) const {
+    ps_copy(WH, X);
+    ps_scale(X, -1.0);
+    ps_increment(IMat, X, e_max, 0.0);
+    ps_scale(X, 1.0 / (e_max - e_min));
+  }
+  void begin_loop() {
+    log_iterations_header(p);
+    last_trace().setup_ms = ms_since(t0);
+    t1 = Clock::now();
+  }
+  // tail of one iteration, given the energy of the new iterate X: true when the loop is over
+  bool converged(double energy, double sigma, const PSMatrix& X) {
+    const double energy_old = energy_value;
+    energy_value = energy;
+    monitor_append(mon, energy_value - energy_old);
+    trace_rec(energy_value - energy_old, energy_value, sigma, X);
+    if (monitor_converged(mon, p.be_verbose)) return true;
+    if (p.be_verbose) {
+      log_enter();
+      log_element("Energy Value", energy_value);
+      log_exit();
+    }
+    return false;
+  }
+  // epilogue, once the iterate X is back in compressed columns: II is the loop counter as the loop left it
+  void finish(int II, PSMatrix& X, const PSMatrix& ISQ, PSMatrix& K, double* energy_out) {
+    last_trace().loop_ms = ms_since(t1);
+    if (p.be_verbose) {
+      log_exit();
+      log_element("Total Iterations", II);
+      print_matrix_information(X);
+    }
+    if (energy_out) *energy_out = energy_value;
+    balance_undo(X, p);
+    ps_similarity(X, ISQT, ISQ, K, p.threshold);
+    // what the fused / relabelled steps keep for the NEXT solve on the same operand (the expanded WH, WH in the recovered
+    // band order: about 8 (nnz + 32 columns) + 12 nnz + 8 n bytes, 1.3 GB at N = 262 144) goes now when the caller said so
+    if (!options().operand_cache) drop_operand_caches();
+    if (p.be_verbose) log_exit();
+  }
+};
+
+// The chemical potential from the recorded sigmas: bisection on [0, 1] for the point that the loop's scalar polynomials
+// z <- step(z, sigma_JJ), JJ = 1 .. total_iterations, carry to 1/2.  Returns the midpoint; the map back to an energy is the solver's.
+template <class Step>
+double bisect_mu(const std::vector<double>& sigma_array, int total_iterations, const SolverParameters& p, Step step) {
+  double interval_a = 0.0, interval_b = 1.0, midpoint = 0.0;
+  for (int it = 1; it <= p.max_iterations; ++it) {
+    midpoint = (interval_b - interval_a) / 2.0 + interval_a;
+    double z = midpoint;
+    for (int JJ = 1; JJ <= total_iterations; ++JJ) z = step(z, sigma_array[(size_t)JJ]);
+    if (z < 0.5) interval_a = midpoint;
+    else interval_b = midpoint;
+    if (std::fabs(z - 0.5) < p.converge_diff) break;
+  }
+  return midpoint;
 }
 }  // namespace
 
@@ -262,165 +352,38 @@ void solver_trs2(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
         solver_trs2(*in[0], *in[1], trace, *out[0], energy_out, mu_out, p);
       }))
     return;
-  trace_reset();
-  auto t0 = Clock::now();
-  Monitor mon;
-  monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  density_header("TRS2", "niklasson2002expansion", p);
+  DensityFrame f("TRS2", "niklasson2002expansion", H, ISQ, p);    // :344-365
   std::vector<double> sigma_array((size_t)p.max_iterations + 1, 0.0);
-  PSMatrix WH, IMat, ISQT, X, X2;
-  double e_min, e_max;
-  density_setup(H, ISQ, p, IMat, ISQT, WH, &e_min, &e_max);       // :344-365
-  ps_copy(WH, X);                                                  // :368-371
-  ps_scale(X, -1.0);
-  ps_increment(IMat, X, e_max, 0.0);
-  ps_scale(X, 1.0 / (e_max - e_min));
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
-  last_trace().setup_ms = ms_since(t0);
-  auto t1 = Clock::now();
-  double energy_value = 0.0, energy_old;
+  PSMatrix X, X2;
+  f.start_iterate(X);                                              // :368-371
+  f.begin_loop();
   double trace_x = std::nan("");  // trace of the current iterate, handed from step to step
   trs2_complex_reset();
   int II;
   for (II = 1; II <= p.max_iterations; ++II) {                     // :380-413
-    energy_old = energy_value;
     static const bool step_times = std::getenv("NTPOLY_AMD_DEBUG_STEPTIME") != nullptr;   // (host clock per iteration, rank 0)
     const auto ts0 = Clock::now();
-    energy_value = trs2_step(X, X2, WH, trace, p.threshold, &sigma_array[(size_t)II], &trace_x);
+    const double energy_value = trs2_step(X, X2, f.WH, trace, p.threshold, &sigma_array[(size_t)II], &trace_x);
     const double ts_step = step_times ? ms_since(ts0) : 0.0;   // (ms_since waits for the stream: only when asked for)
-    monitor_append(mon, energy_value - energy_old);
-    trace_rec(energy_value - energy_old, energy_value, sigma_array[(size_t)II], X);
+    const bool done = f.converged(energy_value, sigma_array[(size_t)II], X);
     if (step_times && world().rank == 0)
       std::fprintf(stderr, "[trs2] iteration %d: step %.3f ms, with the trace record %.3f ms\n", II, ts_step, ms_since(ts0));
-    if (monitor_converged(mon, p.be_verbose)) break;
-    if (p.be_verbose) {
-      log_enter();
-      log_element("Energy Value", energy_value);
-      log_exit();
-    }
+    if (done) break;
   }
   const int total_iterations = II - 1;
   pack(X.loc);  // (the steps leave the iterate loose, kernels.hpp)
-  last_trace().loop_ms = ms_since(t1);
-  if (p.be_verbose) {
-    log_exit();
-    log_element("Total Iterations", II);
-    print_matrix_information(X);
-  }
-  if (energy_out) *energy_out = energy_value;
-  density_finish(X, ISQT, ISQ, K, p);                              // :427-434
+  f.finish(II, X, ISQ, K, energy_out);                             // :427-434
   if (mu_out) {                                                    // :444-472
-    double interval_a = 0.0, interval_b = 1.0, midpoint = 0.0;
-    for (int it = 1; it <= p.max_iterations; ++it) {
-      midpoint = (interval_b - interval_a) / 2.0 + interval_a;
-      double zero_value = midpoint;
-      for (int JJ = 1; JJ <= total_iterations; ++JJ) {
-        if (sigma_array[(size_t)JJ] < 0.0) zero_value = zero_value * zero_value;
-        else zero_value = 2.0 * zero_value - zero_value * zero_value;
-      }
-      if (zero_value < 0.5) interval_a = midpoint;
-      else interval_b = midpoint;
-      if (std::fabs(zero_value - 0.5) < p.converge_diff) break;
-    }
-    *mu_out = e_max + (e_min - e_max) * midpoint;
+    const double midpoint = bisect_mu(sigma_array, total_iterations, p, [](double zero_value, double sg) {
+      if (sg < 0.0) zero_value = zero_value * zero_value;
+      else zero_value = 2.0 * zero_value - zero_value * zero_value;
+      return zero_value;
+    });
+    *mu_out = f.e_max + (f.e_min - f.e_max) * midpoint;
   }
-  if (p.be_verbose) log_exit();
 }
 
 // ------------------------------------------------------------------ TRS4
-// ------------------------------------------------------------------ ScaleAndFold
-// DensityMatrixSolversModule.F90:953-1117 (rubensson2011nonmonotonic): like TRS2 with the polynomials scaled by the
-// running estimates Beta / BetaBar of where lumo and homo have moved to
-void solver_scale_and_fold(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K, double homo, double lumo,
-                           double* energy_out, const SolverParameters& p) {
-  CommScope cs(H.grid);
-  trace_reset();
-  auto t0 = Clock::now();
-  Monitor mon;
-  monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  density_header("Scale and Fold", "rubensson2011nonmonotonic", p);
-  PSMatrix WH, IMat, ISQT, X, X2;
-  double e_min, e_max;
-  density_setup(H, ISQ, p, IMat, ISQT, WH, &e_min, &e_max);       // :1022-1034
-  ps_copy(WH, X);                                                  // :1036-1039
-  ps_scale(X, -1.0);
-  ps_increment(IMat, X, e_max, 0.0);
-  ps_scale(X, 1.0 / (e_max - e_min));
-  double Beta = (e_max - lumo) / (e_max - e_min);
-  double BetaBar = (e_max - homo) / (e_max - e_min);
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
-  last_trace().setup_ms = ms_since(t0);
-  auto t1 = Clock::now();
-  double energy_value = 0.0, energy_old;
-  int II;
-  SlabSession slab(!X.cplx && !WH.cplx);
-  for (II = 1; II <= p.max_iterations; ++II) {                     // :1049-1081
-    const double trace_value = ps_trace(X);
-    double alpha;
-    if (trace_value > trace) {
-      alpha = 2.0 / (2.0 - Beta);
-      ps_axpby(IMat, X, 1.0 - alpha, alpha, 0.0);                   // ScaleMatrix(X, alpha); IncrementMatrix(I, X, 1 - alpha)
-      ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
-      std::swap(X.loc, X2.loc);  // CopyMatrix(X_k2, X_k); X2 is scratch
-      Beta = (alpha * Beta + 1 - alpha) * (alpha * Beta + 1 - alpha);
-      BetaBar = (alpha * BetaBar + 1 - alpha) * (alpha * BetaBar + 1 - alpha);
-    } else {
-      alpha = 2.0 / (1.0 + BetaBar);
-      ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
-      ps_axpby(X2, X, -1.0 * alpha * alpha, 2 * alpha, 0.0);        // ScaleMatrix(X, 2 alpha); IncrementMatrix(X2, X, -alpha^2)
-      Beta = 2.0 * alpha * Beta - alpha * alpha * Beta * Beta;
-      BetaBar = 2.0 * alpha * BetaBar - alpha * alpha * BetaBar * BetaBar;
-    }
-    energy_old = energy_value;
-    energy_value = 2.0 * real_dot(X, WH);
-    monitor_append(mon, energy_value - energy_old);
-    trace_rec(energy_value - energy_old, energy_value, trace_value > trace ? -1.0 : 1.0, X);
-    if (monitor_converged(mon, p.be_verbose)) break;
-    if (p.be_verbose) {
-      log_enter();
-      log_element("Energy Value", energy_value);
-      log_exit();
-    }
-  }
-  slab.close();
-  ps_slab_leave(X);
-  last_trace().loop_ms = ms_since(t1);
-  if (p.be_verbose) {
-    log_exit();
-    log_element("Total Iterations", II);
-    print_matrix_information(X);
-  }
-  if (energy_out) *energy_out = energy_value;
-  density_finish(X, ISQT, ISQ, K, p);                              // :1095-1101
-  if (p.be_verbose) log_exit();
-}
-
-// EnergyDensityMatrix (:1165-1187): ED = D H D
-void energy_density_matrix(const PSMatrix& H, const PSMatrix& D, PSMatrix& ED, double threshold) {
-  CommScope cs(H.grid);
-  ps_similarity(H, D, D, ED, threshold);
-}
-
-// McWeenyStep (:1190-1231): DOut = 3 DSD - 2 DSDSD
-void mcweeny_step(const PSMatrix& D, PSMatrix& DOut, const PSMatrix* S, double threshold) {
-  CommScope cs(D.grid);
-  PSMatrix DS, DSD;
-  if (S) ps_multiply(D, *S, DS, 1.0, 0.0, threshold);
-  else ps_copy(D, DS);
-  ps_multiply(DS, D, DSD, 1.0, 0.0, threshold);
-  PSMatrix Out;
-  ps_multiply(DS, DSD, Out, -2.0, 0.0, threshold);
-  ps_increment(DSD, Out, 3.0, 0.0);
-  DOut.grid = Out.grid; DOut.dim = Out.dim; DOut.cplx = Out.cplx; DOut.c0 = Out.c0; DOut.c1 = Out.c1;
-  DOut.loc = std::move(Out.loc);
-}
-
 void solver_trs4(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K, double* energy_out, double* mu_out,
                  const SolverParameters& p) {
   CommScope cs(H.grid);
@@ -429,27 +392,13 @@ void solver_trs4(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
         solver_trs4(*in[0], *in[1], trace, *out[0], energy_out, mu_out, p);
       }))
     return;
-  trace_reset();
-  auto t0 = Clock::now();
   const double sigma_min = 0.0, sigma_max = 6.0;
-  Monitor mon;
-  monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  density_header("TRS4", "niklasson2002expansion", p);
+  DensityFrame f("TRS4", "niklasson2002expansion", H, ISQ, p);
+  const PSMatrix &WH = f.WH, &IMat = f.IMat;
   std::vector<double> sigma_array((size_t)p.max_iterations + 1, 0.0);
-  PSMatrix WH, IMat, ISQT, X, X2, Fx, Gx, Temp;
-  double e_min, e_max;
-  density_setup(H, ISQ, p, IMat, ISQT, WH, &e_min, &e_max);
-  ps_copy(WH, X);
-  ps_scale(X, -1.0);
-  ps_increment(IMat, X, e_max, 0.0);
-  ps_scale(X, 1.0 / (e_max - e_min));
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
-  last_trace().setup_ms = ms_since(t0);
-  auto t1 = Clock::now();
-  double energy_value = 0.0, energy_old;
+  PSMatrix X, X2, Fx, Gx, Temp;
+  f.start_iterate(X);
+  f.begin_loop();
   int II;
   SlabSession slab(!X.cplx && !WH.cplx);   // (the loop's matrices stay in slab form between its operations where they can)
   for (II = 1; II <= p.max_iterations; ++II) {                     // :586-638
@@ -485,50 +434,25 @@ void solver_trs4(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
     // :630-631 IncrementMatrix(TempMat, X_k, -1) is overwritten by the copy that follows it; the copy itself is a
     // hand-over here (Temp is rebuilt in every iteration)
     std::swap(X.loc, Temp.loc);
-    energy_old = energy_value;
-    energy_value = real_dot(X, WH);
-    monitor_append(mon, energy_value - energy_old);
-    trace_rec(energy_value - energy_old, energy_value, sigma_array[(size_t)II], X);
-    if (monitor_converged(mon, p.be_verbose)) break;
-    if (p.be_verbose) {
-      log_enter();
-      log_element("Energy Value", energy_value);
-      log_exit();
-    }
+    if (f.converged(real_dot(X, WH), sigma_array[(size_t)II], X)) break;
   }
   const int total_iterations = II - 1;
   slab.close();
   ps_slab_leave(X);
-  last_trace().loop_ms = ms_since(t1);
-  if (p.be_verbose) {
-    log_exit();
-    log_element("Total Iterations", II);
-    print_matrix_information(X);
-  }
-  if (energy_out) *energy_out = energy_value;
-  density_finish(X, ISQT, ISQ, K, p);
+  f.finish(II, X, ISQ, K, energy_out);
   if (mu_out) {                                                    // :669-704
-    double interval_a = 0.0, interval_b = 1.0, midpoint = 0.0;
-    for (int it = 1; it <= p.max_iterations; ++it) {
-      midpoint = (interval_b - interval_a) / 2.0 + interval_a;
-      double z = midpoint;
-      for (int JJ = 1; JJ <= total_iterations; ++JJ) {
-        const double sg = sigma_array[(size_t)JJ];
-        if (sg > sigma_max) z = 2.0 * z - z * z;
-        else if (sg < sigma_min) z = z * z;
-        else {
-          const double tempfx = (z * z) * (4.0 * z - 3.0 * z * z);
-          const double tempgx = (z * z) * (1.0 - z) * (1.0 - z);
-          z = tempfx + sg * tempgx;
-        }
+    const double midpoint = bisect_mu(sigma_array, total_iterations, p, [=](double z, double sg) {
+      if (sg > sigma_max) z = 2.0 * z - z * z;
+      else if (sg < sigma_min) z = z * z;
+      else {
+        const double tempfx = (z * z) * (4.0 * z - 3.0 * z * z);
+        const double tempgx = (z * z) * (1.0 - z) * (1.0 - z);
+        z = tempfx + sg * tempgx;
       }
-      if (z < 0.5) interval_a = midpoint;
-      else interval_b = midpoint;
-      if (std::fabs(z - 0.5) < p.converge_diff) break;
-    }
-    *mu_out = e_max + (e_min - e_max) * midpoint;
+      return z;
+    });
+    *mu_out = f.e_max + (f.e_min - f.e_max) * midpoint;
   }
-  if (p.be_verbose) log_exit();
 }
 
 // ------------------------------------------------------------------ PM
@@ -540,15 +464,11 @@ void solver_pm(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K
         solver_pm(*in[0], *in[1], trace, *out[0], energy_out, mu_out, p);
       }))
     return;
-  trace_reset();
-  auto t0 = Clock::now();
-  Monitor mon;
-  monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  density_header("PM", "palser1998canonical", p);
+  DensityFrame f("PM", "palser1998canonical", H, ISQ, p);         // :96-118
+  const PSMatrix &WH = f.WH, &IMat = f.IMat;
+  const double e_min = f.e_min, e_max = f.e_max;
   std::vector<double> sigma_array((size_t)p.max_iterations + 1, 0.0);
-  PSMatrix WH, IMat, ISQT, X, X2, X3, Temp;
-  double e_min, e_max;
-  density_setup(H, ISQ, p, IMat, ISQT, WH, &e_min, &e_max);       // :96-118
+  PSMatrix X, X2, X3, Temp;
   ps_copy(WH, X);
   const double dim = (double)H.dim;
   double trace_value = ps_trace(X);                                // :124-125
@@ -560,13 +480,7 @@ void solver_pm(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K
   ps_scale(X, factor);
   factor = (alpha * lambda + trace) / dim;
   ps_increment(IMat, X, factor, 0.0);
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
-  last_trace().setup_ms = ms_since(t0);
-  auto t1 = Clock::now();
-  double energy_value = 0.0, energy_old;
+  f.begin_loop();
   int II;
   // (no slab session here: whenever sigma > 1/2 the update scales X by a1 = 0 -- stored zeros whose tails steer the merges
   // that follow, which the slab form cannot hold -- so half the iterations would fall back and convert to and fro)
@@ -592,48 +506,23 @@ void solver_pm(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K
     }
     ps_axpby(X2, X, a2, a1, p.threshold);                           // ScaleMatrix(X, a1); IncrementMatrix(X2, X, a2)
     ps_increment(X3, X, a3, p.threshold);
-    energy_old = energy_value;
-    energy_value = real_dot(X, WH);
-    monitor_append(mon, energy_value - energy_old);
-    trace_rec(energy_value - energy_old, energy_value, sg, X);
-    if (monitor_converged(mon, p.be_verbose)) break;
-    if (p.be_verbose) {
-      log_enter();
-      log_element("Energy Value", energy_value);
-      log_exit();
-    }
+    if (f.converged(real_dot(X, WH), sg, X)) break;
   }
   const int total_iterations = II - 1;
-  last_trace().loop_ms = ms_since(t1);
-  if (p.be_verbose) {
-    log_exit();
-    log_element("Total Iterations", II);
-    print_matrix_information(X);
-  }
-  if (energy_out) *energy_out = energy_value;
-  density_finish(X, ISQT, ISQ, K, p);
+  f.finish(II, X, ISQ, K, energy_out);
   if (mu_out) {                                                    // :234-268
-    double interval_a = 0.0, interval_b = 1.0, midpoint = 0.0;
-    for (int it = 1; it <= p.max_iterations; ++it) {
-      midpoint = (interval_b - interval_a) / 2.0 + interval_a;
-      double z = midpoint;
-      for (int JJ = 1; JJ <= total_iterations; ++JJ) {
-        const double sg = sigma_array[(size_t)JJ];
-        if (sg > 0.5) {
-          z = ((1.0 + sg) * (z * z)) - (z * z * z);
-          z = z / sg;
-        } else {
-          z = ((1.0 - 2.0 * sg) * z) + ((1.0 + sg) * (z * z)) - (z * z * z);
-          z = z / (1.0 - sg);
-        }
+    const double midpoint = bisect_mu(sigma_array, total_iterations, p, [](double z, double sg) {
+      if (sg > 0.5) {
+        z = ((1.0 + sg) * (z * z)) - (z * z * z);
+        z = z / sg;
+      } else {
+        z = ((1.0 - 2.0 * sg) * z) + ((1.0 + sg) * (z * z)) - (z * z * z);
+        z = z / (1.0 - sg);
       }
-      if (z < 0.5) interval_a = midpoint;
-      else interval_b = midpoint;
-      if (std::fabs(z - 0.5) < p.converge_diff) break;
-    }
+      return z;
+    });
     *mu_out = lambda - (dim * midpoint - trace) / alpha;
   }
-  if (p.be_verbose) log_exit();
 }
 
 // ------------------------------------------------------------------ HPCP
@@ -645,15 +534,11 @@ void solver_hpcp(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
         solver_hpcp(*in[0], *in[1], trace, *out[0], energy_out, mu_out, p);
       }))
     return;
-  trace_reset();
-  auto t0 = Clock::now();
-  Monitor mon;
-  monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  density_header("HPCP", "truflandier2016communication", p);
+  DensityFrame f("HPCP", "truflandier2016communication", H, ISQ, p);   // :789-808
+  const PSMatrix &WH = f.WH, &IMat = f.IMat;
+  const double e_min = f.e_min, e_max = f.e_max;
   std::vector<double> sigma_array((size_t)p.max_iterations + 1, 0.0);
-  PSMatrix WH, IMat, ISQT, TempMat, D1, DH, DDH, D2DH;
-  double e_min, e_max;
-  density_setup(H, ISQ, p, IMat, ISQT, WH, &e_min, &e_max);       // :789-808
+  PSMatrix TempMat, D1, DH, DDH, D2DH;
   const double dim = (double)H.dim;
   double mu = ps_trace(WH) / dim;                                  // :809-817
   const double sigma_bar = (dim - trace) / dim;
@@ -669,13 +554,8 @@ void solver_hpcp(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
   ps_increment(WH, TempMat, -1.0, 0.0);
   ps_scale(TempMat, beta_2);
   ps_increment(TempMat, D1, 1.0, 0.0);
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
-  last_trace().setup_ms = ms_since(t0);
-  auto t1 = Clock::now();
-  double energy_value = 0.0, energy_old, trace_value = 0.0;
+  f.begin_loop();
+  double trace_value = 0.0;
   int II;
   SlabSession slab(!D1.cplx && !WH.cplx);
   for (II = 1; II <= p.max_iterations; ++II) {                     // :836-872
@@ -688,42 +568,78 @@ void solver_hpcp(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
     sigma_array[(size_t)II] = ps_trace(D2DH) / trace_value;
     ps_increment(D2DH, D1, 2.0, 0.0);
     ps_increment(DDH, D1, -1.0 * 2.0 * sigma_array[(size_t)II], 0.0);
-    energy_old = energy_value;
-    energy_value = real_dot(D1, WH);
-    monitor_append(mon, energy_value - energy_old);
-    trace_rec(energy_value - energy_old, energy_value, sigma_array[(size_t)II], D1);
-    if (monitor_converged(mon, p.be_verbose)) break;
-    if (p.be_verbose) {
-      log_enter();
-      log_element("Energy Value", energy_value);
-      log_exit();
-    }
+    if (f.converged(real_dot(D1, WH), sigma_array[(size_t)II], D1)) break;
   }
   const int total_iterations = II - 1;
   slab.close();
   ps_slab_leave(D1);
-  last_trace().loop_ms = ms_since(t1);
-  if (p.be_verbose) {
-    log_exit();
-    log_element("Total Iterations", II);
-    print_matrix_information(D1);
-  }
-  if (energy_out) *energy_out = energy_value;
-  density_finish(D1, ISQT, ISQ, K, p);
+  f.finish(II, D1, ISQ, K, energy_out);
   if (mu_out) {                                                    // :896-921
-    double interval_a = 0.0, interval_b = 1.0, midpoint = 0.0;
-    for (int it = 1; it <= p.max_iterations; ++it) {
-      midpoint = (interval_b - interval_a) / 2.0 + interval_a;
-      double z = midpoint;
-      for (int JJ = 1; JJ <= total_iterations; ++JJ)
-        z = z + 2.0 * (((z * z)) * (1.0 - z) - sigma_array[(size_t)JJ] * z * (1.0 - z));
-      if (z < 0.5) interval_a = midpoint;
-      else interval_b = midpoint;
-      if (std::fabs(z - 0.5) < p.converge_diff) break;
-    }
+    const double midpoint = bisect_mu(sigma_array, total_iterations, p, [](double z, double sg) {
+      return z + 2.0 * (((z * z)) * (1.0 - z) - sg * z * (1.0 - z));
+    });
     *mu_out = mu + (beta_1 - midpoint) / beta_2;
   }
-  if (p.be_verbose) log_exit();
+}
+
+// ------------------------------------------------------------------ ScaleAndFold
+// DensityMatrixSolversModule.F90:953-1117 (rubensson2011nonmonotonic): like TRS2 with the polynomials scaled by the
+// running estimates Beta / BetaBar of where lumo and homo have moved to
+void solver_scale_and_fold(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K, double homo, double lumo,
+                           double* energy_out, const SolverParameters& p) {
+  CommScope cs(H.grid);
+  DensityFrame f("Scale and Fold", "rubensson2011nonmonotonic", H, ISQ, p);   // :1022-1034
+  const PSMatrix &WH = f.WH, &IMat = f.IMat;
+  const double e_min = f.e_min, e_max = f.e_max;
+  PSMatrix X, X2;
+  f.start_iterate(X);                                              // :1036-1039
+  double Beta = (e_max - lumo) / (e_max - e_min);
+  double BetaBar = (e_max - homo) / (e_max - e_min);
+  f.begin_loop();
+  int II;
+  SlabSession slab(!X.cplx && !WH.cplx);
+  for (II = 1; II <= p.max_iterations; ++II) {                     // :1049-1081
+    const double trace_value = ps_trace(X);
+    double alpha;
+    if (trace_value > trace) {
+      alpha = 2.0 / (2.0 - Beta);
+      ps_axpby(IMat, X, 1.0 - alpha, alpha, 0.0);                   // ScaleMatrix(X, alpha); IncrementMatrix(I, X, 1 - alpha)
+      ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
+      std::swap(X.loc, X2.loc);  // CopyMatrix(X_k2, X_k); X2 is scratch
+      Beta = (alpha * Beta + 1 - alpha) * (alpha * Beta + 1 - alpha);
+      BetaBar = (alpha * BetaBar + 1 - alpha) * (alpha * BetaBar + 1 - alpha);
+    } else {
+      alpha = 2.0 / (1.0 + BetaBar);
+      ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
+      ps_axpby(X2, X, -1.0 * alpha * alpha, 2 * alpha, 0.0);        // ScaleMatrix(X, 2 alpha); IncrementMatrix(X2, X, -alpha^2)
+      Beta = 2.0 * alpha * Beta - alpha * alpha * Beta * Beta;
+      BetaBar = 2.0 * alpha * BetaBar - alpha * alpha * BetaBar * BetaBar;
+    }
+    if (f.converged(2.0 * real_dot(X, WH), trace_value > trace ? -1.0 : 1.0, X)) break;
+  }
+  slab.close();
+  ps_slab_leave(X);
+  f.finish(II, X, ISQ, K, energy_out);                             // :1095-1101
+}
+
+// EnergyDensityMatrix (:1165-1187): ED = D H D
+void energy_density_matrix(const PSMatrix& H, const PSMatrix& D, PSMatrix& ED, double threshold) {
+  CommScope cs(H.grid);
+  ps_similarity(H, D, D, ED, threshold);
+}
+
+// McWeenyStep (:1190-1231): DOut = 3 DSD - 2 DSDSD
+void mcweeny_step(const PSMatrix& D, PSMatrix& DOut, const PSMatrix* S, double threshold) {
+  CommScope cs(D.grid);
+  PSMatrix DS, DSD;
+  if (S) ps_multiply(D, *S, DS, 1.0, 0.0, threshold);
+  else ps_copy(D, DS);
+  ps_multiply(DS, D, DSD, 1.0, 0.0, threshold);
+  PSMatrix Out;
+  ps_multiply(DS, DSD, Out, -2.0, 0.0, threshold);
+  ps_increment(DSD, Out, 3.0, 0.0);
+  DOut.grid = Out.grid; DOut.dim = Out.dim; DOut.cplx = Out.cplx; DOut.c0 = Out.c0; DOut.c1 = Out.c1;
+  DOut.loc = std::move(Out.loc);
 }
 
 // ------------------------------------------------------------------ Sign / Polar
@@ -736,23 +652,16 @@ void sign_core(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters& 
   PSMatrix Identity, Temp1, Temp2, OutMatT, Out;
   ps_construct_like(Identity, InMat);
   ps_fill_identity(Identity);
-  if (p.do_load_balancing) {
-    ps_permute(Identity, Identity, p.balance_permutation, false);
-    ps_permute(InMat, Out, p.balance_permutation, false);
-  } else {
-    ps_copy(InMat, Out);
-  }
+  balance_permute(Identity, p);
+  balance_copy(InMat, Out, p);
   double e_min, e_max;
   ps_gershgorin(InMat, &e_min, &e_max);
   double xk = std::fabs(e_min / e_max);
   ps_scale(Out, 1.0 / std::fabs(e_max));
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
+  log_iterations_header(p);
   int II;
   // (complex operands under FMA arithmetic: the loop's products, identity increment and norm take them in slab form as well)
-  const bool complex_session = Out.cplx && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0;
+  const bool complex_session = complex_slab_loop(Out);
   SlabSession slab(!needs_transpose && (!Out.cplx || complex_session), false, complex_session);
   for (II = 1; II <= p.max_iterations; ++II) {
     const double alpha_k = std::fmin(std::sqrt(3.0 / (1.0 + xk + xk * xk)), alpha);
@@ -783,7 +692,7 @@ void sign_core(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters& 
     log_element("Total Iterations", II - 1);
     print_matrix_information(Out);
   }
-  if (p.do_load_balancing) ps_permute(Out, Out, p.balance_permutation, true);
+  balance_undo(Out, p);
   OutMat = std::move(Out);
 }
 }  // namespace
@@ -793,15 +702,7 @@ void solver_sign(const PSMatrix& A, PSMatrix& Out, const SolverParameters& p) {
   if (band_scope_try({&A}, {&Out}, [&](const std::vector<const PSMatrix*>& in, const std::vector<PSMatrix*>& out) { solver_sign(*in[0], *out[0], p); }))
     return;
   trace_reset();
-  if (p.be_verbose) {
-    log_header("Sign Function Solver");
-    log_enter();
-    log_header("Citations");
-    log_enter();
-    log_list_element("nicholas2008functions");
-    log_exit();
-    print_parameters(p);
-  }
+  solver_header("Sign Function Solver", "nicholas2008functions", p);
   sign_core(A, Out, p, false);
   if (p.be_verbose) log_exit();
 }
@@ -809,15 +710,7 @@ void solver_sign(const PSMatrix& A, PSMatrix& Out, const SolverParameters& p) {
 void solver_polar(const PSMatrix& A, PSMatrix& U, PSMatrix* Hm, const SolverParameters& p) {
   CommScope cs(A.grid);
   trace_reset();
-  if (p.be_verbose) {
-    log_header("Polar Decomposition Solver");
-    log_enter();
-    log_header("Citations");
-    log_enter();
-    log_list_element("nicholas2008functions");
-    log_exit();
-    print_parameters(p);
-  }
+  solver_header("Polar Decomposition Solver", "nicholas2008functions", p);
   sign_core(A, U, p, true);
   if (Hm) {  // SignSolversModule.F90:129-137
     PSMatrix UT;
@@ -833,35 +726,20 @@ namespace {
 void invert_core(const PSMatrix& InputMat, PSMatrix& OutputMat, const SolverParameters& p, bool log_top) {
   Monitor mon;
   monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  if (p.be_verbose) {
-    log_header("Inverse Solver");
-    log_enter();
-    log_header("Citations");
-    log_enter();
-    log_list_element("palser1998canonical");
-    log_exit();
-    print_parameters(p);
-  }
+  solver_header("Inverse Solver", "palser1998canonical", p);
   PSMatrix Temp1, Temp2, Identity, Balanced, Out;
   ps_construct_like(Identity, InputMat);
   ps_fill_identity(Identity);
-  if (p.do_load_balancing) {
-    ps_permute(Identity, Identity, p.balance_permutation, false);
-    ps_permute(InputMat, Balanced, p.balance_permutation, false);
-  } else {
-    ps_copy(InputMat, Balanced);
-  }
+  balance_permute(Identity, p);
+  balance_copy(InputMat, Balanced, p);
   const double sigma = ps_sigma(Balanced);
   ps_copy(Balanced, Out);
   ps_scale(Out, sigma);
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
+  log_iterations_header(p);
   double norm_value = p.converge_diff + 1.0;
   int II;
   // (complex operands under FMA arithmetic: products, merges, scalings, copies and norms take them in slab form as well)
-  const bool complex_session = Out.cplx && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0;
+  const bool complex_session = complex_slab_loop(Out);
   SlabSession slab(!Out.cplx || complex_session, false, complex_session);
   for (II = 1; II <= p.max_iterations; ++II) {
     if (log_top && p.be_verbose && II > 1) log_list_element("Convergence", norm_value);
@@ -884,7 +762,7 @@ void invert_core(const PSMatrix& InputMat, PSMatrix& OutputMat, const SolverPara
     log_element("Total Iterations", II - 1);
     print_matrix_information(Out);
   }
-  if (p.do_load_balancing) ps_permute(Out, Out, p.balance_permutation, true);
+  balance_undo(Out, p);
   if (p.be_verbose) log_exit();
   OutputMat = std::move(Out);
 }
@@ -907,22 +785,11 @@ void solver_pseudoinverse(const PSMatrix& A, PSMatrix& Out, const SolverParamete
 
 // ------------------------------------------------------------------ (inverse) square root
 namespace {
-void isr_header(const SolverParameters& p) {
-  if (!p.be_verbose) return;
-  log_header("Newton Schultz Inverse Square Root");
-  log_enter();
-  log_header("Citations");
-  log_enter();
-  log_list_element("jansik2007linear");
-  log_exit();
-  print_parameters(p);
-}
-
 // NewtonSchultzISROrder2 (SquareRootSolversModule.F90:198-338)
 void isr_order2(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters& p, bool compute_inverse) {
   Monitor mon;
   monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  isr_header(p);
+  solver_header("Newton Schultz Inverse Square Root", "jansik2007linear", p);
   PSMatrix X, T, Temp, Identity, SR, ISR;
   ps_construct_like(Identity, InMat);
   ps_fill_identity(Identity);
@@ -933,15 +800,10 @@ void isr_order2(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters&
   ps_construct_like(ISR, InMat);
   ps_fill_identity(ISR);
   ps_copy(InMat, SR);
-  if (p.do_load_balancing) {
-    ps_permute(SR, SR, p.balance_permutation, false);
-    ps_permute(Identity, Identity, p.balance_permutation, false);
-    ps_permute(ISR, ISR, p.balance_permutation, false);
-  }
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
+  balance_permute(SR, p);
+  balance_permute(Identity, p);
+  balance_permute(ISR, p);
+  log_iterations_header(p);
   int II;
   SlabSession slab(!SR.cplx);
   for (II = 1; II <= p.max_iterations; ++II) {
@@ -977,7 +839,7 @@ void isr_order2(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters&
   }
   PSMatrix Out;
   ps_copy(compute_inverse ? ISR : SR, Out);
-  if (p.do_load_balancing) ps_permute(Out, Out, p.balance_permutation, true);
+  balance_undo(Out, p);
   if (p.be_verbose) log_exit();
   OutMat = std::move(Out);
 }
@@ -986,7 +848,7 @@ void isr_order2(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters&
 void isr_taylor(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters& p, int order, bool compute_inverse) {
   Monitor mon;
   monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  isr_header(p);
+  solver_header("Newton Schultz Inverse Square Root", "jansik2007linear", p);
   PSMatrix X, Temp, Temp2, Identity, SR, ISR;
   ps_construct_like(Identity, InMat);
   ps_fill_identity(Identity);
@@ -998,18 +860,13 @@ void isr_taylor(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters&
   ps_fill_identity(ISR);
   ps_copy(InMat, SR);
   ps_scale(SR, lambda);
-  if (p.do_load_balancing) {                                       // :399-406
-    ps_permute(SR, SR, p.balance_permutation, false);
-    ps_permute(Identity, Identity, p.balance_permutation, false);
-    ps_permute(ISR, ISR, p.balance_permutation, false);
-  }
-  if (p.be_verbose) {
-    log_header("Iterations");
-    log_enter();
-  }
+  balance_permute(SR, p);                                          // :399-406
+  balance_permute(Identity, p);
+  balance_permute(ISR, p);
+  log_iterations_header(p);
   int II;
   // (complex operands under FMA arithmetic: the loop's whole vocabulary takes them in slab form -- SquareRootSolversModule.F90:415-497)
-  const bool complex_session = SR.cplx && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0;
+  const bool complex_session = complex_slab_loop(SR);
   SlabSession slab(!SR.cplx || complex_session, false, complex_session);
   for (II = 1; II <= p.max_iterations; ++II) {                     // :415-497
     ps_multiply(ISR, SR, X, 1.0, 0.0, p.threshold);
@@ -1058,7 +915,7 @@ void isr_taylor(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters&
     ps_scale(SR, 1.0 / std::sqrt(lambda));
     ps_copy(SR, Out);
   }
-  if (p.do_load_balancing) ps_permute(Out, Out, p.balance_permutation, true);
+  balance_undo(Out, p);
   if (p.be_verbose) log_exit();
   OutMat = std::move(Out);
 }

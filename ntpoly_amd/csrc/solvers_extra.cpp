@@ -51,14 +51,9 @@ void solver_cg(const PSMatrix& AMat, PSMatrix& XMat, const PSMatrix& BMat, const
   PSMatrix Identity, ABalanced, BBalanced, RMat, PMat, QMat, RMatT, PMatT, TempMat, X;
   ps_construct_like(Identity, AMat);
   ps_fill_identity(Identity);
-  if (p.do_load_balancing) {
-    ps_permute(Identity, Identity, p.balance_permutation, false);
-    ps_permute(AMat, ABalanced, p.balance_permutation, false);
-    ps_permute(BMat, BBalanced, p.balance_permutation, false);
-  } else {
-    ps_copy(AMat, ABalanced);
-    ps_copy(BMat, BBalanced);
-  }
+  balance_permute(Identity, p);
+  balance_copy(AMat, ABalanced, p);
+  balance_copy(BMat, BBalanced, p);
   ps_copy(Identity, X);                                                        // initial guess X = I (:89)
   ps_multiply(ABalanced, X, TempMat, 1.0, 0.0, p.threshold);
   ps_copy(BBalanced, RMat);
@@ -95,7 +90,7 @@ void solver_cg(const PSMatrix& AMat, PSMatrix& XMat, const PSMatrix& BMat, const
     log_element("Total Iterations", II - 1);
     print_matrix_information(X);
   }
-  if (p.do_load_balancing) ps_permute(X, X, p.balance_permutation, true);
+  balance_undo(X, p);
   if (p.be_verbose) log_exit();
   XMat = std::move(X);
 }
@@ -164,24 +159,13 @@ void purification_extrapolate(const PSMatrix& PreviousDensity, const PSMatrix& O
   CommScope cs(PreviousDensity.grid);                  // :24-136
   Monitor mon;
   const SolverParameters p = with_monitor(p_in, mon);
-  if (p.be_verbose) {
-    log_header("Density Matrix Extrapolator");
-    log_enter();
-    log_element("Method", "Purification");
-    log_header("Citations");
-    log_enter();
-    log_list_element("niklasson2010trace");
-    log_exit();
-    print_parameters(p);
-  }
+  solver_header("Density Matrix Extrapolator", "niklasson2010trace", p, "Purification");
   PSMatrix NewDensity, WorkingDensity, WorkingOverlap, TempMat;
   ps_construct_like(NewDensity, PreviousDensity);
   ps_copy(PreviousDensity, WorkingDensity);
   ps_copy(Overlap, WorkingOverlap);
-  if (p.do_load_balancing) {
-    ps_permute(WorkingDensity, WorkingDensity, p.balance_permutation, false);
-    ps_permute(WorkingOverlap, WorkingOverlap, p.balance_permutation, false);
-  }
+  balance_permute(WorkingDensity, p);
+  balance_permute(WorkingOverlap, p);
   if (p.be_verbose) {
     log_header("Iterations");
     log_enter();
@@ -213,7 +197,7 @@ void purification_extrapolate(const PSMatrix& PreviousDensity, const PSMatrix& O
     log_element("Total Iterations", II);
     print_matrix_information(NewDensity);
   }
-  if (p.do_load_balancing) ps_permute(NewDensity, NewDensity, p.balance_permutation, true);
+  balance_undo(NewDensity, p);
   if (p.be_verbose) log_exit();
   NewDensityOut = std::move(NewDensity);
 }
@@ -221,16 +205,7 @@ void purification_extrapolate(const PSMatrix& PreviousDensity, const PSMatrix& O
 void lowdin_extrapolate(const PSMatrix& PreviousDensity, const PSMatrix& OldOverlap, const PSMatrix& NewOverlap,
                         PSMatrix& NewDensity, const SolverParameters& p) {
   CommScope cs(PreviousDensity.grid);     // :137-214
-  if (p.be_verbose) {
-    log_header("Density Matrix Extrapolator");
-    log_enter();
-    log_element("Method", "Lowdin");
-    log_header("Citations");
-    log_enter();
-    log_list_element("exner2002comparison");
-    log_exit();
-    print_parameters(p);
-  }
+  solver_header("Density Matrix Extrapolator", "exner2002comparison", p, "Lowdin");
   PSMatrix SQRMat, ISQMat, TempMat, Out;
   solver_square_root(OldOverlap, SQRMat, p, false, 5);
   solver_square_root(NewOverlap, ISQMat, p, true, 5);
@@ -556,10 +531,8 @@ void solver_wom(const PSMatrix& H, const PSMatrix& ISQ, PSMatrix& K, double inv_
   ps_fill_identity(IMat);
   ps_transpose(ISQ, ISQT);
   ps_similarity(H, ISQ, ISQT, WH, p.threshold);
-  if (p.do_load_balancing) {
-    ps_permute(WH, WH, p.balance_permutation, false);
-    ps_permute(IMat, IMat, p.balance_permutation, false);
-  }
+  balance_permute(WH, p);
+  balance_permute(IMat, p);
   ps_copy(WH, A);
   if (GC) ps_increment(IMat, A, -1.0 * (*mu_in), 0.0);
   ps_copy(IMat, W);
@@ -633,7 +606,7 @@ void solver_wom(const PSMatrix& H, const PSMatrix& ISQ, PSMatrix& K, double inv_
     ps_dot(WH, KOrth, d);
     *energy_out = d[0];
   }
-  if (p.do_load_balancing) ps_permute(KOrth, KOrth, p.balance_permutation, true);
+  balance_undo(KOrth, p);
   ps_similarity(KOrth, ISQT, ISQ, Out, p.threshold);
   if (p.be_verbose) log_exit();
   K = std::move(Out);
@@ -654,10 +627,7 @@ void ps_cholesky(const PSMatrix& A, PSMatrix& L, int rank, const SolverParameter
     } else {
       log_element("Method", "Pivoted Cholesky Decomposition");
       log_element("Target_Rank", rank);
-      log_header("Citations");
-      log_enter();
-      log_list_element("aquilante2006fast");
-      log_exit();
+      log_citations({"aquilante2006fast"});
     }
     print_parameters(p);
   }

@@ -116,21 +116,13 @@ void compute_exponential(const PSMatrix& In, PSMatrix& Out, const SolverParamete
                                1.992124801999838e-07, 1.103677287249654e-08, 5.505891628277851e-10, 2.498021534339559e-11,
                                1.038827668772902e-12, 4.032447357431817e-14, 2.127980007794583e-15, -1.629151584468762e-16};
   chebyshev_compute(Scaled, R, std::vector<double>(c, c + 16), sub);
-  if (p.do_load_balancing) {
-    PSMatrix t;
-    ps_permute(R, t, p.balance_permutation, false);
-    R = std::move(t);
-  }
+  balance_permute(R, p);
   for (int k = 1; k <= sigma_counter - 1; ++k) {
     ps_multiply(R, R, Temp, 1.0, 0.0, p.threshold);
     std::swap(R.loc, Temp.loc);
   }
   if (p.be_verbose) print_matrix_information(R);
-  if (p.do_load_balancing) {
-    PSMatrix t;
-    ps_permute(R, t, p.balance_permutation, true);
-    R = std::move(t);
-  }
+  balance_undo(R, p);
   Out = std::move(R);
   if (p.be_verbose) log_exit();
 }
@@ -142,12 +134,7 @@ void scale_square_trig(const PSMatrix& In, PSMatrix& Out, const SolverParameters
     log_header("Trigonometry Solver");
     log_enter();
     log_element("Method", "Chebyshev");
-    log_header("Citations");
-    log_enter();
-    log_list_element("serbin1980algorithm");
-    log_list_element("higham2003computing");
-    log_list_element("yau1993reducing");
-    log_exit();
+    log_citations({"serbin1980algorithm", "higham2003computing", "yau1993reducing"});
     print_parameters(p);
   }
   double e_min, e_max;
@@ -164,13 +151,8 @@ void scale_square_trig(const PSMatrix& In, PSMatrix& Out, const SolverParameters
   ps_scale(Scaled, 1.0 / sigma_val);
   ps_construct_like(Ident, In);
   ps_fill_identity(Ident);
-  if (p.do_load_balancing) {
-    PSMatrix t, u;
-    ps_permute(Scaled, t, p.balance_permutation, false);
-    Scaled = std::move(t);
-    ps_permute(Ident, u, p.balance_permutation, false);
-    Ident = std::move(u);
-  }
+  balance_permute(Scaled, p);
+  balance_permute(Ident, p);
   // Chebyshev coefficients of cos on [-1, 1], even terms only (:309-325), 1-based as in the reference
   double c[18] = {0};
   c[1] = 7.651976865579664e-01;  c[3] = -2.298069698638004e-01; c[5] = 4.953277928219409e-03;
@@ -209,11 +191,7 @@ void scale_square_trig(const PSMatrix& In, PSMatrix& Out, const SolverParameters
   }
   slab.close();
   ps_slab_leave(R);
-  if (p.do_load_balancing) {
-    PSMatrix t;
-    ps_permute(R, t, p.balance_permutation, true);
-    R = std::move(t);
-  }
+  balance_undo(R, p);
   Out = std::move(R);
   if (p.be_verbose) log_exit();
 }
@@ -240,15 +218,7 @@ namespace {
 void inverse_root_impl(const PSMatrix& In, PSMatrix& Out, int root, const SolverParameters& p) {  // :177-337
   Monitor mon;
   monitor_construct(mon, p.monitor_convergence, p.converge_diff);
-  if (p.be_verbose) {
-    log_header("Root Solver");
-    log_enter();
-    log_header("Citations");
-    log_enter();
-    log_list_element("nicholas2008functions");
-    log_exit();
-    print_parameters(p);
-  }
+  solver_header("Root Solver", "nicholas2008functions", p);
   double e_min, e_max;
   ps_gershgorin(In, &e_min, &e_max);
   const double scaling_factor = e_max / std::pow(std::sqrt(2.0), 1.0 / root);
@@ -261,13 +231,8 @@ void inverse_root_impl(const PSMatrix& In, PSMatrix& Out, int root, const Solver
   solver_square_root(SqrtMat, Fthrt, p, false, 5);
   ps_construct_like(Ident, In);
   ps_fill_identity(Ident);
-  if (p.do_load_balancing) {
-    PSMatrix t, u;
-    ps_permute(Fthrt, t, p.balance_permutation, false);
-    Fthrt = std::move(t);
-    ps_permute(Ident, u, p.balance_permutation, false);
-    Ident = std::move(u);
-  }
+  balance_permute(Fthrt, p);
+  balance_permute(Ident, p);
   ps_copy(Ident, R);
   ps_scale(R, 1.0 / scaling_factor);
   ps_copy(Fthrt, Mk);
@@ -317,11 +282,7 @@ void inverse_root_impl(const PSMatrix& In, PSMatrix& Out, int root, const Solver
   }
   slab.close();
   ps_slab_leave(R);
-  if (p.do_load_balancing) {
-    PSMatrix t;
-    ps_permute(R, t, p.balance_permutation, true);
-    R = std::move(t);
-  }
+  balance_undo(R, p);
   Out = std::move(R);
   if (p.be_verbose) log_exit();
 }

@@ -19,21 +19,8 @@ void balanced_setup(const PSMatrix& In, const SolverParameters& p, Balanced& b) 
   ps_construct_like(b.Identity, In);
   ps_fill_identity(b.Identity);
   ps_copy(In, b.Input);
-  if (p.do_load_balancing) {
-    PSMatrix t;
-    ps_permute(b.Identity, t, p.balance_permutation, false);
-    b.Identity = std::move(t);
-    PSMatrix u;
-    ps_permute(b.Input, u, p.balance_permutation, false);
-    b.Input = std::move(u);
-  }
-}
-void balanced_finish(PSMatrix& Out, const SolverParameters& p) {
-  if (p.do_load_balancing) {
-    PSMatrix t;
-    ps_permute(Out, t, p.balance_permutation, true);
-    Out = std::move(t);
-  }
+  balance_permute(b.Identity, p);
+  balance_permute(b.Input, p);
 }
 void poly_header(const char* solver, const char* method, const char* citation, int degree, const SolverParameters& p,
                  bool degree_first) {
@@ -41,12 +28,7 @@ void poly_header(const char* solver, const char* method, const char* citation, i
   log_header(solver);
   log_enter();
   log_element("Method", method);
-  if (citation) {
-    log_header("Citations");
-    log_enter();
-    log_list_element(citation);
-    log_exit();
-  }
+  if (citation) log_citations({citation});
   if (degree_first) log_element("Degree", degree - 1);
   print_parameters(p);
   if (!degree_first) log_element("Degree", degree - 1);
@@ -77,7 +59,7 @@ void polynomial_horner(const PSMatrix& In, PSMatrix& Out, const std::vector<doub
   }
   slab.close();
   ps_slab_leave(R);
-  balanced_finish(R, p);
+  balance_undo(R, p);
   Out = std::move(R);
   if (p.be_verbose) log_exit();
 }
@@ -175,7 +157,7 @@ void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<doub
   slab.close();
   ps_slab_leave(R);
   if (p.be_verbose) print_matrix_information(R);
-  balanced_finish(R, p);
+  balance_undo(R, p);
   Out = std::move(R);
   if (p.be_verbose) log_exit();
 }
@@ -234,7 +216,7 @@ void chebyshev_factorized(const PSMatrix& In, PSMatrix& Out, const std::vector<d
   slab.close();
   ps_slab_leave(R);
   if (p.be_verbose) print_matrix_information(R);
-  balanced_finish(R, p);
+  balance_undo(R, p);
   Out = std::move(R);
   if (p.be_verbose) log_exit();
 }
@@ -273,7 +255,7 @@ void hermite_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double
   slab.close();
   ps_slab_leave(R);
   if (p.be_verbose) print_matrix_information(R);
-  balanced_finish(R, p);
+  balance_undo(R, p);
   Out = std::move(R);
   if (p.be_verbose) log_exit();
 }
