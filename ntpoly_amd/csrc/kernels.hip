@@ -2711,6 +2711,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_SLAB_ALGEBRA")) e->slab_algebra = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_PANEL_SESSIONS")) e->panel_sessions = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PANELS")) e->complex_panels = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_THIN_SLAB_COMPLEX")) e->thin_slab_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_DENSITY")) e->complex_density = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_SCOPE_COMPLEX")) e->block_scope_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_UNFUSED")) e->block_unfused = std::atoi(v);
@@ -6639,13 +6640,17 @@ bool slab_multiply(const DevMat& A, const DevMat& B, DevMat& C, double alpha, do
   fo->val.alloc(oslots);
   // ---- a thin operand (an identity, the near-diagonal factor of a square-root loop): the gather kernels of spgemm_thin.hip
   // on the same plan and output slots -- a handful of products per entry instead of the whole k range of the block
-  const int thin_mode = (options().thin_left == 0 || fa.labelled() || fb.labelled() || A.rows != A.cols || left) ? 0
-                        : (A.nnz <= 8 * (int64_t)A.cols && B.nnz >= A.nnz)                                 ? 1
-                        : (B.nnz <= 8 * (int64_t)n)                                                          ? 2
-                                                                                                             : 0;
+  // (a panel product: the decision comes with the halo -- global entry counts, the same on every rank and what one rank decides)
+  const int thin_mode = (options().thin_left == 0 || fa.labelled() || fb.labelled() || (!left && A.rows != A.cols)) ? 0
+                        : left                                                                             ? left->thin
+                                                                                                           : slab_thin_rule(A.nnz, B.nnz, A.cols);
+  bool on_fetch_done = false;
   if (thin_mode) {
     DevMat AT;
-    if (thin_mode == 1) {
+    ThinRows rows;   // (a panel product: the rows of the halo's columns, from their runs)
+    if (thin_mode == 1 && left) {
+      thin_rows_from_runs(false, afirst, alast, left->addr - ka, nullptr, nullptr, ka, ka + nka, A.rows, left->nnz_a, rows);
+    } else if (thin_mode == 1) {
       DevMat Ap = packed_copy(A);
       AT = transpose(Ap);
     }
@@ -6655,8 +6660,10 @@ bool slab_multiply(const DevMat& A, const DevMat& B, DevMat& C, double alpha, do
     ThinSlabArgs ta;
     ta.blk_lo = P.blk_lo.p; ta.blk_w = P.blk_w.p; ta.blk_toff = P.blk_toff.p;
     ta.bfirst = fb.first.p; ta.blast = fb.last.p; ta.boff = fb.off.p; ta.bval = fb.val.p;
-    ta.afirst = fa.first.p; ta.alast = fa.last.p; ta.aoff = fa.off.p; ta.aval = fa.val.p;
-    if (thin_mode == 1) { ta.at_outer = AT.outer.p; ta.at_inner = AT.inner.p; ta.at_val = AT.val.p; }
+    ta.afirst = afirst; ta.alast = alast; ta.aoff = fa.off.p; ta.aval = fa.val.p;
+    if (left) ta.aaddr = left->addr - ka;
+    if (thin_mode == 1 && left) { ta.at_outer = rows.outer.p; ta.at_inner = rows.inner.p; ta.at_val = rows.val.p; }
+    else if (thin_mode == 1) { ta.at_outer = AT.outer.p; ta.at_inner = AT.inner.p; ta.at_val = AT.val.p; }
     ta.out_val = fo->val.p; ta.count = fo->count.p; ta.ofirst = fo->first.p; ta.olast = fo->last.p; ta.ooff = fo->off.p;
     ta.alpha = alpha; ta.threshold = threshold; ta.dense_rule = dense_rule ? 1 : 0; ta.ncols = n; ta.nrows = A.rows; ta.flag = tflag.p;
     launch_thin_slab(ta, thin_mode == 1);
@@ -6668,6 +6675,7 @@ bool slab_multiply(const DevMat& A, const DevMat& B, DevMat& C, double alpha, do
       ScalarFetch f;
       f.add(tot.p, 1, &nnz);
       f.add(tflag.p, 1, &fl);
+      if (left && left->on_fetch) { left->on_fetch(f); on_fetch_done = true; }
       f.run();
     }
     if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
@@ -6684,6 +6692,8 @@ bool slab_multiply(const DevMat& A, const DevMat& B, DevMat& C, double alpha, do
       SpgemmStats st;
       st.nnz_a = A.nnz; st.nnz_b = B.nnz; st.nnz_c = nnz; st.slab = 1; st.thin = 1; st.tmp_entries = P.total;
       last_spgemm_stats() = st;
+      thin_slab_counts()[thin_mode - 1] += 1;
+      if (left) thin_slab_counts()[4] += 1;
       SpgemmAccum& acc = spgemm_accum();
       acc.calls += 1;
       acc.nnz_c += nnz;
@@ -6735,7 +6745,7 @@ bool slab_multiply(const DevMat& A, const DevMat& B, DevMat& C, double alpha, do
     ScalarFetch f;
     f.add(tot.p, 1, &nnz);
     if (used_tile2) f.add(t2fail.p, 1, &t2f);
-    if (left && left->on_fetch) left->on_fetch(f);
+    if (left && left->on_fetch && !on_fetch_done) left->on_fetch(f);
     f.run();
   }
   if (used_tile2 && (int)(t2f & 0xffffffffll) != 0) {
@@ -6788,6 +6798,10 @@ __global__ __launch_bounds__(256) void k_count_zero_values_c(Csc A, unsigned lon
   if (m && lane == 0) atomicAdd(out, 1ull);
 }
 }  // namespace
+long long* thin_slab_counts() {
+  static long long counts[6] = {0, 0, 0, 0, 0, 0};
+  return counts;
+}
 bool sa_operand_c(const DevMat& M) {
   return M.expanded() && M.cplx && !M.slab->labelled() && !M.slab->origin && (M.rows == M.cols || g_panels_ok) && M.slab->row_pad % 16 == 0;
 }
@@ -6899,6 +6913,69 @@ bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, 
     return false;
   }
   const int ka = left ? left->ka : 0, nka = left ? left->kb - left->ka : A.cols;
+  std::unique_ptr<SlabForm> fo(new SlabForm());
+  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
+  fo->count.zero();
+  fo->val.alloc(((size_t)total + kIndexSlack) * 2);
+  // ---- a thin operand (an identity, the near-diagonal factor of a square-root loop): the complex gather kernels of
+  // spgemm_thin.hip on the same plan and output slots (option thin_slab_complex) -- the reference's own multiply-add, bit for
+  // bit, and no hand-back: the right-hand kernel takes every column.  A panel product's decision comes with the halo (global
+  // entry counts): every rank, and one rank alone, take the same kernel for the same product.
+  const int thin_mode = (options().thin_left == 0 || options().thin_slab_complex == 0 || (!left && A.rows != A.cols)) ? 0
+                        : left                                                                                         ? left->thin
+                                                                                                                       : slab_thin_rule(A.nnz, B.nnz, A.cols);
+  if (thin_mode) {
+    const int32_t* afirst = left ? left->first - ka : fa.first.p;   // (global column numbers through biased pointers)
+    const int32_t* alast = left ? left->last - ka : fa.last.p;
+    ThinRows rows;
+    if (thin_mode == 1)
+      thin_rows_from_runs(true, afirst, alast, left ? left->addr - ka : nullptr, fa.off.p, fa.val.p, ka, ka + nka, A.rows,
+                          left ? left->nnz_a : A.nnz, rows);
+    t_num.start();
+    ThinSlabArgs ta;
+    ta.blk_lo = P.blk_lo.p; ta.blk_w = P.blk_w.p; ta.blk_toff = P.blk_toff.p;
+    ta.bfirst = fb.first.p; ta.blast = fb.last.p; ta.boff = fb.off.p; ta.bval = fb.val.p;
+    ta.afirst = afirst; ta.alast = alast; ta.aoff = fa.off.p; ta.aval = fa.val.p;
+    if (left) ta.aaddr = left->addr - ka;
+    if (thin_mode == 1) { ta.at_outer = rows.outer.p; ta.at_inner = rows.inner.p; ta.at_val = rows.val.p; }
+    ta.out_val = fo->val.p; ta.count = fo->count.p; ta.ofirst = fo->first.p; ta.olast = fo->last.p; ta.ooff = fo->off.p;
+    ta.alpha = alpha; ta.threshold = threshold; ta.dense_rule = dense_rule ? 1 : 0; ta.ncols = n; ta.nrows = A.rows; ta.nblocks = snb;
+    launch_thin_slab(ta, thin_mode == 1, true);
+    t_num.stop();
+    DevBuf<long long> tot;
+    sa_sum_counts(fo->count.p, n, tot);
+    int64_t nnz = 0;
+    {
+      ScalarFetch f;
+      f.add(tot.p, 1, &nnz);
+      if (left && left->on_fetch) left->on_fetch(f);
+      f.run();
+    }
+    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+      std::fprintf(stderr, "[slab_multiply_c] thin %s: nnzA %lld nnzB %lld nnzC %lld slots %lld max_w %d max_kn %d\n", thin_mode == 1 ? "left" : "right",
+                   (long long)A.nnz, (long long)B.nnz, (long long)nnz, (long long)total, max_w, max_kn);
+    t_all.stop();
+    if (timing) {
+      if (pending_timings().size() >= 4096) flush_spgemm_timers();
+      pending_timings().push_back(TimedCall{{t_all.a, t_all.b, t_num.a, t_num.b}});
+    }
+    fo->row_pad = 16;
+    fo->slots = total;
+    SpgemmStats st;
+    st.nnz_a = A.nnz; st.nnz_b = B.nnz; st.nnz_c = nnz; st.slab = 1; st.thin = 1; st.tmp_entries = total;
+    last_spgemm_stats() = st;
+    thin_slab_counts()[1 + thin_mode] += 1;
+    if (left) thin_slab_counts()[5] += 1;
+    SpgemmAccum& acc = spgemm_accum();
+    acc.calls += 1;
+    acc.nnz_c += nnz;
+    acc.alg_bytes += 20.0 * ((double)A.nnz + (double)B.nnz + (double)nnz) + 4.0 * ((double)A.cols + 2.0 * n + 3.0);
+    DevMat R;
+    R.rows = A.rows; R.cols = n; R.cplx = true; R.nnz = nnz; R.zero_free = 1;
+    R.slab = std::move(fo);
+    C = std::move(R);
+    return true;
+  }
   DevBuf<char> runs(((size_t)nka + 4) * sizeof(SlabRun));
   if (left)
     hipLaunchKernelGGL(k_slab_runs_addr, dim3(cdiv(nka + 4, 256)), dim3(256), 0, stream(), left->first, left->last, left->addr,
@@ -6906,10 +6983,6 @@ bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, 
   else
     hipLaunchKernelGGL(k_slab_runs, dim3(cdiv(A.cols + 4, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fa.off.p,
                        reinterpret_cast<const char*>(fa.val.p), 16, reinterpret_cast<SlabRun*>(runs.p), A.cols);
-  std::unique_ptr<SlabForm> fo(new SlabForm());
-  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
-  fo->count.zero();
-  fo->val.alloc(((size_t)total + kIndexSlack) * 2);
   t_num.start();
   TileLaunch tl;
   tl.runs = reinterpret_cast<const SlabRun*>(runs.p) - ka;   // (indexed by global column numbers)

@@ -88,6 +88,7 @@ struct EngineOptions {
   int block_match = 0;         // block path, an experiment (profiles/README.md 94): 1 = the matches of every candidate super-tile (the K with super-tiles on both sides) are found once, by a kernel of its own (k_bs_match), and read by the numeric kernel; 0: the numeric kernel searches itself.  Measured: no difference (37.4 against 37.2 iterations/s on the 64^3 lattice).  Results do not depend on it
   int block_unfused = 0;       // the block path (spgemm_block.hip) in UNFUSED arithmetic too: products rounded, then added, on the vector units, in ascending POSITION of the block order -- the reference's default build on the matrix relabelled by that order (what its own load balancer does), 1e-13 of the sums over ascending labels.  0 (default): operands without runs keep the label-ordered kernels in unfused arithmetic, bit for bit the reference on the caller's labels
   int panel_sessions = 1;      // slab sessions (TRS4, sign, inverse, square roots, polynomials ...) on more than one rank: the loops' matrices stay in slab form as column panels, a product exchanges the runs of the left operand's halo (psmatrix.cpp panel_slab_multiply); 0: compressed columns across ranks
+  int thin_slab_complex = 1;   // complex slab sessions (one rank and column panels across ranks): a product with a thin operand on the complex gather kernels of spgemm_thin.hip (the reference's own multiply-add, bit for bit) instead of the complex tile kernel; 0: every complex session product on the tile kernel; thin_left = 0 switches these off too
   int complex_panels = 1;      // complex loops (sign, inverse, square roots) on more than one rank: the iterates stay complex column panels in slab form, a product exchanges the complex runs of the left operand's halo (psmatrix.cpp panel_slab_multiply, complex tile kernel); needs panel_sessions and complex_sessions; 0: compressed columns across ranks
   int complex_density = 1;     // complex TRS2 on one rank (FMA arithmetic, complex_tile, complex_sessions): the iterate stays out of compressed columns from step to step -- run-like iterates in complex slab form (X*X on the complex tile kernel, then the merge pass, then one energy / trace pass), iterates without runs in complex block form (block_complex, block_path: X*X on k_bs_numeric_c, the complex block merge, block_dot_trace) (psmatrix.cpp complex_trs2_step); 0: every complex density solve as before
   int ghash_mfma = 1;          // grouped LDS-hash SpGEMM, real operands, FMA arithmetic: the products of a phase (four steps) as ONE v_mfma_f64_16x16x4_f64 per tile of 16 slots x 16 columns instead of 64 vector FMAs -- the same chain of fma() over ascending k, bit for bit; 0: vector units
@@ -204,6 +205,10 @@ struct SlabHalo {   // A side of a panel step: the columns ka .. kb (global numb
   // exchange layout (slab_plan_panel_async) -- the step then launches without a read-back of its own (and may keep
   // the plan's buffers for its result)
   SlabPlan* plan = nullptr;
+  // the product's thin-operand decision (slab_thin_rule on the entry counts summed over the ranks and the global dimension;
+  // psmatrix.cpp panel_slab_multiply): the same on every rank, and what one rank decides for the same product
+  int thin = 0;
+  int64_t nnz_a = 0;   // entries of the whole left operand (bounds the non-zeros of the halo's columns)
   // optional (slab_multiply with a left halo): called with the fetch of the product's entry count before it runs -- what the
   // caller adds comes back on the same host round trip
   std::function<void(ScalarFetch& fetch)> on_fetch;
@@ -405,8 +410,9 @@ void halo_bounds_async(const DevMat& A, int32_t c0, const int32_t* d_sa, const i
 // dense branch's order of threshold and alpha, bit 1 fma accumulation (real operands)
 bool spgemm_thin_left(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, int dense_rule_bits, int64_t* products,
                       hipEvent_t ev_begin, hipEvent_t ev_end);
-// thin operands inside a slab session (spgemm_thin.hip; real, FMA arithmetic): the plan's block windows and output slots, B
-// (and, thin right operand, A) as the runs of the slab form, a thin left operand as the compressed columns of its transpose
+// thin operands inside a slab session (spgemm_thin.hip; FMA arithmetic, real or complex): the plan's block windows and output
+// slots, B (and, thin right operand, A) as the runs of the slab form, a thin left operand as the compressed columns of its
+// transpose.  Complex: the value pointers name (re, im) pairs, offsets and slots count elements.
 struct ThinSlabArgs {
   const int32_t *blk_lo = nullptr, *blk_w = nullptr;
   const int64_t* blk_toff = nullptr;
@@ -424,9 +430,31 @@ struct ThinSlabArgs {
   int64_t* ooff = nullptr;
   double alpha = 1.0, threshold = 0.0;
   int dense_rule = 0, ncols = 0, nrows = 0;
-  int* flag = nullptr;   // thin right operand: raised when a column lists more non-zeros than the kernel holds
+  int* flag = nullptr;   // thin right operand, real: raised when a column lists more non-zeros than the kernel holds
+  // a panel product (thin right operand): afirst / alast / aaddr are indexed by GLOBAL column numbers (biased pointers),
+  // aaddr[k] = address of the first row of the run of A's column k (SlabHalo::addr); aoff / aval are then unused
+  const unsigned long long* aaddr = nullptr;
+  int nblocks = 0;       // > 0: ooff[ncols] = blk_toff[nblocks] is written too (the complex slab form, as its tile kernel does)
 };
-void launch_thin_slab(const ThinSlabArgs& a, bool left);
+void launch_thin_slab(const ThinSlabArgs& a, bool left, bool cplx = false);
+// the rows of a thin left operand given as the runs of its columns ka .. kb - 1 (first / last / addr or off indexed by global
+// column number; addr == nullptr: run k starts at base + off[k] elements) as compressed columns of its transpose, entries in
+// ascending k; cap: an upper bound of the non-zeros (the operand's entry count).  Asynchronous, no host round trip.
+struct ThinRows {
+  DevBuf<int64_t> outer;
+  DevBuf<int32_t> inner;
+  DevBuf<double> val;
+};
+void thin_rows_from_runs(bool cplx, const int32_t* first, const int32_t* last, const unsigned long long* addr, const int64_t* off,
+                         const double* base, int32_t ka, int32_t kb, int32_t nrows, int64_t cap, ThinRows& out);
+// which gather kernel a product of a slab session takes (0: none, 1: thin left operand, 2: thin right operand) -- from the
+// GLOBAL entry counts and the global dimension, so that every rank of a panel product, and one rank alone, decide alike
+inline int slab_thin_rule(int64_t nnz_a, int64_t nnz_b, int64_t dim) {
+  return (nnz_a <= 8 * dim && nnz_b >= nnz_a) ? 1 : (nnz_b <= 8 * dim) ? 2 : 0;
+}
+// since start: products of slab sessions on the gather kernels -- [0] real left, [1] real right, [2] complex left, [3] complex
+// right; of those, panel products: [4] real, [5] complex
+long long* thin_slab_counts();
 // counts the operations that change the values of a matrix in place (scale, conjugate, ...): together with the serial
 // number of the value buffer's allocation it tells whether a cached derivative of a matrix is still that matrix
 unsigned long long matrix_value_epoch();

@@ -812,6 +812,10 @@ bool panel_slab_multiply(const PSMatrix& A, const PSMatrix& B, DevMat& AB, doubl
   bool fetched = false;
   if (ok) {
     SlabHalo halo = pe.halo(A.loc, row_pad);
+    // (a thin operand: the gather kernels, decided on the entry counts of the whole operands -- they came with the requests --
+    // and the global dimension: the same on every rank, and what one rank decides for this product)
+    halo.thin = slab_thin_rule(nnz_a, nnz_b, A.dim);
+    halo.nnz_a = nnz_a;
     halo.on_fetch = [&](ScalarFetch& f) {
       f.add(d_declined.p, 1, reinterpret_cast<unsigned long long*>(&declined[0]));
       fetched = true;

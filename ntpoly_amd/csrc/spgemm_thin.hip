@@ -159,11 +159,20 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_spgemm_thin(Csc AT, Csc B, co
   }
 }
 
-// ---- thin operands inside a slab session (kernels.hpp slab algebra; real, FMA arithmetic).  Operands and result in slab
-// form: column j of the result is written as a dense run over the row window of its block of 16 columns (the plan of
-// slab_multiply: a superset of the rows any product of the column can reach), zeros = no entry.  Every entry is the fma
-// chain over ascending k the MFMA tile kernel computes (zero padding adds exact zeros there), so the two agree bit for bit.
-constexpr int THIN_MAXK = 64;   // non-zeros of a column of a thin right operand the kernel lists in LDS (more: the step is handed back)
+// ---- thin operands inside a slab session (kernels.hpp slab algebra; FMA arithmetic).  Operands and result in slab
+// form: column j of the result is written as a dense run over the row window of its block of THIN_BJ<T> columns (the plan of
+// slab_multiply / slab_multiply_c: a superset of the rows any product of the column can reach), zeros = no entry.
+// Real: every entry is the fma chain over ascending k the MFMA tile kernel computes (zero padding adds exact zeros there),
+// so the two agree bit for bit.  Complex (runs of (re, im) pairs, blocks of SLAB_CJ = 8 columns): the reference's own
+// complex multiply-add, rounded step by step, over ascending k -- bit for bit the reference's product, where the complex
+// tile kernel is a tolerance mode (spgemm_tile_c.hip).
+constexpr int THIN_MAXK = 64;   // non-zeros of a column of a thin right operand the kernel lists in LDS at a time
+template <typename T>
+struct ThinBlk;
+template <>
+struct ThinBlk<double> { static constexpr int shift = 4; };    // SLAB_J = 16 columns per plan block
+template <>
+struct ThinBlk<double2> { static constexpr int shift = 3; };   // SLAB_CJ = 8
 
 __device__ inline void thin_finish(const ThinSlabArgs& a, int j, int64_t slot, int lo, int cnt, int f, int l) {
   a.count[j] = cnt;
@@ -176,29 +185,45 @@ __device__ inline void thin_finish(const ThinSlabArgs& a, int j, int64_t slot, i
 // since the last written one (gap = first unwritten row behind it; INT_MAX: nothing written yet).  Chunks before the first
 // and behind the last kept entry are never written: a column's slot is only read over [first, last] widened to the row pad,
 // which the chunks (multiples of it) cover.
-__device__ inline void thin_store(double* __restrict__ col, int gap, int rb, int re, int lane, double v) {
+template <typename T>
+__device__ inline void thin_store(T* __restrict__ col, int gap, int rb, int re, int lane, T v) {
   if (gap < rb)
-    for (int r = gap + lane; r < rb; r += WAVE) col[r] = 0.0;
+    for (int r = gap + lane; r < rb; r += WAVE) col[r] = Sc<T>::zero();
   if (rb + lane < re) col[rb + lane] = v;
+}
+// |v| > threshold (PruneList.f90:8-38): a complex value is decided without the hypot wherever max(|re|, |im|) or
+// |re| + |im| already tells (as the complex tile kernel's epilogue does)
+__device__ inline bool thin_over(double v, double thr) { return fabs(v) > thr; }
+__device__ inline bool thin_over(double2 v, double thr) {
+  const double ax = fabs(v.x), ay = fabs(v.y);
+  if (fmax(ax, ay) > thr) return true;
+  if (!(__dadd_rn(ax, ay) > thr)) return false;
+  return hypot(v.x, v.y) > thr;
 }
 
 // LEFT operand thin: lane = candidate row i, walks row i of A (column i of A^T) ONCE for THIN_CW adjacent columns of the
 // result (they share the block's row window) and gathers B(k, j) from the runs of those columns
 constexpr int THIN_CW = 4, THIN_UL = 2;
+template <typename T>
 __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_left(const ThinSlabArgs a) {
   const int ngroups = (a.ncols + THIN_CW - 1) / THIN_CW;
   const int nb4 = (ngroups + THIN_NW - 1) / THIN_NW;
   const int blk = xcd_block(nb4);
   if (blk < 0) return;
+  if (blk == 0 && threadIdx.x == 0 && a.nblocks > 0) a.ooff[a.ncols] = a.blk_toff[a.nblocks];
   const int wave = threadIdx.x / WAVE, lane = lane_id();
   const int grp = blk * THIN_NW + wave;
   if (grp >= ngroups) return;
-  const int j0 = grp * THIN_CW;               // (16 is a multiple of THIN_CW: the columns of a group belong to one block)
-  const int b = j0 >> 4;
+  constexpr int BS = ThinBlk<T>::shift, BM = (1 << BS) - 1;
+  const int j0 = grp * THIN_CW;               // (the block width is a multiple of THIN_CW: the columns of a group belong to one block)
+  const int b = j0 >> BS;
   const int lo = a.blk_lo[b], w = a.blk_w[b];
+  const T* __restrict__ Bval = reinterpret_cast<const T*>(a.bval);
+  const T* __restrict__ ATval = reinterpret_cast<const T*>(a.at_val);
+  T* __restrict__ Oval = reinterpret_cast<T*>(a.out_val);
   int bf[THIN_CW];
   unsigned ext[THIN_CW];
-  const double* bp[THIN_CW];
+  const T* bp[THIN_CW];
   int64_t slot[THIN_CW];
   bool live[THIN_CW];
   bool any_live = false;
@@ -206,12 +231,12 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_left(const ThinSlab
   for (int c = 0; c < THIN_CW; ++c) {
     const int j = j0 + c;
     const int jc = min(j, a.ncols - 1);
-    slot[c] = a.blk_toff[b] + (int64_t)(jc & 15) * w;
+    slot[c] = a.blk_toff[b] + (int64_t)(jc & BM) * w;
     const int f0 = a.bfirst[jc], l0 = a.blast[jc];
     live[c] = j < a.ncols && l0 >= f0 && w > 0;
     bf[c] = live[c] ? f0 : 0;
     ext[c] = live[c] ? (unsigned)(l0 - f0) : 0u;
-    bp[c] = a.bval + (live[c] ? a.boff[jc] - f0 : 0);   // bp[c][k] = B(k, j0 + c), bf <= k <= bf + ext
+    bp[c] = Bval + (live[c] ? a.boff[jc] - f0 : 0);   // bp[c][k] = B(k, j0 + c), bf <= k <= bf + ext
     any_live |= live[c];
     if (!live[c] && j < a.ncols && lane == 0) thin_finish(a, j, slot[c], lo, 0, INT_MAX, -1);
   }
@@ -226,13 +251,13 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_left(const ThinSlab
     gap[c] = INT_MAX;
   }
   for (int r0 = lo; r0 < lo + w; r0 += THIN_UL * WAVE) {
-    double acc[THIN_UL][THIN_CW];
+    T acc[THIN_UL][THIN_CW];
     int64_t p[THIN_UL], e[THIN_UL];
 #pragma unroll
     for (int u = 0; u < THIN_UL; ++u) {
       const int i = r0 + u * WAVE + lane;
 #pragma unroll
-      for (int c = 0; c < THIN_CW; ++c) acc[u][c] = 0.0;
+      for (int c = 0; c < THIN_CW; ++c) acc[u][c] = Sc<T>::zero();
       p[u] = 0;
       e[u] = 0;
       if (i < lo + w && i < a.nrows) {
@@ -244,7 +269,7 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_left(const ThinSlab
       // (one entry of each of the THIN_UL rows per round; the loads of a round are issued together)
       bool v[THIN_UL], any = false;
       int k[THIN_UL];
-      double av[THIN_UL];
+      T av[THIN_UL];
 #pragma unroll
       for (int u = 0; u < THIN_UL; ++u) {
         v[u] = p[u] < e[u];
@@ -254,23 +279,23 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_left(const ThinSlab
 #pragma unroll
       for (int u = 0; u < THIN_UL; ++u) {
         k[u] = v[u] ? a.at_inner[p[u]] : INT_MIN;
-        av[u] = v[u] ? a.at_val[p[u]] : 0.0;
+        av[u] = v[u] ? ATval[p[u]] : Sc<T>::zero();
       }
-      double bv[THIN_UL][THIN_CW];
+      T bv[THIN_UL][THIN_CW];
       bool in[THIN_UL][THIN_CW];
 #pragma unroll
       for (int u = 0; u < THIN_UL; ++u) {
 #pragma unroll
         for (int c = 0; c < THIN_CW; ++c) {
           in[u][c] = v[u] && live[c] && (unsigned)(k[u] - bf[c]) <= ext[c];
-          bv[u][c] = in[u][c] ? bp[c][k[u]] : 0.0;
+          bv[u][c] = in[u][c] ? bp[c][k[u]] : Sc<T>::zero();
         }
       }
 #pragma unroll
       for (int u = 0; u < THIN_UL; ++u) {
 #pragma unroll
         for (int c = 0; c < THIN_CW; ++c)
-          if (in[u][c]) acc[u][c] = __fma_rn(av[u], bv[u][c], acc[u][c]);
+          if (in[u][c]) acc[u][c] = Sc<T>::fmadd(av[u], bv[u][c], acc[u][c], true);
         p[u] += v[u] ? 1 : 0;
       }
     }
@@ -279,11 +304,11 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_left(const ThinSlab
       const int rb = r0 + u * WAVE, i = rb + lane;
 #pragma unroll
       for (int c = 0; c < THIN_CW; ++c) {
-        const double sv = __dmul_rn(a.alpha, acc[u][c]);
-        const bool keep = live[c] && i < lo + w && (dense_rule ? (fabs(acc[u][c]) > a.threshold) : (fabs(sv) > a.threshold));
+        const T sv = Sc<T>::scale(a.alpha, acc[u][c]);
+        const bool keep = live[c] && i < lo + w && thin_over(dense_rule ? acc[u][c] : sv, a.threshold);
         const unsigned long long m = __ballot(keep);
         if (m) {
-          thin_store(a.out_val + slot[c] - lo, gap[c], rb, min(rb + WAVE, lo + w), lane, keep ? sv : 0.0);
+          thin_store<T>(Oval + slot[c] - lo, gap[c], rb, min(rb + WAVE, lo + w), lane, keep ? sv : Sc<T>::zero());
           gap[c] = rb + WAVE;
           cnt[c] += __popcll(m);
           f[c] = min(f[c], rb + (int)__builtin_ctzll(m));
@@ -300,18 +325,25 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_left(const ThinSlab
 }
 
 // RIGHT operand thin: the wave lists the non-zeros (k, b) of the run of column j of B, then lane = row i adds
-// A(i, k) * b over the list in ascending k from the runs of A
+// A(i, k) * b over the list in ascending k from the runs of A (its own, or the halo's: ThinSlabArgs::aaddr).
+// A column that lists more than THIN_MAXK non-zeros: real -- not this kernel's column, the flag is raised and the host
+// repeats the product on the tile kernel (the same chain, the same bits); complex -- the tile kernel is another
+// arithmetic, so the kernel takes the column itself: every row chunk lists the run again, 64 rows of it at a time, and
+// accumulates list after list, still in ascending k.
+template <typename T>
 __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_right(const ThinSlabArgs a) {
-  __shared__ int s_k[THIN_NW][THIN_MAXK], s_af[THIN_NW][THIN_MAXK], s_al[THIN_NW][THIN_MAXK];
-  __shared__ double s_b[THIN_NW][THIN_MAXK];
-  __shared__ long long s_ao[THIN_NW][THIN_MAXK];
+  __shared__ int s_af[THIN_NW][THIN_MAXK], s_al[THIN_NW][THIN_MAXK];
+  __shared__ T s_b[THIN_NW][THIN_MAXK];
+  __shared__ const T* s_ap[THIN_NW][THIN_MAXK];   // row 0 of the run of A's column k (hypothetical: read over [first, last] only)
   const int nb4 = (a.ncols + THIN_NW - 1) / THIN_NW;
   const int blk = xcd_block(nb4);
   if (blk < 0) return;
+  if (blk == 0 && threadIdx.x == 0 && a.nblocks > 0) a.ooff[a.ncols] = a.blk_toff[a.nblocks];
   const int wave = threadIdx.x / WAVE, lane = lane_id();
   const int j = blk * THIN_NW + wave;
   if (j >= a.ncols) return;
-  const int b = j >> 4, jj = j & 15;
+  constexpr int BS = ThinBlk<T>::shift, BM = (1 << BS) - 1;
+  const int b = j >> BS, jj = j & BM;
   const int lo = a.blk_lo[b], w = a.blk_w[b];
   const int64_t slot = a.blk_toff[b] + (int64_t)jj * w;
   const int bf = a.bfirst[j], bl = a.blast[j];
@@ -319,57 +351,75 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_right(const ThinSla
     if (lane == 0) thin_finish(a, j, slot, lo, 0, INT_MAX, -1);
     return;
   }
-  const double* __restrict__ bp = a.bval + (a.boff[j] - bf);
-  int nk = 0;
-  for (int k0 = bf; k0 <= bl; k0 += WAVE) {
+  const T* __restrict__ Aval = reinterpret_cast<const T*>(a.aval);
+  T* __restrict__ Oval = reinterpret_cast<T*>(a.out_val);
+  const T* __restrict__ bp = reinterpret_cast<const T*>(a.bval) + (a.boff[j] - bf);
+  // the non-zeros of rows k0 .. k0 + 63 of the run, listed behind the `at` already there; returns how many
+  auto list = [&](int k0, int at) -> int {
     const int k = k0 + lane;
-    const double v = k <= bl ? bp[k] : 0.0;
-    const unsigned long long m = __ballot(v != 0.0);
-    const int q = nk + (int)__popcll(m & lanemask_lt());
-    if (v != 0.0 && q < THIN_MAXK) {
-      s_k[wave][q] = k;
+    const T v = k <= bl ? bp[k] : Sc<T>::zero();
+    const bool nz = !Sc<T>::is_zero(v);
+    const unsigned long long m = __ballot(nz);
+    const int q = at + (int)__popcll(m & lanemask_lt());
+    if (nz && q < THIN_MAXK) {
+      const int af = a.afirst[k];
       s_b[wave][q] = v;
-      s_af[wave][q] = a.afirst[k];
+      s_af[wave][q] = af;
       s_al[wave][q] = a.alast[k];
-      s_ao[wave][q] = a.aoff[k];
+      s_ap[wave][q] = (a.aaddr ? reinterpret_cast<const T*>(a.aaddr[k]) : Aval + a.aoff[k]) - af;
     }
-    nk += (int)__popcll(m);
-  }
-  if (nk > THIN_MAXK) {   // not this kernel's column: the host repeats the product on the tile kernel
+    return (int)__popcll(m);
+  };
+  int nk = 0;
+  for (int k0 = bf; k0 <= bl; k0 += WAVE) nk += list(k0, nk);
+  if (!Sc<T>::cplx && nk > THIN_MAXK) {   // not this kernel's column: the host repeats the product on the tile kernel
     if (lane == 0) atomicOr(a.flag, 1);
     return;
   }
+  const bool once = nk <= THIN_MAXK;
   __builtin_amdgcn_wave_barrier();
   const bool dense_rule = (a.dense_rule & 1) != 0;
   int cnt = 0, f = INT_MAX, l = -1, gap = INT_MAX;
   for (int r0 = lo; r0 < lo + w; r0 += THIN_U * WAVE) {
-    double acc[THIN_U];
+    T acc[THIN_U];
 #pragma unroll
-    for (int u = 0; u < THIN_U; ++u) acc[u] = 0.0;
-    for (int t = 0; t < nk; ++t) {
-      const int af = s_af[wave][t], al = s_al[wave][t];
-      const double bt = s_b[wave][t];
-      const double* __restrict__ ap = a.aval + (s_ao[wave][t] - af);
-      double av[THIN_U];
+    for (int u = 0; u < THIN_U; ++u) acc[u] = Sc<T>::zero();
+    auto accumulate = [&](int n) {
+      for (int t = 0; t < n; ++t) {
+        const int af = s_af[wave][t], al = s_al[wave][t];
+        const T bt = s_b[wave][t];
+        const T* __restrict__ ap = s_ap[wave][t];
+        T av[THIN_U];
 #pragma unroll
-      for (int u = 0; u < THIN_U; ++u) {
-        const int i = r0 + u * WAVE + lane;
-        av[u] = (i >= af && i <= al) ? ap[i] : 0.0;
+        for (int u = 0; u < THIN_U; ++u) {
+          const int i = r0 + u * WAVE + lane;
+          av[u] = (i >= af && i <= al) ? ap[i] : Sc<T>::zero();
+        }
+#pragma unroll
+        for (int u = 0; u < THIN_U; ++u) {
+          const int i = r0 + u * WAVE + lane;
+          if (i >= af && i <= al) acc[u] = Sc<T>::fmadd(av[u], bt, acc[u], true);
+        }
       }
-#pragma unroll
-      for (int u = 0; u < THIN_U; ++u) {
-        const int i = r0 + u * WAVE + lane;
-        if (i >= af && i <= al) acc[u] = __fma_rn(av[u], bt, acc[u]);
+    };
+    if (once) {
+      accumulate(nk);
+    } else {
+      for (int k0 = bf; k0 <= bl; k0 += WAVE) {
+        __builtin_amdgcn_wave_barrier();
+        const int n = list(k0, 0);
+        __builtin_amdgcn_wave_barrier();
+        accumulate(n);
       }
     }
 #pragma unroll
     for (int u = 0; u < THIN_U; ++u) {
       const int rb = r0 + u * WAVE, i = rb + lane;
-      const double sv = __dmul_rn(a.alpha, acc[u]);
-      const bool keep = i < lo + w && (dense_rule ? (fabs(acc[u]) > a.threshold) : (fabs(sv) > a.threshold));
+      const T sv = Sc<T>::scale(a.alpha, acc[u]);
+      const bool keep = i < lo + w && thin_over(dense_rule ? acc[u] : sv, a.threshold);
       const unsigned long long m = __ballot(keep);
       if (m) {
-        thin_store(a.out_val + slot - lo, gap, rb, min(rb + WAVE, lo + w), lane, keep ? sv : 0.0);
+        thin_store<T>(Oval + slot - lo, gap, rb, min(rb + WAVE, lo + w), lane, keep ? sv : Sc<T>::zero());
         gap = rb + WAVE;
         cnt += __popcll(m);
         f = min(f, rb + (int)__builtin_ctzll(m));
@@ -378,6 +428,55 @@ __global__ __launch_bounds__(THIN_NW* WAVE) void k_thin_slab_right(const ThinSla
     }
   }
   if (lane == 0) thin_finish(a, j, slot, lo, cnt, f, l);
+}
+
+// ---- the rows of a thin left operand given as the runs of its columns ka .. kb - 1 (a slab form's own, or a halo's:
+// extents and run addresses per global column) as compressed columns of its transpose, entries of a row in ascending k.
+// reach[0] / reach[1] = how far a run reaches above / below its column's diagonal position: row i can only be named by
+// the columns i - reach[1] .. i + reach[0].  A wave owns 64 rows and walks those columns in ascending order (extents read
+// once per wave, a covering run read coalesced); counted, scanned, then filled the same way -- no atomics, no host round trip.
+__global__ void k_thin_reach(const int32_t* __restrict__ first, const int32_t* __restrict__ last, int ka, int kb, int* __restrict__ reach) {
+  const int k = ka + blockIdx.x * blockDim.x + threadIdx.x;
+  int up = 0, dn = 0;
+  if (k < kb && last[k] >= first[k]) {
+    up = max(0, k - first[k]);
+    dn = max(0, last[k] - k);
+  }
+  up = wave_max_i32(up);
+  dn = wave_max_i32(dn);
+  if (lane_id() == 0) {
+    if (up) atomicMax(&reach[0], up);
+    if (dn) atomicMax(&reach[1], dn);
+  }
+}
+template <typename T, bool FILL>
+__global__ __launch_bounds__(256) void k_thin_rows(const int32_t* __restrict__ first, const int32_t* __restrict__ last,
+                                                   const unsigned long long* __restrict__ addr, const int64_t* __restrict__ off,
+                                                   const T* __restrict__ base, int ka, int kb, int nrows, const int* __restrict__ reach,
+                                                   int32_t* __restrict__ rowcnt, const int64_t* __restrict__ at_outer,
+                                                   int32_t* __restrict__ at_inner, T* __restrict__ at_val, int64_t cap) {
+  const int r0 = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE) * WAVE;
+  if (r0 >= nrows) return;
+  const int i = r0 + lane_id(), rl = r0 + WAVE - 1;
+  const int k0 = max(ka, r0 - reach[1]), k1 = min(kb - 1, rl + reach[0]);
+  const int64_t pos = (FILL && i < nrows) ? at_outer[i] : 0;
+  int c = 0;
+  for (int k = k0; k <= k1; ++k) {
+    const int f = first[k], l = last[k];
+    if (l < f || f > rl || l < r0) continue;   // (uniform over the wave)
+    const T* __restrict__ run = addr ? reinterpret_cast<const T*>(addr[k]) : base + off[k];
+    if (i >= f && i <= l && i < nrows) {
+      const T v = run[i - f];
+      if (!Sc<T>::is_zero(v)) {
+        if (FILL && pos + c < cap) {
+          at_inner[pos + c] = k;
+          at_val[pos + c] = v;
+        }
+        ++c;
+      }
+    }
+  }
+  if (!FILL && i < nrows) rowcnt[i] = c;
 }
 
 // rows of a thin left operand as columns, kept per matrix (spgemm_thin_left); released with the other operand caches
@@ -398,10 +497,32 @@ void drop_thin_transposes() {
   for (int ki = 0; ki < 2; ++ki) kept[ki] = KeptTranspose();
 }
 
-void launch_thin_slab(const ThinSlabArgs& a, bool left) {
-  const int nb4 = cdiv(a.ncols, THIN_NW);
-  if (left) hipLaunchKernelGGL(k_thin_slab_left, dim3(xcd_grid(cdiv(cdiv(a.ncols, THIN_CW), THIN_NW))), dim3(THIN_NW * WAVE), 0, stream(), a);
-  else hipLaunchKernelGGL(k_thin_slab_right, dim3(xcd_grid(nb4)), dim3(THIN_NW * WAVE), 0, stream(), a);
+void launch_thin_slab(const ThinSlabArgs& a, bool left, bool cplx) {
+  dispatch_type(cplx, [&](auto tag) {
+    using T = decltype(tag);
+    if (left) hipLaunchKernelGGL(k_thin_slab_left<T>, dim3(xcd_grid(cdiv(cdiv(a.ncols, THIN_CW), THIN_NW))), dim3(THIN_NW * WAVE), 0, stream(), a);
+    else hipLaunchKernelGGL(k_thin_slab_right<T>, dim3(xcd_grid(cdiv(a.ncols, THIN_NW))), dim3(THIN_NW * WAVE), 0, stream(), a);
+  });
+}
+
+void thin_rows_from_runs(bool cplx, const int32_t* first, const int32_t* last, const unsigned long long* addr, const int64_t* off,
+                         const double* base, int32_t ka, int32_t kb, int32_t nrows, int64_t cap, ThinRows& out) {
+  out.outer.alloc((size_t)nrows + 1);
+  out.inner.alloc((size_t)cap + kIndexSlack);
+  out.val.alloc(((size_t)cap + kIndexSlack) * (cplx ? 2 : 1));
+  DevBuf<int> reach(2);
+  reach.zero();
+  DevBuf<int32_t> rowcnt((size_t)nrows);
+  hipLaunchKernelGGL(k_thin_reach, dim3(cdiv(kb - ka, 256)), dim3(256), 0, stream(), first, last, ka, kb, reach.p);
+  const dim3 grid(cdiv((int64_t)cdiv(nrows, WAVE) * WAVE, 256));
+  dispatch_type(cplx, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((k_thin_rows<T, false>), grid, dim3(256), 0, stream(), first, last, addr, off, reinterpret_cast<const T*>(base), ka, kb,
+                       nrows, reach.p, rowcnt.p, (const int64_t*)nullptr, (int32_t*)nullptr, (T*)nullptr, cap);
+    scan_i32_async(rowcnt.p, out.outer.p, (int64_t)nrows);
+    hipLaunchKernelGGL((k_thin_rows<T, true>), grid, dim3(256), 0, stream(), first, last, addr, off, reinterpret_cast<const T*>(base), ka, kb,
+                       nrows, reach.p, rowcnt.p, out.outer.p, out.inner.p, reinterpret_cast<T*>(out.val.p), cap);
+  });
 }
 
 // false: not taken (C untouched)

@@ -110,6 +110,7 @@ void local_print(const DevMat& m, const char* path) {
   if (path) std::fclose(f);
   else std::fflush(f);
 }
+std::unique_ptr<SlabSession> g_test_session;   // (ntpoly_amd_session_begin / _end: a diagnostic surface)
 }  // namespace
 
 extern "C" {
@@ -190,6 +191,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "complex_tile") options().complex_tile = *value;
   else if (n == "block_complex") options().block_complex = *value;
   else if (n == "thin_left") options().thin_left = *value;
+  else if (n == "thin_slab_complex") options().thin_slab_complex = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -222,6 +224,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "complex_tile") return options().complex_tile;
   if (n == "block_complex") return options().block_complex;
   if (n == "thin_left") return options().thin_left;
+  if (n == "thin_slab_complex") return options().thin_slab_complex;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -247,6 +250,22 @@ void ntpoly_amd_last_grouped_stats(long long* out, double* ratio) {
 }
 // 1: the last SpGEMM ran on the thin-left kernel (spgemm_thin.hip)
 int ntpoly_amd_last_spgemm_thin() { return last_spgemm_stats().thin; }
+// products of slab sessions computed by the thin-operand gather kernels (spgemm_thin.hip) since start: out[0] real, thin left
+// operand; [1] real, thin right; [2] complex left; [3] complex right; of those, panel products (slab sessions on several
+// ranks): [4] real, [5] complex
+void ntpoly_amd_thin_slab_counts(long long* out) {
+  for (int q = 0; q < 6; ++q) out[q] = thin_slab_counts()[q];
+}
+// DIAGNOSTIC surface (like ntpoly_amd_trs2_step): a session of the kind the solver loops open (engine.hpp SlabSession), held
+// open across the vocabulary calls that follow -- MatrixMultiply, IncrementMatrix, ScaleMatrix, CopyMatrix keep their
+// matrices in slab form between the calls; *complex_ok != 0: complex operands too, which the one-call sessions of the C ABI
+// do not take in slab form.  Every other entry point still sees compressed columns (it packs on access).  Tests reach the
+// session kernels with operands of their own this way; one session at a time, ended by ntpoly_amd_session_end.
+void ntpoly_amd_session_begin(const int* complex_ok) {
+  if (g_test_session) NTP_FATAL("ntpoly_amd_session_begin: a session is already open");
+  g_test_session.reset(new SlabSession(true, false, *complex_ok != 0));
+}
+void ntpoly_amd_session_end() { g_test_session.reset(); }
 // block path of the last SpGEMM (spgemm_block.hip): out[0..2] = used, 16 x 16 x 16 tile products issued, candidate output
 // super-tiles; fill = entries / (256 tiles) of the left operand
 void ntpoly_amd_last_block_stats(long long* out, double* fill) {

@@ -7,6 +7,7 @@ Same method names and argument meaning as the reference so that the parity tests
 the reference's tests.  numpy arrays are only used at the boundary (triplets in / out); all
 matrix data lives in HBM.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -968,6 +969,26 @@ def panel_product_counts():
     out = (C.c_longlong * 3)()
     lib.ntpoly_amd_panel_product_counts(out)
     return dict(slab=out[0], declined=out[1], host_syncs=out[2])
+
+
+def thin_slab_counts():
+    """products of slab sessions on the thin-operand gather kernels (csrc/spgemm_thin.hip) since start: real / complex, thin left /
+    right operand; of those, the panel products (slab sessions on several ranks), real and complex"""
+    out = (C.c_longlong * 6)()
+    lib.ntpoly_amd_thin_slab_counts(out)
+    return dict(real_left=out[0], real_right=out[1], complex_left=out[2], complex_right=out[3], panel_real=out[4], panel_complex=out[5])
+
+
+@contextlib.contextmanager
+def solver_session(complex_ok=True):
+    """DIAGNOSTIC (like trs2_step): a session of the kind the solver loops open, held across the vocabulary calls made inside the
+    `with` block -- their matrices stay in slab form between the calls, complex ones too with complex_ok (the one-call sessions
+    of the C ABI do not take complex operands in slab form).  Reading a matrix back packs it, as ever."""
+    lib.ntpoly_amd_session_begin(C.byref(C.c_int(1 if complex_ok else 0)))
+    try:
+        yield
+    finally:
+        lib.ntpoly_amd_session_end()
 
 
 def last_grouped_stats():
