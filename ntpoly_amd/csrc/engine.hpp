@@ -148,12 +148,20 @@ bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatr
 // MatrixNorm of alpha A + beta B (ScaleMatrix(B, beta); IncrementMatrix(A, B, alpha, 0); MatrixNorm(B)) for the loops
 // that build the sum only for its norm; false: not done (outside a slab session, operands in compressed columns ...)
 bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double beta, double* norm);
+// The recurrence step of the Chebyshev / Hermite loops on complex operands in a complex slab session (option
+// complex_poly_sessions = 2): IncrementMatrix(Tkm2, P, a, 0) with its result in Tk (which may be P), then
+// IncrementMatrix(Tk, R, c, 0), in one pass (slab_extra.hip slab_recurrence_step_c: the same values bit for bit); false:
+// not done and nothing changed -- the caller makes the two ps_increment calls
+bool ps_recurrence_step(const PSMatrix& P, const PSMatrix& Tkm2, PSMatrix& Tk, PSMatrix& R, double a, double c);
+// solvers.cpp: this loop may take a complex operand like m in slab form (FMA arithmetic, complex tile kernel, complex_sessions)
+bool complex_slab_loop(const PSMatrix& m);
 void ps_slab_leave(PSMatrix& m);   // back to compressed columns (no-op for a matrix that is not in slab form)
 const long long* column_fused_counts();   // [2] since start: IncrementMatrix(Identity, .) done in place, norms of differences taken without forming them (column_fused.hip)
 const long long* block_algebra_counts();  // [2] since start: operations done in block form (spgemm_block.hpp block algebra); fallbacks
 long long block_scope_products();   // panel products of block-order solves that took the block path (psmatrix.cpp)
 bool block_scope_active();   // band_scope.cpp: the solve in progress runs on operands redistributed in a block order (several ranks)
 const long long* panel_product_counts();  // [3] products of slab sessions across ranks: in slab form on every rank; declined; host synchronisations inside the former
+long long recurrence_step_count();         // fused recurrence steps taken since start (each also counted as two merges below)
 const long long* slab_algebra_counts();   // [4] since start: products, merges / copies, other operations done in slab form; refusals
 void ps_fill_identity(PSMatrix& m);
 void ps_fill_permutation(PSMatrix& m, const std::vector<int32_t>& lookup /*1-based*/, bool rows);

@@ -2712,6 +2712,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_PANEL_SESSIONS")) e->panel_sessions = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PANELS")) e->complex_panels = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_THIN_SLAB_COMPLEX")) e->thin_slab_complex = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_POLY_SESSIONS")) e->complex_poly_sessions = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_DENSITY")) e->complex_density = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_SCOPE_COMPLEX")) e->block_scope_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_UNFUSED")) e->block_unfused = std::atoi(v);

@@ -89,6 +89,7 @@ struct EngineOptions {
   int block_unfused = 0;       // the block path (spgemm_block.hip) in UNFUSED arithmetic too: products rounded, then added, on the vector units, in ascending POSITION of the block order -- the reference's default build on the matrix relabelled by that order (what its own load balancer does), 1e-13 of the sums over ascending labels.  0 (default): operands without runs keep the label-ordered kernels in unfused arithmetic, bit for bit the reference on the caller's labels
   int panel_sessions = 1;      // slab sessions (TRS4, sign, inverse, square roots, polynomials ...) on more than one rank: the loops' matrices stay in slab form as column panels, a product exchanges the runs of the left operand's halo (psmatrix.cpp panel_slab_multiply); 0: compressed columns across ranks
   int thin_slab_complex = 1;   // complex slab sessions (one rank and column panels across ranks): a product with a thin operand on the complex gather kernels of spgemm_thin.hip (the reference's own multiply-add, bit for bit) instead of the complex tile kernel; 0: every complex session product on the tile kernel; thin_left = 0 switches these off too
+  int complex_poly_sessions = 2;   // complex operands of the polynomial and function families (Horner, Paterson-Stockmeyer, the two Chebyshev evaluations, Hermite, the exponential's squarings, sine / cosine): 1: their loops open a complex slab session as the sign loop does (needs complex_sessions, FMA arithmetic, complex_tile; across ranks complex_panels); 2: and the two merges behind a product of the Chebyshev / Hermite recurrence are one kernel (slab_extra.hip slab_recurrence_step_c, the same values bit for bit); 0: compressed columns between the operations
   int complex_panels = 1;      // complex loops (sign, inverse, square roots) on more than one rank: the iterates stay complex column panels in slab form, a product exchanges the complex runs of the left operand's halo (psmatrix.cpp panel_slab_multiply, complex tile kernel); needs panel_sessions and complex_sessions; 0: compressed columns across ranks
   int complex_density = 1;     // complex TRS2 on one rank (FMA arithmetic, complex_tile, complex_sessions): the iterate stays out of compressed columns from step to step -- run-like iterates in complex slab form (X*X on the complex tile kernel, then the merge pass, then one energy / trace pass), iterates without runs in complex block form (block_complex, block_path: X*X on k_bs_numeric_c, the complex block merge, block_dot_trace) (psmatrix.cpp complex_trs2_step); 0: every complex density solve as before
   int ghash_mfma = 1;          // grouped LDS-hash SpGEMM, real operands, FMA arithmetic: the products of a phase (four steps) as ONE v_mfma_f64_16x16x4_f64 per tile of 16 slots x 16 columns instead of 64 vector FMAs -- the same chain of fma() over ascending k, bit for bit; 0: vector units
@@ -258,6 +259,9 @@ bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, 
 bool slab_multiply_c_takes_panel(const DevMat& A, const DevMat& B, int left_row_pad, int32_t ka, int32_t kb, const SlabPlan* plan);
 bool slab_add_diagonal_c(DevMat& B, double alpha, int32_t col_offset);                      // slab_extra.hip
 bool slab_norm_axpby_c(const DevMat& A, const DevMat& B, double alpha, double beta, double* out);   // slab_extra.hip
+// slab_extra.hip: Tk = P + a Tkm2 and R <- R + c Tk in one pass, the values of slab_axpby_c(Tkm2, P, a, 1, 0) followed by
+// slab_axpby_c(Tk, R, c, 1, 0) bit for bit (Tk may be P); false: what either call would decline, nothing changed
+bool slab_recurrence_step_c(const DevMat& P, const DevMat& Tkm2, DevMat& Tk, DevMat& R, double a, double c);
 // slab_extra.hip: dot = (Re, Im) of sum conj(A) B for a complex slab-form A and a complex B in slab form or packed compressed
 // columns (B == nullptr: none), trace = sum of the real parts of A's diagonal (col_offset: A's first column); fixed-shape sums
 bool slab_dot_trace_c(const DevMat& A, const DevMat* B, int32_t col_offset, double dot[2], double* trace);

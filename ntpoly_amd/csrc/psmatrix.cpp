@@ -205,6 +205,7 @@ bool slab_on() { return g_slab_depth > 0 && !g_slab_failed; }
 DevMat& mut(const PSMatrix& m) { return const_cast<DevMat&>(m.loc); }
 int g_slab_refusals = 0;
 bool g_complex_session = false;   // the open session's loop takes complex operands in slab form (SlabSession complex_ok)
+long long g_recurrence_steps = 0;   // fused recurrence steps taken (ps_recurrence_step returned true)
 long long g_slab_counts[4] = {0, 0, 0, 0};   // products, merges / copies, other operations in slab form; refusals
 // the slab algebra of one element kind, for the operations that exist for both (kernels.hpp: name, name_c)
 struct SlabKind {
@@ -276,6 +277,7 @@ void slab_pack_if(std::initializer_list<const PSMatrix*> ms) {
 }  // namespace
 
 const long long* slab_algebra_counts() { return g_slab_counts; }
+long long recurrence_step_count() { return g_recurrence_steps; }
 const long long* block_algebra_counts() { return g_block_counts; }
 const long long* column_fused_counts() { return g_column_fused; }
 
@@ -1185,6 +1187,24 @@ bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double be
     }
   }
   return false;
+}
+
+bool ps_recurrence_step(const PSMatrix& P, const PSMatrix& Tkm2, PSMatrix& Tk, PSMatrix& R, double a, double c) {
+  CommScope cs(P.grid);
+  if (options().complex_poly_sessions != 2 || !slab_on() || !P.cplx || !Tkm2.cplx || !R.cplx || !session_takes(true)) return false;
+  if (blk_any({&P, &Tkm2, &R}) || P.dim != Tkm2.dim || P.dim != R.dim || &P == &Tkm2 || &P == &R || &Tkm2 == &R || &Tk == &R || &Tk == &Tkm2)
+    return false;
+  // (an operand still in compressed columns -- the identity as T0, the input as T1, the sum before the first product -- is
+  // turned into slab form as ps_axpby would; one that cannot be is left to the two merges, which count the refusal.  Every
+  // rank of a panel session decides for itself: neither this step nor the two merges hold a collective)
+  if (!(P.loc.expanded() || Tkm2.loc.expanded() || R.loc.expanded()) || !slab_enter_c(mut(P)) || !slab_enter_c(mut(Tkm2)) || !slab_enter_c(R.loc))
+    return false;
+  DevMat T;
+  if (!slab_recurrence_step_c(P.loc, Tkm2.loc, T, R.loc, a, c)) return false;
+  install(Tk, P.grid, P.dim, true, P.c0, P.c1, std::move(T));
+  g_slab_counts[1] += 2;
+  g_recurrence_steps += 1;
+  return true;
 }
 
 bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx) {

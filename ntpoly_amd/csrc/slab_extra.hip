@@ -556,6 +556,207 @@ bool slab_dot_trace_c(const DevMat& A, const DevMat* B, int32_t col_offset, doub
   return true;
 }
 
+// ------------------------------------------------------------------ the recurrence step of the polynomial loops, complex
+// Chebyshev and Hermite evaluation do two merges behind every product P: Tk = P + a Tkm2 (IncrementMatrix(Tkm2, P, a)) and
+// R <- R + c Tk (IncrementMatrix(Tk, R, c)), both at threshold 0.  One pass per column does both: P, Tkm2 and R are read
+// once, Tk and the new R are written once.  Element for element the arithmetic and the keep / drop decisions are those of
+// k_sa_axpby<double2, true> (kernels.hip) called twice with beta = 1 and threshold 0 -- the scaled addend rounded, then
+// added; a sum that cancels exactly is dropped -- so the two results are those of the two calls bit for bit.
+namespace {
+// one element of IncrementMatrix(A, B, alpha, 0) on runs: a, b the operands' values at row r (zero: no entry), amax / bmax the
+// last rows of A's / B's runs (-1: empty).  The keep rules are k_sa_axpby's own expressions at thr = 0 and beta = 1 (b is its own
+// scaled value), so that the two kernels decide alike on every input, non-finite sums included.  keep && zero result: an addend that underflowed
+// beyond the other run's end, which the slab form cannot hold (k_sa_axpby's stat bit 1).
+__device__ inline double2 step_merge(double2 a, double2 b, double alpha, int r, int amax, int bmax, bool& keep) {
+  const bool ha = !Sc<double2>::is_zero(a), hb = !Sc<double2>::is_zero(b);
+  const double2 wa = Sc<double2>::scale(alpha, a);
+  double2 o = Sc<double2>::zero();
+  keep = false;
+  if (ha && hb) { o = Sc<double2>::add(wa, b); keep = Sc<double2>::mag(o) > 0.0; }
+  else if (ha) { o = wa; keep = (r > bmax) ? true : (Sc<double2>::mag(wa) > 0.0); }
+  else if (hb) { o = b; keep = (r > amax) ? true : (Sc<double2>::mag(b) > 0.0); }
+  return o;
+}
+// slots of the two results per column: Tk's is the aligned hull of P's and Tkm2's extents, R's the aligned hull of its old
+// extent and Tk's slot
+__global__ void k_sa_step_span(const int32_t* __restrict__ fp, const int32_t* __restrict__ lp, const int32_t* __restrict__ fq,
+                               const int32_t* __restrict__ lq, const int32_t* __restrict__ fr, const int32_t* __restrict__ lr, int n, int al,
+                               int32_t* __restrict__ span_t, int32_t* __restrict__ span_r) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  int f = INT_MAX, l = -1;
+  if (lp[j] >= fp[j]) { f = fp[j]; l = lp[j]; }
+  if (lq[j] >= fq[j]) { f = min(f, fq[j]); l = max(l, lq[j]); }
+  int a0 = 0, a1 = 0;
+  if (l >= f) { a0 = f / al * al; a1 = (l / al + 1) * al; }
+  span_t[j] = a1 - a0;
+  if (lr[j] >= fr[j]) {
+    const int b0 = fr[j] / al * al, b1 = (lr[j] / al + 1) * al;
+    if (a1 > a0) { a0 = min(a0, b0); a1 = max(a1, b1); }
+    else { a0 = b0; a1 = b1; }
+  }
+  span_r[j] = a1 - a0;
+}
+// One wave per column.  Lane i takes the rows = i (mod 64) in both loops, so the Tk values the second loop reads back are
+// the lane's own stores (rows outside Tk's kept extent read as zero without a load).  16-byte loads and stores, consecutive
+// lanes on consecutive rows of a run.  stat[0] |= 1: a kept zero (see step_merge), |= 2: a slot beyond its buffer (runs far
+// apart: nothing is written for that column) -- the host then declines and the caller's operands are as they were.
+__global__ __launch_bounds__(256) void k_sa_recurrence_step_c(
+    int n, const int32_t* __restrict__ fp, const int32_t* __restrict__ lp, const int64_t* __restrict__ offp, const double2* __restrict__ vp,
+    const int32_t* __restrict__ fq, const int32_t* __restrict__ lq, const int64_t* __restrict__ offq, const double2* __restrict__ vq,
+    const int32_t* __restrict__ fr, const int32_t* __restrict__ lr, const int64_t* __restrict__ offr, const double2* __restrict__ vr,
+    const int64_t* __restrict__ base_t, const int64_t* __restrict__ base_r, int al, double a, double c, double2* out_t,
+    double2* __restrict__ out_r, int32_t* __restrict__ tfirst, int32_t* __restrict__ tlast, int32_t* __restrict__ tcount,
+    int64_t* __restrict__ toff, int32_t* __restrict__ rfirst, int32_t* __restrict__ rlast, int32_t* __restrict__ rcount,
+    int64_t* __restrict__ roff, unsigned long long* __restrict__ stat, int64_t bound_t, int64_t bound_r) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id();
+  const int fP = fp[j], lP = lp[j], fQ = fq[j], lQ = lq[j], fR = fr[j], lR = lr[j];
+  const bool anyP = lP >= fP, anyQ = lQ >= fQ, anyR = lR >= fR;
+  const int64_t slot_t = base_t[j], slot_r = base_r[j];
+  // Tk's slot [t0, t1), R's slot [r0, r1) (k_sa_step_span)
+  int t0 = 0, t1 = 0;
+  if (anyP || anyQ) {
+    const int f = anyP ? (anyQ ? min(fP, fQ) : fP) : fQ, l = anyP ? (anyQ ? max(lP, lQ) : lP) : lQ;
+    t0 = f / al * al;
+    t1 = (l / al + 1) * al;
+  }
+  int r0 = t0, r1 = t1;
+  if (anyR) {
+    const int b0 = fR / al * al, b1 = (lR / al + 1) * al;
+    if (t1 > t0) { r0 = min(t0, b0); r1 = max(t1, b1); }
+    else { r0 = b0; r1 = b1; }
+  }
+  if (slot_t + (int64_t)(t1 - t0) > bound_t || slot_r + (int64_t)(r1 - r0) > bound_r) {
+    if (lane == 0) {
+      tfirst[j] = INT_MAX; tlast[j] = -1; tcount[j] = 0; toff[j] = slot_t;
+      rfirst[j] = INT_MAX; rlast[j] = -1; rcount[j] = 0; roff[j] = slot_r;
+      atomicOr(stat, 2ull);
+    }
+    return;
+  }
+  const double2* __restrict__ pp = anyP ? vp + (offp[j] - fP) : vp;
+  const double2* __restrict__ pq = anyQ ? vq + (offq[j] - fQ) : vq;
+  const double2* __restrict__ pr = anyR ? vr + (offr[j] - fR) : vr;
+  double2* dt = out_t + (slot_t - t0);
+  double2* __restrict__ dr = out_r + (slot_r - r0);
+  int zk = 0;
+  // Tk = P + a Tkm2: IncrementMatrix(Tkm2, P, a)
+  int cnt = 0, kf = INT_MAX, kl = -1;
+  {
+    const int pmax = anyP ? lP : -1, qmax = anyQ ? lQ : -1;
+    for (int r = (t0 & ~(WAVE - 1)) + lane; r < t1; r += WAVE) {
+      if (r < t0) continue;
+      const double2 q = (anyQ && r >= fQ && r <= lQ) ? pq[r] : Sc<double2>::zero();
+      const double2 p = (anyP && r >= fP && r <= lP) ? pp[r] : Sc<double2>::zero();
+      bool keep;
+      const double2 o = step_merge(q, p, a, r, qmax, pmax, keep);
+      dt[r] = keep ? o : Sc<double2>::zero();
+      zk |= (keep && Sc<double2>::is_zero(o)) ? 1 : 0;
+      cnt += keep ? 1 : 0;
+      kf = min(kf, keep ? r : INT_MAX);
+      kl = max(kl, keep ? r : -1);
+    }
+    cnt = (int)wave_sum_i64(cnt);
+    kf = wave_min_i32(kf);
+    kl = wave_max_i32(kl);
+    if (lane == 0) {
+      tfirst[j] = kf; tlast[j] = kl; tcount[j] = cnt;
+      toff[j] = slot_t + (cnt ? kf - t0 : 0);
+    }
+  }
+  // R <- R + c Tk: IncrementMatrix(Tk, R, c), Tk's run is [kf, kl] now
+  {
+    const bool anyT = kl >= kf;
+    const int rmax = anyR ? lR : -1, tmax = anyT ? kl : -1;
+    int rc = 0, rf = INT_MAX, rl = -1;
+    for (int r = (r0 & ~(WAVE - 1)) + lane; r < r1; r += WAVE) {
+      if (r < r0) continue;
+      const double2 t = (anyT && r >= kf && r <= kl) ? dt[r] : Sc<double2>::zero();
+      const double2 b = (anyR && r >= fR && r <= lR) ? pr[r] : Sc<double2>::zero();
+      bool keep;
+      const double2 o = step_merge(t, b, c, r, tmax, rmax, keep);
+      dr[r] = keep ? o : Sc<double2>::zero();
+      zk |= (keep && Sc<double2>::is_zero(o)) ? 1 : 0;
+      rc += keep ? 1 : 0;
+      rf = min(rf, keep ? r : INT_MAX);
+      rl = max(rl, keep ? r : -1);
+    }
+    rc = (int)wave_sum_i64(rc);
+    rf = wave_min_i32(rf);
+    rl = wave_max_i32(rl);
+    if (lane == 0) {
+      rfirst[j] = rf; rlast[j] = rl; rcount[j] = rc;
+      roff[j] = slot_r + (rc ? rf - r0 : 0);
+    }
+  }
+  if (__ballot(zk != 0) && lane == 0) atomicOr(stat, 1ull);
+}
+}  // namespace
+
+// Tk = P + a Tkm2 and R <- R + c Tk on complex matrices in slab form (or column panels of them), what
+// slab_axpby_c(Tkm2, P, a, 1, 0) and slab_axpby_c(Tk, R, c, 1, 0) leave behind; Tk may be P.  false: not taken (whatever one
+// of the two calls would decline), nothing changed.
+bool slab_recurrence_step_c(const DevMat& P, const DevMat& Tkm2, DevMat& Tk, DevMat& R, double a, double c) {
+  if (!sa_operand_c(P) || !sa_operand_c(Tkm2) || !sa_operand_c(R)) return false;
+  if (P.cols != Tkm2.cols || P.cols != R.cols || P.rows != Tkm2.rows || P.rows != R.rows) return false;
+  if (&P == &Tkm2 || &P == &R || &Tkm2 == &R || &Tk == &R || &Tk == &Tkm2) return false;
+  if (a == 0.0 || c == 0.0 || P.zero_free != 1 || Tkm2.zero_free != 1 || R.zero_free != 1) return false;
+  const SlabForm &sp = *P.slab, &sq = *Tkm2.slab, &sr = *R.slab;
+  const int n = P.cols;
+  const int al = std::max(sp.row_pad, std::max(sq.row_pad, sr.row_pad));
+  if (al % sp.row_pad != 0 || al % sq.row_pad != 0 || al % sr.row_pad != 0) return false;
+  // (the buffers of the two merges: the operands' slots and the padding of a union per column)
+  const int64_t bound_t = sp.slots + sq.slots + 2LL * al * n, bound_r = bound_t + sr.slots + 2LL * al * n;
+  std::unique_ptr<SlabForm> ft(new SlabForm()), fr(new SlabForm());
+  for (SlabForm* f : {ft.get(), fr.get()}) {
+    f->first.alloc((size_t)n); f->last.alloc((size_t)n); f->count.alloc((size_t)n); f->off.alloc((size_t)n + 1);
+  }
+  DevBuf<int32_t> span_t((size_t)n), span_r((size_t)n);
+  DevBuf<int64_t> base_t((size_t)n + 1), base_r((size_t)n + 1);
+  DevBuf<unsigned long long> stat(1), tot(2);
+  stat.zero();
+  tot.zero();
+  hipLaunchKernelGGL(k_sa_step_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), sp.first.p, sp.last.p, sq.first.p, sq.last.p, sr.first.p,
+                     sr.last.p, n, al, span_t.p, span_r.p);
+  scan_i32_async(span_t.p, base_t.p, (int64_t)n);
+  scan_i32_async(span_r.p, base_r.p, (int64_t)n);
+  ft->val.alloc(((size_t)bound_t + kIndexSlack) * 2);
+  fr->val.alloc(((size_t)bound_r + kIndexSlack) * 2);
+  hipLaunchKernelGGL(k_sa_recurrence_step_c, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, sp.first.p, sp.last.p, sp.off.p,
+                     reinterpret_cast<const double2*>(sp.val.p), sq.first.p, sq.last.p, sq.off.p, reinterpret_cast<const double2*>(sq.val.p),
+                     sr.first.p, sr.last.p, sr.off.p, reinterpret_cast<const double2*>(sr.val.p), base_t.p, base_r.p, al, a, c,
+                     reinterpret_cast<double2*>(ft->val.p), reinterpret_cast<double2*>(fr->val.p), ft->first.p, ft->last.p, ft->count.p,
+                     ft->off.p, fr->first.p, fr->last.p, fr->count.p, fr->off.p, stat.p, bound_t, bound_r);
+  const dim3 sum_grid(std::max(1, std::min(256, cdiv(n, 1024))));
+  hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), ft->count.p, n, tot.p);
+  hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), fr->count.p, n, tot.p + 1);
+  int64_t nnz[2] = {0, 0}, slots_t = 0, slots_r = 0;
+  unsigned long long hs = 0;
+  {
+    ScalarFetch f;
+    f.add(tot.p, 2, nnz);
+    f.add(base_t.p + n, 1, &slots_t);
+    f.add(base_r.p + n, 1, &slots_r);
+    f.add(stat.p, 1, &hs);
+    f.run();
+  }
+  if (hs != 0) return false;
+  ft->row_pad = al; ft->slots = slots_t;
+  fr->row_pad = al; fr->slots = slots_r;
+  DevMat T, S;
+  T.rows = P.rows; T.cols = n; T.cplx = true; T.nnz = nnz[0]; T.zero_free = 1;
+  T.slab = std::move(ft);
+  S.rows = R.rows; S.cols = n; S.cplx = true; S.nnz = nnz[1]; S.zero_free = 1;
+  S.slab = std::move(fr);
+  bump_matrix_value_epoch();   // (two merges in place, as slab_axpby_c counts them)
+  bump_matrix_value_epoch();
+  Tk = std::move(T);
+  R = std::move(S);
+  return true;
+}
+
 // ------------------------------------------------------------------ how dense the runs are
 namespace {
 __global__ __launch_bounds__(256) void k_sa_span_sum(const int32_t* __restrict__ first, const int32_t* __restrict__ last, int n,

@@ -203,6 +203,12 @@ void balance_undo(PSMatrix& m, const SolverParameters& p) {
   if (p.do_load_balancing) ps_permute(m, m, p.balance_permutation, true);
 }
 
+// "this loop may take complex operands in slab form": FMA arithmetic and the complex tile kernel (sign, inverse, square roots;
+// the polynomial and function families of solvers_poly.cpp / solvers_func.cpp under option complex_poly_sessions)
+bool complex_slab_loop(const PSMatrix& m) {
+  return m.cplx && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0;
+}
+
 namespace {
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) {
@@ -225,10 +231,6 @@ double real_dot(const PSMatrix& A, const PSMatrix& B) {
   double out[2];
   ps_dot(A, B, out);
   return out[0];
-}
-// "this loop may take complex operands in slab form": FMA arithmetic and the complex tile kernel (sign, inverse, square roots)
-bool complex_slab_loop(const PSMatrix& m) {
-  return m.cplx && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0;
 }
 void log_iterations_header(const SolverParameters& p) {
   if (!p.be_verbose) return;

@@ -117,9 +117,17 @@ void compute_exponential(const PSMatrix& In, PSMatrix& Out, const SolverParamete
                                1.038827668772902e-12, 4.032447357431817e-14, 2.127980007794583e-15, -1.629151584468762e-16};
   chebyshev_compute(Scaled, R, std::vector<double>(c, c + 16), sub);
   balance_permute(R, p);
-  for (int k = 1; k <= sigma_counter - 1; ++k) {
-    ps_multiply(R, R, Temp, 1.0, 0.0, p.threshold);
-    std::swap(R.loc, Temp.loc);
+  {
+    // (complex operands: the squarings on an iterate kept in slab form, as the sign loop keeps its own -- option
+    // complex_poly_sessions; real operands: no session, as ever)
+    const bool complex_session = complex_slab_loop(R) && options().complex_poly_sessions != 0;
+    SlabSession slab(complex_session, false, complex_session);
+    for (int k = 1; k <= sigma_counter - 1; ++k) {
+      ps_multiply(R, R, Temp, 1.0, 0.0, p.threshold);
+      std::swap(R.loc, Temp.loc);
+    }
+    slab.close();
+    ps_slab_leave(R);
   }
   if (p.be_verbose) print_matrix_information(R);
   balance_undo(R, p);
@@ -158,7 +166,8 @@ void scale_square_trig(const PSMatrix& In, PSMatrix& Out, const SolverParameters
   c[1] = 7.651976865579664e-01;  c[3] = -2.298069698638004e-01; c[5] = 4.953277928219409e-03;
   c[7] = -4.187667600472235e-05; c[9] = 1.884468822397086e-07;  c[11] = -5.261224549346905e-10;
   c[13] = 9.999906645345580e-13; c[15] = -2.083597362700025e-15; c[17] = 9.181480886537484e-17;
-  SlabSession slab(!Scaled.cplx);   // (engine.hpp: the Chebyshev evaluation and the squarings on matrices kept in slab form)
+  const bool complex_session = complex_slab_loop(Scaled) && options().complex_poly_sessions != 0;
+  SlabSession slab(!Scaled.cplx || complex_session, false, complex_session);   // (engine.hpp: the Chebyshev evaluation and the squarings on matrices kept in slab form)
   ps_multiply(Scaled, Scaled, T2, 2.0, 0.0, p.threshold);
   ps_increment(Ident, T2, -1.0, 0.0);
   ps_multiply(T2, T2, T4, 2.0, 0.0, p.threshold);

@@ -22,6 +22,9 @@ void balanced_setup(const PSMatrix& In, const SolverParameters& p, Balanced& b) 
   balance_permute(b.Identity, p);
   balance_permute(b.Input, p);
 }
+// the evaluation's session: real operands as ever; complex ones in slab form too where the loop may take them (option
+// complex_poly_sessions, on top of what the sign loop's complex session needs)
+bool complex_poly_session(const PSMatrix& In) { return complex_slab_loop(In) && options().complex_poly_sessions != 0; }
 void poly_header(const char* solver, const char* method, const char* citation, int degree, const SolverParameters& p,
                  bool degree_first) {
   if (!p.be_verbose) return;
@@ -43,7 +46,8 @@ void polynomial_horner(const PSMatrix& In, PSMatrix& Out, const std::vector<doub
   poly_header("Polynomial Solver", "Horner", nullptr, degree, p, false);
   Balanced b;
   balanced_setup(In, p, b);
-  SlabSession slab(!In.cplx);   // (engine.hpp: products, merges and scalings of the evaluation on matrices kept in slab form)
+  const bool complex_session = complex_poly_session(In);
+  SlabSession slab(!In.cplx || complex_session, false, complex_session);   // (engine.hpp: products, merges and scalings of the evaluation on matrices kept in slab form)
   PSMatrix R, Temporary;
   ps_copy(b.Identity, R);
   if (degree == 1) {
@@ -77,7 +81,8 @@ void polynomial_paterson_stockmeyer(const PSMatrix& In, PSMatrix& Out, const std
   PSMatrix Identity;
   ps_construct_like(Identity, In);
   ps_fill_identity(Identity);
-  SlabSession slab(!In.cplx);
+  const bool complex_session = complex_poly_session(In);
+  SlabSession slab(!In.cplx || complex_session, false, complex_session);
   std::vector<PSMatrix> x_powers((size_t)s_value + 1);
   ps_construct_like(x_powers[0], In);
   ps_fill_identity(x_powers[0]);
@@ -130,7 +135,8 @@ void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<doub
   poly_header("Chebyshev Solver", "Standard", nullptr, degree, p, true);
   Balanced b;
   balanced_setup(In, p, b);
-  SlabSession slab(!In.cplx);
+  const bool complex_session = complex_poly_session(In);
+  SlabSession slab(!In.cplx || complex_session, false, complex_session);
   PSMatrix Tk, Tkminus1, Tkminus2, R;
   ps_copy(b.Identity, Tkminus2);
   if (degree == 1) {
@@ -143,14 +149,18 @@ void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<doub
     ps_increment(Tkminus1, R, c[1], 0.0);
     if (degree > 2) {
       ps_multiply(b.Input, Tkminus1, Tk, 2.0, 0.0, p.threshold);
-      ps_increment(Tkminus2, Tk, -1.0, 0.0);
-      ps_increment(Tk, R, c[2], 0.0);
+      if (!ps_recurrence_step(Tk, Tkminus2, Tk, R, -1.0, c[2])) {   // (complex session: the two merges in one pass)
+        ps_increment(Tkminus2, Tk, -1.0, 0.0);
+        ps_increment(Tk, R, c[2], 0.0);
+      }
       for (int II = 4; II <= degree; ++II) {
         std::swap(Tkminus2.loc, Tkminus1.loc);  // Tkminus2 <- Tkminus1
         std::swap(Tkminus1.loc, Tk.loc);        // Tkminus1 <- Tk (Tk now holds scratch)
         ps_multiply(b.Input, Tkminus1, Tk, 2.0, 0.0, p.threshold);
-        ps_increment(Tkminus2, Tk, -1.0, 0.0);
-        ps_increment(Tk, R, c[(size_t)II - 1], 0.0);
+        if (!ps_recurrence_step(Tk, Tkminus2, Tk, R, -1.0, c[(size_t)II - 1])) {
+          ps_increment(Tkminus2, Tk, -1.0, 0.0);
+          ps_increment(Tk, R, c[(size_t)II - 1], 0.0);
+        }
       }
     }
   }
@@ -197,7 +207,8 @@ void chebyshev_factorized(const PSMatrix& In, PSMatrix& Out, const std::vector<d
   poly_header("Chebyshev Solver", "Recursive", nullptr, degree, p, true);
   Balanced b;
   balanced_setup(In, p, b);
-  SlabSession slab(!In.cplx);
+  const bool complex_session = complex_poly_session(In);
+  SlabSession slab(!In.cplx || complex_session, false, complex_session);
   int log2degree = 1;
   while ((1 << log2degree) <= degree) ++log2degree;
   std::vector<PSMatrix> T((size_t)log2degree);
@@ -229,7 +240,8 @@ void hermite_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double
   poly_header("Hermite Solver", "Standard", nullptr, degree, p, true);
   Balanced b;
   balanced_setup(In, p, b);
-  SlabSession slab(!In.cplx);
+  const bool complex_session = complex_poly_session(In);
+  SlabSession slab(!In.cplx || complex_session, false, complex_session);
   PSMatrix Hk, Hkminus1, Hkplus1, Hkprime, R;
   ps_copy(b.Identity, Hkminus1);
   ps_copy(Hkminus1, R);
@@ -243,12 +255,17 @@ void hermite_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double
       ps_scale(Hkprime, 2.0);
       for (int II = 3; II <= degree; ++II) {
         ps_multiply(b.Input, Hk, Hkplus1, 2.0, 0.0, p.threshold);
-        ps_increment(Hkprime, Hkplus1, -1.0, 0.0);
+        // (HermiteSolversModule.F90:150-156: IncrementMatrix(Hkprime, Hkplus1, -1), two copies and a scaling of OTHER
+        // matrices, IncrementMatrix(Hk = Hkplus1, OutputMat, c).  Hkprime already carries the coefficient 2 (k - 1), so the
+        // recurrence's -2 (k - 1) H_{k-1} is a = -1 here; nothing between the two merges reads or writes Hkplus1 or the
+        // output, so the second merge done right behind the first leaves the same values)
+        const bool stepped = ps_recurrence_step(Hkplus1, Hkprime, Hkplus1, R, -1.0, c[(size_t)II - 1]);
+        if (!stepped) ps_increment(Hkprime, Hkplus1, -1.0, 0.0);
         ps_copy(Hk, Hkprime);
         ps_scale(Hkprime, (double)(2 * (II - 1)));
         std::swap(Hkminus1.loc, Hk.loc);   // Hkminus1 <- Hk
         std::swap(Hk.loc, Hkplus1.loc);    // Hk <- Hkplus1
-        ps_increment(Hk, R, c[(size_t)II - 1], 0.0);
+        if (!stepped) ps_increment(Hk, R, c[(size_t)II - 1], 0.0);
       }
     }
   }

@@ -192,6 +192,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "block_complex") options().block_complex = *value;
   else if (n == "thin_left") options().thin_left = *value;
   else if (n == "thin_slab_complex") options().thin_slab_complex = *value;
+  else if (n == "complex_poly_sessions") options().complex_poly_sessions = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -225,6 +226,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "block_complex") return options().block_complex;
   if (n == "thin_left") return options().thin_left;
   if (n == "thin_slab_complex") return options().thin_slab_complex;
+  if (n == "complex_poly_sessions") return options().complex_poly_sessions;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -266,6 +268,15 @@ void ntpoly_amd_session_begin(const int* complex_ok) {
   g_test_session.reset(new SlabSession(true, false, *complex_ok != 0));
 }
 void ntpoly_amd_session_end() { g_test_session.reset(); }
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin (complex_ok) and _end: the fused recurrence step of the
+// Chebyshev / Hermite loops on caller-held complex matrices (engine.hpp ps_recurrence_step: Tk = P + a Tkm2, R <- R + c Tk);
+// returns 1 when the step was taken, 0 when it declined and left every matrix as it was
+int ntpoly_amd_recurrence_step(const int* ih_P, const int* ih_Tkm2, int* ih_Tk, int* ih_R, const double* a, const double* c) {
+  return ps_recurrence_step(*get_unpacked(ih_P), *get_unpacked(ih_Tkm2), *get_unpacked(ih_Tk), *get_unpacked(ih_R), *a, *c) ? 1 : 0;
+}
+// fused recurrence steps taken since start, by the Chebyshev / Hermite loops and by ntpoly_amd_recurrence_step (each is also
+// counted as the two merges it replaces in ntpoly_amd_slab_algebra_counts; a declined step counts nothing here)
+void ntpoly_amd_recurrence_step_count(long long* out) { *out = recurrence_step_count(); }
 // block path of the last SpGEMM (spgemm_block.hip): out[0..2] = used, 16 x 16 x 16 tile products issued, candidate output
 // super-tiles; fill = entries / (256 tiles) of the left operand
 void ntpoly_amd_last_block_stats(long long* out, double* fill) {

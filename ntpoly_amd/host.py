@@ -991,6 +991,22 @@ def solver_session(complex_ok=True):
         lib.ntpoly_amd_session_end()
 
 
+def recurrence_step(P, Tkm2, Tk, R, a, c):
+    """DIAGNOSTIC, inside `with solver_session():` -- the fused recurrence step of the Chebyshev / Hermite loops on complex
+    matrices (option complex_poly_sessions = 2; csrc/slab_extra.hip): Tk = P + a Tkm2 and R <- R + c Tk in one pass.
+    True: taken; False: declined, every matrix as it was (the caller makes the two IncrementMatrix calls)."""
+    lib.ntpoly_amd_recurrence_step.restype = C.c_int
+    return bool(lib.ntpoly_amd_recurrence_step(P.ih, Tkm2.ih, Tk.ih, R.ih, d(a), d(c)))
+
+
+def recurrence_step_count():
+    """fused recurrence steps taken since start (option complex_poly_sessions = 2), by the Chebyshev / Hermite loops and by
+    recurrence_step(); slab_algebra_counts() counts each as the two merges it replaces, a declined step counts nothing here"""
+    out = C.c_longlong()
+    lib.ntpoly_amd_recurrence_step_count(C.byref(out))
+    return int(out.value)
+
+
 def last_grouped_stats():
     """grouped LDS-hash path of the last SpGEMM (csrc/spgemm_grouped.hip)"""
     out = (C.c_longlong * 6)()
