@@ -2713,6 +2713,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PANELS")) e->complex_panels = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_THIN_SLAB_COMPLEX")) e->thin_slab_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_POLY_SESSIONS")) e->complex_poly_sessions = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_STORED_ZERO_VIEWS")) e->stored_zero_views = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_DENSITY")) e->complex_density = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_SCOPE_COMPLEX")) e->block_scope_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_UNFUSED")) e->block_unfused = std::atoi(v);
@@ -2930,16 +2931,22 @@ struct DotOperand {
   int64_t max_tile = 0;   // largest sum of the spans of 16 consecutive columns (the kernel keeps that tile in LDS)
   int align = 1;          // columns in aligned zero-padded slots of that many rows (k_span_aligned), 1: packed back to back
 };
-// stored values that are exactly zero (real matrices; columns may be loose): one wave per column
-__global__ __launch_bounds__(256) void k_count_zero_values(Csc A, unsigned long long* __restrict__ out) {
+// stored values that are exactly zero (T = double: real, double2: complex; columns may be loose): one wave per column, out +=
+// the columns that have one; zlast (optional): zlast[j] = row of the last stored zero of column j, -1 if none (SlabForm::zlast)
+template <typename T>
+__global__ __launch_bounds__(256) void k_count_zero_values(Csc A, unsigned long long* __restrict__ out, int32_t* __restrict__ zlast) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= A.cols) return;
   const int lane = lane_id();
-  const double* __restrict__ v = static_cast<const double*>(A.val);
-  int c = 0;
-  for (int64_t p = A.outer[j] + lane, e = col_end(A, j); p < e; p += WAVE) c += v[p] == 0.0 ? 1 : 0;
-  const unsigned long long m = __ballot(c != 0);
-  if (m && lane == 0) atomicAdd(out, 1ull);
+  const T* __restrict__ v = static_cast<const T*>(A.val);
+  int zl = -1;
+  for (int64_t p = A.outer[j] + lane, e = col_end(A, j); p < e; p += WAVE)
+    if (Sc<T>::is_zero(v[p])) zl = max(zl, A.inner[p]);
+  zl = wave_max_i32(zl);
+  if (lane == 0) {
+    if (zlast) zlast[j] = zl;
+    if (zl >= 0) atomicAdd(out, 1ull);
+  }
 }
 __global__ void k_span_block_max(const int32_t* __restrict__ span, int n, int J, unsigned long long* __restrict__ out) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3818,7 +3825,7 @@ void spgemm(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double th
       // solve: the results of the fused steps are zero-free by construction)
       DevBuf<unsigned long long> zc(1);
       zc.zero();
-      hipLaunchKernelGGL(k_count_zero_values, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), lview(B), zc.p);
+      hipLaunchKernelGGL(k_count_zero_values<double>, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), lview(B), zc.p, (int32_t*)nullptr);
       unsigned long long hz = 0;
       ScalarFetch f;
       f.add(zc.p, 1, &hz);
@@ -5822,7 +5829,7 @@ bool relabel_enter(DevMat& X, const DevMat& D) {
     hipLaunchKernelGGL(k_span_of, dim3(cdiv(n, 256)), dim3(256), 0, stream(), f.p, l.p, span.p, n);
     scan_async<int32_t>(span.p, pre.p, (int64_t)n);
     if (X.zero_free != 1)
-      hipLaunchKernelGGL(k_count_zero_values, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), view(X), zc.p);
+      hipLaunchKernelGGL(k_count_zero_values<double>, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), view(X), zc.p, (int32_t*)nullptr);
     int64_t tot = 0;
     unsigned long long hz = 0;
     ScalarFetch ft;
@@ -6064,6 +6071,10 @@ __global__ void k_sa_span(const int32_t* __restrict__ fa, const int32_t* __restr
 // the multiple of al below the union's first row; pads and dropped rows zero).  HAVE_B false: a copy of A (alpha = 1).
 // stat[0] |= 1 when a kept value is exactly zero (an unfiltered tail that underflowed: the slab form cannot hold it).
 // (T = double2: complex runs of (re, im) pairs, offsets in elements, threshold on the modulus -- the complex sessions)
+// zla / zlb (optional, SlabForm::zlast of a read-only view): the row of the last STORED ZERO of A's / B's column.  A stored zero
+// under the other operand's extent merges as a hole does (both present: the other value alone decides; a hole at or above
+// the other's last row: alpha 0 fails |.| > thr), so the pass below is exact; one BEYOND the other operand's last row is an
+// unfiltered tail entry that compressed columns keep as a stored zero and no run can hold: stat[0] |= 4, the host declines.
 template <typename T, bool HAVE_B>
 __global__ __launch_bounds__(256) void k_sa_axpby(int n, const int32_t* __restrict__ fa, const int32_t* __restrict__ la,
                                                   const int64_t* __restrict__ offa, const T* __restrict__ va,
@@ -6072,7 +6083,8 @@ __global__ __launch_bounds__(256) void k_sa_axpby(int n, const int32_t* __restri
                                                   const int64_t* __restrict__ base, int al, double alpha, double beta, double thr,
                                                   T* __restrict__ out, int32_t* __restrict__ ofirst, int32_t* __restrict__ olast,
                                                   int32_t* __restrict__ ocount, int64_t* __restrict__ ooff,
-                                                  unsigned long long* __restrict__ stat, int64_t bound) {
+                                                  unsigned long long* __restrict__ stat, int64_t bound,
+                                                  const int32_t* __restrict__ zla, const int32_t* __restrict__ zlb) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= n) return;
   const int lane = lane_id();
@@ -6080,6 +6092,7 @@ __global__ __launch_bounds__(256) void k_sa_axpby(int n, const int32_t* __restri
   int fB = INT_MAX, lB = -1;
   if (HAVE_B) { fB = fb[j]; lB = lb[j]; }
   const bool anyA = lA >= fA, anyB = lB >= fB;
+  if (HAVE_B && lane == 0 && ((zla && zla[j] > (anyB ? lB : -1)) || (zlb && zlb[j] > (anyA ? lA : -1)))) atomicOr(stat, 4ull);
   const int64_t slot = base[j];
   if (!anyA && !anyB) {
     if (lane == 0) { ofirst[j] = INT_MAX; olast[j] = -1; ocount[j] = 0; ooff[j] = slot; }
@@ -6211,7 +6224,36 @@ bool g_panels_ok = false;   // a slab session across ranks (psmatrix.cpp): opera
 bool sa_operand(const DevMat& M) {
   return M.expanded() && !M.cplx && !M.slab->labelled() && (M.rows == M.cols || g_panels_ok);
 }
+// what a merge reads as it is: no stored zero, or a read-only view that knows its last stored zero per column (k_sa_axpby)
+bool sa_mergeable(const DevMat& M) {
+  return M.zero_free == 1 || (options().stored_zero_views != 0 && M.slab->origin && M.slab->zlast.p != nullptr);
+}
+bool sa_view(const DevMat& M) { return options().stored_zero_views != 0 && M.slab->origin && M.slab->zlast.p != nullptr; }
+template <typename T>
+void dup_buf(DevBuf<T>& dst, const DevBuf<T>& src) {
+  dst.alloc(src.n);
+  if (src.n) HIP_CHECK(hipMemcpyAsync(dst.p, src.p, src.n * sizeof(T), hipMemcpyDeviceToDevice, stream()));
+}
+// CopyMatrix of a view: the runs as they are (stored zeros included in extents and counts), zlast, and a copy of the compressed columns
+void sa_clone_view(const DevMat& A, DevMat& Out) {
+  const SlabForm& f = *A.slab;
+  std::unique_ptr<SlabForm> g(new SlabForm());
+  dup_buf(g->first, f.first); dup_buf(g->last, f.last); dup_buf(g->count, f.count); dup_buf(g->off, f.off); dup_buf(g->val, f.val);
+  dup_buf(g->zlast, f.zlast);
+  g->slots = f.slots;
+  g->row_pad = f.row_pad;
+  g->origin.reset(new DevMat(f.origin->clone()));
+  DevMat R;
+  R.rows = A.rows; R.cols = A.cols; R.cplx = A.cplx; R.nnz = A.nnz; R.zero_free = 0;
+  R.slab = std::move(g);
+  Out = std::move(R);
+  slab_view_counts()[2] += 1;
+}
 }  // namespace
+long long* slab_view_counts() {
+  static long long counts[4] = {0, 0, 0, 0};
+  return counts;
+}
 void slab_allow_panels(bool on) { g_panels_ok = on; }
 bool slab_panels_ok() { return g_panels_ok; }
 bool slab_plan_fits_tile(int max_kn, int max_w) { return max_w > 0 && spgemm_tile_fits(max_kn, max_w); }
@@ -6232,8 +6274,11 @@ bool slab_enter(DevMat& M) {
   hipLaunchKernelGGL(k_col_extent, dim3(cdiv(n, 256)), dim3(256), 0, stream(), view(M), f->first.p, f->last.p, f->count.p);
   hipLaunchKernelGGL(k_span_aligned, dim3(cdiv(n, 256)), dim3(256), 0, stream(), f->first.p, f->last.p, span.p, n, al);
   scan_async<int32_t>(span.p, f->off.p, (int64_t)n);
-  if (M.zero_free != 1)
-    hipLaunchKernelGGL(k_count_zero_values, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), view(M), zc.p);
+  const bool views = options().stored_zero_views != 0;   // (a view then knows its last stored zero per column: merges take it)
+  if (M.zero_free != 1) {
+    if (views) f->zlast.alloc((size_t)n);
+    hipLaunchKernelGGL(k_count_zero_values<double>, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), view(M), zc.p, f->zlast.p);
+  }
   int64_t tot = 0;
   unsigned long long hz = 0;
   {
@@ -6242,6 +6287,7 @@ bool slab_enter(DevMat& M) {
     ft.add(zc.p, 1, &hz);
     ft.run();
   }
+  if (hz == 0) f->zlast.release();
   const bool dbg = std::getenv("NTPOLY_AMD_DEBUG_SPGEMM") != nullptr;
   if (hz == 0) M.zero_free = 1;
   if ((double)tot > 2.0 * (double)M.nnz + 2.0 * al * (double)n) {   // (mostly holes: not run-like)
@@ -6260,6 +6306,7 @@ bool slab_enter(DevMat& M) {
   R.rows = M.rows; R.cols = n; R.cplx = false; R.nnz = M.nnz; R.zero_free = hz == 0 ? 1 : 0;
   if (hz != 0) {   // (stored zeros: the slab form is a read-only view, the compressed columns stay -- SlabForm::origin)
     f->origin.reset(new DevMat(std::move(M)));
+    if (views) slab_view_counts()[0] += 1;
   }
   R.slab = std::move(f);
   M = std::move(R);
@@ -6294,19 +6341,20 @@ static bool sa_axpby_impl(const DevMat* A, const DevMat& Bin, DevMat& Out, doubl
     if (have_b)
       hipLaunchKernelGGL((k_sa_axpby<double2, true>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
                          va, fb->first.p, fb->last.p, fb->off.p, vb, base.p, al, alpha, beta, thr, vo, fo->first.p, fo->last.p, fo->count.p,
-                         fo->off.p, stat.p, bound);
+                         fo->off.p, stat.p, bound, fa.zlast.p, fb->zlast.p);
     else
       hipLaunchKernelGGL((k_sa_axpby<double2, false>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
                          va, (const int32_t*)nullptr, (const int32_t*)nullptr, (const int64_t*)nullptr, (const double2*)nullptr, base.p, al, 1.0, 0.0,
-                         0.0, vo, fo->first.p, fo->last.p, fo->count.p, fo->off.p, stat.p, bound);
+                         0.0, vo, fo->first.p, fo->last.p, fo->count.p, fo->off.p, stat.p, bound, (const int32_t*)nullptr, (const int32_t*)nullptr);
   } else if (have_b)
     hipLaunchKernelGGL((k_sa_axpby<double, true>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
                        fa.val.p, fb->first.p, fb->last.p, fb->off.p, fb->val.p, base.p, al, alpha, beta, thr, fo->val.p, fo->first.p,
-                       fo->last.p, fo->count.p, fo->off.p, stat.p, bound);
+                       fo->last.p, fo->count.p, fo->off.p, stat.p, bound, fa.zlast.p, fb->zlast.p);
   else
     hipLaunchKernelGGL((k_sa_axpby<double, false>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
                        fa.val.p, (const int32_t*)nullptr, (const int32_t*)nullptr, (const int64_t*)nullptr, (const double*)nullptr,
-                       base.p, al, 1.0, 0.0, 0.0, fo->val.p, fo->first.p, fo->last.p, fo->count.p, fo->off.p, stat.p, bound);
+                       base.p, al, 1.0, 0.0, 0.0, fo->val.p, fo->first.p, fo->last.p, fo->count.p, fo->off.p, stat.p, bound, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr);
   DevBuf<long long> tot;
   sa_sum_counts(fo->count.p, n, tot);
   int64_t nnz = 0, slots = 0;
@@ -6318,7 +6366,9 @@ static bool sa_axpby_impl(const DevMat* A, const DevMat& Bin, DevMat& Out, doubl
     ft.add(stat.p, 1, &hs);
     ft.run();
   }
+  if (hs & 4ull) slab_view_counts()[3] += 1;   // (a stored zero of a view beyond the other operand: compressed columns keep it)
   if (hs != 0) return false;
+  if (have_b && (fa.origin || fb->origin)) slab_view_counts()[2] += 1;
   fo->row_pad = al;
   fo->slots = slots;
   DevMat R;
@@ -6331,7 +6381,7 @@ static bool sa_axpby_impl(const DevMat* A, const DevMat& Bin, DevMat& Out, doubl
 bool slab_axpby(const DevMat& A, DevMat& B, double alpha, double beta, double threshold) {
   if (!sa_operand(A) || !sa_operand(B) || A.cols != B.cols || &A == &B) return false;
   if (alpha == 0.0 || beta == 0.0) return false;   // (ScaleMatrix by zero leaves stored zeros: not a slab)
-  if (A.zero_free != 1 || B.zero_free != 1) return false;
+  if (!sa_mergeable(A) || !sa_mergeable(B)) return false;
   DevMat R;
   if (!sa_axpby_impl(&A, B, R, alpha, beta, threshold)) return false;
   value_epoch() += 1;
@@ -6342,7 +6392,7 @@ bool slab_axpby(const DevMat& A, DevMat& B, double alpha, double beta, double th
 // Out = alpha A + beta B, B left as it is (CopyMatrix(B, Out) followed by the merge above, without the copy)
 bool slab_axpby_to(const DevMat& A, const DevMat& B, DevMat& Out, double alpha, double beta, double threshold) {
   if (!sa_operand(A) || !sa_operand(B) || A.cols != B.cols || &A == &B) return false;
-  if (alpha == 0.0 || beta == 0.0 || A.zero_free != 1 || B.zero_free != 1) return false;
+  if (alpha == 0.0 || beta == 0.0 || !sa_mergeable(A) || !sa_mergeable(B)) return false;
   DevMat R;
   if (!sa_axpby_impl(&A, B, R, alpha, beta, threshold)) return false;
   Out = std::move(R);
@@ -6350,14 +6400,19 @@ bool slab_axpby_to(const DevMat& A, const DevMat& B, DevMat& Out, double alpha, 
 }
 
 bool slab_clone(const DevMat& A, DevMat& Out) {
+  if (sa_operand(A) && sa_view(A)) { sa_clone_view(A, Out); return true; }
   if (!sa_operand(A) || A.zero_free != 1) return false;
   return sa_axpby_impl(nullptr, A, Out, 1.0, 0.0, 0.0);
 }
 
 bool slab_scale(DevMat& A, double c) {
-  if (!sa_operand(A) || c == 0.0 || A.slab->origin) return false;
-  value_epoch() += 1;
+  if (!sa_operand(A) || c == 0.0 || (A.slab->origin && !sa_view(A))) return false;
   SlabForm& f = *A.slab;
+  if (f.origin) {   // (a view: the compressed columns it hands back are scaled with the runs; a stored zero stays one)
+    scale(*f.origin, c);
+    slab_view_counts()[2] += 1;
+  }
+  value_epoch() += 1;
   hipLaunchKernelGGL(k_sa_scale<double>, dim3(cdiv((int64_t)A.cols * WAVE, 256)), dim3(256), 0, stream(), A.cols, f.first.p, f.last.p, f.off.p,
                      f.val.p, c);
   f.tiles.release();       // (the multiplier tiles are rebuilt from the runs when the matrix is next a right operand)
@@ -6787,18 +6842,6 @@ bool slab_multiply(const DevMat& A, const DevMat& B, DevMat& C, double alpha, do
 // ------------------------------------------------------------------ complex operands in slab form (a session that allows them:
 // the SignFunction loop).  The same form -- a dense run of (re, im) pairs per column in a slot aligned to 16 rows -- produced and
 // consumed by the complex MFMA tile kernel (spgemm_tile_c.hip): between two products of a loop nothing is expanded or packed.
-namespace {
-__global__ __launch_bounds__(256) void k_count_zero_values_c(Csc A, unsigned long long* __restrict__ out) {
-  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  if (j >= A.cols) return;
-  const int lane = lane_id();
-  const double2* __restrict__ v = static_cast<const double2*>(A.val);
-  int c = 0;
-  for (int64_t p = A.outer[j] + lane, e = col_end(A, j); p < e; p += WAVE) c += (v[p].x == 0.0 && v[p].y == 0.0) ? 1 : 0;
-  const unsigned long long m = __ballot(c != 0);
-  if (m && lane == 0) atomicAdd(out, 1ull);
-}
-}  // namespace
 long long* thin_slab_counts() {
   static long long counts[6] = {0, 0, 0, 0, 0, 0};
   return counts;
@@ -6806,8 +6849,12 @@ long long* thin_slab_counts() {
 bool sa_operand_c(const DevMat& M) {
   return M.expanded() && M.cplx && !M.slab->labelled() && !M.slab->origin && (M.rows == M.cols || g_panels_ok) && M.slab->row_pad % 16 == 0;
 }
-bool slab_enter_c(DevMat& M, bool* not_run_like) {
-  if (M.expanded()) return sa_operand_c(M);
+bool sa_readable_c(const DevMat& M) {
+  return M.expanded() && M.cplx && !M.slab->labelled() && (!M.slab->origin || sa_view(M)) && (M.rows == M.cols || g_panels_ok) &&
+         M.slab->row_pad % 16 == 0;
+}
+bool slab_enter_c(DevMat& M, bool* not_run_like, bool allow_view) {
+  if (M.expanded()) return allow_view ? sa_readable_c(M) : sa_operand_c(M);
   if (!M.cplx || M.blocked() || M.loose() || (M.rows != M.cols && !g_panels_ok) || M.nnz == 0 || M.slab_hint < 0 || options().spgemm_fma != 1 ||
       options().complex_tile == 0)
     return false;
@@ -6820,8 +6867,11 @@ bool slab_enter_c(DevMat& M, bool* not_run_like) {
   hipLaunchKernelGGL(k_col_extent, dim3(cdiv(n, 256)), dim3(256), 0, stream(), view(M), f->first.p, f->last.p, f->count.p);
   hipLaunchKernelGGL(k_span_aligned, dim3(cdiv(n, 256)), dim3(256), 0, stream(), f->first.p, f->last.p, span.p, n, al);
   scan_async<int32_t>(span.p, f->off.p, (int64_t)n);
-  if (M.zero_free != 1)
-    hipLaunchKernelGGL(k_count_zero_values_c, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), view(M), zc.p);
+  const bool views = options().stored_zero_views != 0;
+  if (M.zero_free != 1) {
+    if (views && allow_view) f->zlast.alloc((size_t)n);
+    hipLaunchKernelGGL(k_count_zero_values<double2>, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), view(M), zc.p, f->zlast.p);
+  }
   int64_t tot = 0;
   unsigned long long hz = 0;
   {
@@ -6830,12 +6880,17 @@ bool slab_enter_c(DevMat& M, bool* not_run_like) {
     ft.add(zc.p, 1, &hz);
     ft.run();
   }
-  if (hz == 0) M.zero_free = 1;
-  // (stored zeros would read as "no entry"; mostly holes: not run-like)
-  if (hz != 0 || (double)tot > 2.0 * (double)M.nnz + 2.0 * al * (double)n) {
+  if (hz == 0) {
+    M.zero_free = 1;
+    f->zlast.release();
+  }
+  const bool holes = (double)tot > 2.0 * (double)M.nnz + 2.0 * al * (double)n;   // (mostly holes: not run-like)
+  // (stored zeros would read as "no entry": without option stored_zero_views the input is refused; with it the slab form
+  // becomes a read-only view below -- unless this caller takes none, who leaves the matrix free to become one later)
+  if (holes || (hz != 0 && !(views && allow_view))) {
     if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
       std::fprintf(stderr, "[slab_enter_c] refused: slots %lld for %lld entries, columns with stored zeros %llu\n", (long long)tot, (long long)M.nnz, hz);
-    M.slab_hint = -1;
+    if (holes || !views) M.slab_hint = -1;
     if (not_run_like && hz == 0) *not_run_like = true;
     return false;
   }
@@ -6847,7 +6902,11 @@ bool slab_enter_c(DevMat& M, bool* not_run_like) {
   f->row_pad = al;
   f->slots = tot;
   DevMat R;
-  R.rows = M.rows; R.cols = n; R.cplx = true; R.nnz = M.nnz; R.zero_free = 1;
+  R.rows = M.rows; R.cols = n; R.cplx = true; R.nnz = M.nnz; R.zero_free = hz == 0 ? 1 : 0;
+  if (hz != 0) {   // (stored zeros: a read-only view, the compressed columns stay -- SlabForm::origin, as slab_enter)
+    f->origin.reset(new DevMat(std::move(M)));
+    slab_view_counts()[0] += 1;
+  }
   R.slab = std::move(f);
   M = std::move(R);
   return true;
@@ -6858,7 +6917,7 @@ bool slab_enter_c(DevMat& M, bool* not_run_like) {
 // slab_multiply_takes_panel: a rank that says yes there cannot say no later)
 bool slab_multiply_c_takes_panel(const DevMat& A, const DevMat& B, int left_row_pad, int32_t ka, int32_t kb, const SlabPlan* plan) {
   if (options().spgemm_fma != 1 || options().complex_tile == 0 || kb <= ka) return false;
-  if (!sa_operand_c(A) || !sa_operand_c(B) || options().spgemm_variant >= 0 || options().spgemm_force_bin > 0) return false;
+  if (!sa_readable_c(A) || !sa_readable_c(B) || options().spgemm_variant >= 0 || options().spgemm_force_bin > 0) return false;
   if (left_row_pad % 16 != 0) return false;
   if (!plan || plan->align != 16 || (int64_t)plan->blk_lo.n != cdiv(B.cols, SLAB_CJ)) return false;
   return plan->max_w > 0 && plan->max_w <= 16384 && spgemm_tile_c_fits(plan->max_kn, plan->max_w);
@@ -6870,7 +6929,7 @@ bool slab_multiply_c_takes_panel(const DevMat& A, const DevMat& B, int left_row_
 // numbers, runs in this rank's buffer or in the receive buffer), the plan comes with it
 bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule, const SlabHalo* left) {
   if (left && !slab_multiply_c_takes_panel(A, B, left->row_pad, left->ka, left->kb, left->plan)) return false;
-  if (!sa_operand_c(A) || !sa_operand_c(B) || (!left && A.cols != B.rows) || options().spgemm_fma != 1 || options().complex_tile == 0 ||
+  if (!sa_readable_c(A) || !sa_readable_c(B) || (!left && A.cols != B.rows) || options().spgemm_fma != 1 || options().complex_tile == 0 ||
       options().spgemm_variant >= 0 || options().spgemm_force_bin > 0) {
     if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM")) std::fprintf(stderr, "[slab_multiply_c] refused: operands / options\n");
     return false;
@@ -7030,8 +7089,8 @@ bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, 
 // inverse-square-root loops: InverseSolversModule.F90:29-149, SquareRootSolversModule.F90:342-531): merge by the
 // AddSparseVectors rules with the threshold on the modulus, copy, scaling by a real constant, the largest column sum of moduli
 bool slab_axpby_c(const DevMat& A, DevMat& B, double alpha, double beta, double threshold) {
-  if (!sa_operand_c(A) || !sa_operand_c(B) || A.cols != B.cols || &A == &B) return false;
-  if (alpha == 0.0 || beta == 0.0 || A.zero_free != 1 || B.zero_free != 1) return false;
+  if (!sa_readable_c(A) || !sa_readable_c(B) || A.cols != B.cols || &A == &B) return false;
+  if (alpha == 0.0 || beta == 0.0 || !sa_mergeable(A) || !sa_mergeable(B)) return false;
   DevMat R;
   if (!sa_axpby_impl(&A, B, R, alpha, beta, threshold)) return false;
   value_epoch() += 1;
@@ -7039,27 +7098,32 @@ bool slab_axpby_c(const DevMat& A, DevMat& B, double alpha, double beta, double 
   return true;
 }
 bool slab_axpby_to_c(const DevMat& A, const DevMat& B, DevMat& Out, double alpha, double beta, double threshold) {
-  if (!sa_operand_c(A) || !sa_operand_c(B) || A.cols != B.cols || &A == &B) return false;
-  if (alpha == 0.0 || beta == 0.0 || A.zero_free != 1 || B.zero_free != 1) return false;
+  if (!sa_readable_c(A) || !sa_readable_c(B) || A.cols != B.cols || &A == &B) return false;
+  if (alpha == 0.0 || beta == 0.0 || !sa_mergeable(A) || !sa_mergeable(B)) return false;
   DevMat R;
   if (!sa_axpby_impl(&A, B, R, alpha, beta, threshold)) return false;
   Out = std::move(R);
   return true;
 }
 bool slab_clone_c(const DevMat& A, DevMat& Out) {
+  if (sa_readable_c(A) && A.slab->origin) { sa_clone_view(A, Out); return true; }
   if (!sa_operand_c(A) || A.zero_free != 1) return false;
   return sa_axpby_impl(nullptr, A, Out, 1.0, 0.0, 0.0);
 }
 bool slab_scale_c(DevMat& A, double c) {
-  if (!sa_operand_c(A) || c == 0.0) return false;
-  value_epoch() += 1;
+  if (!sa_readable_c(A) || c == 0.0) return false;
   SlabForm& f = *A.slab;
+  if (f.origin) {   // (a view: the compressed columns it hands back are scaled with the runs)
+    scale(*f.origin, c);
+    slab_view_counts()[2] += 1;
+  }
+  value_epoch() += 1;
   hipLaunchKernelGGL(k_sa_scale<double2>, dim3(cdiv((int64_t)A.cols * WAVE, 256)), dim3(256), 0, stream(), A.cols, f.first.p, f.last.p, f.off.p,
                      reinterpret_cast<double2*>(f.val.p), c);
   return true;
 }
 bool slab_norm_c(const DevMat& A, double* out) {
-  if (!sa_operand_c(A)) return false;
+  if (!sa_readable_c(A)) return false;
   const SlabForm& f = *A.slab;
   DevBuf<double> cs((size_t)A.cols);
   hipLaunchKernelGGL(k_sa_colstat<double2>, dim3(cdiv((int64_t)A.cols * WAVE, 256)), dim3(256), 0, stream(), A.cols, f.first.p, f.last.p, f.off.p,

@@ -90,6 +90,7 @@ struct EngineOptions {
   int panel_sessions = 1;      // slab sessions (TRS4, sign, inverse, square roots, polynomials ...) on more than one rank: the loops' matrices stay in slab form as column panels, a product exchanges the runs of the left operand's halo (psmatrix.cpp panel_slab_multiply); 0: compressed columns across ranks
   int thin_slab_complex = 1;   // complex slab sessions (one rank and column panels across ranks): a product with a thin operand on the complex gather kernels of spgemm_thin.hip (the reference's own multiply-add, bit for bit) instead of the complex tile kernel; 0: every complex session product on the tile kernel; thin_left = 0 switches these off too
   int complex_poly_sessions = 2;   // complex operands of the polynomial and function families (Horner, Paterson-Stockmeyer, the two Chebyshev evaluations, Hermite, the exponential's squarings, sine / cosine): 1: their loops open a complex slab session as the sign loop does (needs complex_sessions, FMA arithmetic, complex_tile; across ranks complex_panels); 2: and the two merges behind a product of the Chebyshev / Hermite recurrence are one kernel (slab_extra.hip slab_recurrence_step_c, the same values bit for bit); 0: compressed columns between the operations
+  int stored_zero_views = 1;   // an operand in compressed columns that STORES zero values (a Hamiltonian with a zero on its diagonal) enters a slab session as a read-only view (SlabForm::origin keeps the compressed columns, SlabForm::zlast the row of the last stored zero per column): complex operands as real ones already did, products / dots / norms read the runs, and a merge on a view is done in slab form wherever no stored zero of one operand lies beyond the other operand's last row (k_sa_axpby; otherwise that one merge runs on compressed columns and the view stays); copies and scalings keep the view.  0: complex operands with stored zeros are refused by slab_enter_c, real views refuse merges
   int complex_panels = 1;      // complex loops (sign, inverse, square roots) on more than one rank: the iterates stay complex column panels in slab form, a product exchanges the complex runs of the left operand's halo (psmatrix.cpp panel_slab_multiply, complex tile kernel); needs panel_sessions and complex_sessions; 0: compressed columns across ranks
   int complex_density = 1;     // complex TRS2 on one rank (FMA arithmetic, complex_tile, complex_sessions): the iterate stays out of compressed columns from step to step -- run-like iterates in complex slab form (X*X on the complex tile kernel, then the merge pass, then one energy / trace pass), iterates without runs in complex block form (block_complex, block_path: X*X on k_bs_numeric_c, the complex block merge, block_dot_trace) (psmatrix.cpp complex_trs2_step); 0: every complex density solve as before
   int ghash_mfma = 1;          // grouped LDS-hash SpGEMM, real operands, FMA arithmetic: the products of a phase (four steps) as ONE v_mfma_f64_16x16x4_f64 per tile of 16 slots x 16 columns instead of 64 vector FMAs -- the same chain of fma() over ascending k, bit for bit; 0: vector units
@@ -253,7 +254,16 @@ void slab_allow_panels(bool on);   // a slab session across ranks: the operands 
 // slots aligned to 16 rows -- what the complex MFMA tile kernel reads and writes.  Each returns false when it does not take
 // its operands (nothing changed): the caller packs and the compressed-column path does the work.
 bool sa_operand_c(const DevMat& M);
-bool slab_enter_c(DevMat& M, bool* not_run_like = nullptr);   // (not_run_like: set when it refused because the columns are not run-like)
+// sa_operand_c, or the read-only view of a complex matrix with stored zeros (SlabForm::origin, option stored_zero_views): what
+// the products, norms and dots read -- a stored zero is a zero of the run
+bool sa_readable_c(const DevMat& M);
+// (not_run_like: set when it refused because the columns are not run-like; allow_view false: an input with stored zeros is
+// refused as without option stored_zero_views, but keeps its chance to become a view later)
+bool slab_enter_c(DevMat& M, bool* not_run_like = nullptr, bool allow_view = true);
+// [4] since start: views built from compressed columns (real and complex); products with a view operand done in slab form;
+// merges / copies / scalings with a view operand done in slab form; merges on a view declined because the result would hold
+// a stored zero
+long long* slab_view_counts();
 bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule, const SlabHalo* left = nullptr);
 // true: slab_multiply_c with a left halo of these columns, this alignment and this plan will NOT decline (the one predicate it uses itself)
 bool slab_multiply_c_takes_panel(const DevMat& A, const DevMat& B, int left_row_pad, int32_t ka, int32_t kb, const SlabPlan* plan);

@@ -241,6 +241,29 @@ void slab_refused(std::initializer_list<const PSMatrix*> ms) {
                  g_slab_failed ? ": compressed columns from here on" : "");
   for (const PSMatrix* m : ms) pack(mut(*m));
 }
+// a read-only slab view of a matrix with stored zeros (SlabForm::origin, option stored_zero_views)
+bool is_view(const PSMatrix& m) { return m.loc.expanded() && m.loc.slab->origin != nullptr; }
+void count_view_product(const PSMatrix& A, const PSMatrix& B) {
+  if (is_view(A) || is_view(B)) slab_view_counts()[1] += 1;
+}
+// the compressed columns of an operand for ONE operation that the slab form cannot do: a view's own (no copy), otherwise a
+// packed copy in `tmp` -- the operand itself stays in slab form
+const DevMat& columns_of(const PSMatrix& m, DevMat& tmp) {
+  if (is_view(m)) return *m.loc.slab->origin;
+  if (!m.loc.expanded() && !m.loc.loose() && !m.loc.blocked()) return m.loc;
+  tmp = packed_copy(m.loc);
+  return tmp;
+}
+// A merge on a view was declined because its result has to STORE a zero (kernels.hip k_sa_axpby, stat bit 4): a refusal like
+// any other in the session's books, but nobody loses its slab form over it -- the caller does this one merge on compressed
+// columns (columns_of) and the view stands for the next product
+void slab_refused_view_merge() {
+  g_slab_refusals += 1;
+  g_slab_counts[3] += 1;
+  if (g_slab_refusals > 4) g_slab_failed = true;
+  if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+    std::fprintf(stderr, "[slab session] a merge on a view keeps a stored zero: this one on compressed columns (%d refusals so far)\n", g_slab_refusals);
+}
 // Block form (DevMat::blk: what the block path's products leave behind for the C ABI's MatrixMultiply and the TRS2 loop)
 // is understood by ps_multiply and the TRS2 steps only: every other operation takes compressed columns
 void unblock(std::initializer_list<const PSMatrix*> ms) {
@@ -978,6 +1001,7 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
     // and every rank takes the same branch)
     if (panel_slab_multiply(A, B, AB, alpha, threshold)) {
       g_slab_counts[0] += 1;
+      count_view_product(A, B);
       install(C, A.grid, A.dim, A.cplx, B.c0, B.c1, std::move(AB));
       return;
     }
@@ -996,6 +1020,7 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
     if (k.enter(mut(A)) && (&A == &B || k.enter(mut(B))) && (A.cplx || (runs_dense(A.loc) && runs_dense(B.loc))) &&
         k.multiply(A.loc, B.loc, AB, alpha, threshold, dense_branch(A.dim, A.loc.nnz, B.loc.nnz), nullptr)) {
       g_slab_counts[0] += 1;
+      count_view_product(A, B);
       if (!A.cplx && options().time_kernels != 0) {   // (statistics mode: the products a plan over compressed columns would have counted)
         const long long pr = slab_product_count(A.loc, B.loc);
         last_spgemm_stats().products = pr;
@@ -1119,7 +1144,16 @@ void ps_axpby(const PSMatrix& A, PSMatrix& B, double alpha, double beta, double 
     // (a slab session: the operand still in compressed columns -- an identity, the Hamiltonian -- is turned into slab form;
     // complex operands in a session that takes them: the merge on runs of (re, im) pairs; mixed kinds: the general path)
     const SlabKind& k = slab_kind(A.cplx);
+    const long long declined = slab_view_counts()[3];
     if (k.enter(mut(A)) && k.enter(B.loc) && k.axpby(A.loc, B.loc, alpha, beta, threshold)) { g_slab_counts[1] += 1; return; }
+    if (slab_view_counts()[3] != declined) {
+      slab_refused_view_merge();
+      DevMat tmp;
+      const DevMat& Ac = columns_of(A, tmp);
+      pack(B.loc);   // (B is replaced by the result, which stores a zero: compressed columns)
+      axpby(Ac, B.loc, alpha, beta, threshold, nullptr, nullptr);
+      return;
+    }
     slab_refused({&A, &B});
   } else {
     slab_pack_if({&A, &B});
@@ -1251,8 +1285,18 @@ void ps_copy_axpby(const PSMatrix& B, const PSMatrix& A, PSMatrix& Out, double a
       A.dim == B.dim) {
     const SlabKind& k = slab_kind(A.cplx);
     DevMat R;
+    const long long declined = slab_view_counts()[3];
     if (k.enter(mut(A)) && k.enter(mut(B)) && k.axpby_to(A.loc, B.loc, R, alpha, beta, threshold)) {
       g_slab_counts[1] += 1;
+      install(Out, B.grid, B.dim, A.cplx, B.c0, B.c1, std::move(R));
+      return;
+    }
+    if (slab_view_counts()[3] != declined) {
+      slab_refused_view_merge();
+      DevMat tmp;
+      const DevMat& Ac = columns_of(A, tmp);
+      R = is_view(B) ? B.loc.slab->origin->clone() : packed_copy(B.loc);
+      axpby(Ac, R, alpha, beta, threshold, nullptr, nullptr);
       install(Out, B.grid, B.dim, A.cplx, B.c0, B.c1, std::move(R));
       return;
     }
@@ -1529,7 +1573,7 @@ bool complex_trs2_step(PSMatrix& B, int mode, double threshold, const PSMatrix& 
   if (B.loc.blocked()) return complex_trs2_block(B, mode, threshold, dense_rule, D, out);
   if (!B.loc.expanded()) {
     bool not_runs = false;
-    if (!slab_enter_c(B.loc, &not_runs)) {
+    if (!slab_enter_c(B.loc, &not_runs, false)) {   // (no view iterate: stored zeros refuse as ever)
       if (!not_runs) return false;   // (stored zeros: this step the old way)
       if (complex_trs2_block(B, mode, threshold, dense_rule, D, out)) return true;
       ctrs2_set_off(D);

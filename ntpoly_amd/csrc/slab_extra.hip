@@ -430,7 +430,7 @@ bool slab_add_diagonal_c(DevMat& B, double alpha, int32_t col_offset) {
 
 // MatrixNorm(alpha A + beta B) of two complex slab-form matrices, nothing built
 bool slab_norm_axpby_c(const DevMat& A, const DevMat& B, double alpha, double beta, double* out) {
-  if (!sa_operand_c(A) || !sa_operand_c(B) || A.cols != B.cols) return false;
+  if (!sa_readable_c(A) || !sa_readable_c(B) || A.cols != B.cols) return false;   // (a view's stored zero adds nothing to a column sum)
   const SlabForm &fa = *A.slab, &fb = *B.slab;
   const int n = A.cols;
   DevBuf<double> cs((size_t)n);
@@ -523,10 +523,12 @@ __global__ __launch_bounds__(256) void k_sa_dot_trace_c(int n, const int32_t* __
 }  // namespace
 
 bool slab_dot_trace_c(const DevMat& A, const DevMat* B, int32_t col_offset, double dot[2], double* trace) {
-  if (!A.expanded() || !A.cplx || A.slab->labelled() || A.slab->origin) return false;
+  // (read-only views of operands with stored zeros are read as they are: a stored zero adds an exact zero to either sum)
+  auto view_ok = [](const DevMat& M) { return !M.slab->origin || (options().stored_zero_views != 0 && M.slab->zlast.p != nullptr); };
+  if (!A.expanded() || !A.cplx || A.slab->labelled() || !view_ok(A)) return false;
   if (B) {
     if (!B->cplx || B->cols != A.cols || B->rows != A.rows || B->blocked() || B->loose()) return false;
-    if (B->expanded() && (B->slab->labelled() || B->slab->origin)) return false;
+    if (B->expanded() && (B->slab->labelled() || !view_ok(*B))) return false;
   }
   const SlabForm& fa = *A.slab;
   const int n = A.cols;

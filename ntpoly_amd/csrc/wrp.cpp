@@ -193,6 +193,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "thin_left") options().thin_left = *value;
   else if (n == "thin_slab_complex") options().thin_slab_complex = *value;
   else if (n == "complex_poly_sessions") options().complex_poly_sessions = *value;
+  else if (n == "stored_zero_views") options().stored_zero_views = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -227,6 +228,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "thin_left") return options().thin_left;
   if (n == "thin_slab_complex") return options().thin_slab_complex;
   if (n == "complex_poly_sessions") return options().complex_poly_sessions;
+  if (n == "stored_zero_views") return options().stored_zero_views;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -414,6 +416,12 @@ void ntpoly_amd_block_algebra_counts(long long* out) {
 }
 void ntpoly_amd_slab_algebra_counts(long long* out) {
   for (int q = 0; q < 4; ++q) out[q] = slab_algebra_counts()[q];
+}
+// read-only slab views of operands with stored zeros (option stored_zero_views) since start: out[0] = views built from compressed
+// columns, out[1] = products with a view operand done in slab form, out[2] = merges / copies / scalings with a view operand done in
+// slab form, out[3] = merges on a view declined because the result would hold a stored zero (done on compressed columns instead)
+void ntpoly_amd_slab_view_counts(long long out[4]) {
+  for (int q = 0; q < 4; ++q) out[q] = slab_view_counts()[q];
 }
 // products of slab sessions on more than one rank since start: done in slab form on every rank, declined (compressed columns),
 // host synchronisations inside the former (measured)

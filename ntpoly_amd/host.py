@@ -964,6 +964,15 @@ def slab_algebra_counts():
     return dict(products=out[0], merges=out[1], others=out[2], refusals=out[3])
 
 
+def slab_view_counts():
+    """read-only slab views of operands that store zeros (option stored_zero_views) since start: views built from compressed
+    columns, products / merges-copies-scalings with a view operand done in slab form, merges on a view declined because the
+    result would hold a stored zero"""
+    out = (C.c_longlong * 4)()
+    lib.ntpoly_amd_slab_view_counts(out)
+    return dict(built=out[0], products=out[1], taken=out[2], declined=out[3])
+
+
 def panel_product_counts():
     """products of slab sessions on more than one rank since start: done in slab form on every rank, declined"""
     out = (C.c_longlong * 3)()

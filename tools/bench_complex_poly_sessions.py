@@ -6,6 +6,9 @@ estimate for it is negative too, and ComputeExponential(H) -- as the reference's
 sigma = 4, two squarings behind the degree-15 fit.)  The generator's 131 diagonal entries that are exactly zero are not stored:
 complex slab form cannot hold a stored zero, and an input with stored zeros has every product that reads it refused -- after five
 refusals the session gives up and the evaluation runs on compressed columns whatever the option says (--stored-zeros 1 measures that).
+With option stored_zero_views (--views 1, the default of the library) such an input enters the session as a read-only view instead;
+--views 0 is the behaviour without views, and --views -1 leaves the option alone (a library built before the option existed,
+NTPOLY_AMD_LIB).  The views' counters are reported where the library has them.
 
 ONE configuration per invocation, in this process -- the caller runs the six lines (option 0, 1, 2; one rank, and a 1-rank RCCL
 communicator: every collective of a panel product a real RCCL call, nothing has to travel) one after the other, each under its
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--degree", type=int, default=16)
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--stored-zeros", type=int, choices=(0, 1), default=0, help="1: keep the generator's zero-valued diagonal entries")
+    ap.add_argument("--views", type=int, choices=(-1, 0, 1), default=-1, help="stored_zero_views; -1: leave the library's own setting")
     args = ap.parse_args()
     os.environ["NTPOLY_AMD_FORCE_RCCL"] = str(args.rccl)
     os.environ.pop("NTPOLY_AMD_COMM", None)
@@ -50,6 +54,9 @@ def main():
     nt.ConstructGlobalProcessGrid(1, 1, 1)
     nt.set_option("spgemm_fma", 1)
     nt.set_option("complex_poly_sessions", args.option)
+    if args.views >= 0:
+        nt.set_option("stored_zero_views", args.views)
+    have_views = hasattr(nt.lib, "ntpoly_amd_slab_view_counts")
     n = args.n
     col, row, val = banded_triplets(n, args.h, complex_=True)
     if not args.stored_zeros:
@@ -68,27 +75,30 @@ def main():
         O = nt.Matrix_ps(n)
         nt.synchronize()
         s0, q0 = nt.slab_algebra_counts(), nt.panel_product_counts()
+        v0 = nt.slab_view_counts() if have_views else {}
         t0 = time.perf_counter()
         fn(O)
         nt.synchronize()
         ms = (time.perf_counter() - t0) * 1e3
         s1, q1 = nt.slab_algebra_counts(), nt.panel_product_counts()
-        return ms, {k: s1[k] - s0[k] for k in s0}, q1["slab"] - q0["slab"], O.GetSize()
+        v1 = nt.slab_view_counts() if have_views else {}
+        return ms, {k: s1[k] - s0[k] for k in s0}, q1["slab"] - q0["slab"], O.GetSize(), {k: v1[k] - v0[k] for k in v0}
 
     out = {"option": args.option, "rccl": args.rccl, "n": n, "h": args.h, "threshold": args.threshold, "blocks": args.blocks,
-           "stored_zeros": args.stored_zeros}
+           "stored_zeros": args.stored_zeros, "views": nt.get_option("stored_zero_views") if have_views else None,
+           "library": os.environ.get("NTPOLY_AMD_LIB", "")}
     for name, fn in work.items():
         timed(fn)   # (untimed: first launches, allocator pools)
     blocks = {name: [] for name in work}
     last = {}
     for _ in range(args.blocks):
         for name, fn in work.items():
-            ms, slab, panel, nnz = timed(fn)
+            ms, slab, panel, nnz, views = timed(fn)
             blocks[name].append(ms)
-            last[name] = (slab, panel, nnz)
+            last[name] = (slab, panel, nnz, views)
     for name in work:
         out[name] = dict(ms=round(statistics.median(blocks[name]), 3), blocks_ms=[round(x, 3) for x in blocks[name]],
-                         slab_operations=last[name][0], panel_products=last[name][1], nnz=last[name][2])
+                         slab_operations=last[name][0], panel_products=last[name][1], nnz=last[name][2], view_operations=last[name][3])
     print(json.dumps(out))
 
 
