@@ -117,6 +117,13 @@ __device__ inline double wave_sum_f64(double v) {
   return v;
 }
 __device__ inline unsigned long long lanemask_lt() { return (1ull << lane_id()) - 1ull; }
+// the value of lane l ^ 1 (every lane of the wave active).  Where lanes 2 c and 2 c + 1 hold (re, im) of complex column c -- the
+// interleaved columns of the complex matrix-core kernels -- this is the other part of the same complex number
+__device__ inline double partner(double x) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), 0xb1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), 0xb1, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
 
 // XCD-aware block index: hardware deals consecutive block ids round-robin over the 8 XCDs
 // (MI355X_MICROARCH.md, "Workgroup dispatch"), each XCD has its own 4 MiB L2.  Give every XCD a

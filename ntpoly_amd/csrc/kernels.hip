@@ -2712,6 +2712,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_PANEL_SESSIONS")) e->panel_sessions = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PANELS")) e->complex_panels = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_THIN_SLAB_COMPLEX")) e->thin_slab_complex = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_GHASH_MFMA_COMPLEX")) e->ghash_mfma_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_POLY_SESSIONS")) e->complex_poly_sessions = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_STORED_ZERO_VIEWS")) e->stored_zero_views = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_DENSITY")) e->complex_density = std::atoi(v);
@@ -3273,6 +3274,16 @@ static bool spgemm_striped(const DevMat& A, const DevMat& B, DevMat& C, double a
 }
 
 namespace {
+// dimension whose previous multiply the grouped kernel computed without handing a column back (real / complex): the next one
+// of that dimension goes to it first (spgemm() below)
+int grouped_first_n[2] = {-1, -1};
+}  // namespace
+void drop_grouped_caches() {
+  grouped_first_n[0] = grouped_first_n[1] = -1;
+  drop_grouped_order_caches();
+}
+
+namespace {
 // the block path (spgemm_block.hip) with spgemm()'s book-keeping around it
 int g_block_keep = 0;           // > 0: a caller that understands DevMat::blk is waiting for the product (BlockKeepScope)
 // (complex operands: FMA arithmetic with complex_tile and block_complex -- where complex products are a tolerance mode already)
@@ -3489,7 +3500,6 @@ void spgemm(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double th
   // that): no slab planning, no per-column plan -- fixed output slots of the largest table class per column
   DevBuf<int32_t> tmp_inner;
   DevBuf<double> tmp_val;
-  static int grouped_first_n[2] = {-1, -1};
   bool grouped_done = false;
   // (bit 0: the dense branch's order of threshold and alpha; bit 1: FMA accumulation, option spgemm_fma, real operands)
   const int dr = (dense_rule ? 1 : 0) | ((options().spgemm_fma && !A.cplx) ? 2 : 0);

@@ -94,6 +94,7 @@ struct EngineOptions {
   int complex_panels = 1;      // complex loops (sign, inverse, square roots) on more than one rank: the iterates stay complex column panels in slab form, a product exchanges the complex runs of the left operand's halo (psmatrix.cpp panel_slab_multiply, complex tile kernel); needs panel_sessions and complex_sessions; 0: compressed columns across ranks
   int complex_density = 1;     // complex TRS2 on one rank (FMA arithmetic, complex_tile, complex_sessions): the iterate stays out of compressed columns from step to step -- run-like iterates in complex slab form (X*X on the complex tile kernel, then the merge pass, then one energy / trace pass), iterates without runs in complex block form (block_complex, block_path: X*X on k_bs_numeric_c, the complex block merge, block_dot_trace) (psmatrix.cpp complex_trs2_step); 0: every complex density solve as before
   int ghash_mfma = 1;          // grouped LDS-hash SpGEMM, real operands, FMA arithmetic: the products of a phase (four steps) as ONE v_mfma_f64_16x16x4_f64 per tile of 16 slots x 16 columns instead of 64 vector FMAs -- the same chain of fma() over ascending k, bit for bit; 0: vector units
+  int ghash_mfma_complex = 1;  // grouped LDS-hash SpGEMM, COMPLEX operands, FMA arithmetic with complex_tile (where complex products are a tolerance mode already): table class 0 (512 slots) on the matrix cores -- two v_mfma_f64_16x16x4_f64 per tile of 16 slots x 8 complex columns and phase, Re x against the interleaved multiplier row, Im x against the row with its parts swapped and the new real part negated; every part of an entry is the sum of two FMA chains over ascending k (1e-13 of the largest entry, as complex_tile and block_complex).  Classes 1 and 2 stay on the vector units (LDS).  0, unfused arithmetic or complex_tile = 0: the reference's complex multiply-add on the vector units, bit for bit
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
   int plan_fused = 1;          // the maxima and prefix sums of a slab step's plan in ONE launch (k_slab_offsets: every workgroup sums what lies before its part itself) instead of four to seven; 0: separate launches
@@ -264,6 +265,14 @@ bool slab_enter_c(DevMat& M, bool* not_run_like = nullptr, bool allow_view = tru
 // merges / copies / scalings with a view operand done in slab form; merges on a view declined because the result would hold
 // a stored zero
 long long* slab_view_counts();
+// [4] since start: groups finished by the grouped LDS-hash kernel (spgemm_grouped.hip), by path: real operands on the matrix
+// cores (option ghash_mfma), real on the vector units, complex on the matrix cores (option ghash_mfma_complex, table class 0),
+// complex on the vector units
+long long* ghash_class_counts();
+// forgets everything the grouped path keeps between products (the kept column orders, the table class hints, the dimensions
+// whose next product goes to the grouped kernel first): which class a product starts in then no longer depends on the products
+// before it
+void drop_grouped_caches();
 bool slab_multiply_c(const DevMat& A, const DevMat& B, DevMat& C, double alpha, double threshold, bool dense_rule, const SlabHalo* left = nullptr);
 // true: slab_multiply_c with a left halo of these columns, this alignment and this plan will NOT decline (the one predicate it uses itself)
 bool slab_multiply_c_takes_panel(const DevMat& A, const DevMat& B, int left_row_pad, int32_t ka, int32_t kb, const SlabPlan* plan);

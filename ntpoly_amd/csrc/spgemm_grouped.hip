@@ -18,7 +18,9 @@
 // The epilogue sorts the (row, slot) pairs of the group once (bitonic, in LDS), gathers every column's sums in row
 // order through LDS, prunes (sparse_includes/PruneList.f90:22, strict >) and compacts with ballot + popcount prefix.
 // Results are bit-identical to the per-column kernels and to the reference: every C(i, j) sees the same products in the
-// same ascending-k order with the same unfused multiply and add.
+// same ascending-k order with the same unfused multiply and add.  (One exception, on request of the arithmetic mode: complex
+// operands in FMA arithmetic with complex_tile run table class 0 on the matrix cores as a 1e-13 tolerance mode, option
+// ghash_mfma_complex -- see the MF notes above k_spgemm_ghash.)
 //
 // Groups whose row union outgrows a table class are retried with the next class (512 / 1024 / 1536 slots) and are
 // finally handed back to the per-column LDS hash kernel (kernels.hip), so any operand is accepted.
@@ -459,6 +461,18 @@ struct GhTable {
 // (tools/micro/mfma_f64_probe.hip), so the results are bit for bit the same; a slot a column does not touch contributes
 // fma(0, b, acc) = acc.  A lane then owns (4 slots x 1 column) per tile instead of (1 slot x 16 columns) per chunk; the
 // epilogue is the same prune / rank-bitmap / compaction re-indexed.
+//
+// MF, COMPLEX operands (table class 0 only; FMA arithmetic with complex_tile, option ghash_mfma_complex): the identity of
+// spgemm_tile_c.hip.  A multiplier tile row -- 8 interleaved (re, im) pairs -- IS a real row of 16, B'(k, 2 c + p) = part p of
+// B(k, c), and  [Re C | Im C] = Re x * B' + Im x * B''  with B'' = B' with the parts of every column swapped and the new real part
+// negated (the value of lane l ^ 1, sign flipped in the even lanes).  Two matrix instructions per tile of 16 slots and phase; a
+// lane reads its (re, im) of x once, as 16 bytes, and feeds both.  The two partial sums stay in accumulators of their own and
+// are added once, after the last phase: every part of an entry is the sum of two chains of fma() over ascending k, a zero
+// contribution is an exact no-op, so the bits do not depend on how the union's steps fall into phases (ONE accumulator for both
+// instructions would interleave the chains phase by phase, and the bits would depend on the grouping).  Not the reference's
+// complex multiply-add (products, difference / sum and accumulates rounded one by one): a TOLERANCE mode, 1e-13 of the largest
+// entry, as the complex tile kernel and the complex block path are.  Lane l then holds part l & 1 of complex column
+// (l & 15) >> 1; the prune rule needs both parts, the other one comes from lane l ^ 1 (partner(), device_util.hpp).
 template <typename T, int NW, int SL, int WPC, bool MF = false>
 __global__ __launch_bounds__(NW* WAVE) __attribute__((amdgpu_waves_per_eu((SL == 1 && !Sc<T>::cplx) ? 6 : 2))) void k_spgemm_ghash(
     Csc A, const int32_t* __restrict__ cols, const int32_t* __restrict__ grp_kn, const int32_t* __restrict__ grp_maxlen,
@@ -473,8 +487,14 @@ __global__ __launch_bounds__(NW* WAVE) __attribute__((amdgpu_waves_per_eu((SL ==
   constexpr unsigned long long EMPTY = ~0ull;
   static_assert(NW % WPC == 0 && KB >= 1 && 2 * KB * CAP >= 2 * CAP, "geometry");
   __shared__ __attribute__((aligned(16))) unsigned long long htab[TH];   // (row << 32 | slot); the epilogue sorts (row, slot) pairs in the same memory
-  static_assert(!MF || (!Sc<T>::cplx && KB == 4 && CAP % (16 * NW) == 0), "matrix-core products: real operands, four steps per phase");
-  constexpr int XP = MF ? CAP + 16 : CAP;   // (MF: rows 16 slots apart in the banks -- the four steps a lane group reads do not collide)
+  static_assert(!MF || (KB == 4 && CAP % (16 * NW) == 0), "matrix-core products: four steps per phase");
+  static_assert(!MF || !Sc<T>::cplx || (NW == 8 && SL == 1), "complex matrix-core products: table class 0 only (the x buffers of 1024 slots do not fit the LDS)");
+  // (MF, real: rows 16 slots apart in the banks -- the four steps a lane group reads do not collide.  MF, complex: a lane reads 16
+  // bytes, and ds_read_b128 serves the wave in four groups of 16 lanes that each take 8 lanes of one step row and 4 + 4 of another
+  // with COMPLEMENTARY slots of the tile ({0-3, 12-15} with {4-11}: MI355X LDS lane groups), so rows a multiple of 256 bytes apart
+  // are conflict-free as they stand -- 512 x 16 B is one; any pad that is not a multiple of 16 elements would put the two rows of
+  // a group on the same banks)
+  constexpr int XP = (MF && !Sc<T>::cplx) ? CAP + 16 : CAP;
   constexpr int NTILE = CAP / (16 * NW);    // MF: tiles of 16 slots per wave (tile u of wave w = slots 16 (u NW + w) ..)
   __shared__ T xbuf[2][KB][XP];             // slot-indexed copies of the A columns of two consecutive phases
   __shared__ int slot_row[CAP];
@@ -507,8 +527,18 @@ __global__ __launch_bounds__(NW* WAVE) __attribute__((amdgpu_waves_per_eu((SL ==
 
   T acc[MF ? 1 : SL][MF ? 1 : G];
   typedef double mf_v4d __attribute__((ext_vector_type(4)));
-  [[maybe_unused]] mf_v4d macc[MF ? NTILE : 1];   // MF: element v of tile u = slot 16 (u NW + wave) + 4 v + lane / 16, column lane % 16
-  if constexpr (MF) {
+  constexpr bool MFC = MF && Sc<T>::cplx;
+  [[maybe_unused]] mf_v4d macc[(MF && !MFC) ? NTILE : 1];   // MF, real: element v of tile u = slot 16 (u NW + wave) + 4 v + lane / 16, column lane % 16
+  // MF, complex: macc_re_plane = Re x * B', macc_im_plane = Im x * B'' -- element v of tile u = part lane & 1 of complex column
+  // (lane & 15) >> 1, same slot; kept apart until the last phase is done
+  [[maybe_unused]] mf_v4d macc_re_plane[MFC ? NTILE : 1], macc_im_plane[MFC ? NTILE : 1];
+  if constexpr (MFC) {
+#pragma unroll
+    for (int u = 0; u < NTILE; ++u) {
+      macc_re_plane[u] = mf_v4d{0.0, 0.0, 0.0, 0.0};
+      macc_im_plane[u] = mf_v4d{0.0, 0.0, 0.0, 0.0};
+    }
+  } else if constexpr (MF) {
 #pragma unroll
     for (int u = 0; u < NTILE; ++u) macc[u] = mf_v4d{0.0, 0.0, 0.0, 0.0};
   } else {
@@ -646,14 +676,27 @@ __global__ __launch_bounds__(NW* WAVE) __attribute__((amdgpu_waves_per_eu((SL ==
       // this lane's multiplier: row t0 + lane / 16, column lane % 16 of the tile (rows beyond the union: zero, whatever the
       // padding of the tile holds)
       const int q = lane >> 4, jj = lane & 15;
-      double bv = 0.0;
-      if constexpr (!Sc<T>::cplx) bv = (q < nstep) ? tile[(int64_t)(t0 + q) * G + jj] : 0.0;
+      // (complex: real column lane % 16 of the row of 8 interleaved pairs)
+      const double bv = (q < nstep) ? reinterpret_cast<const double*>(tile)[(int64_t)(t0 + q) * 16 + jj] : 0.0;
+      // complex: the multiplier of the imaginary plane, B''(k, 2 c) = -Im B(k, c), B''(k, 2 c + 1) = Re B(k, c)
+      [[maybe_unused]] double bs = 0.0;
+      if constexpr (MFC) {
+        const double other = partner(bv);   // (every lane: the whole wave is here)
+        bs = (q < nstep) ? ((lane & 1) ? other : -other) : 0.0;
+      }
       // (tried and measured slower by 8 %: all of the wave's tiles read up front, the two entries of a bucket in one 16-byte read)
 #pragma unroll
       for (int u = 0; u < NTILE; ++u) {
         const int s0 = 16 * (u * NW + wave);
         if (s0 < nsl) {
-          if constexpr (!Sc<T>::cplx) {
+          if constexpr (MFC) {
+            const T xv = xbuf[set][q][s0 + jj];
+            if (__ballot(!Sc<T>::is_zero(xv)) != 0ull) {
+              xbuf[set][q][s0 + jj] = Sc<T>::zero();
+              macc_re_plane[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv.x, bv, macc_re_plane[u], 0, 0, 0);
+              macc_im_plane[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv.y, bs, macc_im_plane[u], 0, 0, 0);
+            }
+          } else {
             const double xv = xbuf[set][q][s0 + jj];
             if (__ballot(xv != 0.0) != 0ull) {
               xbuf[set][q][s0 + jj] = 0.0;
@@ -773,7 +816,33 @@ __global__ __launch_bounds__(NW* WAVE) __attribute__((amdgpu_waves_per_eu((SL ==
   __syncthreads();
   unsigned long long keepbits = 0;   // bit s * G + g (MF: bit 4 u + v)
   int myrank[SL], myrow[SL];
-  if constexpr (MF) {
+  if constexpr (MFC) {
+    // (a lane's sums: part lane & 1 of complex column (lane & 15) >> 1, slots 16 (u NW + wave) + 4 v + lane / 16.  The two planes
+    // are added here, once; the modulus needs the other part, held by lane ^ 1 for the same slot -- both lanes of a pair take the
+    // same decision from the same (re, im), the even one sets the rank bit)
+    const int q = lane >> 4, part = lane & 1, g = (lane & 15) >> 1;
+#pragma unroll
+    for (int u = 0; u < NTILE; ++u) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const double mine = __dadd_rn(macc_re_plane[u][v], macc_im_plane[u][v]);
+        macc_re_plane[u][v] = mine;
+        const double other = partner(mine);   // (every lane, before any divergence)
+        const int slot = 16 * (u * NW + wave) + 4 * v + q;
+        const int row = slot < nsl ? slot_row[slot] : -1;
+        if (row >= 0) {
+          const T z = part ? make_double2(other, mine) : make_double2(mine, other);
+          if (Sc<T>::mag((dense_rule & 1) ? z : Sc<T>::scale(alpha, z)) > threshold) {
+            keepbits |= 1ull << (4 * u + v);
+            if (part == 0) {
+              const int rk = rank_s[slot];
+              atomicOr(&bm[g * NWORD + (rk >> 6)], 1ull << (rk & 63));
+            }
+          }
+        }
+      }
+    }
+  } else if constexpr (MF) {
     // (a lane's sums: slots 16 (u NW + wave) + 4 v + lane / 16 of column lane % 16)
     const int q = lane >> 4, g = lane & 15;
 #pragma unroll
@@ -822,7 +891,24 @@ __global__ __launch_bounds__(NW* WAVE) __attribute__((amdgpu_waves_per_eu((SL ==
     }
   }
   __syncthreads();
-  if constexpr (MF) {
+  if constexpr (MFC) {
+    const int q = lane >> 4, part = lane & 1, g = (lane & 15) >> 1;
+    double* __restrict__ out_parts = reinterpret_cast<double*>(out_val);   // (re, im) interleaved
+#pragma unroll
+    for (int u = 0; u < NTILE; ++u) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        if ((keepbits >> (4 * u + v)) & 1ull) {
+          const int slot = 16 * (u * NW + wave) + 4 * v + q;
+          const int rk = rank_s[slot];
+          const int w = rk >> 6, bit = rk & 63;
+          const int64_t pos = colbase[g] + pre[g * NWORD + w] + __popcll(bm[g * NWORD + w] & ((1ull << bit) - 1ull));
+          if (part == 0) out_inner[pos] = slot_row[slot];
+          out_parts[2 * pos + part] = __dmul_rn(alpha, macc_re_plane[u][v]);
+        }
+      }
+    }
+  } else if constexpr (MF) {
     const int q = lane >> 4, g = lane & 15;
 #pragma unroll
     for (int u = 0; u < NTILE; ++u) {
@@ -893,7 +979,28 @@ void launch_ghash(const DevMat& A, int ngroups, const int32_t* cols, const int32
                      reinterpret_cast<T*>(tmp_val), count, state, stats, alpha, thr, dr, ngroups, ablate);
 }
 
+// What the grouped path keeps between products (drop_grouped_order_caches forgets it).
+// The column order of the last multiply of this dimension is kept: purification iterates keep their similarity
+// structure from one multiply to the next, so the clustering is only redone when the kept order stops paying
+// (its union ratio has grown by more than 15 % since it was made).
+struct OrderCache {
+  int n = -1, ngroups = 0, minhash = 0;
+  double ratio0 = 0;
+  DevBuf<int32_t> cols;
+};
+OrderCache* g_order_cache[2] = {new OrderCache(), new OrderCache()};   // real / complex (leaked on purpose, like the context)
+int g_class_hint[2] = {0, 0};  // table class that took most groups last time (real / complex)
+long long g_class_counts[4] = {0, 0, 0, 0};
+
 }  // namespace
+
+long long* ghash_class_counts() { return g_class_counts; }
+void drop_grouped_order_caches() {
+  for (int q = 0; q < 2; ++q) {
+    *g_order_cache[q] = OrderCache();
+    g_class_hint[q] = 0;
+  }
+}
 
 bool spgemm_grouped(const DevMat& A, const DevMat& B, const int64_t* tmpoff, int32_t* tmp_inner, double* tmp_val,
                     int32_t* count, uint8_t* bin_arr, double alpha, double threshold, int dense_rule, int mode,
@@ -933,16 +1040,7 @@ bool spgemm_grouped(const DevMat& A, const DevMat& B, const int64_t* tmpoff, int
     return total;
   };
 
-  // The column order of the last multiply of this dimension is kept: purification iterates keep their similarity
-  // structure from one multiply to the next, so the clustering is only redone when the kept order stops paying
-  // (its union ratio has grown by more than 15 % since it was made).
-  struct OrderCache {
-    int n = -1, ngroups = 0, minhash = 0;
-    double ratio0 = 0;
-    DevBuf<int32_t> cols;
-  };
-  static OrderCache* cache[2] = {new OrderCache(), new OrderCache()};   // real / complex (leaked on purpose, like the context)
-  OrderCache& oc = *cache[A.cplx ? 1 : 0];
+  OrderCache& oc = *g_order_cache[A.cplx ? 1 : 0];
   const double ideal = std::max(1.0, (double)B.nnz / (double)G);
   int64_t cost = 0, total = 0;
   double ratio = 0;
@@ -1067,15 +1165,25 @@ bool spgemm_grouped(const DevMat& A, const DevMat& B, const int64_t* tmpoff, int
   });
 
   if (numeric_begin) HIP_CHECK(hipEventRecord(numeric_begin, stream()));
-  static int hint[2] = {0, 0};  // table class that took most groups last time (real / complex)
-  int& start = hint[A.cplx ? 1 : 0];
+  int& start = g_class_hint[A.cplx ? 1 : 0];
   int64_t todo = ngroups;
   const int first = start;
   for (int level = first; level < 3; ++level) {
     stats.zero();
     // (real operands in FMA arithmetic: the products on the matrix cores, four steps per phase -- option ghash_mfma)
     const bool mf = !A.cplx && (dense_rule & 2) != 0 && options().ghash_mfma != 0;
-    if (mf) {
+    // (complex operands where complex products are a tolerance mode already -- FMA arithmetic with complex_tile, the condition of
+    // the complex block path -- and option ghash_mfma_complex: table class 0 on the matrix cores, two FMA chains per part of an
+    // entry.  Classes 1 and 2 of a complex product stay on the vector units with the reference's complex multiply-add: two sets
+    // of four slot-indexed columns of 1024 complex slots are 133 KB, and with the table and the rows beyond the LDS of a CU.  In
+    // unfused arithmetic or with complex_tile = 0 the option is ignored)
+    const bool mfc = A.cplx && B.cplx && level == 0 && options().spgemm_fma == 1 && options().complex_tile != 0 &&
+                     options().ghash_mfma_complex != 0;
+    const bool on_cores = mfc || (mf && level < 2);
+    if (mfc)
+      launch_ghash<double2, 8, 1, 2, true>(A, ngroups, colp, grp_kn.p, grp_maxlen.p, grp_off.p, recs.p, tiles.p, tmpoff, tmp_inner, tmp_val,
+                                           count, state.p, stats.p, alpha, threshold, dense_rule);
+    else if (mf) {
       if (level == 0)
         launch_ghash<double, 8, 1, 2, true>(A, ngroups, colp, grp_kn.p, grp_maxlen.p, grp_off.p, recs.p, tiles.p, tmpoff, tmp_inner, tmp_val,
                                             count, state.p, stats.p, alpha, threshold, dense_rule);
@@ -1116,6 +1224,7 @@ bool spgemm_grouped(const DevMat& A, const DevMat& B, const int64_t* tmpoff, int
       if (left * 2 > todo && level < 2) start = level + 1;
       else if (left == 0 && level > 0 && (int64_t)h[1] * 10 <= (int64_t)(level == 1 ? 512 : 1024) * 8) start = level - 1;
     }
+    g_class_counts[(A.cplx ? 2 : 0) + (on_cores ? 0 : 1)] += todo - left;   // groups this level finished
     todo = left;
     if (left == 0) break;
   }

@@ -30,4 +30,8 @@ bool spgemm_grouped(const DevMat& A, const DevMat& B, const int64_t* tmpoff, int
 // mode 0: as described; 1: forced (also with dissimilar columns); 2: only with the kept min-hash column order of the
 // previous multiply of this dimension (returns false at once otherwise)
 
+// forgets what the grouped path keeps between products: the kept column order per kind (real / complex) and the table class
+// the next product starts in (kernels.hip drop_grouped_caches adds its own memory of "grouped kernel first")
+void drop_grouped_order_caches();
+
 }  // namespace ntp

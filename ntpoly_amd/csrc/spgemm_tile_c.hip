@@ -37,12 +37,7 @@ constexpr int CPF = 6;           // run loads (k groups) in flight per wave; a m
 constexpr int CRPAD = 4;         // one group of empty records behind the last
 
 __device__ inline v2d ld_c(unsigned long long addr) { return *reinterpret_cast<const v2d __attribute__((address_space(1)))*>(addr); }
-// the other part of the same complex number: lanes 2 c and 2 c + 1 hold (re, im) of column c
-__device__ inline double partner(double x) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), 0xb1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), 0xb1, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
+// (the other part of the same complex number -- lanes 2 c and 2 c + 1 hold (re, im) of column c: partner(), device_util.hpp)
 
 struct alignas(16) CRec {
   unsigned long long rz;   // address of (hypothetical) row 0 of the run

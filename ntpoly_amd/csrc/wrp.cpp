@@ -177,6 +177,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "tile_off32") options().tile_off32 = *value;
   else if (n == "tile_bbuf") options().tile_bbuf = *value;
   else if (n == "ghash_mfma") options().ghash_mfma = *value;
+  else if (n == "ghash_mfma_complex") options().ghash_mfma_complex = *value;
   else if (n == "block_unfused") options().block_unfused = *value;
   else if (n == "block_match") options().block_match = *value;
   else if (n == "block_scope") options().block_scope = *value;
@@ -214,6 +215,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "tile_off32") return options().tile_off32;
   if (n == "tile_bbuf") return options().tile_bbuf;
   if (n == "ghash_mfma") return options().ghash_mfma;
+  if (n == "ghash_mfma_complex") return options().ghash_mfma_complex;
   if (n == "block_unfused") return options().block_unfused;
   if (n == "block_match") return options().block_match;
   if (n == "block_scope") return options().block_scope;
@@ -252,6 +254,15 @@ void ntpoly_amd_last_grouped_stats(long long* out, double* ratio) {
   out[5] = s.gh_tile_rows;
   *ratio = s.gh_union_ratio;
 }
+// groups finished by the grouped LDS-hash kernel since start, by path: out[0] real operands on the matrix cores (option
+// ghash_mfma), [1] real on the vector units, [2] complex on the matrix cores (option ghash_mfma_complex: table class 0 in FMA
+// arithmetic with complex_tile), [3] complex on the vector units
+void ntpoly_amd_ghash_class_counts(long long out[4]) {
+  for (int q = 0; q < 4; ++q) out[q] = ghash_class_counts()[q];
+}
+// forgets what the grouped path keeps between products (kept column orders, table class hints, "grouped kernel first"
+// dimensions): the class a product starts in then does not depend on earlier products of the process
+void ntpoly_amd_drop_grouped_caches() { drop_grouped_caches(); }
 // 1: the last SpGEMM ran on the thin-left kernel (spgemm_thin.hip)
 int ntpoly_amd_last_spgemm_thin() { return last_spgemm_stats().thin; }
 // products of slab sessions computed by the thin-operand gather kernels (spgemm_thin.hip) since start: out[0] real, thin left

@@ -973,6 +973,21 @@ def slab_view_counts():
     return dict(built=out[0], products=out[1], taken=out[2], declined=out[3])
 
 
+def ghash_class_counts():
+    """groups finished by the grouped LDS-hash kernel (csrc/spgemm_grouped.hip) since start, by path: real operands on the matrix
+    cores (option ghash_mfma) / on the vector units, complex operands on the matrix cores (option ghash_mfma_complex: table class 0
+    in FMA arithmetic with complex_tile, two FMA chains per part of an entry) / on the vector units"""
+    out = (C.c_longlong * 4)()
+    lib.ntpoly_amd_ghash_class_counts(out)
+    return dict(real_mfma=out[0], real_vector=out[1], complex_mfma=out[2], complex_vector=out[3])
+
+
+def drop_grouped_caches():
+    """forget what the grouped LDS-hash path keeps between products (the kept column orders, the table class hints, the dimensions
+    whose next product goes to the grouped kernel first): the class a product starts in then does not depend on earlier products"""
+    lib.ntpoly_amd_drop_grouped_caches()
+
+
 def panel_product_counts():
     """products of slab sessions on more than one rank since start: done in slab form on every rank, declined"""
     out = (C.c_longlong * 3)()
