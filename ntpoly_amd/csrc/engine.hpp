@@ -145,6 +145,20 @@ void ps_increment_identity(const PSMatrix& Identity, PSMatrix& B, double alpha);
 // done, the caller runs the sequence of merges and dots): the two traces, then P = Fx + sigma Gx
 bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx);
 bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P);
+// PM purification with the iterate X kept in slab form (zero-free runs) and the rows compressed columns would hold as stored
+// zeros in Z (kernels.hpp ZeroList; option pm_session), inside a real slab session, one rank or column panels across ranks.
+// ps_pm_sigma: trace and dot(., X) of X - X2 merged at `threshold`, X - X2 not formed.  Collective: the two sums and "some rank
+// cannot" travel in one reduction; false on EVERY rank then, nothing changed.
+// ps_pm_update: X <- a1 X + a2 X2 + a3 X3 as ScaleMatrix and two IncrementMatrix calls, Z <- the new list.  Local: false when THIS
+// rank cannot -- it has then materialised its iterate and made the two merges on compressed columns (Z is empty); the caller
+// hands that to ps_pm_energy, whose reduction tells every rank.
+// ps_pm_energy: dot(X, WH) as ps_dot, with "this rank left the fused path" carried by the same reduction; *some_refused: on any rank.
+// ps_pm_materialise: X to compressed columns with Z's rows inserted as stored zeros -- what the loop on compressed columns holds.
+bool ps_pm_sigma(const PSMatrix& X, const ZeroList& Z, const PSMatrix& X2, double threshold, double* trace_value, double* dot_value);
+bool ps_pm_update(PSMatrix& X, ZeroList& Z, const PSMatrix& X2, const PSMatrix& X3, double a1, double a2, double a3, double threshold);
+double ps_pm_energy(const PSMatrix& X, const PSMatrix& WH, bool refused_here, bool* some_refused);
+void ps_pm_materialise(PSMatrix& X, ZeroList& Z);
+long long* pm_session_counts();   // since start: [0] sigma passes fused, [1] updates fused, [2] stored zeros carried (summed over the updates), [3] solves that left the fused path; [4] the longest zero list an update left on this rank
 // MatrixNorm of alpha A + beta B (ScaleMatrix(B, beta); IncrementMatrix(A, B, alpha, 0); MatrixNorm(B)) for the loops
 // that build the sum only for its norm; false: not done (outside a slab session, operands in compressed columns ...)
 bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double beta, double* norm);

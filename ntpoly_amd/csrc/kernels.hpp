@@ -95,6 +95,7 @@ struct EngineOptions {
   int complex_density = 1;     // complex TRS2 on one rank (FMA arithmetic, complex_tile, complex_sessions): the iterate stays out of compressed columns from step to step -- run-like iterates in complex slab form (X*X on the complex tile kernel, then the merge pass, then one energy / trace pass), iterates without runs in complex block form (block_complex, block_path: X*X on k_bs_numeric_c, the complex block merge, block_dot_trace) (psmatrix.cpp complex_trs2_step); 0: every complex density solve as before
   int ghash_mfma = 1;          // grouped LDS-hash SpGEMM, real operands, FMA arithmetic: the products of a phase (four steps) as ONE v_mfma_f64_16x16x4_f64 per tile of 16 slots x 16 columns instead of 64 vector FMAs -- the same chain of fma() over ascending k, bit for bit; 0: vector units
   int ghash_mfma_complex = 1;  // grouped LDS-hash SpGEMM, COMPLEX operands, FMA arithmetic with complex_tile (where complex products are a tolerance mode already): table class 0 (512 slots) on the matrix cores -- two v_mfma_f64_16x16x4_f64 per tile of 16 slots x 8 complex columns and phase, Re x against the interleaved multiplier row, Im x against the row with its parts swapped and the new real part negated; every part of an entry is the sum of two FMA chains over ascending k (1e-13 of the largest entry, as complex_tile and block_complex).  Classes 1 and 2 stay on the vector units (LDS).  0, unfused arithmetic or complex_tile = 0: the reference's complex multiply-add on the vector units, bit for bit
+  int pm_session = 1;          // PM purification, real operands, wherever a real slab session opens (one rank and column panels across ranks): the iterate stays in slab form, the scalars of sigma come from one pass over X and X2 without forming X - X2, the update a1 X + a2 X2 + a3 X3 is one pass over the three runs, and the stored zeros that compressed columns would carry (ScaleMatrix by a1 = 0 when sigma > 1/2, unfiltered tails) travel in a per-panel zero list next to the zero-free runs (slab_extra.hip k_pm_sigma / k_pm_update); 0: the loop on compressed columns, bit for bit as before
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
   int plan_fused = 1;          // the maxima and prefix sums of a slab step's plan in ONE launch (k_slab_offsets: every workgroup sums what lies before its part itself) instead of four to seven; 0: separate launches
@@ -303,6 +304,26 @@ bool slab_add_diagonal(DevMat& B, double alpha, int32_t col_offset);   // B <- B
 bool slab_trs4_traces(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx);
 bool slab_trs4_operand(const DevMat& X, const DevMat& X2, double sigma, int32_t col_offset, DevMat& Out);
 bool slab_norm_axpby(const DevMat& A, const DevMat& B, double alpha, double beta, double* out);   // MatrixNorm(alpha A + beta B), nothing built
+// PM purification on a slab-form iterate (slab_extra.hip).  The rows of each column that compressed columns would hold as STORED
+// ZEROS (a1 = 0 when sigma > 1/2, unfiltered tails that underflow) travel next to the zero-free runs: rows row[off[j] .. off[j + 1])
+// of column j, ascending, disjoint from the run's non-zeros.  off.p == nullptr: no such row.
+struct ZeroList {
+  DevBuf<int64_t> off;   // cols + 1
+  DevBuf<int32_t> row;
+  int64_t count = 0;
+  void clear() { off.release(); row.release(); count = 0; }
+};
+// trace and dot(., X) of CopyMatrix(X, Temp); IncrementMatrix(X2, Temp, -1, thr) without forming Temp: LOCAL sums, out2 = (trace, dot)
+bool slab_pm_sigma(const DevMat& X, const ZeroList& Z, const DevMat& X2, double thr, int32_t col_offset, double out2[2]);
+// ScaleMatrix(X, a1); IncrementMatrix(X2, X, a2, thr); IncrementMatrix(X3, X, a3, thr) in one pass: Out (zero-free runs) and Zout;
+// false: refused (operands not in slab form / labelled / a view, or a union extent beyond the output), nothing changed
+bool slab_pm_update(const DevMat& X, const ZeroList& Z, const DevMat& X2, const DevMat& X3, double a1, double a2, double a3, double thr,
+                    DevMat& Out, ZeroList& Zout);
+// compressed columns with the list's rows inserted as stored zeros (M packed, real); every entry of both is kept
+void insert_stored_zeros(DevMat& M, const ZeroList& Z);
+// the stored pattern of a packed matrix as a zero list (the diagnostic entry point's Z), and a list as a matrix of stored zeros
+void zero_list_from_pattern(const DevMat& M, ZeroList& Z);
+DevMat zero_list_matrix(const ZeroList& Z, int32_t rows, int32_t cols);
 bool slab_trace(const DevMat& A, int32_t col_offset, double* out);   // sum of the diagonal entries held by the local columns
 int64_t slab_span_sum(const DevMat& M);   // rows covered by the runs (cached in the form)
 long long slab_product_count(const DevMat& A, const DevMat& B);   // statistics (slab_extra.hip): intermediate products of A B

@@ -1273,6 +1273,60 @@ bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatr
   return true;
 }
 
+long long* pm_session_counts() {
+  static long long counts[5] = {0, 0, 0, 0, 0};
+  return counts;
+}
+bool ps_pm_sigma(const PSMatrix& X, const ZeroList& Z, const PSMatrix& X2, double threshold, double* trace_value, double* dot_value) {
+  CommScope cs(X.grid);
+  double t[3] = {0.0, 0.0, 0.0};
+  const bool ok = slab_on() && !X.cplx && !X2.cplx && !blk_any({&X, &X2}) && X.loc.expanded() && X2.loc.expanded() &&
+                  slab_pm_sigma(X.loc, Z, X2.loc, threshold, X.c0, t);
+  if (world().active()) {
+    // (a session across ranks: the decision is collective -- the sums and "some rank declined" in one reduction)
+    if (!ok) { t[0] = t[1] = 0.0; t[2] = 1.0; }
+    comm_allreduce_sum(t, 3);
+    if (t[2] != 0.0) return false;
+  } else if (!ok) {
+    return false;
+  }
+  *trace_value = t[0];
+  *dot_value = t[1];
+  g_slab_counts[2] += 1;
+  pm_session_counts()[0] += 1;
+  return true;
+}
+bool ps_pm_update(PSMatrix& X, ZeroList& Z, const PSMatrix& X2, const PSMatrix& X3, double a1, double a2, double a3, double threshold) {
+  CommScope cs(X.grid);
+  DevMat R;
+  ZeroList zn;
+  if (slab_on() && !X.cplx && !X2.cplx && !X3.cplx && !blk_any({&X, &X2, &X3}) && X.loc.expanded() && X2.loc.expanded() && X3.loc.expanded() &&
+      slab_pm_update(X.loc, Z, X2.loc, X3.loc, a1, a2, a3, threshold, R, zn)) {
+    X.loc = std::move(R);
+    Z = std::move(zn);
+    bump_matrix_value_epoch();
+    g_slab_counts[1] += 2;
+    pm_session_counts()[1] += 1;
+    pm_session_counts()[2] += Z.count;
+    pm_session_counts()[4] = std::max<long long>(pm_session_counts()[4], Z.count);
+    return true;
+  }
+  // this rank cannot: its iterate as compressed columns hold it, and the two merges there (they are local to the panel)
+  g_slab_counts[3] += 1;
+  ps_pm_materialise(X, Z);
+  unblock({&X2, &X3});
+  DevMat t2, t3;
+  axpby(columns_of(X2, t2), X.loc, a2, a1, threshold, nullptr, nullptr);
+  axpby(columns_of(X3, t3), X.loc, a3, 1.0, threshold, nullptr, nullptr);
+  return false;
+}
+void ps_pm_materialise(PSMatrix& X, ZeroList& Z) {
+  CommScope cs(X.grid);
+  ps_slab_leave(X);
+  insert_stored_zeros(X.loc, Z);
+  Z.clear();
+}
+
 void ps_copy_axpby(const PSMatrix& B, const PSMatrix& A, PSMatrix& Out, double alpha, double beta, double threshold) {
   CommScope cs(B.grid);
   if (blk_any({&A, &B}) && blk_kinds(A, B) && &A != &B && &Out != &A && &Out != &B) {
@@ -1743,8 +1797,16 @@ void ps_pairwise(const PSMatrix& A, const PSMatrix& B, PSMatrix& C) {
 
 // DotMatrix_psr/psc (PSMatrixAlgebraModule.F90:387-410, distributed_algebra_includes/DotMatrix.f90):
 // sum conj(A).B; fused, no Hadamard temporary.
-void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) {
+namespace {
+// extra (optional): one more number summed over the ranks by the reduction the dot makes anyway
+void ps_dot_with(const PSMatrix& A, const PSMatrix& B, double out[2], double* extra) {
   CommScope cs(A.grid);
+  auto reduce = [&]() {
+    if (!extra) { comm_allreduce_sum(out, 2); return; }
+    double t[3] = {out[0], out[1], *extra};
+    comm_allreduce_sum(t, 3);
+    out[0] = t[0]; out[1] = t[1]; *extra = t[2];
+  };
   if (blk_any({&A, &B}) && blk_kinds(A, B)) {
     double d[2] = {0.0, 0.0};
     // (the sum runs over the super-tiles of its first operand: the one in block form; sum conj(b) a = conj(sum conj(a) b))
@@ -1763,7 +1825,7 @@ void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) {
     // (a rank whose operands left slab form computes its share from compressed columns: the sum over the ranks follows either way)
     if (slab_enter(mut(A)) && slab_enter(mut(B)) && slab_dot(A.loc, B.loc, out)) {
       g_slab_counts[2] += 1;
-      comm_allreduce_sum(out, 2);
+      reduce();
       return;
     }
     slab_refused({&A, &B});
@@ -1778,7 +1840,15 @@ void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) {
   } else {
     dot(A.loc, B.loc, out);
   }
-  comm_allreduce_sum(out, 2);
+  reduce();
+}
+}  // namespace
+void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) { ps_dot_with(A, B, out, nullptr); }
+double ps_pm_energy(const PSMatrix& X, const PSMatrix& WH, bool refused_here, bool* some_refused) {
+  double out[2], flag = refused_here ? 1.0 : 0.0;
+  ps_dot_with(X, WH, out, &flag);
+  *some_refused = flag != 0.0;
+  return out[0];
 }
 
 double ps_trace(const PSMatrix& A) {

@@ -793,6 +793,350 @@ int64_t slab_span_sum(const DevMat& M) {
   return f.span_sum;
 }
 
+// ------------------------------------------------------------------ PM purification on a slab-form iterate
+// DensityMatrixSolversModule.F90:145-200 per iteration, after the two products X2 = X X and X3 = X X2:
+//   CopyMatrix(X, Temp); IncrementMatrix(X2, Temp, -1, thr); trace(Temp), dot(Temp, X)                      (the sigma pass)
+//   ScaleMatrix(X, a1); IncrementMatrix(X2, X, a2, thr); IncrementMatrix(X3, X, a3, thr)                    (the update)
+// Whenever sigma > 1/2 the update scales X by a1 = 0: compressed columns then hold STORED ZEROS, and AddSparseVectors copies
+// the tail of a column beyond the other operand's last row unfiltered -- a stored zero there survives the merge and its
+// row steers the tail rule of the merges that follow.  The runs of a slab form read a zero as "no entry", so those rows
+// travel in a ZeroList next to zero-free runs.  "Present" below: a non-zero of the run or a row of the list; exh = last
+// present row of a column.  Element arithmetic: __dmul_rn / __dadd_rn in the order of the vocabulary calls.
+namespace {
+struct PmRuns {   // the runs of one slab-form operand
+  const int32_t* __restrict__ first;
+  const int32_t* __restrict__ last;
+  const int64_t* __restrict__ off;
+  const double* __restrict__ val;
+};
+PmRuns pm_runs(const DevMat& M) { return PmRuns{M.slab->first.p, M.slab->last.p, M.slab->off.p, M.slab->val.p}; }
+struct PmCol {    // one column of it: rows f .. l (l < f: empty) at p[r]
+  int f, l;
+  const double* __restrict__ p;
+  __device__ double at(int r) const { return (r >= f && r <= l) ? p[r] : 0.0; }
+};
+__device__ inline PmCol pm_col(const PmRuns& m, int j) {
+  PmCol c;
+  c.f = m.first[j]; c.l = m.last[j];
+  c.p = c.l >= c.f ? m.val + (m.off[j] - c.f) : m.val;
+  if (c.l < c.f) { c.f = INT_MAX; c.l = -1; }
+  return c;
+}
+// row r among the (few, ascending) listed rows zrow[z0 .. z1) of the column: the loop is uniform over the wave
+__device__ inline bool pm_listed(const int32_t* __restrict__ zrow, int64_t z0, int64_t z1, int r) {
+  bool in = false;
+  for (int64_t q = z0; q < z1; ++q) in |= zrow[q] == r;
+  return in;
+}
+// one row of o = alpha a + b by the AddSparseVectors rules (kernels.hip inc_decide): ha / hb = present, wa = alpha a and b as they
+// enter the sum, amax / bmax = last present row of the column of a / of b.  Returns "kept"; *o = the value (may be exactly zero
+// where a tail is copied unfiltered)
+__device__ inline bool pm_merge(bool ha, bool hb, double wa, double b, int r, int amax, int bmax, double thr, double* o) {
+  if (ha && hb) { *o = __dadd_rn(wa, b); return fabs(*o) > thr; }
+  if (ha) { *o = wa; return (r > bmax) ? true : (fabs(wa) > thr); }
+  if (hb) { *o = b; return (r > amax) ? true : (fabs(b) > thr); }
+  *o = 0.0;
+  return false;
+}
+// part[2 j] = trace, part[2 j + 1] = dot(., X) of column j of Temp = X - X2 (merged at thr), Temp itself not formed
+__global__ __launch_bounds__(256) void k_pm_sigma(int n, PmRuns X, const int64_t* __restrict__ zoff, const int32_t* __restrict__ zrow,
+                                                  PmRuns X2, int col_offset, int al, double thr, double* __restrict__ part) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id(), dg = j + col_offset;
+  const PmCol cx = pm_col(X, j), c2 = pm_col(X2, j);
+  const int64_t z0 = zoff ? zoff[j] : 0, z1 = zoff ? zoff[j + 1] : 0;
+  const int exhx = max(cx.l, z1 > z0 ? zrow[z1 - 1] : -1);
+  // (a listed row outside both runs merges to an exact zero: it adds nothing to either sum)
+  const int lo = min(cx.f, c2.f), hi = max(cx.l, c2.l);
+  double st = 0.0, sd = 0.0;
+  if (hi >= lo) {
+    const int r0 = lo / al * al, r1 = (hi / al + 1) * al;
+    for (int r = r0 + lane; r < r1; r += WAVE) {
+      const double x = cx.at(r), x2 = c2.at(r);
+      const bool px = x != 0.0 || pm_listed(zrow, z0, z1, r);
+      double o;
+      const bool keep = pm_merge(x2 != 0.0, px, __dmul_rn(-1.0, x2), x, r, c2.l, exhx, thr, &o);
+      if (keep) {
+        if (r == dg) st = __dadd_rn(st, o);
+        sd = __dadd_rn(sd, __dmul_rn(o, x));
+      }
+    }
+  }
+  st = wave_sum_f64(st);
+  sd = wave_sum_f64(sd);
+  if (lane == 0) { part[2 * (size_t)j] = st; part[2 * (size_t)j + 1] = sd; }
+}
+// aligned union of the three runs per column (0: all empty), the output slot of the update
+__global__ void k_pm_span(const int32_t* __restrict__ fa, const int32_t* __restrict__ la, const int32_t* __restrict__ fb,
+                          const int32_t* __restrict__ lb, const int32_t* __restrict__ fc, const int32_t* __restrict__ lc, int n, int al,
+                          int32_t* __restrict__ span) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  int f = INT_MAX, l = -1;
+  if (la[j] >= fa[j]) { f = min(f, fa[j]); l = max(l, la[j]); }
+  if (lb[j] >= fb[j]) { f = min(f, fb[j]); l = max(l, lb[j]); }
+  if (lc[j] >= fc[j]) { f = min(f, fc[j]); l = max(l, lc[j]); }
+  span[j] = l >= f ? (l / al + 1) * al - f / al * al : 0;
+}
+// One wave per column.  Loop 1: Y = a2 X2 + a1 X (kept rows, values may be zero) only to find exh(Y); loop 2: Y again and
+// o = a3 X3 + Y.  Columns of up to PM_KC * 64 rows keep x, x2 and x3 in registers between the loops (every load of the column is
+// requested before the first use); longer ones read the runs again.
+// MODE 0: kept non-zeros into the slot at base[j] (row r at base + r - a0, pads and dropped rows zero), first / last / count / offset
+//         as k_sa_axpby writes them; zcnt[j] = kept rows whose value is exactly zero.  stat |= 2: a union extent beyond the output.
+// MODE 1: those rows, ascending, to zout[nzoff[j] ...] (columns with none return at once).
+constexpr int PM_KC = 4;
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pm_update(int n, PmRuns X, const int64_t* __restrict__ zoff, const int32_t* __restrict__ zrow,
+                                                   PmRuns X2, PmRuns X3, double a1, double a2, double a3, double thr, int al,
+                                                   const int64_t* __restrict__ base, double* __restrict__ out, int32_t* __restrict__ ofirst,
+                                                   int32_t* __restrict__ olast, int32_t* __restrict__ ocount, int64_t* __restrict__ ooff,
+                                                   int32_t* __restrict__ zcnt, const int64_t* __restrict__ nzoff, int32_t* __restrict__ zout,
+                                                   int64_t bound, unsigned long long* __restrict__ stat) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id();
+  int64_t zdst = 0;
+  if (MODE == 1) {
+    zdst = nzoff[j];
+    if (nzoff[j + 1] == zdst) return;
+  }
+  const PmCol cx = pm_col(X, j), c2 = pm_col(X2, j), c3 = pm_col(X3, j);
+  const int64_t z0 = zoff ? zoff[j] : 0, z1 = zoff ? zoff[j + 1] : 0;
+  const int zf = z1 > z0 ? zrow[z0] : INT_MAX, zl = z1 > z0 ? zrow[z1 - 1] : -1;
+  const int exhx = max(cx.l, zl);
+  const int f = min(cx.f, min(c2.f, c3.f)), l = max(cx.l, max(c2.l, c3.l));   // the runs: where a non-zero can come out
+  const int a0 = l >= f ? f / al * al : 0, a1r = l >= f ? (l / al + 1) * al : 0;
+  const int64_t slot = MODE == 0 ? base[j] : 0;
+  if (MODE == 0) {
+    // (runs that lie far apart: the union is not bounded by the operands' slots -- nothing is written, the host refuses)
+    const int own = (cx.l >= cx.f ? (cx.l / al + 1) * al - cx.f / al * al : 0) + (c2.l >= c2.f ? (c2.l / al + 1) * al - c2.f / al * al : 0) +
+                    (c3.l >= c3.f ? (c3.l / al + 1) * al - c3.f / al * al : 0);
+    if (a1r - a0 > own + 2 * al || slot + (int64_t)(a1r - a0) > bound) {
+      if (lane == 0) { ofirst[j] = INT_MAX; olast[j] = -1; ocount[j] = 0; ooff[j] = slot; zcnt[j] = 0; atomicOr(stat, 2ull); }
+      return;
+    }
+  }
+  const int lo = min(f, zf), hi = max(l, zl);   // the rows to walk: the runs and the listed rows
+  if (hi < lo) {
+    if (MODE == 0 && lane == 0) { ofirst[j] = INT_MAX; olast[j] = -1; ocount[j] = 0; ooff[j] = slot; zcnt[j] = 0; }
+    return;
+  }
+  const int r0 = lo / al * al, r1 = (hi / al + 1) * al;
+  const bool fits = r1 - r0 <= PM_KC * WAVE;
+  double vx[PM_KC], v2[PM_KC], v3[PM_KC];
+  unsigned pm = 0;   // bit c: the row of chunk c is present in X
+  int ey = -1;
+  if (fits) {
+#pragma unroll
+    for (int c = 0; c < PM_KC; ++c) {
+      const int r = r0 + c * WAVE + lane;
+      const bool in = r < r1;
+      vx[c] = in ? cx.at(r) : 0.0;
+      v2[c] = in ? c2.at(r) : 0.0;
+      v3[c] = in ? c3.at(r) : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < PM_KC; ++c) {
+      const int r = r0 + c * WAVE + lane;
+      const bool px = r < r1 && (vx[c] != 0.0 || pm_listed(zrow, z0, z1, r));
+      pm |= px ? (1u << c) : 0u;
+      double y;
+      if (pm_merge(v2[c] != 0.0, px, __dmul_rn(a2, v2[c]), __dmul_rn(a1, vx[c]), r, c2.l, exhx, thr, &y)) ey = max(ey, r);
+    }
+  } else {
+    for (int r = r0 + lane; r < r1; r += WAVE) {
+      const double x = cx.at(r), x2 = c2.at(r);
+      const bool px = x != 0.0 || pm_listed(zrow, z0, z1, r);
+      double y;
+      if (pm_merge(x2 != 0.0, px, __dmul_rn(a2, x2), __dmul_rn(a1, x), r, c2.l, exhx, thr, &y)) ey = max(ey, r);
+    }
+  }
+  ey = wave_max_i32(ey);
+  double* __restrict__ dst = MODE == 0 ? out + (slot - a0) : out;
+  int cnt = 0, kf = INT_MAX, kl = -1, nz = 0;
+  // one chunk of 64 rows of loop 2 (every lane of the wave comes here: MODE 1 orders its rows with a ballot)
+  auto row2 = [&](int r, bool in, double x, bool px, double x2, double x3) {
+    double y, o;
+    const bool py = in && pm_merge(x2 != 0.0, px, __dmul_rn(a2, x2), __dmul_rn(a1, x), r, c2.l, exhx, thr, &y);
+    const bool keep = in && pm_merge(x3 != 0.0, py, __dmul_rn(a3, x3), py ? y : 0.0, r, c3.l, ey, thr, &o);
+    const bool kz = keep && o == 0.0, kv = keep && o != 0.0;
+    if (MODE == 0) {
+      if (in && r >= a0 && r < a1r) dst[r] = kv ? o : 0.0;
+      cnt += kv ? 1 : 0;
+      nz += kz ? 1 : 0;
+      kf = min(kf, kv ? r : INT_MAX);
+      kl = max(kl, kv ? r : -1);
+    } else {
+      const unsigned long long m = __ballot(kz);
+      if (kz) zout[zdst + nz + __popcll(m & lanemask_lt())] = r;
+      nz += __popcll(m);
+    }
+  };
+  if (fits) {
+#pragma unroll
+    for (int c = 0; c < PM_KC; ++c) {
+      const int r = r0 + c * WAVE + lane;
+      row2(r, r < r1, vx[c], (pm >> c) & 1u, v2[c], v3[c]);
+    }
+  } else {
+    for (int rb = r0; rb < r1; rb += WAVE) {
+      const int r = rb + lane;
+      const bool in = r < r1;
+      const double x = in ? cx.at(r) : 0.0;
+      row2(r, in, x, in && (x != 0.0 || pm_listed(zrow, z0, z1, r)), in ? c2.at(r) : 0.0, in ? c3.at(r) : 0.0);
+    }
+  }
+  if (MODE == 0) {
+    cnt = (int)wave_sum_i64(cnt);
+    nz = (int)wave_sum_i64(nz);
+    kf = wave_min_i32(kf);
+    kl = wave_max_i32(kl);
+    if (lane == 0) {
+      ofirst[j] = kf; olast[j] = kl; ocount[j] = cnt; zcnt[j] = nz;
+      ooff[j] = slot + (cnt ? kf - a0 : 0);
+    }
+  }
+}
+bool pm_operands(const DevMat& X, const DevMat& X2, const DevMat* X3) {
+  if (!trs4_operands(X, X2)) return false;
+  return !X3 || (trs4_operands(X, *X3) && X.rows == X3->rows);
+}
+// column j of Out = column j of A with the rows zrow[zoff[j] ..) inserted as stored zeros (both ascending and disjoint)
+__global__ __launch_bounds__(256) void k_insert_zeros(Csc A, const int64_t* __restrict__ zoff, const int32_t* __restrict__ zrow,
+                                                      int64_t* __restrict__ oouter, int32_t* __restrict__ oinner, double* __restrict__ oval) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= A.cols) return;
+  const int lane = lane_id();
+  const int64_t as = A.outer[j], ae = A.outer[j + 1], z0 = zoff[j], z1 = zoff[j + 1], dst = as + z0;
+  const double* __restrict__ av = static_cast<const double*>(A.val);
+  for (int64_t p = as + lane; p < ae; p += WAVE) {
+    const int r = A.inner[p];
+    int k = 0;
+    for (int64_t q = z0; q < z1; ++q) k += zrow[q] < r ? 1 : 0;
+    oinner[dst + (p - as) + k] = r;
+    oval[dst + (p - as) + k] = av[p];
+  }
+  for (int64_t q = z0 + lane; q < z1; q += WAVE) {
+    const int r = zrow[q];
+    int64_t a = as, b = ae;   // entries of the column below row r
+    while (a < b) {
+      const int64_t m = (a + b) / 2;
+      if (A.inner[m] < r) a = m + 1;
+      else b = m;
+    }
+    oinner[dst + (q - z0) + (a - as)] = r;
+    oval[dst + (q - z0) + (a - as)] = 0.0;
+  }
+  if (lane == 0) {
+    oouter[j] = dst;
+    if (j == A.cols - 1) oouter[j + 1] = ae + z1;
+  }
+}
+}  // namespace
+
+bool slab_pm_sigma(const DevMat& X, const ZeroList& Z, const DevMat& X2, double thr, int32_t col_offset, double out2[2]) {
+  if (!pm_operands(X, X2, nullptr)) return false;
+  const int n = X.cols;
+  DevBuf<double> part((size_t)2 * n), res(2);
+  hipLaunchKernelGGL(k_pm_sigma, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, pm_runs(X), Z.count ? Z.off.p : nullptr, Z.row.p,
+                     pm_runs(X2), col_offset, std::max(1, X.slab->row_pad), thr, part.p);
+  sum_pairs_async(part.p, n, res.p);
+  unsigned long long h[2] = {0, 0};
+  ScalarFetch ft;
+  ft.add(res.p, 2, h);
+  ft.run();
+  std::memcpy(out2, h, sizeof(h));
+  return true;
+}
+
+bool slab_pm_update(const DevMat& X, const ZeroList& Z, const DevMat& X2, const DevMat& X3, double a1, double a2, double a3, double thr,
+                    DevMat& Out, ZeroList& Zout) {
+  if (!pm_operands(X, X2, &X3)) return false;
+  const SlabForm &fx = *X.slab, &f2 = *X2.slab, &f3 = *X3.slab;
+  const int n = X.cols, al = std::max(1, fx.row_pad);
+  std::unique_ptr<SlabForm> fo(new SlabForm());
+  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
+  DevBuf<int32_t> span((size_t)n), zcnt((size_t)n);
+  DevBuf<int64_t> base((size_t)n + 1);
+  ZeroList zn;
+  zn.off.alloc((size_t)n + 1);
+  hipLaunchKernelGGL(k_pm_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), fx.first.p, fx.last.p, f2.first.p, f2.last.p, f3.first.p, f3.last.p,
+                     n, al, span.p);
+  scan_i32_async(span.p, base.p, (int64_t)n);
+  // (a column's slot is at most its operands' three slots and two pads: what the kernel refuses beyond)
+  const int64_t bound = fx.slots + f2.slots + f3.slots + 2LL * al * n;
+  fo->val.alloc((size_t)bound + kIndexSlack);
+  DevBuf<unsigned long long> stat(1), tot(1);
+  stat.zero();
+  tot.zero();
+  const int64_t* zoff = Z.count ? Z.off.p : nullptr;
+  const dim3 grid(cdiv((int64_t)n * WAVE, 256));
+  hipLaunchKernelGGL((k_pm_update<0>), grid, dim3(256), 0, stream(), n, pm_runs(X), zoff, Z.row.p, pm_runs(X2), pm_runs(X3), a1, a2, a3, thr, al,
+                     base.p, fo->val.p, fo->first.p, fo->last.p, fo->count.p, fo->off.p, zcnt.p, (const int64_t*)nullptr, (int32_t*)nullptr,
+                     bound, stat.p);
+  scan_i32_async(zcnt.p, zn.off.p, (int64_t)n);
+  hipLaunchKernelGGL(k_sa_count_sum, dim3(std::max(1, std::min(256, cdiv(n, 1024)))), dim3(256), 0, stream(), fo->count.p, n, tot.p);
+  int64_t nnz = 0, slots = 0, nzero = 0;
+  unsigned long long hs = 0;
+  {
+    ScalarFetch ft;
+    ft.add(tot.p, 1, &nnz);
+    ft.add(base.p + n, 1, &slots);
+    ft.add(zn.off.p + n, 1, &nzero);
+    ft.add(stat.p, 1, &hs);
+    ft.run();
+  }
+  if (hs != 0) return false;
+  if (nzero > 0) {
+    zn.row.alloc((size_t)nzero);
+    hipLaunchKernelGGL((k_pm_update<1>), grid, dim3(256), 0, stream(), n, pm_runs(X), zoff, Z.row.p, pm_runs(X2), pm_runs(X3), a1, a2, a3, thr,
+                       al, (const int64_t*)nullptr, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
+                       (int64_t*)nullptr, (int32_t*)nullptr, zn.off.p, zn.row.p, bound, (unsigned long long*)nullptr);
+  }
+  zn.count = nzero;
+  fo->row_pad = al;
+  fo->slots = slots;
+  DevMat R;
+  R.rows = X.rows; R.cols = n; R.cplx = false; R.nnz = nnz; R.zero_free = 1;
+  R.slab = std::move(fo);
+  Out = std::move(R);
+  Zout = std::move(zn);
+  return true;
+}
+
+void insert_stored_zeros(DevMat& M, const ZeroList& Z) {
+  if (Z.count == 0) return;
+  if (M.cplx) NTP_FATAL("internal: insert_stored_zeros takes real matrices");
+  pack(M);
+  DevMat R;
+  R.alloc(M.rows, M.cols, false, M.nnz + Z.count);
+  hipLaunchKernelGGL(k_insert_zeros, dim3(cdiv((int64_t)M.cols * WAVE, 256)), dim3(256), 0, stream(), view(M), Z.off.p, Z.row.p, R.outer.p,
+                     R.inner.p, R.val.p);
+  M = std::move(R);
+}
+
+void zero_list_from_pattern(const DevMat& M, ZeroList& Z) {
+  Z.clear();
+  if (M.nnz == 0) return;
+  const Csc v = view(M);
+  Z.off.alloc((size_t)M.cols + 1);
+  Z.row.alloc((size_t)M.nnz);
+  HIP_CHECK(hipMemcpyAsync(Z.off.p, v.outer, sizeof(int64_t) * ((size_t)M.cols + 1), hipMemcpyDeviceToDevice, stream()));
+  HIP_CHECK(hipMemcpyAsync(Z.row.p, v.inner, sizeof(int32_t) * (size_t)M.nnz, hipMemcpyDeviceToDevice, stream()));
+  Z.count = M.nnz;
+}
+
+DevMat zero_list_matrix(const ZeroList& Z, int32_t rows, int32_t cols) {
+  DevMat R;
+  if (Z.count == 0) { R.reset_empty(rows, cols, false); return R; }
+  R.alloc(rows, cols, false, Z.count);
+  HIP_CHECK(hipMemcpyAsync(R.outer.p, Z.off.p, sizeof(int64_t) * ((size_t)cols + 1), hipMemcpyDeviceToDevice, stream()));
+  HIP_CHECK(hipMemcpyAsync(R.inner.p, Z.row.p, sizeof(int32_t) * (size_t)Z.count, hipMemcpyDeviceToDevice, stream()));
+  HIP_CHECK(hipMemsetAsync(R.val.p, 0, sizeof(double) * (size_t)Z.count, stream()));
+  return R;
+}
+
 long long slab_product_count(const DevMat& A, const DevMat& B) {
   if (!A.expanded() || !B.expanded() || A.cplx || B.cplx) return 0;
   const SlabForm &fa = *A.slab, &fb = *B.slab;

@@ -219,12 +219,13 @@ void trace_reset() {   // (every solver's first statement: whatever a panel step
   last_trace() = SolverTrace();
   drop_pending_exchange();
 }
-void trace_rec(double value, double energy, double sigma, const PSMatrix& X) {
+// (extra_nnz: entries of the iterate held beside X.loc -- the stored zeros of PM's slab-form iterate)
+void trace_rec(double value, double energy, double sigma, const PSMatrix& X, int64_t extra_nnz = 0) {
   SolverTrace& t = last_trace();
   t.value.push_back(value);
   t.energy.push_back(energy);
   t.sigma.push_back(sigma);
-  t.nnz.push_back(X.loc.nnz);
+  t.nnz.push_back(X.loc.nnz + extra_nnz);
   t.iterations += 1;
 }
 double real_dot(const PSMatrix& A, const PSMatrix& B) {
@@ -277,11 +278,11 @@ struct DensityFrame {
     t1 = Clock::now();
   }
   // tail of one iteration, given the energy of the new iterate X: true when the loop is over
-  bool converged(double energy, double sigma, const PSMatrix& X) {
+  bool converged(double energy, double sigma, const PSMatrix& X, int64_t extra_nnz = 0) {
     const double energy_old = energy_value;
     energy_value = energy;
     monitor_append(mon, energy_value - energy_old);
-    trace_rec(energy_value - energy_old, energy_value, sigma, X);
+    trace_rec(energy_value - energy_old, energy_value, sigma, X, extra_nnz);
     if (monitor_converged(mon, p.be_verbose)) return true;
     if (p.be_verbose) {
       log_enter();
@@ -484,15 +485,36 @@ void solver_pm(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K
   ps_increment(IMat, X, factor, 0.0);
   f.begin_loop();
   int II;
-  // (no slab session here: whenever sigma > 1/2 the update scales X by a1 = 0 -- stored zeros whose tails steer the merges
-  // that follow, which the slab form cannot hold -- so half the iterations would fall back and convert to and fro)
+  // Option pm_session, real operands: the loop's matrices stay in slab form, as in TRS4.  Whenever sigma > 1/2 the update scales X
+  // by a1 = 0 -- stored zeros whose tails steer the merges that follow, which the runs of a slab form cannot hold: those rows travel
+  // in `zeros` beside a zero-free X (slab_extra.hip), the scalars of sigma and the update are one pass each.  Every decision to
+  // leave that path is collective and rides on a reduction the iteration makes anyway; it is taken once per solve: the iterate
+  // is materialised (compressed columns with the listed rows as stored zeros), the session closed, the loop body below as it was.
+  SlabSession slab(options().pm_session != 0 && !X.cplx && !WH.cplx);
+  const bool in_session = slab.opened;
+  bool fused = slab.opened;
+  ZeroList zeros;
+  auto leave_fused = [&]() {
+    ps_pm_materialise(X, zeros);
+    slab.close();
+    ps_slab_leave(X2);
+    ps_slab_leave(X3);
+    ps_slab_leave(f.WH);
+    fused = false;
+    pm_session_counts()[3] += 1;
+  };
   for (II = 1; II <= p.max_iterations; ++II) {                     // :145-200
     ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
     ps_multiply(X, X2, X3, 1.0, 0.0, p.threshold);
-    ps_copy(X, Temp);
-    ps_increment(X2, Temp, -1.0, p.threshold);
-    trace_value = ps_trace(Temp);
-    const double trace_value2 = real_dot(Temp, X);
+    double trace_value2 = 0.0;
+    // (an iterate that is no zero-free slab -- the starting iterate stores a zero, a product declined -- is refused here, on every rank)
+    if (fused && !ps_pm_sigma(X, zeros, X2, p.threshold, &trace_value, &trace_value2)) leave_fused();
+    if (!fused) {
+      ps_copy(X, Temp);
+      ps_increment(X2, Temp, -1.0, p.threshold);
+      trace_value = ps_trace(Temp);
+      trace_value2 = real_dot(Temp, X);
+    }
     if (trace_value <= 2.2250738585072014e-308) sigma_array[(size_t)II] = 1.0;
     else sigma_array[(size_t)II] = trace_value2 / trace_value;
     const double sg = sigma_array[(size_t)II];
@@ -506,9 +528,22 @@ void solver_pm(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K
       a2 = (1.0 + sg) / (1.0 - sg);
       a3 = -1.0 / (1.0 - sg);
     }
-    ps_axpby(X2, X, a2, a1, p.threshold);                           // ScaleMatrix(X, a1); IncrementMatrix(X2, X, a2)
-    ps_increment(X3, X, a3, p.threshold);
-    if (f.converged(real_dot(X, WH), sg, X)) break;
+    double energy;
+    if (fused) {
+      const bool here = ps_pm_update(X, zeros, X2, X3, a1, a2, a3, p.threshold);
+      bool some_refused = false;
+      energy = ps_pm_energy(X, WH, !here, &some_refused);
+      if (some_refused) leave_fused();
+    } else {
+      ps_axpby(X2, X, a2, a1, p.threshold);                         // ScaleMatrix(X, a1); IncrementMatrix(X2, X, a2)
+      ps_increment(X3, X, a3, p.threshold);
+      energy = real_dot(X, WH);
+    }
+    if (f.converged(energy, sg, X, zeros.count)) break;
+  }
+  if (in_session) {
+    slab.close();
+    ps_pm_materialise(X, zeros);
   }
   const int total_iterations = II - 1;
   f.finish(II, X, ISQ, K, energy_out);

@@ -195,6 +195,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "thin_slab_complex") options().thin_slab_complex = *value;
   else if (n == "complex_poly_sessions") options().complex_poly_sessions = *value;
   else if (n == "stored_zero_views") options().stored_zero_views = *value;
+  else if (n == "pm_session") options().pm_session = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -231,6 +232,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "thin_slab_complex") return options().thin_slab_complex;
   if (n == "complex_poly_sessions") return options().complex_poly_sessions;
   if (n == "stored_zero_views") return options().stored_zero_views;
+  if (n == "pm_session") return options().pm_session;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -286,6 +288,41 @@ void ntpoly_amd_session_end() { g_test_session.reset(); }
 // returns 1 when the step was taken, 0 when it declined and left every matrix as it was
 int ntpoly_amd_recurrence_step(const int* ih_P, const int* ih_Tkm2, int* ih_Tk, int* ih_R, const double* a, const double* c) {
   return ps_recurrence_step(*get_unpacked(ih_P), *get_unpacked(ih_Tkm2), *get_unpacked(ih_Tk), *get_unpacked(ih_R), *a, *c) ? 1 : 0;
+}
+// PM purification on a slab-form iterate (option pm_session; engine.hpp ps_pm_sigma / ps_pm_update) since start: out[0] = sigma passes
+// fused, out[1] = updates fused, out[2] = stored zeros carried beside the runs (summed over the updates), out[3] = solves that left
+// the fused path
+void ntpoly_amd_pm_session_counts(long long out[4]) {
+  for (int q = 0; q < 4; ++q) out[q] = pm_session_counts()[q];
+}
+// the longest zero list an update of the fused PM loop has left on this rank since start (rows of one panel)
+void ntpoly_amd_pm_session_longest_list(long long* out) { *out = pm_session_counts()[4]; }
+// DIAGNOSTIC surface (one rank, real matrices): one sigma pass and one update of the PM loop's fused path on caller-held operands.
+// X: the iterate's non-zeros; Z: a matrix whose STORED PATTERN is the iterate's zero list (rows that compressed columns would hold
+// as stored zeros; disjoint from X's pattern); X2, X3: what the loop's two products would be.  sc[0], sc[1] = trace and dot(., X)
+// of X - X2 merged at thr; Out = the non-zeros of ScaleMatrix(X u Z, a1); IncrementMatrix(X2, ., a2, thr); IncrementMatrix(X3, ., a3,
+// thr) and Zout = its stored zeros (as a pattern with zero values), both in compressed columns.  Returns 1 when taken, 0 when
+// refused: nothing is written then.  The operands are left as they are either way.
+int ntpoly_amd_pm_fused_step(const int* ih_X, const int* ih_Z, const int* ih_X2, const int* ih_X3, const double* a1, const double* a2,
+                             const double* a3, const double* thr, int* ih_Out, int* ih_Zout, double* sc) {
+  const PSMatrix &X = *get<PSMatrix>(ih_X), &Z = *get<PSMatrix>(ih_Z), &X2 = *get<PSMatrix>(ih_X2), &X3 = *get<PSMatrix>(ih_X3);
+  PSMatrix &Out = *get<PSMatrix>(ih_Out), &Zout = *get<PSMatrix>(ih_Zout);
+  CommScope cs(X.grid);
+  if (world().active() || X.cplx || Z.cplx || X2.cplx || X3.cplx || X.dim != Z.dim || X.dim != X2.dim || X.dim != X3.dim) return 0;
+  DevMat x = X.loc.clone(), x2 = X2.loc.clone(), x3 = X3.loc.clone();
+  if (!slab_enter(x) || !slab_enter(x2) || !slab_enter(x3)) return 0;
+  ZeroList zl, zn;
+  zero_list_from_pattern(Z.loc, zl);
+  DevMat R;
+  double t[2] = {0.0, 0.0};
+  if (!slab_pm_sigma(x, zl, x2, *thr, X.c0, t) || !slab_pm_update(x, zl, x2, x3, *a1, *a2, *a3, *thr, R, zn)) return 0;
+  sc[0] = t[0];
+  sc[1] = t[1];
+  pack(R);
+  for (PSMatrix* m : {&Out, &Zout}) { m->grid = X.grid; m->dim = X.dim; m->cplx = false; m->c0 = X.c0; m->c1 = X.c1; }
+  Out.loc = std::move(R);
+  Zout.loc = zero_list_matrix(zn, X.loc.rows, X.loc.cols);
+  return 1;
 }
 // fused recurrence steps taken since start, by the Chebyshev / Hermite loops and by ntpoly_amd_recurrence_step (each is also
 // counted as the two merges it replaces in ntpoly_amd_slab_algebra_counts; a declined step counts nothing here)

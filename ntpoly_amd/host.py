@@ -1031,6 +1031,31 @@ def recurrence_step_count():
     return int(out.value)
 
 
+def pm_session_counts():
+    """PM purification on a slab-form iterate (option pm_session; csrc/slab_extra.hip) since start: sigma passes fused, updates fused,
+    stored zeros carried beside the runs (summed over the updates), solves that left the fused path"""
+    out = (C.c_longlong * 4)()
+    lib.ntpoly_amd_pm_session_counts(out)
+    return dict(sigma=int(out[0]), updates=int(out[1]), zeros=int(out[2]), left=int(out[3]))
+
+
+def pm_session_longest_list():
+    """the longest zero list an update of the fused PM loop has left on this rank since start"""
+    out = C.c_longlong()
+    lib.ntpoly_amd_pm_session_longest_list(C.byref(out))
+    return int(out.value)
+
+
+def pm_fused_step(X, Z, X2, X3, a1, a2, a3, thr, Out, Zout):
+    """DIAGNOSTIC: one sigma pass and one update of the PM loop's fused path on caller-held real matrices (one rank).  Z's stored
+    pattern is the iterate's zero list.  Returns (trace, dot) of X - X2 merged at thr when taken -- Out then holds the update's
+    non-zeros and Zout its stored zeros, in compressed columns -- or None when refused (nothing written)."""
+    sc = (C.c_double * 2)()
+    lib.ntpoly_amd_pm_fused_step.restype = C.c_int
+    ok = lib.ntpoly_amd_pm_fused_step(X.ih, Z.ih, X2.ih, X3.ih, d(a1), d(a2), d(a3), d(thr), Out.ih, Zout.ih, sc)
+    return (sc[0], sc[1]) if ok else None
+
+
 def last_grouped_stats():
     """grouped LDS-hash path of the last SpGEMM (csrc/spgemm_grouped.hip)"""
     out = (C.c_longlong * 6)()
