@@ -167,6 +167,24 @@ bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double be
 // IncrementMatrix(Tk, R, c, 0), in one pass (slab_extra.hip slab_recurrence_step_c: the same values bit for bit); false:
 // not done and nothing changed -- the caller makes the two ps_increment calls
 bool ps_recurrence_step(const PSMatrix& P, const PSMatrix& Tkm2, PSMatrix& Tk, PSMatrix& R, double a, double c);
+// The polynomial chain of the Taylor square-root step (SquareRootSolversModule.F90:425-479) in one pass over the runs of X and
+// X2 = X X (option isr_chain; slab_extra.hip k_sa_isr_chain), inside an open slab session that takes the operands' kind, both in
+// slab form.  ps_isr_chain5: what ps_increment(X, T, a, 0); ps_copy_axpby(I, X, Temp2, 1, b, 0); ps_increment(T, Temp2, 1, 0);
+// ps_increment_identity(I, T, c) leave in Temp2 and T, with T = X2 on entry and Temp on return (Temp may be X2).
+// ps_isr_chain3: what ps_axpby(I, X, 1, -1/2, 0); ps_increment(X2, X, 0.375, 0) leave in X.  The same bits and patterns.  false:
+// not done and nothing changed -- the caller makes the calls.  Local to a rank (no collective), and silent: a refusal is not
+// a refusal of the session.  Counted in slab_algebra_counts() as the merges replaced (four, two).  Gates (the option off, no open
+// session for the operands' kind, X and X2 both in compressed columns, a labelled slab form) return false before anything is
+// counted: such a step is neither fused nor refused in isr_chain_counts().  "Nothing changed" holds for values, not for the
+// representation: an operand still in compressed columns is turned into slab form where it is before the kernel decides, and stays
+// so -- if X enters and X2 cannot (not run-like), the vocabulary calls that follow repeat the failing conversion, count a session
+// refusal and pack both: the same bits, at the cost of one conversion more on that path.
+bool ps_isr_chain5(const PSMatrix& X, const PSMatrix& X2, double a, double b, double c, PSMatrix& Temp2, PSMatrix& Temp);
+bool ps_isr_chain3(PSMatrix& X, const PSMatrix& X2);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_isr_chain_step): X and X2 are brought into slab form where they are, one chain of the given
+// order runs, the outputs are packed into Out1 (order 5: Temp2, order 3: the new X) and Out2 (order 5: Temp; order 3: untouched)
+bool ps_isr_chain_step(const PSMatrix& X, const PSMatrix& X2, int order, double a, double b, double c, PSMatrix& Out1, PSMatrix& Out2);
+long long* isr_chain_counts();   // since start: [0] order-5 chains fused, [1] order-3 chains fused, [2] chains refused (past the gates: a gated step counts nowhere)
 // solvers.cpp: this loop may take a complex operand like m in slab form (FMA arithmetic, complex tile kernel, complex_sessions)
 bool complex_slab_loop(const PSMatrix& m);
 void ps_slab_leave(PSMatrix& m);   // back to compressed columns (no-op for a matrix that is not in slab form)

@@ -1273,6 +1273,79 @@ bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatr
   return true;
 }
 
+long long* isr_chain_counts() {
+  static long long counts[3] = {0, 0, 0};
+  return counts;
+}
+namespace {
+// the gates of the fused chain: the option, an open session that takes the operands' kind, an operand in slab form (in unfused
+// arithmetic a product whose operands are sparse inside wide extents goes to the general kernels: an X and an X X that both come
+// back in compressed columns are left to the vocabulary, which decides call by call), none of them in labelled slab form (a
+// relabelled band: the kernel walks rows in the caller's order).  A step the gates keep out is neither fused nor counted as refused
+bool isr_chain_on(const PSMatrix& X, const PSMatrix& X2) {
+  return options().isr_chain != 0 && slab_on() && X.cplx == X2.cplx && session_takes(X.cplx) && X.dim == X2.dim && &X != &X2 &&
+         !blk_any({&X, &X2}) && (X.loc.expanded() || X2.loc.expanded()) && !(X.loc.expanded() && X.loc.slab->labelled()) &&
+         !(X2.loc.expanded() && X2.loc.slab->labelled());
+}
+// (an operand still in compressed columns is turned into slab form where it is, as ps_axpby does before a merge)
+bool isr_chain_enter(const PSMatrix& X, const PSMatrix& X2) {
+  const SlabKind& k = slab_kind(X.cplx);
+  return k.enter(mut(X)) && k.enter(mut(X2));
+}
+}  // namespace
+bool ps_isr_chain5(const PSMatrix& X, const PSMatrix& X2, double a, double b, double c, PSMatrix& Temp2, PSMatrix& Temp) {
+  CommScope cs(X.grid);
+  if (!isr_chain_on(X, X2)) return false;
+  DevMat q, p;
+  if (!isr_chain_enter(X, X2) || !slab_isr_chain5(X.loc, X2.loc, a, b, c, X.c0, q, p)) {
+    isr_chain_counts()[2] += 1;
+    return false;
+  }
+  const ProcessGrid* grid = X.grid;
+  const int32_t dim = X.dim, c0 = X.c0, c1 = X.c1;
+  const bool cplx = X.cplx;
+  install(Temp2, grid, dim, cplx, c0, c1, std::move(q));
+  install(Temp, grid, dim, cplx, c0, c1, std::move(p));
+  g_slab_counts[1] += 4;
+  isr_chain_counts()[0] += 1;
+  return true;
+}
+bool ps_isr_chain3(PSMatrix& X, const PSMatrix& X2) {
+  CommScope cs(X.grid);
+  if (!isr_chain_on(X, X2)) return false;
+  DevMat o;
+  if (!isr_chain_enter(X, X2) || !slab_isr_chain3(X.loc, X2.loc, X.c0, o)) {
+    isr_chain_counts()[2] += 1;
+    return false;
+  }
+  X.loc = std::move(o);
+  g_slab_counts[1] += 2;
+  isr_chain_counts()[1] += 1;
+  return true;
+}
+bool ps_isr_chain_step(const PSMatrix& X, const PSMatrix& X2, int order, double a, double b, double c, PSMatrix& Out1, PSMatrix& Out2) {
+  CommScope cs(X.grid);
+  if ((order != 5 && order != 3) || options().isr_chain == 0 || !slab_on() || X.cplx != X2.cplx || !session_takes(X.cplx) || X.dim != X2.dim ||
+      &X == &X2 || &Out1 == &X || &Out1 == &X2 || &Out2 == &X || &Out2 == &X2 || &Out1 == &Out2)
+    return false;
+  unblock({&X, &X2});
+  DevMat q, p;
+  const bool ok = isr_chain_enter(X, X2) && (order == 5 ? slab_isr_chain5(X.loc, X2.loc, a, b, c, X.c0, q, p) : slab_isr_chain3(X.loc, X2.loc, X.c0, q));
+  if (!ok) {
+    isr_chain_counts()[2] += 1;
+    return false;
+  }
+  pack(q);
+  install(Out1, X.grid, X.dim, X.cplx, X.c0, X.c1, std::move(q));
+  if (order == 5) {
+    pack(p);
+    install(Out2, X.grid, X.dim, X.cplx, X.c0, X.c1, std::move(p));
+  }
+  g_slab_counts[1] += order == 5 ? 4 : 2;
+  isr_chain_counts()[order == 5 ? 0 : 1] += 1;
+  return true;
+}
+
 long long* pm_session_counts() {
   static long long counts[5] = {0, 0, 0, 0, 0};
   return counts;

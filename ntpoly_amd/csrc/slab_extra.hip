@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 
@@ -1135,6 +1137,213 @@ DevMat zero_list_matrix(const ZeroList& Z, int32_t rows, int32_t cols) {
   HIP_CHECK(hipMemcpyAsync(R.inner.p, Z.row.p, sizeof(int32_t) * (size_t)Z.count, hipMemcpyDeviceToDevice, stream()));
   HIP_CHECK(hipMemsetAsync(R.val.p, 0, sizeof(double) * (size_t)Z.count, stream()));
   return R;
+}
+
+// ------------------------------------------------------------------ the polynomial chain of the square-root step
+// NewtonSchultzISRTaylor (SquareRootSolversModule.F90:425-479) builds, between the product X2 = X X and the next product, with
+// IncrementMatrix / CopyMatrix / ScaleMatrix at threshold 0 (d = the identity's entry: 1 on the diagonal):
+//   order 5:  t = x2 + a x,   u = x + b d,   q = t + u (Temp2),   p = t + c d (Temp)
+//   order 3:  y = d + (-1/2) x,   o = 0.375 x2 + y (the new X)
+// One pass per column reads X and X2 once and writes the outputs.  Every merge is AddSparseVectors at threshold 0 on two
+// operands: both present -> the sum of the two scaled values, each rounded on its own, an exact zero dropped; one present ->
+// its scaled value; the result of a merge enters the next one as present iff it was kept.  A scaled value that is exactly zero
+// for an entry that is not (an underflow) would be a stored zero of an unfiltered tail or a dropped one-sided entry, depending
+// on the other operand's extent: stat |= 1 and the host refuses.  All constants are real: complex operands part by part.
+namespace {
+__device__ inline double isr_one(double) { return 1.0; }
+__device__ inline double2 isr_one(double2) { return make_double2(1.0, 0.0); }
+// sa a + sb b of one row; ha / hb: present.  *present: the result is an entry (returned as zero otherwise)
+template <typename T>
+__device__ inline T isr_merge(double sa, T a, bool ha, double sb, T b, bool hb, bool* present, int* underflow) {
+  const T wa = Sc<T>::scale(sa, a), wb = Sc<T>::scale(sb, b);
+  *underflow |= ((ha && Sc<T>::is_zero(wa)) || (hb && Sc<T>::is_zero(wb))) ? 1 : 0;
+  const T o = ha ? (hb ? Sc<T>::add(wa, wb) : wa) : wb;
+  *present = (ha || hb) && Sc<T>::mag(o) > 0.0;
+  return *present ? o : Sc<T>::zero();
+}
+struct IsrOut {   // one output: values into the slot at base[j], the kept extent and count per column
+  void* val;
+  int32_t* first;
+  int32_t* last;
+  int32_t* count;
+  int64_t* off;
+};
+constexpr int ISR_KC = 4;   // chunks of 64 rows whose loads are all requested before the first of them is used
+// One wave per column, lanes on consecutive rows of the aligned union [a0, a1) of the two runs and the diagonal row.
+// ORDER 5: o1 = Temp2 (q), o2 = Temp (p); ORDER 3: o1 = the new X, s1 = -1/2, s2 = 0.375, o2 unused.
+// stat |= 1: an underflow (see above); |= 2: a union extent that the operands' slots do not bound (the two runs far apart, or
+// diagonals so far from their runs that the output buffer ends) -- nothing is written for that column.
+template <typename T, int ORDER>
+__global__ __launch_bounds__(256) void k_sa_isr_chain(int n, const int32_t* __restrict__ fa, const int32_t* __restrict__ la,
+                                                      const int64_t* __restrict__ offa, const T* __restrict__ va,
+                                                      const int32_t* __restrict__ fb, const int32_t* __restrict__ lb,
+                                                      const int64_t* __restrict__ offb, const T* __restrict__ vb, int col_offset, double s1,
+                                                      double s2, double s3, int al, const int64_t* __restrict__ base, IsrOut o1, IsrOut o2,
+                                                      int64_t bound, unsigned long long* __restrict__ stat) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id();
+  const int fA = fa[j], lA = la[j], fB = fb[j], lB = lb[j], dg = j + col_offset;
+  const bool anyA = lA >= fA, anyB = lB >= fB;
+  int f = dg, l = dg;   // (the identity's entry is always there)
+  if (anyA) { f = min(f, fA); l = max(l, lA); }
+  if (anyB) { f = min(f, fB); l = max(l, lB); }
+  const int a0 = f / al * al, a1 = (l / al + 1) * al;
+  const int64_t slot = base[j];
+  // (the two runs far apart: their union is not bounded by the two slots and two pads -- refused per column, as k_pm_update does.
+  // The diagonal row may lie anywhere -- a lone entry of a converged X beside an empty X2 --: what it adds is bounded over all
+  // columns by the output buffer, as in k_sa_axpby and k_sa_trs4)
+  bool apart = false;
+  if (anyA && anyB) {
+    const int own = ((lA / al + 1) * al - fA / al * al) + ((lB / al + 1) * al - fB / al * al);
+    apart = (max(lA, lB) / al + 1) * al - min(fA, fB) / al * al > own + 2 * al;
+  }
+  if (apart || slot + (int64_t)(a1 - a0) > bound) {
+    if (lane == 0) {
+      o1.first[j] = INT_MAX; o1.last[j] = -1; o1.count[j] = 0; o1.off[j] = slot;
+      if (ORDER == 5) { o2.first[j] = INT_MAX; o2.last[j] = -1; o2.count[j] = 0; o2.off[j] = slot; }
+      atomicOr(stat, 2ull);
+    }
+    return;
+  }
+  const T* __restrict__ pa = anyA ? va + (offa[j] - fA) : va;
+  const T* __restrict__ pb = anyB ? vb + (offb[j] - fB) : vb;
+  T* __restrict__ d1 = static_cast<T*>(o1.val) + (slot - a0);
+  T* __restrict__ d2 = ORDER == 5 ? static_cast<T*>(o2.val) + (slot - a0) : nullptr;
+  const T one = isr_one(T{});
+  int uf = 0, c1 = 0, f1 = INT_MAX, l1 = -1, c2 = 0, f2 = INT_MAX, l2 = -1;
+  for (int rb = a0; rb < a1; rb += ISR_KC * WAVE) {
+    T vx[ISR_KC], v2[ISR_KC];
+#pragma unroll
+    for (int k = 0; k < ISR_KC; ++k) {
+      const int r = rb + k * WAVE + lane;
+      vx[k] = (anyA && r >= fA && r <= lA) ? pa[r] : Sc<T>::zero();
+      v2[k] = (anyB && r >= fB && r <= lB) ? pb[r] : Sc<T>::zero();
+    }
+#pragma unroll
+    for (int k = 0; k < ISR_KC; ++k) {
+      const int r = rb + k * WAVE + lane;
+      if (r >= a1) continue;
+      const T x = vx[k], x2 = v2[k];
+      const bool hx = !Sc<T>::is_zero(x), h2 = !Sc<T>::is_zero(x2), hd = r == dg;
+      if (ORDER == 5) {
+        bool ht, hu, hq, hp;
+        const T t = isr_merge<T>(s1, x, hx, 1.0, x2, h2, &ht, &uf);     // IncrementMatrix(X, Temp, a)
+        const T u = isr_merge<T>(1.0, x, hx, s2, one, hd, &hu, &uf);    // Temp2 = b I, then IncrementMatrix(X, Temp2)
+        const T q = isr_merge<T>(1.0, t, ht, 1.0, u, hu, &hq, &uf);     // IncrementMatrix(Temp, Temp2)
+        const T p = isr_merge<T>(s3, one, hd, 1.0, t, ht, &hp, &uf);    // IncrementMatrix(Identity, Temp, c)
+        d1[r] = q;
+        d2[r] = p;
+        c1 += hq ? 1 : 0; f1 = min(f1, hq ? r : INT_MAX); l1 = max(l1, hq ? r : -1);
+        c2 += hp ? 1 : 0; f2 = min(f2, hp ? r : INT_MAX); l2 = max(l2, hp ? r : -1);
+      } else {
+        bool hy, ho;
+        const T y = isr_merge<T>(1.0, one, hd, s1, x, hx, &hy, &uf);    // ScaleMatrix(X, -1/2); IncrementMatrix(Identity, X)
+        const T o = isr_merge<T>(s2, x2, h2, 1.0, y, hy, &ho, &uf);     // IncrementMatrix(Temp, X, 0.375)
+        d1[r] = o;
+        c1 += ho ? 1 : 0; f1 = min(f1, ho ? r : INT_MAX); l1 = max(l1, ho ? r : -1);
+      }
+    }
+  }
+  c1 = (int)wave_sum_i64(c1);
+  f1 = wave_min_i32(f1);
+  l1 = wave_max_i32(l1);
+  if (ORDER == 5) {
+    c2 = (int)wave_sum_i64(c2);
+    f2 = wave_min_i32(f2);
+    l2 = wave_max_i32(l2);
+  }
+  if (__ballot(uf != 0) && lane == 0) atomicOr(stat, 1ull);
+  if (lane == 0) {
+    o1.first[j] = f1; o1.last[j] = l1; o1.count[j] = c1;
+    o1.off[j] = slot + (c1 ? f1 - a0 : 0);
+    if (ORDER == 5) {
+      o2.first[j] = f2; o2.last[j] = l2; o2.count[j] = c2;
+      o2.off[j] = slot + (c2 ? f2 - a0 : 0);
+    }
+  }
+}
+// trs4_operands, complex operands too (both of one kind)
+bool isr_operands(const DevMat& X, const DevMat& X2) {
+  auto ok = [](const DevMat& M) {
+    return M.expanded() && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1 &&
+           (!M.cplx || M.slab->row_pad % 16 == 0);
+  };
+  const bool take = &X != &X2 && ok(X) && ok(X2) && X.cplx == X2.cplx && X.cols == X2.cols && X.rows == X2.rows && X.slab->row_pad == X2.slab->row_pad;
+  if (!take && std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+    std::fprintf(stderr, "[isr chain] operands not taken: slab form %d %d, views %d %d, zero-free %d %d, alignment %d %d\n", (int)X.expanded(),
+                 (int)X2.expanded(), X.expanded() && X.slab->origin ? 1 : 0, X2.expanded() && X2.slab->origin ? 1 : 0, X.zero_free, X2.zero_free,
+                 X.expanded() ? X.slab->row_pad : -1, X2.expanded() ? X2.slab->row_pad : -1);
+  return take;
+}
+// the chain on X and X2: Out1 (and Out2 in order 5) as fresh slab-form matrices; false: refused, nothing written to them
+template <typename T, int ORDER>
+bool isr_chain_run(const DevMat& X, const DevMat& X2, double s1, double s2, double s3, int32_t col_offset, DevMat& Out1, DevMat* Out2) {
+  const SlabForm &fa = *X.slab, &fb = *X2.slab;
+  const int n = X.cols, al = std::max(1, fa.row_pad), outs = ORDER == 5 ? 2 : 1;
+  const size_t w = Sc<T>::cplx ? 2 : 1;
+  std::unique_ptr<SlabForm> fo[2];
+  IsrOut o[2] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};
+  // (the operands' slots, and per column the diagonal's slot and the pads of a union -- with room for diagonals away from their runs)
+  const int64_t bound = fa.slots + fb.slots + 4LL * al * n;
+  for (int q = 0; q < outs; ++q) {
+    fo[q].reset(new SlabForm());
+    fo[q]->first.alloc((size_t)n); fo[q]->last.alloc((size_t)n); fo[q]->count.alloc((size_t)n); fo[q]->off.alloc((size_t)n + 1);
+    fo[q]->val.alloc(((size_t)bound + kIndexSlack) * w);
+    o[q] = IsrOut{fo[q]->val.p, fo[q]->first.p, fo[q]->last.p, fo[q]->count.p, fo[q]->off.p};
+  }
+  DevBuf<int32_t> span((size_t)n);
+  DevBuf<int64_t> base((size_t)n + 1);
+  DevBuf<unsigned long long> stat(1), tot(2);
+  stat.zero();
+  tot.zero();
+  hipLaunchKernelGGL(k_sa_trs4_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fb.first.p, fb.last.p, n, col_offset,
+                     al, span.p);
+  scan_i32_async(span.p, base.p, (int64_t)n);
+  hipLaunchKernelGGL((k_sa_isr_chain<T, ORDER>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
+                     reinterpret_cast<const T*>(fa.val.p), fb.first.p, fb.last.p, fb.off.p, reinterpret_cast<const T*>(fb.val.p), col_offset, s1,
+                     s2, s3, al, base.p, o[0], o[1], bound, stat.p);
+  const dim3 sum_grid(std::max(1, std::min(256, cdiv(n, 1024))));
+  for (int q = 0; q < outs; ++q) hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), fo[q]->count.p, n, tot.p + q);
+  int64_t nnz[2] = {0, 0}, slots = 0;
+  unsigned long long hs = 0;
+  {
+    ScalarFetch ft;
+    ft.add(tot.p, 2, nnz);
+    ft.add(base.p + n, 1, &slots);
+    ft.add(stat.p, 1, &hs);
+    ft.run();
+  }
+  if (hs != 0) {
+    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+      std::fprintf(stderr, "[isr chain] refused:%s%s\n", (hs & 1ull) ? " a scaled entry underflows to zero" : "", (hs & 2ull) ? " runs far apart" : "");
+    return false;
+  }
+  DevMat R[2];
+  for (int q = 0; q < outs; ++q) {
+    fo[q]->row_pad = al;
+    fo[q]->slots = slots;
+    R[q].rows = X.rows; R[q].cols = n; R[q].cplx = Sc<T>::cplx; R[q].nnz = nnz[q]; R[q].zero_free = 1;
+    R[q].slab = std::move(fo[q]);
+  }
+  bump_matrix_value_epoch();   // (of the calls it replaces, two are merges in place: slab_axpby counts them so)
+  bump_matrix_value_epoch();
+  Out1 = std::move(R[0]);
+  if (ORDER == 5) *Out2 = std::move(R[1]);
+  return true;
+}
+}  // namespace
+
+bool slab_isr_chain5(const DevMat& X, const DevMat& X2, double a, double b, double c, int32_t col_offset, DevMat& Temp2, DevMat& Temp) {
+  if (!isr_operands(X, X2) || &Temp2 == &Temp || &Temp2 == &X) return false;
+  if (X.cplx) return isr_chain_run<double2, 5>(X, X2, a, b, c, col_offset, Temp2, &Temp);
+  return isr_chain_run<double, 5>(X, X2, a, b, c, col_offset, Temp2, &Temp);
+}
+
+bool slab_isr_chain3(const DevMat& X, const DevMat& X2, int32_t col_offset, DevMat& Out) {
+  if (!isr_operands(X, X2)) return false;
+  if (X.cplx) return isr_chain_run<double2, 3>(X, X2, -0.5, 0.375, 0.0, col_offset, Out, nullptr);
+  return isr_chain_run<double, 3>(X, X2, -0.5, 0.375, 0.0, col_offset, Out, nullptr);
 }
 
 long long slab_product_count(const DevMat& A, const DevMat& B) {

@@ -911,8 +911,10 @@ void isr_taylor(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters&
     const double norm_value = ps_norm(X);
     if (order == 3) {                                              // :425-433
       ps_multiply(X, X, Temp, 1.0, 0.0, p.threshold);
-      ps_axpby(Identity, X, 1.0, -0.5, 0.0);                        // ScaleMatrix(X, -1/2); IncrementMatrix(I, X)
-      ps_increment(Temp, X, 0.375, 0.0);
+      if (!ps_isr_chain3(X, Temp)) {                                // (option isr_chain: the two merges in one pass over X and X X)
+        ps_axpby(Identity, X, 1.0, -0.5, 0.0);                      // ScaleMatrix(X, -1/2); IncrementMatrix(I, X)
+        ps_increment(Temp, X, 0.375, 0.0);
+      }
     } else {                                                       // :434-479 (Knuth's 2-multiply quartic)
       const double aa = -40.0 / 35.0, bb = 48.0 / 35.0, cc = -64.0 / 35.0, dd = 128.0 / 35.0;
       const double a = (aa - 1.0) / 2.0;
@@ -920,10 +922,12 @@ void isr_taylor(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters&
       const double c = bb - b - a * (a + 1.0);
       const double d = dd - b * c;
       ps_multiply(X, X, Temp, 1.0, 0.0, p.threshold);
-      ps_increment(X, Temp, a, 0.0);
-      ps_copy_axpby(Identity, X, Temp2, 1.0, b, 0.0);               // CopyMatrix(Identity, Temp2); ScaleMatrix(Temp2, b); IncrementMatrix(X, Temp2)
-      ps_increment(Temp, Temp2, 1.0, 0.0);
-      ps_increment_identity(Identity, Temp, c);
+      if (!ps_isr_chain5(X, Temp, a, b, c, Temp2, Temp)) {          // (option isr_chain: the four calls in one pass over X and X X)
+        ps_increment(X, Temp, a, 0.0);
+        ps_copy_axpby(Identity, X, Temp2, 1.0, b, 0.0);             // CopyMatrix(Identity, Temp2); ScaleMatrix(Temp2, b); IncrementMatrix(X, Temp2)
+        ps_increment(Temp, Temp2, 1.0, 0.0);
+        ps_increment_identity(Identity, Temp, c);
+      }
       ps_multiply(Temp2, Temp, X, 1.0, 0.0, p.threshold);
       ps_increment_identity(Identity, X, d);
       ps_scale(X, 35.0 / 128.0);

@@ -196,6 +196,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "complex_poly_sessions") options().complex_poly_sessions = *value;
   else if (n == "stored_zero_views") options().stored_zero_views = *value;
   else if (n == "pm_session") options().pm_session = *value;
+  else if (n == "isr_chain") options().isr_chain = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -233,6 +234,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "complex_poly_sessions") return options().complex_poly_sessions;
   if (n == "stored_zero_views") return options().stored_zero_views;
   if (n == "pm_session") return options().pm_session;
+  if (n == "isr_chain") return options().isr_chain;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -288,6 +290,22 @@ void ntpoly_amd_session_end() { g_test_session.reset(); }
 // returns 1 when the step was taken, 0 when it declined and left every matrix as it was
 int ntpoly_amd_recurrence_step(const int* ih_P, const int* ih_Tkm2, int* ih_Tk, int* ih_R, const double* a, const double* c) {
   return ps_recurrence_step(*get_unpacked(ih_P), *get_unpacked(ih_Tkm2), *get_unpacked(ih_Tk), *get_unpacked(ih_R), *a, *c) ? 1 : 0;
+}
+// The polynomial chain of the Taylor square-root step in one pass (option isr_chain; engine.hpp ps_isr_chain5 / ps_isr_chain3) since
+// start: out[0] = order-5 chains fused, out[1] = order-3 chains fused, out[2] = chains refused (the vocabulary calls ran instead).
+// A step that never reaches the kernel's decision -- the option off, no session for the operands' kind, X and X X both in compressed
+// columns (unfused arithmetic near convergence), a labelled slab form -- is neither fused nor counted as refused
+void ntpoly_amd_isr_chain_counts(long long out[3]) {
+  for (int q = 0; q < 3; ++q) out[q] = isr_chain_counts()[q];
+}
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: one fused chain on caller-held matrices X and X2 (what
+// the loop's product X X would be), real or -- in a session with complex_ok -- complex.  The two operands are brought into slab
+// form, the chain of *order (5 or 3) runs, the outputs are packed into the result handles: order 5: Out1 = (X2 + a X) + (X + b I)
+// and Out2 = (X2 + a X) + c I; order 3: Out1 = 0.375 X2 + (I - X / 2), Out2 untouched (a, b, c unused).  Returns 1 when taken, 0 when
+// refused: every handle is then as it was.
+int ntpoly_amd_isr_chain_step(const int* ih_X, const int* ih_X2, const int* order, const double* a, const double* b, const double* c,
+                              int* ih_Out1, int* ih_Out2) {
+  return ps_isr_chain_step(*get_unpacked(ih_X), *get_unpacked(ih_X2), *order, *a, *b, *c, *get_unpacked(ih_Out1), *get_unpacked(ih_Out2)) ? 1 : 0;
 }
 // PM purification on a slab-form iterate (option pm_session; engine.hpp ps_pm_sigma / ps_pm_update) since start: out[0] = sigma passes
 // fused, out[1] = updates fused, out[2] = stored zeros carried beside the runs (summed over the updates), out[3] = solves that left

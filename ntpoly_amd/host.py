@@ -1056,6 +1056,25 @@ def pm_fused_step(X, Z, X2, X3, a1, a2, a3, thr, Out, Zout):
     return (sc[0], sc[1]) if ok else None
 
 
+def isr_chain_counts():
+    """the polynomial chain of the Taylor square-root step in one pass (option isr_chain; csrc/slab_extra.hip k_sa_isr_chain) since
+    start: order-5 chains fused, order-3 chains fused, chains refused (the vocabulary calls ran instead); slab_algebra_counts()
+    counts a fused chain as the four / two merges it replaces.  A step kept out by a gate (the option off, no session for the
+    operands' kind, X and X X both in compressed columns, a labelled slab form) is neither fused nor counted as refused"""
+    out = (C.c_longlong * 3)()
+    lib.ntpoly_amd_isr_chain_counts(out)
+    return dict(order5=int(out[0]), order3=int(out[1]), refused=int(out[2]))
+
+
+def isr_chain_step(X, X2, order, a, b, c, Out1, Out2):
+    """DIAGNOSTIC, inside `with solver_session():` -- one fused chain of the square-root step on caller-held matrices (X2: what the
+    product X X would be).  Order 5: Out1 = (X2 + a X) + (X + b I), Out2 = (X2 + a X) + c I; order 3: Out1 = 0.375 X2 + (I - X / 2),
+    Out2 untouched.  True: taken; None: refused, every matrix as it was."""
+    lib.ntpoly_amd_isr_chain_step.restype = C.c_int
+    ok = lib.ntpoly_amd_isr_chain_step(X.ih, X2.ih, C.byref(C.c_int(int(order))), d(a), d(b), d(c), Out1.ih, Out2.ih)
+    return True if ok else None
+
+
 def last_grouped_stats():
     """grouped LDS-hash path of the last SpGEMM (csrc/spgemm_grouped.hip)"""
     out = (C.c_longlong * 6)()
