@@ -139,6 +139,13 @@ struct SlabForm {
   DevBuf<int64_t> off;        // cols + 1
   DevBuf<int64_t> tile_off;   // blocks + 1
   DevBuf<double> val, tiles;
+  // optional, forms with row_pad == 32 only (the one tile height the test is built for; its producers and its reader hard-code
+  // 32): amax[s] >= |v| for every value v of the 32 consecutive slots val[32 s .. 32 s + 31] (zeros of padding and holes
+  // count as 0; val.n / 32 + 1 entries) -- a slot holds row r at a position = r (mod 32), so segment s of a column
+  // is the rows of ONE tile of the MFMA tile kernel, which skips tiles whose products provably stay below the threshold
+  // (spgemm_tile.hip, option tile_skip).  Written by the step that produced the form (kernels.hip slab_step) or by one pass
+  // over val (slab_segmax); absent = unknown, nothing is skipped.  Whatever writes into val IN PLACE must release it.
+  DevBuf<double> amax;
   int64_t slots = 0;          // doubles addressable in val / tiles
   bool no_tile2 = false;      // a step on this iterate (or its predecessor) did not fit the two-block geometry of spgemm_tile2.hip: k_spgemm_tile from now on
   // the plan of the NEXT step on this iterate (kernels.hip slab_step, option plan_ahead): blocks' windows and k ranges

@@ -3018,6 +3018,10 @@ long long* tile2_counts() {
   static long long c[2] = {0, 0};
   return c;
 }
+long long* tile_skip_counts() {
+  static long long c[2] = {0, 0};
+  return c;
+}
 
 void flush_spgemm_timers() {
   auto& pend = pending_timings();
@@ -4377,6 +4381,28 @@ void launch_slab_plan(SlabPlan& P, int n, const int32_t* first, const int32_t* l
 }
 }  // namespace
 
+namespace {
+// SlabForm::amax of a form that has none: one pass over its values, 16 lanes x 2 values per segment of 32 slots
+__global__ __launch_bounds__(256) void k_slab_segmax(const double* __restrict__ val, int64_t n, double* __restrict__ amax, int64_t nseg) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // values 2 i, 2 i + 1 (whole waves: nseg * 16 is padded to 64)
+  double mx = 0.0;
+  if (2 * i + 1 < n) {
+    const double2 v = reinterpret_cast<const double2*>(val)[i];
+    mx = fmax(fabs(v.x), fabs(v.y));
+  } else if (2 * i < n) mx = fabs(val[2 * i]);
+  for (int o = 8; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, WAVE));
+  if ((threadIdx.x & 15) == 0 && (i >> 4) < nseg) amax[i >> 4] = mx;
+}
+}  // namespace
+
+// SlabForm::amax from the values as they stand (a form that did not come out of slab_step: once per solve)
+static void slab_segmax(SlabForm& f) {
+  const int64_t nseg = (int64_t)f.val.n / 32 + 1;
+  f.amax.alloc((size_t)nseg);
+  const int64_t threads = (nseg * 16 + 255) / 256 * 256;
+  hipLaunchKernelGGL(k_slab_segmax, dim3((unsigned)(threads / 256)), dim3(256), 0, stream(), f.val.p, (int64_t)f.val.n, f.amax.p, nseg);
+}
+
 bool slab_step(DevMat& X, SlabFusion& fu, double threshold, bool dense_rule, const SlabHalo* halo) {
   fu.done = false;
   if (!X.expanded() || X.cplx || (!halo && X.rows != X.cols) || !fu.D || fu.D->cplx || fu.D->loose() || fu.D->expanded() ||
@@ -4471,6 +4497,11 @@ bool slab_step(DevMat& X, SlabFusion& fu, double threshold, bool dense_rule, con
   // loop and the panel steps take their multiplier rows from tiles in memory and keep them)
   const bool runs_only = tile && !halo && options().tile_runs_only != 0;
   DevBuf<double> oval(oslots), otiles(runs_only ? 0 : oslots);
+  // (tile skip, spgemm_tile.hip: the operand's segment maxima -- left by the step that produced it, or made here once per solve
+  // -- and the result's, written by the kernel; tiles of 32 rows that are the segments of the slots only)
+  const bool want_skip = tile && !halo && options().tile_skip != 0 && trows == 2 && in.row_pad == 32 && plan_align == 32 && !in.labelled();
+  DevBuf<double> oamax;
+  bool skip_ran = false;
   SlabFuseArgs fz;
   fz.am = fu.am; fz.bm = fu.bm; fz.thr_m = fu.threshold;
   fz.xexp = in.val.p; fz.xoff = in.off.p; fz.xmin = in.first.p; fz.xmax = in.last.p;
@@ -4565,7 +4596,17 @@ bool slab_step(DevMat& X, SlabFusion& fu, double threshold, bool dense_rule, con
     // geometry first where it can apply: one rank, runs only, two rows per lane; a pair that does not fit after all leaves a
     // mark that comes back with the totals -- the step is then repeated on k_spgemm_tile
     if (!halo && options().tile2 != 0 && !in.no_tile2) used_tile2 = launch_spgemm_tile2(tl, reinterpret_cast<int*>(fz_flag) + 2);
-    if (!used_tile2) launch_spgemm_tile(tl);
+    if (!used_tile2) {
+      if (want_skip) {   // (the maxima are made only where the launch takes them: not with 64-bit addressing or five / six waves)
+        tl.amax_bytes = ((size_t)in.val.n / 32 + 1) * sizeof(double);
+        if (spgemm_tile_skips(tl)) {
+          if (!in.amax.p) slab_segmax(*X.slab);
+          oamax.alloc(oslots / 32 + 1);
+          tl.amax = in.amax.p; tl.amax_bytes = in.amax.n * sizeof(double); tl.oamax = oamax.p;
+        }
+      }
+      skip_ran = launch_spgemm_tile(tl);
+    }
   } else if (rowoff) {
     if (max_w > 6 * SLAB_SL * WAVE) by_mode(std::integral_constant<int, 8>{}, std::integral_constant<int, 9>{});
     else if (max_w > SLAB_NW * SLAB_SL * WAVE) by_mode(std::integral_constant<int, 6>{}, std::integral_constant<int, 9>{});
@@ -4610,6 +4651,7 @@ bool slab_step(DevMat& X, SlabFusion& fu, double threshold, bool dense_rule, con
   R.slab->off = tile ? std::move(tile_ooff) : std::move(tmpoff);
   if (tile) R.slab->tile_off = std::move(tile_otoff);   // (the slab loop's result takes the plan's tile offsets below, once the step has succeeded)
   R.slab->val = std::move(oval);
+  if (skip_ran) R.slab->amax = std::move(oamax);
   if (runs_only) { R.slab->tile_off.release(); } else R.slab->tiles = std::move(otiles);
   R.slab->slots = tmp_total;
   {
@@ -4633,8 +4675,9 @@ bool slab_step(DevMat& X, SlabFusion& fu, double threshold, bool dense_rule, con
     next->max_kn = (int)next_hs[1];
   }
   if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
-    std::fprintf(stderr, "[slab_step] mode %d slots %lld w %llu kn %llu in-slots %lld nnz-in %lld plan %s\n", fu.mode, (long long)tmp_total,
-                 hst[0], hst[1], (long long)in.slots, (long long)X.nnz, plan == &own_plan ? "made here" : "left by the step before");
+    std::fprintf(stderr, "[slab_step] mode %d slots %lld w %llu kn %llu in-slots %lld nnz-in %lld plan %s; tile skip %s, tiles tested %lld skipped %lld\n", fu.mode, (long long)tmp_total,
+                 hst[0], hst[1], (long long)in.slots, (long long)X.nnz, plan == &own_plan ? "made here" : "left by the step before",
+                 skip_ran ? "on" : want_skip ? "wanted, not in this instantiation" : "off", (long long)((uint64_t)flagv[0] >> 32), (long long)((uint64_t)flagv[1] >> 32));
   if (timing) {
     if (pending_timings().size() >= 4096) flush_spgemm_timers();
     pending_timings().push_back(TimedCall{{t_all.a, t_all.b, t_num.a, t_num.b}});
@@ -4645,6 +4688,10 @@ bool slab_step(DevMat& X, SlabFusion& fu, double threshold, bool dense_rule, con
     return slab_step(X, fu, threshold, dense_rule, halo);
   }
   if (used_tile2) tile2_counts()[0] += 1;
+  if (skip_ran) {   // (tiles tested / skipped: the upper words of the two flags)
+    tile_skip_counts()[0] += (long long)(uint32_t)((uint64_t)flagv[0] >> 32);
+    tile_skip_counts()[1] += (long long)(uint32_t)((uint64_t)flagv[1] >> 32);
+  }
   if ((int32_t)flagv[0] != 0) {   // (SlabFuseArgs) X is untouched: the caller repeats the step on the unfused path
     fu.refused += 1;
     fusion_counts()[2] += 1;
@@ -6430,6 +6477,7 @@ bool slab_scale(DevMat& A, double c) {
   f.tiles.release();       // (the multiplier tiles are rebuilt from the runs when the matrix is next a right operand)
   f.tile_off.release();
   f.next_plan.reset();
+  f.amax.release();        // (SlabForm::amax: the values changed in place)
   return true;
 }
 

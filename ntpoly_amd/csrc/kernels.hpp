@@ -72,6 +72,10 @@ struct EngineOptions {
                                // 16 x 16 tiles, two FMA chains per part of an entry -- the tolerance mode of complex_tile); the same rule as
                                // real operands (block_path).  0: never (the grouped LDS-hash kernel)
   int tile2 = 0;               // run-like real operands in FMA arithmetic: the two-block chunk-streaming geometry of the MFMA kernel (spgemm_tile2.hip) (1) where it fits -- slower than k_spgemm_tile as measured in round 5 (profiles/README.md 83): 0 by default
+  int tile_skip = 1;           // TRS2 steps on the tile kernel (one rank, tiles of 32 rows, 32-bit offsets): iterates carry the largest modulus of
+                               // every 32 slots (SlabForm::amax) and the kernel skips, before it loads anything for them, the tiles whose products
+                               // are bounded at or below the threshold by them -- exact: such a tile stores nothing (spgemm_tile.hip, DESIGN.md
+                               // section 4); 0: no test, amax neither read nor written
   int tile_runs_only = 1;      // TRS2 steps on the tile kernel (one rank): the result is written as runs only and the next step builds its
                                // multiplier tiles from them (1.5 GB -> 1.0 GB written per launch at the headline size, no tile read);
                                // 0: runs + multiplier tiles as the unfused loop needs them
@@ -369,6 +373,7 @@ long long* fusion_counts();
 long long* complex_fusion_counts();
 // [0] multiplies done in the two-block geometry (spgemm_tile2.hip), [1] launches of it that did not fit and were repeated on k_spgemm_tile
 long long* tile2_counts();
+long long* tile_skip_counts();   // [0] tiles the MFMA tile kernel tested against the operand's segment maxima, [1] tiles it skipped (option tile_skip), since the last reset_spgemm_accum
 long long& band_searches();   // searches for a bandwidth-reducing order since start (one per sparsity PATTERN: relabel_enter)
 
 // B <- alpha*A + B (AddSparseVectors semantics), same shape and scalar type.

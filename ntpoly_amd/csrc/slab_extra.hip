@@ -104,6 +104,7 @@ bool slab_add_diagonal(DevMat& B, double alpha, int32_t col_offset) {
   B.nnz += (long long)h[1];
   f.tiles.release();      // (the multiplier tiles held the old diagonal; the next step's plan depends on the extents only)
   f.tile_off.release();
+  f.amax.release();       // (SlabForm::amax: the diagonal changed in place)
   return true;
 }
 

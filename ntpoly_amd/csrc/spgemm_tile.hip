@@ -131,6 +131,11 @@ struct TileArgs {
   // TRS2 step), the expanded D operand in [dbase, dbase + dbytes) -- the epilogue's reads go through buffer resources too
   const void* dbase;
   uint32_t dbytes;
+  // tile skip (EPI 1 / 2, R = 2, OFF32, not label-aware; all three nullptr / 0 otherwise): SlabForm::amax of the operand behind
+  // abase -- one double per 32 slots: an upper bound of their moduli -- and of the result (next to out_val)
+  const double* amax;
+  uint32_t amax_bytes;
+  double* oamax;
   int ablate;           // experiment build (-DNTP_ABLATIONS) only
 #ifdef NTP_TILE_STAMPS
   long long* stamps;    // diagnostic build: [block][wave][64] s_memtime stamps
@@ -624,6 +629,22 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
   const int mid = (T - 1) >> 1;
 
   [[maybe_unused]] int sidx = 4;
+  // (tile skip: see the test in the loop.  The result's segment maxima are written wherever the test is on)
+  constexpr bool SKIPK = EPI != 0 && R == 2 && OFF32 && !LAB && (TILE_NW == 4 || TILE_NW == 8);
+  [[maybe_unused]] const bool skip_on = SKIPK && a.amax != nullptr && a.oamax != nullptr;
+  // the maximum modulus of the 16 R values of this lane's column that the tile is about to store (all lanes of the wave)
+  [[maybe_unused]] auto seg_max = [&](const typename RowVec<R>::type (&x)[4]) {
+    double mx = 0.0;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+#pragma unroll
+      for (int m = 0; m < R; ++m) mx = fmax(mx, fabs(rv_get<R>(x[v], m)));
+    }
+    mx = fmax(mx, __shfl_xor(mx, 16, WAVE));
+    return fmax(mx, __shfl_xor(mx, 32, WAVE));
+  };
+  // (the segment of row r of this lane's column: its slot / 32 -- windows and slots are multiples of 32 rows)
+  [[maybe_unused]] auto seg_of = [&](int r) { return ((int64_t)(orun - a.out_val) + r) >> 5; };
 #ifdef NTP_TILE_STATIC
   for (int ti = 0;; ++ti) {   // (snake order over the waves: every wave gets tiles from both ends of each round)
     const int ts = ti * TILE_NW + ((ti & 1) ? TILE_NW - 1 - wave : wave);
@@ -650,6 +671,46 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
       if (m) {
         if (g0 == INT_MAX) g0 = c + (int)__builtin_ctzll(m);
         g1 = c + 63 - (int)__builtin_clzll(m);
+      }
+    }
+    // Tile skip: about half of a window's tiles hold nothing but products beyond the band that survives the threshold.  Most of
+    // them are recognised HERE, before a load is issued for them, from the segment maxima of the operand (SlabForm::amax):
+    // every entry of the tile is bounded by  sum over k of  max |A(tile rows, k)| * max |B(k, block columns)|, and the value
+    // of its FMA chain of n terms by that sum times (1 + u)^n.  The sum below is computed with at most 2 n + 6 roundings,
+    // n <= 2048: both corrections stay below 2^-40, the factor 1 + 2^-30 covers them.  A NaN bound (Inf * 0, an unknown
+    // segment) fails the comparison: no skip.  NaN operands are dropped from the maxima -- a product they enter is NaN and
+    // never passes |v| > threshold.  A skipped tile is the `live == 0` tile of the epilogue below, nothing else.
+    // Candidates (wave-uniform, a heuristic that decides cost only): EPI 1: at most half of the k groups reach the tile;
+    // EPI 2: no column of the block has a row of X in the tile -- which a skip NEEDS there: an entry of X keeps a tile alive
+    if constexpr (SKIPK) {
+      if (skip_on && g1 >= g0) {
+        bool cand;
+        if constexpr (EPI == 2) cand = __ballot(xf <= r0 + TROWS - 1 && xlrow >= r0) == 0ull;
+        else cand = 2 * (g1 - g0 + 1) <= KG;
+        if (cand) {
+          const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(a.amax), 0, a.amax_bytes, 0x00020000);
+          double bsum = 0.0;
+          for (int kk = 4 * g0 + lane; kk <= 4 * g1 + 3; kk += WAVE) {   // (lane l: k = first reachable k + l, + 64, ...)
+            const uint4 rc = reinterpret_cast<const uint4*>(recs)[kk];   // (offset of row 0, -, first - (R - 1), last - first + R - 1)
+            const bool meets = (int)rc.z <= r0 + TROWS - R && (int)rc.z + (int)rc.w >= r0;
+            // (the segment of row r0 of column k: slot / 32; outside the run the offset lies beyond the buffer and reads as 0)
+            const double am_k = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(mrsrc, meets ? (((rc.x + (unsigned)r0 * 8u) >> 8) << 3) : TILE_OOB, 0, 0));
+            const double* __restrict__ brow = Bs + kk * BP;   // (pitch 17, lanes differ in k: conflict-free)
+            double bm_k = 0.0;
+#pragma unroll
+            for (int c = 0; c < SLAB_J; ++c) bm_k = fmax(bm_k, fabs(brow[c]));
+            bsum = __dadd_rn(bsum, __dmul_rn(am_k, bm_k));
+          }
+          bsum = wave_sum_f64(bsum);
+          if (!dense_rule) bsum = __dmul_rn(bsum, fabs(alpha));
+          const bool skipped = __ballot(!(__dmul_rn(bsum, 1.0 + 0x1p-30) <= thr)) == 0ull;
+          if (lane == 0) atomicAdd(&misc[5], skipped ? 0x10001 : 1);   // (tiles tested | skipped << 16: a window has far fewer than 2^15)
+          if (skipped) {
+            if (lane == 0) colmask[t] = 0u;
+            STAMP(sidx); ++sidx;
+            continue;
+          }
+        }
       }
     }
     // what the epilogue reads -- this lane's elements are rows r0 + R (4 v + q) + m of column jj -- is requested when
@@ -822,6 +883,12 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
         }
 #pragma unroll
         for (int v = 0; v < 4; ++v) rv_store<R>(orun + (r0 + R * (4 * v + q)), both[v]);
+        if constexpr (SKIPK) {
+          if (skip_on) {
+            const double mx = seg_max(both);
+            if (q == 0) a.oamax[seg_of(r0)] = mx;
+          }
+        }
         if (otile) {
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
@@ -920,6 +987,12 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
     if ((cm >> jj) & 1u) {   // the column has an entry in this tile: its 16 R rows are written (zeros = holes)
 #pragma unroll
       for (int v = 0; v < 4; ++v) rv_store<R>(orun + (r0 + R * (4 * v + q)), res[v]);
+    }
+    if constexpr (SKIPK) {
+      if (skip_on) {   // (columns without an entry in this tile: zeroed with the holes below, or outside their run -- never read)
+        const double mx = seg_max(res);
+        if (q == 0 && ((cm >> jj) & 1u)) a.oamax[seg_of(r0)] = mx;
+      }
     }
     if constexpr (EPI != 0) {
       if (cm && otile) {
@@ -1021,6 +1094,11 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
       a.otoff[b] = tbase + (tk1 >= tk0 ? (int64_t)(tk0 - lo) * SLAB_J : 0);
       a.fzv.pnnz[b] = misc[1];
       if (a.fzv.prod) a.fzv.prod[b] = *reinterpret_cast<long long*>(misc + 2);
+      if constexpr (SKIPK) {   // (tiles tested / skipped: the spare words behind the flag come home with it)
+        const int sk = misc[5];
+        if (sk & 0xffff) atomicAdd(a.fzv.flag + 1, sk & 0xffff);
+        if (sk >> 16) atomicAdd(a.fzv.flag + 3, sk >> 16);
+      }
     }
     if (tid == 64) {
       double x = 0.0, y = 0.0;
@@ -1050,13 +1128,20 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
   }
   // holes: a tile strictly inside a column's run (inside the block's tile rows) that was skipped above holds zeros
   for (int p = tid; p < T * SLAB_J; p += TILE_NW * WAVE) {
-    const int t = p >> 4, c = p & 15;
+    const int t = p >> 4;
+    int c = p & 15;
+    // (opaque: c of the first round is this thread's jj, and the compiler would otherwise carry jj * w -- two registers -- from
+    // the prologue across the whole tile loop to here)
+    asm volatile("" : "+v"(c));
     const unsigned cmk = colmask[t];
     const int cf = col_first[c], cl = col_last[c];
     const int r0 = lo + TROWS * t;
     if (cl >= cf && r0 + TROWS - 1 >= cf && r0 <= cl && !((cmk >> c) & 1u)) {
       double* dst = a.out_val + (tbase + (int64_t)c * w - lo);
       for (int r = r0; r < min(r0 + TROWS, rend); ++r) dst[r] = 0.0;
+      if constexpr (SKIPK) {
+        if (skip_on) a.oamax[(tbase + (int64_t)c * w + (r0 - lo)) >> 5] = 0.0;
+      }
     }
     if constexpr (EPI != 0) {
       if (a.fzv.tiles && tk1 >= tk0 && r0 + TROWS - 1 >= tk0 && r0 <= tk1 && cmk == 0u) {
@@ -1068,11 +1153,19 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
   if constexpr (EPI == 2) {
     const int nd = min(misc[0], TILE_DEFER);
     if (nd > 0) {
-      __syncthreads();   // (the zeros above first)
+      // (the zeros above first -- and every tile's values and segment maxima: a barrier alone does not wait for the stores of
+      // the waves that reach it, and the stores and the atomic below go to slots other threads have written)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
       for (int i = tid; i < nd; i += TILE_NW * WAVE) {
         const TileDefer e = dlist[i];
         if (!e.pad) continue;
         a.out_val[tbase + (int64_t)e.jj * w + (e.r - lo)] = e.o;
+        if constexpr (SKIPK) {   // (it raises its segment's maximum: non-negative doubles order as their bit patterns)
+          if (skip_on)
+            atomicMax(reinterpret_cast<unsigned long long*>(a.oamax + ((tbase + (int64_t)e.jj * w + (e.r - lo)) >> 5)),
+                      (unsigned long long)__double_as_longlong(fabs(e.o)));
+        }
         if (a.fzv.tiles) a.fzv.tiles[tbase + (int64_t)(e.r - lo) * SLAB_J + e.jj] = e.o;
       }
     }
@@ -1104,8 +1197,52 @@ bool spgemm_tile_fits(int max_kn, int max_w) {
   return max_kn > 0 && max_w > 0 && std::max(tile_lds_bytes(k4, tm, 16 * tm + 64), tile_lds_bytes(k4, tm, 0)) <= 150 * 1024;   // (with the labels of a label-aware step)
 }
 
-void launch_spgemm_tile(const TileLaunch& L) {
+namespace {
+// what the launch derives from its arguments and the options: 32-bit offsets, waves per workgroup, LDS bytes
+struct TileGeometry {
+  bool off32;
+  int nw;
+  size_t lds;
+};
+TileGeometry tile_geometry(const TileLaunch& L) {
+  TileGeometry g;
+  // 32-bit offsets: every run of A in one allocation below 4 GB; with a fused epilogue also X inside that allocation and the
+  // expanded D operand in one of its own
+  g.off32 = options().tile_off32 != 0 && L.abase != nullptr && L.abytes > 0 && L.abytes < 0xfffff000ull;
+  if (g.off32 && L.epi != 0) {
+    const SlabFuseArgs& fzh = *static_cast<const SlabFuseArgs*>(L.fz);
+    const char *a0 = static_cast<const char*>(L.abase), *x0 = reinterpret_cast<const char*>(fzh.xexp);
+    g.off32 = L.dbase != nullptr && L.dbytes > 0 && L.dbytes < 0xfffff000ull && (L.epi != 2 || (x0 >= a0 && x0 < a0 + L.abytes));
+  }
+  const int k4max = std::max(8, (L.max_kn + 3) & ~3);
+  const int trows = 16 * (L.rows == 4 ? 4 : L.rows == 2 ? 2 : 1);
+  const int tmax = (L.max_w + trows - 1) / trows;
+  g.lds = tile_lds_bytes(k4max, tmax, (L.labelled && L.epi != 0) ? tmax * trows : 0);
+  // waves per workgroup (option tile_waves overrides): four when FOUR workgroups fit a CU's LDS (sixteen waves, four per SIMD --
+  // what 128 registers per lane admit -- in four independent blocks: the prologue of one runs under the main loop of the
+  // others), eight when fewer do: two workgroups of eight are again sixteen waves where three of four would be twelve.  (Up to
+  // round 5 three workgroups of four were preferred to two of eight; since a wave takes its tiles from a counter, eight waves
+  // share a window without waiting for one another at its end, and the fourth wave per SIMD pays: headline 683 -> 696
+  // iterations/s, profiles/README.md round 6.  LDS is granted in units of 512 bytes.)
+#ifdef NTP_TILE_WIDE3   // (A/B builds: the rule up to round 5 -- eight waves only where fewer than THREE workgroups of four fit)
+  const bool wide = 3 * ((g.lds + 511) & ~(size_t)511) > 160 * 1024;
+#else
+  const bool wide = 4 * ((g.lds + 511) & ~(size_t)511) > 160 * 1024;
+#endif
+  const int tw = options().tile_waves;
+  g.nw = (tw == 4 || tw == 5 || tw == 6 || tw == 8) ? tw : (wide ? 8 : 4);
+  return g;
+}
+}  // namespace
+
+bool spgemm_tile_skips(const TileLaunch& L) {
+  const TileGeometry g = tile_geometry(L);
+  return L.amax_bytes > 0 && L.amax_bytes < 0xffffff00ull && L.epi != 0 && L.rows == 2 && !L.labelled && g.off32 && (g.nw == 4 || g.nw == 8);
+}
+
+bool launch_spgemm_tile(const TileLaunch& L) {
   TileArgs a;
+  const TileGeometry geo = tile_geometry(L);
   a.runs = static_cast<const SlabRun*>(L.runs);
   a.bblk = L.bblk; a.blk_boff = L.blk_boff; a.blk_kmin = L.blk_kmin; a.blk_kn = L.blk_kn; a.blk_lo = L.blk_lo; a.blk_w = L.blk_w;
   a.blk_toff = L.blk_toff; a.out_val = L.out_val; a.count = L.count; a.ofirst = L.ofirst; a.olast = L.olast; a.ooff = L.ooff;
@@ -1125,14 +1262,7 @@ void launch_spgemm_tile(const TileLaunch& L) {
     zeros->zero();
   }
   a.zero = zeros->p;
-  // 32-bit offsets: every run of A in one allocation below 4 GB; with a fused epilogue also X inside that allocation and the
-  // expanded D operand in one of its own
-  bool off32 = options().tile_off32 != 0 && L.abase != nullptr && L.abytes > 0 && L.abytes < 0xfffff000ull;
-  if (off32 && L.epi != 0) {
-    const SlabFuseArgs& fzh = *static_cast<const SlabFuseArgs*>(L.fz);
-    const char *a0 = static_cast<const char*>(L.abase), *x0 = reinterpret_cast<const char*>(fzh.xexp);
-    off32 = L.dbase != nullptr && L.dbytes > 0 && L.dbytes < 0xfffff000ull && (L.epi != 2 || (x0 >= a0 && x0 < a0 + L.abytes));
-  }
+  const bool off32 = geo.off32;
   a.abase = off32 ? L.abase : nullptr;
   a.abytes = off32 ? (uint32_t)L.abytes : 0u;
   a.dbase = off32 ? L.dbase : nullptr;
@@ -1148,20 +1278,13 @@ void launch_spgemm_tile(const TileLaunch& L) {
   blkdur->zero();
   a.blkdur = blkdur->p;
 #endif
-  const size_t lds = tile_lds_bytes(a.k4max, a.tmax, (L.labelled && L.epi != 0) ? a.tmax * trows : 0);
-  // waves per workgroup (option tile_waves overrides): four when FOUR workgroups fit a CU's LDS (sixteen waves, four per SIMD --
-  // what 128 registers per lane admit -- in four independent blocks: the prologue of one runs under the main loop of the
-  // others), eight when fewer do: two workgroups of eight are again sixteen waves where three of four would be twelve.  (Up to
-  // round 5 three workgroups of four were preferred to two of eight; since a wave takes its tiles from a counter, eight waves
-  // share a window without waiting for one another at its end, and the fourth wave per SIMD pays: headline 683 -> 696
-  // iterations/s, profiles/README.md round 6.  LDS is granted in units of 512 bytes.)
-#ifdef NTP_TILE_WIDE3   // (A/B builds: the rule up to round 5 -- eight waves only where fewer than THREE workgroups of four fit)
-  const bool wide = 3 * ((lds + 511) & ~(size_t)511) > 160 * 1024;
-#else
-  const bool wide = 4 * ((lds + 511) & ~(size_t)511) > 160 * 1024;
-#endif
-  const int tw = options().tile_waves;
-  const int nw = (tw == 4 || tw == 5 || tw == 6 || tw == 8) ? tw : (wide ? 8 : 4);
+  const size_t lds = geo.lds;
+  const int nw = geo.nw;
+  // (tile skip: the instantiations that carry the test -- see SKIPK in the kernel)
+  const bool skip = L.amax != nullptr && L.oamax != nullptr && spgemm_tile_skips(L);
+  a.amax = skip ? L.amax : nullptr;
+  a.amax_bytes = skip ? (uint32_t)L.amax_bytes : 0u;
+  a.oamax = skip ? L.oamax : nullptr;
   auto go = [&](auto epi_tag, auto nw_tag, auto r_tag, auto lab_tag, auto off_tag) {
     constexpr int E = decltype(epi_tag)::value, NW = decltype(nw_tag)::value, RR = decltype(r_tag)::value;
     constexpr bool LB = decltype(lab_tag)::value, OF = decltype(off_tag)::value;
@@ -1216,6 +1339,7 @@ void launch_spgemm_tile(const TileLaunch& L) {
     if (FILE* fp = std::fopen((std::string(f) + ".blocks").c_str(), "wb")) { std::fwrite(hb.data(), 8, hb.size(), fp); std::fclose(fp); }
   }
 #endif
+  return skip;
 }
 
 }  // namespace ntp

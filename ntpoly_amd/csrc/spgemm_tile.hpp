@@ -44,6 +44,13 @@ struct TileLaunch {
   size_t abytes = 0;
   const void* dbase = nullptr;       // epi != 0: the allocation that holds the expanded D operand (fz.dexp), for the same purpose
   size_t dbytes = 0;
+  // optional (epi 1 / 2, rows == 2, 32-bit offsets, not labelled; option tile_skip): SlabForm::amax of the operand behind `abase`
+  // -- one double per 32 slots, amax_bytes of them -- and of the result (oamax, next to out_val).  With both set the kernel
+  // skips every tile whose products provably stay at or below the threshold before it loads anything for it, and leaves the
+  // numbers of tiles tested / skipped in the int words 1 and 3 behind SlabFuseArgs::flag
+  const double* amax = nullptr;
+  size_t amax_bytes = 0;
+  double* oamax = nullptr;
   int nrows = 0;                     // rows of the operands (0: ncols -- square); label-aware epilogues index fz.lab by row
   bool labelled = false;             // fz carries labels (SlabFuseArgs::lab, xplast, oplast): the epilogue's "beyond the last entry"
                                      // tests compare the caller's labels.  The k steps are walked in POSITION order (the rounding
@@ -54,7 +61,11 @@ bool spgemm_tile_fits(int max_kn, int max_w);
 // rows per lane the engine uses (option tile_rows: 1, 2 or 4) and the alignment it implies for windows and expanded columns
 int tile_rows();
 inline int tile_expand_align() { return 16 * tile_rows(); }
-void launch_spgemm_tile(const TileLaunch& a);
+// would this launch carry the tile-skip test, given amax / oamax?  Everything launch_spgemm_tile decides on but the two pointers
+// (epi, rows, labelled, amax_bytes, 32-bit offsets, waves per workgroup): the caller builds the maxima only then
+bool spgemm_tile_skips(const TileLaunch& a);
+// true: the tile-skip test ran (TileLaunch::amax) and the result's segment maxima were written to oamax
+bool launch_spgemm_tile(const TileLaunch& a);
 // The same multiply in the two-block geometry (spgemm_tile2.hip: pairs of column blocks share every fragment of A, the
 // multiplier rows stream through LDS in chunks): rows == 2, the right operand given by its runs (brun_*), not labelled.
 // false: not launched (the geometry cannot fit), call launch_spgemm_tile.  true: launched -- *fail (device, zeroed by the

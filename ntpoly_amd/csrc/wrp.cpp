@@ -189,6 +189,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "block_path") options().block_path = *value;
   else if (n == "tile_runs_only") options().tile_runs_only = *value;
   else if (n == "tile2") options().tile2 = *value;
+  else if (n == "tile_skip") options().tile_skip = *value;
   else if (n == "complex_tile") options().complex_tile = *value;
   else if (n == "block_complex") options().block_complex = *value;
   else if (n == "thin_left") options().thin_left = *value;
@@ -209,6 +210,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "plan_ahead") return options().plan_ahead;
   if (n == "tile_rows") return options().tile_rows;
   if (n == "tile2") return options().tile2;
+  if (n == "tile_skip") return options().tile_skip;
   if (n == "block_path") return options().block_path;
   if (n == "label_order") return options().label_order;
   if (n == "band_scope") return options().band_scope;
@@ -408,6 +410,11 @@ void ntpoly_amd_complex_fusion_counts(long long* out) {
 void ntpoly_amd_tile2_counts(long long* out) {
   for (int q = 0; q < 2; ++q) out[q] = tile2_counts()[q];
 }
+// out[0] = tiles the MFMA tile kernel tested against the operand's segment maxima (option tile_skip), out[1] = tiles it skipped,
+// since the last ntpoly_amd_reset_spgemm_accum
+void ntpoly_amd_tile_skip_counts(long long* out) {
+  for (int q = 0; q < 2; ++q) out[q] = tile_skip_counts()[q];
+}
 // GatherMatrixToProcess (PSMatrixModule.F90:1704-1808, distributed_includes/GatherMatrixToProcess.f90, GatherMatrixToAll.f90):
 // the whole distributed matrix as a LOCAL matrix (Matrix_lsr / Matrix_lsc of its scalar type) -- on every process
 // (*within_slice_id < 0: the _all variants) or on the process with that rank inside its slice only (the _id variants: data
@@ -471,7 +478,9 @@ void ntpoly_amd_column_fused_counts(long long* out) {
 // IncrementMatrix(Identity, B, alpha) as the loops call it, and the norm of alpha A + beta B (returns 0 when the engine would
 // form the difference instead)
 void ntpoly_amd_increment_identity(const int* ih_identity, int* ih_matB, const double* alpha) {
-  ps_increment_identity(*get<PSMatrix>(ih_identity), *get<PSMatrix>(ih_matB), *alpha);
+  // (inside ntpoly_amd_session_begin / _end B stays as it is -- slab form included -- as in the solver loops that make this call)
+  PSMatrix* B = (g_test_session && g_test_session->opened) ? get_unpacked(ih_matB) : get<PSMatrix>(ih_matB);
+  ps_increment_identity(*get<PSMatrix>(ih_identity), *B, *alpha);
 }
 int ntpoly_amd_norm_axpby(const int* ih_matA, const int* ih_matB, const double* alpha, const double* beta, double* norm) {
   return ps_norm_axpby(*get<PSMatrix>(ih_matA), *get<PSMatrix>(ih_matB), *alpha, *beta, norm) ? 1 : 0;
@@ -502,6 +511,7 @@ void ntpoly_amd_band_searches(long long* out) { *out = band_searches(); }
 void ntpoly_amd_reset_spgemm_accum() {
   flush_spgemm_timers();
   spgemm_accum() = SpgemmAccum();
+  tile_skip_counts()[0] = tile_skip_counts()[1] = 0;
 }
 // out: calls, products, nnz_c ; dout: alg_bytes, ms_numeric, ms_total
 void ntpoly_amd_get_spgemm_accum(long long* out, double* dout) {

@@ -936,6 +936,13 @@ def tile2_counts():
     return dict(done=out[0], repeated=out[1])
 
 
+def tile_skip_counts():
+    """(tiles the MFMA tile kernel tested against the operand's segment maxima, tiles it skipped) since reset_spgemm_accum"""
+    out = (C.c_longlong * 2)()
+    lib.ntpoly_amd_tile_skip_counts(out)
+    return (int(out[0]), int(out[1]))
+
+
 def band_scope_counts():
     """(solves run in a recovered band order across ranks, operands searched for a hidden band)"""
     out = (C.c_longlong * 2)()
