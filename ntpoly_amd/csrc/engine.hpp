@@ -185,6 +185,30 @@ bool ps_isr_chain3(PSMatrix& X, const PSMatrix& X2);
 // order runs, the outputs are packed into Out1 (order 5: Temp2, order 3: the new X) and Out2 (order 5: Temp; order 3: untouched)
 bool ps_isr_chain_step(const PSMatrix& X, const PSMatrix& X2, int order, double a, double b, double c, PSMatrix& Out1, PSMatrix& Out2);
 long long* isr_chain_counts();   // since start: [0] order-5 chains fused, [1] order-3 chains fused, [2] chains refused (past the gates: a gated step counts nowhere)
+// HPCP purification (DensityMatrixSolversModule.F90:839-878) inside a real slab session, option hpcp_step (slab_extra.hip
+// k_hpcp_traces / k_hpcp_update).
+// ps_hpcp_traces: out = trace(DDH), trace(D2DH), each with the bits of ps_trace, from one pass and one read-back.  Collective: one
+// reduction carries both sums; a rank whose panels the kernel does not take adds the partial sums it computes as ps_trace would
+// (not counted as fused).  false -- before any collective, by gates that are the same on every rank (the option off, no open real
+// session, a complex operand, block form) --: the caller makes the two ps_trace calls.
+// ps_hpcp_update: what ps_increment(D2DH, D1, 2, 0); ps_increment(DDH, D1, -2 sigma, 0) leave in D1, *energy = dot(D1, WH), and in
+// DH what ps_copy(D1, DH); ps_increment_identity(I, DH, -1); ps_scale(DH, -1) would build from that D1: values and patterns bit
+// for bit, the energy to rounding (another summation order; it only feeds the convergence monitor).  Counted in
+// slab_algebra_counts() as the four merges / copies and two other operations replaced.  false: not done, D1 and DH as they were
+// (an operand still in compressed columns may have been turned into slab form, as in ps_isr_chain5) -- the caller makes the two
+// merges and the dot, and builds the next DH with the three calls.  The merges are local to a rank; the energy's reduction has
+// the shape of ps_dot's, so a rank that returns false and calls ps_dot meets the other ranks' reduction with its own partial sum:
+// every rank enters the same collectives in the same order whichever ranks refuse.  Gates (the option off, no open real session,
+// a complex operand, block form, a labelled slab form, all three operands in compressed columns, alignments that differ, a WH
+// that is neither a zero-free slab form nor a read-only view) count nothing; a sigma that is zero or not finite (before launch),
+// an operand the slab form cannot hold, runs far apart and a scaled entry that underflows to zero count as refused.
+bool ps_hpcp_traces(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]);
+bool ps_hpcp_update(PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& DH, double* energy);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_hpcp_update_step): the operands are brought into slab form where they are, one update runs,
+// the new D1 and DH are packed into D1out and DHout
+bool ps_hpcp_update_step(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& D1out,
+                         PSMatrix& DHout, double* energy);
+long long* hpcp_step_counts();   // since start: [0] trace passes fused, [1] updates fused, [2] updates refused (past the gates: a gated step counts nowhere)
 // solvers.cpp: this loop may take a complex operand like m in slab form (FMA arithmetic, complex tile kernel, complex_sessions)
 bool complex_slab_loop(const PSMatrix& m);
 void ps_slab_leave(PSMatrix& m);   // back to compressed columns (no-op for a matrix that is not in slab form)

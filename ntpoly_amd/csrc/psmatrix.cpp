@@ -1346,6 +1346,118 @@ bool ps_isr_chain_step(const PSMatrix& X, const PSMatrix& X2, int order, double 
   return true;
 }
 
+long long* hpcp_step_counts() {
+  static long long counts[3] = {0, 0, 0};
+  return counts;
+}
+namespace {
+// MatrixTrace of the local panel of a matrix that is not in block form: ps_trace without its sum over the ranks
+double trace_local(const PSMatrix& A) {
+  unblock({&A});
+  if (slab_on() && A.loc.expanded() && !A.cplx) {
+    double v = 0.0;
+    if (slab_trace(A.loc, A.c0, &v)) {
+      g_slab_counts[2] += 1;
+      return v;
+    }
+    slab_refused({&A});
+  } else {
+    slab_pack_if({&A});
+  }
+  return trace(A.loc, A.c0);
+}
+// the gates of the fused update (isr_chain_on for three merged operands and WH): a step they keep out is neither fused nor refused
+bool hpcp_update_on(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, const PSMatrix& WH) {
+  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
+  return options().hpcp_step != 0 && slab_on() && !D1.cplx && !DDH.cplx && !D2DH.cplx && !WH.cplx && D1.dim == DDH.dim && D1.dim == D2DH.dim &&
+         D1.dim == WH.dim && &D1 != &DDH && &D1 != &D2DH && &DDH != &D2DH && !blk_any({&D1, &DDH, &D2DH, &WH}) && !WH.loc.blocked() &&
+         (D1.loc.expanded() || DDH.loc.expanded() || D2DH.loc.expanded()) && !labelled(D1) && !labelled(DDH) && !labelled(D2DH) && !labelled(WH);
+}
+// the operands into slab form where they are, as ps_axpby and ps_dot do before their kernels.  *gated: what cannot be fused without
+// being a refusal -- alignments that differ, a WH that is neither a zero-free slab form nor a read-only view
+bool hpcp_update_enter(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, const PSMatrix& WH, bool* gated) {
+  *gated = false;
+  if (!slab_enter(mut(WH)) || !(WH.loc.zero_free == 1 || WH.loc.slab->origin)) { *gated = true; return false; }
+  if (!slab_enter(mut(D1)) || !slab_enter(mut(DDH)) || !slab_enter(mut(D2DH))) return false;
+  if (D1.loc.slab->row_pad != DDH.loc.slab->row_pad || D1.loc.slab->row_pad != D2DH.loc.slab->row_pad) { *gated = true; return false; }
+  return true;
+}
+bool hpcp_sigma_ok(double sigma) { return sigma != 0.0 && std::isfinite(sigma); }
+}  // namespace
+bool ps_hpcp_traces(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]) {
+  CommScope cs(DDH.grid);
+  // (every gate here is the same on every rank: past them each rank enters ONE reduction, and a rank whose panels the kernel does
+  // not take adds the partial sums it computes as ps_trace would)
+  if (options().hpcp_step == 0 || g_slab_depth == 0 || DDH.cplx || D2DH.cplx || DDH.dim != D2DH.dim || &DDH == &D2DH || blk_any({&DDH, &D2DH}) ||
+      (!world().active() && !slab_on()))
+    return false;
+  double t[2] = {0.0, 0.0};
+  if (slab_on() && DDH.loc.expanded() && D2DH.loc.expanded() && slab_hpcp_traces(DDH.loc, D2DH.loc, DDH.c0, t)) {
+    g_slab_counts[2] += 2;
+    hpcp_step_counts()[0] += 1;
+  } else {
+    t[0] = trace_local(DDH);
+    t[1] = trace_local(D2DH);
+  }
+  comm_allreduce_sum(t, 2);
+  out[0] = t[0];
+  out[1] = t[1];
+  return true;
+}
+bool ps_hpcp_update(PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& DH, double* energy) {
+  CommScope cs(D1.grid);
+  if (&DH == &D1 || &DH == &DDH || &DH == &D2DH || &DH == &WH || !hpcp_update_on(D1, DDH, D2DH, WH)) return false;
+  bool gated = false;
+  DevMat o, h;
+  double e[2] = {0.0, 0.0};
+  if (!hpcp_sigma_ok(sigma) || !hpcp_update_enter(D1, DDH, D2DH, WH, &gated) ||
+      !slab_hpcp_update(D1.loc, DDH.loc, D2DH.loc, sigma, WH.loc, D1.c0, o, h, &e[0])) {
+    if (!gated) hpcp_step_counts()[2] += 1;
+    return false;
+  }
+  const ProcessGrid* grid = D1.grid;
+  const int32_t dim = D1.dim, c0 = D1.c0, c1 = D1.c1;
+  D1.loc = std::move(o);
+  install(DH, grid, dim, false, c0, c1, std::move(h));
+  // (the reduction of the dot this replaces, entry for entry: a rank that refused is in ps_dot's with its own partial sum)
+  comm_allreduce_sum(e, 2);
+  *energy = e[0];
+  g_slab_counts[1] += 4;   // two merges into D1; the copy and the identity's merge of DH
+  g_slab_counts[2] += 2;   // the scaling of DH, the dot
+  hpcp_step_counts()[1] += 1;
+  return true;
+}
+bool ps_hpcp_update_step(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& D1out,
+                         PSMatrix& DHout, double* energy) {
+  CommScope cs(D1.grid);
+  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
+  if (options().hpcp_step == 0 || !slab_on() || D1.cplx || DDH.cplx || D2DH.cplx || WH.cplx || D1.dim != DDH.dim || D1.dim != D2DH.dim ||
+      D1.dim != WH.dim || &D1 == &DDH || &D1 == &D2DH || &DDH == &D2DH || &D1out == &DHout || labelled(D1) || labelled(DDH) || labelled(D2DH) ||
+      labelled(WH))
+    return false;
+  for (const PSMatrix* m : {&D1, &DDH, &D2DH, &WH})
+    if (m == &D1out || m == &DHout) return false;
+  unblock({&D1, &DDH, &D2DH, &WH});
+  bool gated = false;
+  DevMat o, h;
+  double e[2] = {0.0, 0.0};
+  if (!hpcp_sigma_ok(sigma) || !hpcp_update_enter(D1, DDH, D2DH, WH, &gated) ||
+      !slab_hpcp_update(D1.loc, DDH.loc, D2DH.loc, sigma, WH.loc, D1.c0, o, h, &e[0])) {
+    if (!gated) hpcp_step_counts()[2] += 1;
+    return false;
+  }
+  pack(o);
+  pack(h);
+  install(D1out, D1.grid, D1.dim, false, D1.c0, D1.c1, std::move(o));
+  install(DHout, D1.grid, D1.dim, false, D1.c0, D1.c1, std::move(h));
+  comm_allreduce_sum(e, 2);
+  *energy = e[0];
+  g_slab_counts[1] += 4;
+  g_slab_counts[2] += 2;
+  hpcp_step_counts()[1] += 1;
+  return true;
+}
+
 long long* pm_session_counts() {
   static long long counts[5] = {0, 0, 0, 0, 0};
   return counts;
@@ -1931,19 +2043,7 @@ double ps_trace(const PSMatrix& A) {
     if (block_dot_trace(A.loc, A.loc, nullptr, &t)) { g_block_counts[0] += 1; return t; }
     g_block_counts[1] += 1;
   }
-  unblock({&A});
-  if (slab_on() && A.loc.expanded() && !A.cplx) {
-    double v = 0.0;
-    if (slab_trace(A.loc, A.c0, &v)) {
-      g_slab_counts[2] += 1;
-      comm_allreduce_sum(&v, 1);
-      return v;
-    }
-    slab_refused({&A});
-  } else {
-    slab_pack_if({&A});
-  }
-  double t = trace(A.loc, A.c0);
+  double t = trace_local(A);
   comm_allreduce_sum(&t, 1);
   return t;
 }

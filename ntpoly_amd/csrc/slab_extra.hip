@@ -1347,6 +1347,211 @@ bool slab_isr_chain3(const DevMat& X, const DevMat& X2, int32_t col_offset, DevM
   return isr_chain_run<double, 3>(X, X2, -0.5, 0.375, 0.0, col_offset, Out, nullptr);
 }
 
+// ------------------------------------------------------------------ HPCP purification: the traces and the update of a step
+// DensityMatrixSolversModule.F90:839-878 builds, around the products DDH = D1 DH and D2DH = D1 DDH, with the vocabulary at threshold 0
+// (d = the identity's entry):
+//   sigma = trace(D2DH) / trace(DDH)
+//   t = d1 + 2 d2dh,   o = t + (-2 sigma) ddh (the new D1),   energy = dot(o, wh),   dh = -(o + (-1) d) (the next step's DH)
+// k_hpcp_traces leaves both diagonals as the pairs that sum_pairs_async sums member by member: the bits of two slab_trace calls.
+// k_hpcp_update reads the three runs and WH once and writes the new D1 and DH; every merge is isr_merge (AddSparseVectors on two
+// operands at threshold 0, see the square-root chain above), the scaling by -1 is exact.
+namespace {
+struct HpcpRuns {   // one operand in slab form
+  const int32_t* first;
+  const int32_t* last;
+  const int64_t* off;
+  const double* val;
+};
+HpcpRuns hpcp_runs(const DevMat& M) { return HpcpRuns{M.slab->first.p, M.slab->last.p, M.slab->off.p, M.slab->val.p}; }
+// one thread per column: part[2 j] = A's diagonal entry, part[2 j + 1] = B's, each read as k_sa_diag reads it
+__global__ __launch_bounds__(256) void k_hpcp_traces(int n, HpcpRuns A, HpcpRuns B, int col_offset, double* __restrict__ part) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int d = j + col_offset, fA = A.first[j], lA = A.last[j], fB = B.first[j], lB = B.last[j];
+  part[2 * (size_t)j] = (lA >= fA && d >= fA && d <= lA) ? A.val[A.off[j] + (d - fA)] : 0.0;
+  part[2 * (size_t)j + 1] = (lB >= fB && d >= fB && d <= lB) ? B.val[B.off[j] + (d - fB)] : 0.0;
+}
+// the aligned hull of the three runs and the diagonal row, per column
+__global__ void k_hpcp_span(HpcpRuns A, HpcpRuns B, HpcpRuns C, int n, int col_offset, int al, int32_t* __restrict__ span) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  int f = j + col_offset, l = j + col_offset;
+  if (A.last[j] >= A.first[j]) { f = min(f, A.first[j]); l = max(l, A.last[j]); }
+  if (B.last[j] >= B.first[j]) { f = min(f, B.first[j]); l = max(l, B.last[j]); }
+  if (C.last[j] >= C.first[j]) { f = min(f, C.first[j]); l = max(l, C.last[j]); }
+  span[j] = (l / al + 1) * al - f / al * al;
+}
+// chunks of 64 rows whose loads (four operands each) are all requested before the first of them is used: 16 loads per lane in 82
+// VGPRs, five waves per SIMD, no scratch -- a hull of up to 256 aligned rows is one trip (ISR_KC's depth with twice the operands)
+constexpr int HPCP_KC = 4;
+// One wave per column, lanes on consecutive rows of the aligned hull [a0, a1) of the runs of A = D1, B = DDH, C = D2DH and the
+// diagonal row.  o1 = the new D1, o2 = DH, both into the slot at base[j]; part[2 j] = sum over the column of o wh, a lane-strided
+// sum then a wave sum (fixed shapes: the same value every run).  s2 = -2 sigma as the host rounds it.
+// stat |= 1: a scaled entry underflows to zero; |= 2: runs far apart or a slot beyond the output buffer -- nothing is written for
+// that column (k_sa_isr_chain).
+__global__ __launch_bounds__(256) void k_hpcp_update(int n, HpcpRuns A, HpcpRuns B, HpcpRuns C, HpcpRuns W, int col_offset, double s2, int al,
+                                                     const int64_t* __restrict__ base, IsrOut o1, IsrOut o2, int64_t bound,
+                                                     double* __restrict__ part, unsigned long long* __restrict__ stat) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id();
+  const int fA = A.first[j], lA = A.last[j], fB = B.first[j], lB = B.last[j], fC = C.first[j], lC = C.last[j], fW = W.first[j], lW = W.last[j];
+  const int dg = j + col_offset;
+  const bool anyA = lA >= fA, anyB = lB >= fB, anyC = lC >= fC, anyW = lW >= fW;
+  int f = dg, l = dg;   // (the identity's entry is always there)
+  int rf = INT_MAX, rl = -1, own = 0;   // the hull of the runs alone, and the rows their own aligned slots hold
+  if (anyA) { rf = min(rf, fA); rl = max(rl, lA); own += (lA / al + 1) * al - fA / al * al; }
+  if (anyB) { rf = min(rf, fB); rl = max(rl, lB); own += (lB / al + 1) * al - fB / al * al; }
+  if (anyC) { rf = min(rf, fC); rl = max(rl, lC); own += (lC / al + 1) * al - fC / al * al; }
+  if (rl >= 0) { f = min(f, rf); l = max(l, rl); }
+  const int a0 = f / al * al, a1 = (l / al + 1) * al;
+  const int64_t slot = base[j];
+  // (runs far apart: their hull is not bounded by the three slots and the pads between them -- refused per column.  The diagonal
+  // row may lie anywhere: what it adds is bounded over all columns by the output buffer)
+  const bool apart = rl >= 0 && (rl / al + 1) * al - rf / al * al > own + 3 * al;
+  if (apart || slot + (int64_t)(a1 - a0) > bound) {
+    if (lane == 0) {
+      o1.first[j] = INT_MAX; o1.last[j] = -1; o1.count[j] = 0; o1.off[j] = slot;
+      o2.first[j] = INT_MAX; o2.last[j] = -1; o2.count[j] = 0; o2.off[j] = slot;
+      part[2 * (size_t)j] = 0.0; part[2 * (size_t)j + 1] = 0.0;
+      atomicOr(stat, 2ull);
+    }
+    return;
+  }
+  const double* __restrict__ pa = anyA ? A.val + (A.off[j] - fA) : A.val;
+  const double* __restrict__ pb = anyB ? B.val + (B.off[j] - fB) : B.val;
+  const double* __restrict__ pc = anyC ? C.val + (C.off[j] - fC) : C.val;
+  const double* __restrict__ pw = anyW ? W.val + (W.off[j] - fW) : W.val;
+  double* __restrict__ d1 = static_cast<double*>(o1.val) + (slot - a0);
+  double* __restrict__ d2 = static_cast<double*>(o2.val) + (slot - a0);
+  int uf = 0, c1 = 0, f1 = INT_MAX, l1 = -1, c2 = 0, f2 = INT_MAX, l2 = -1;
+  double e = 0.0;
+  for (int rb = a0; rb < a1; rb += HPCP_KC * WAVE) {
+    double va[HPCP_KC], vb[HPCP_KC], vc[HPCP_KC], vw[HPCP_KC];
+#pragma unroll
+    for (int k = 0; k < HPCP_KC; ++k) {
+      const int r = rb + k * WAVE + lane;
+      va[k] = (anyA && r >= fA && r <= lA) ? pa[r] : 0.0;
+      vb[k] = (anyB && r >= fB && r <= lB) ? pb[r] : 0.0;
+      vc[k] = (anyC && r >= fC && r <= lC) ? pc[r] : 0.0;
+      vw[k] = (anyW && r >= fW && r <= lW) ? pw[r] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < HPCP_KC; ++k) {
+      const int r = rb + k * WAVE + lane;
+      if (r >= a1) continue;
+      const double x = va[k], xb = vb[k], xc = vc[k];
+      bool ht, ho, hu;
+      const double t = isr_merge<double>(1.0, x, x != 0.0, 2.0, xc, xc != 0.0, &ht, &uf);     // IncrementMatrix(D2DH, D1, 2)
+      const double o = isr_merge<double>(1.0, t, ht, s2, xb, xb != 0.0, &ho, &uf);             // IncrementMatrix(DDH, D1, -2 sigma)
+      const double u = isr_merge<double>(1.0, o, ho, -1.0, 1.0, r == dg, &hu, &uf);            // CopyMatrix(D1, DH); IncrementMatrix(I, DH, -1)
+      d1[r] = o;
+      d2[r] = hu ? -u : 0.0;                                                                   // ScaleMatrix(DH, -1)
+      e = __dadd_rn(e, __dmul_rn(o, vw[k]));                                                   // DotMatrix(D1, WH)
+      c1 += ho ? 1 : 0; f1 = min(f1, ho ? r : INT_MAX); l1 = max(l1, ho ? r : -1);
+      c2 += hu ? 1 : 0; f2 = min(f2, hu ? r : INT_MAX); l2 = max(l2, hu ? r : -1);
+    }
+  }
+  c1 = (int)wave_sum_i64(c1);
+  f1 = wave_min_i32(f1);
+  l1 = wave_max_i32(l1);
+  c2 = (int)wave_sum_i64(c2);
+  f2 = wave_min_i32(f2);
+  l2 = wave_max_i32(l2);
+  e = wave_sum_f64(e);
+  if (__ballot(uf != 0) && lane == 0) atomicOr(stat, 1ull);
+  if (lane == 0) {
+    o1.first[j] = f1; o1.last[j] = l1; o1.count[j] = c1;
+    o1.off[j] = slot + (c1 ? f1 - a0 : 0);
+    o2.first[j] = f2; o2.last[j] = l2; o2.count[j] = c2;
+    o2.off[j] = slot + (c2 ? f2 - a0 : 0);
+    part[2 * (size_t)j] = e; part[2 * (size_t)j + 1] = 0.0;
+  }
+}
+// what the three merged operands must be: trs4_operands for three
+bool hpcp_operand(const DevMat& M) {
+  return M.expanded() && !M.cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1;
+}
+}  // namespace
+
+bool slab_hpcp_traces(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]) {
+  auto ok = [](const DevMat& M) { return M.expanded() && !M.cplx && !M.slab->labelled(); };   // (what slab_trace takes)
+  if (!ok(DDH) || !ok(D2DH) || DDH.cols != D2DH.cols) return false;
+  const int n = DDH.cols;
+  DevBuf<double> part((size_t)2 * n), res(2);
+  hipLaunchKernelGGL(k_hpcp_traces, dim3(cdiv(n, 256)), dim3(256), 0, stream(), n, hpcp_runs(DDH), hpcp_runs(D2DH), col_offset, part.p);
+  sum_pairs_async(part.p, n, res.p);
+  ScalarFetch ft;
+  ft.add(res.p, 2, out2);
+  ft.run();
+  return true;
+}
+
+bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, double sigma, const DevMat& WH, int32_t col_offset, DevMat& OutD1,
+                      DevMat& OutDH, double* energy) {
+  const bool wh_ok = WH.expanded() && !WH.cplx && !WH.slab->labelled() && (WH.rows == WH.cols || slab_panels_ok()) &&
+                     (WH.zero_free == 1 || WH.slab->origin);   // (a view's stored zeros add nothing to the dot)
+  if (!hpcp_operand(D1) || !hpcp_operand(DDH) || !hpcp_operand(D2DH) || !wh_ok || &D1 == &DDH || &D1 == &D2DH || &DDH == &D2DH ||
+      &OutD1 == &OutDH || D1.cols != DDH.cols || D1.cols != D2DH.cols || D1.cols != WH.cols || D1.rows != DDH.rows || D1.rows != D2DH.rows ||
+      D1.rows != WH.rows || D1.slab->row_pad != DDH.slab->row_pad || D1.slab->row_pad != D2DH.slab->row_pad)
+    return false;
+  const SlabForm &fa = *D1.slab, &fb = *DDH.slab, &fc = *D2DH.slab;
+  const int n = D1.cols, al = std::max(1, fa.row_pad);
+  std::unique_ptr<SlabForm> fo[2];
+  IsrOut o[2];
+  // (the operands' slots, and per column the diagonal's slot and the pads of a hull -- with room for diagonals away from their runs)
+  const int64_t bound = fa.slots + fb.slots + fc.slots + 6LL * al * n;
+  for (int q = 0; q < 2; ++q) {
+    fo[q].reset(new SlabForm());
+    fo[q]->first.alloc((size_t)n); fo[q]->last.alloc((size_t)n); fo[q]->count.alloc((size_t)n); fo[q]->off.alloc((size_t)n + 1);
+    fo[q]->val.alloc((size_t)bound + kIndexSlack);
+    o[q] = IsrOut{fo[q]->val.p, fo[q]->first.p, fo[q]->last.p, fo[q]->count.p, fo[q]->off.p};
+  }
+  DevBuf<int32_t> span((size_t)n);
+  DevBuf<int64_t> base((size_t)n + 1);
+  DevBuf<unsigned long long> stat(1), tot(2);
+  DevBuf<double> part((size_t)2 * n), res(2);
+  stat.zero();
+  tot.zero();
+  const HpcpRuns ra = hpcp_runs(D1), rb = hpcp_runs(DDH), rc = hpcp_runs(D2DH);
+  hipLaunchKernelGGL(k_hpcp_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, rc, n, col_offset, al, span.p);
+  scan_i32_async(span.p, base.p, (int64_t)n);
+  hipLaunchKernelGGL(k_hpcp_update, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, rc, hpcp_runs(WH), col_offset,
+                     -1.0 * 2.0 * sigma, al, base.p, o[0], o[1], bound, part.p, stat.p);
+  const dim3 sum_grid(std::max(1, std::min(256, cdiv(n, 1024))));
+  for (int q = 0; q < 2; ++q) hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), fo[q]->count.p, n, tot.p + q);
+  sum_pairs_async(part.p, n, res.p);
+  int64_t nnz[2] = {0, 0}, slots = 0;
+  unsigned long long hs = 0;
+  double e = 0.0;
+  {
+    ScalarFetch ft;
+    ft.add(tot.p, 2, nnz);
+    ft.add(base.p + n, 1, &slots);
+    ft.add(stat.p, 1, &hs);
+    ft.add(res.p, 1, &e);
+    ft.run();
+  }
+  if (hs != 0) {
+    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+      std::fprintf(stderr, "[hpcp update] refused:%s%s\n", (hs & 1ull) ? " a scaled entry underflows to zero" : "", (hs & 2ull) ? " runs far apart" : "");
+    return false;
+  }
+  DevMat R[2];
+  for (int q = 0; q < 2; ++q) {
+    fo[q]->row_pad = al;
+    fo[q]->slots = slots;
+    R[q].rows = D1.rows; R[q].cols = n; R[q].cplx = false; R[q].nnz = nnz[q]; R[q].zero_free = 1;
+    R[q].slab = std::move(fo[q]);
+  }
+  bump_matrix_value_epoch();   // (of the calls it replaces, the two merges into D1 are in place: slab_axpby counts them so)
+  bump_matrix_value_epoch();
+  OutD1 = std::move(R[0]);
+  OutDH = std::move(R[1]);
+  *energy = e;
+  return true;
+}
+
 long long slab_product_count(const DevMat& A, const DevMat& B) {
   if (!A.expanded() || !B.expanded() || A.cplx || B.cplx) return 0;
   const SlabForm &fa = *A.slab, &fb = *B.slab;

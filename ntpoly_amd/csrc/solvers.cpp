@@ -595,17 +595,40 @@ void solver_hpcp(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
   double trace_value = 0.0;
   int II;
   SlabSession slab(!D1.cplx && !WH.cplx);
+  // Option hpcp_step, inside the real session: the two traces in one pass behind the second product (ps_hpcp_traces: the bits of
+  // the two calls), and the two merges, the energy and the NEXT iteration's DH in one pass over the three runs (ps_hpcp_update).
+  // An update that is not taken runs the calls of this iteration, and the next DH is built by the three calls again.
+  const bool step = options().hpcp_step != 0;
+  bool have_dh = false;   // DH = I - D1 came out of the last update
   for (II = 1; II <= p.max_iterations; ++II) {                     // :836-872
-    ps_copy(D1, DH);
-    ps_increment_identity(IMat, DH, -1.0);                         // IncrementMatrix(Identity, DH, -1)
-    ps_scale(DH, -1.0);
+    if (!have_dh) {
+      ps_copy(D1, DH);
+      ps_increment_identity(IMat, DH, -1.0);                       // IncrementMatrix(Identity, DH, -1)
+      ps_scale(DH, -1.0);
+    }
+    have_dh = false;
     ps_multiply(D1, DH, DDH, 1.0, 0.0, p.threshold);
-    trace_value = ps_trace(DDH);
+    double trace_value2;
+    if (!step) trace_value = ps_trace(DDH);
     ps_multiply(D1, DDH, D2DH, 1.0, 0.0, p.threshold);
-    sigma_array[(size_t)II] = ps_trace(D2DH) / trace_value;
-    ps_increment(D2DH, D1, 2.0, 0.0);
-    ps_increment(DDH, D1, -1.0 * 2.0 * sigma_array[(size_t)II], 0.0);
-    if (f.converged(real_dot(D1, WH), sigma_array[(size_t)II], D1)) break;
+    double both[2];
+    if (step && ps_hpcp_traces(DDH, D2DH, both)) {
+      trace_value = both[0];
+      trace_value2 = both[1];
+    } else {
+      if (step) trace_value = ps_trace(DDH);
+      trace_value2 = ps_trace(D2DH);
+    }
+    sigma_array[(size_t)II] = trace_value2 / trace_value;
+    double energy;
+    if (step && ps_hpcp_update(D1, DDH, D2DH, sigma_array[(size_t)II], WH, DH, &energy)) {
+      have_dh = true;
+    } else {
+      ps_increment(D2DH, D1, 2.0, 0.0);
+      ps_increment(DDH, D1, -1.0 * 2.0 * sigma_array[(size_t)II], 0.0);
+      energy = real_dot(D1, WH);
+    }
+    if (f.converged(energy, sigma_array[(size_t)II], D1)) break;
   }
   const int total_iterations = II - 1;
   slab.close();

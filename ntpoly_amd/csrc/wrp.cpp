@@ -198,6 +198,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "stored_zero_views") options().stored_zero_views = *value;
   else if (n == "pm_session") options().pm_session = *value;
   else if (n == "isr_chain") options().isr_chain = *value;
+  else if (n == "hpcp_step") options().hpcp_step = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -237,6 +238,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "stored_zero_views") return options().stored_zero_views;
   if (n == "pm_session") return options().pm_session;
   if (n == "isr_chain") return options().isr_chain;
+  if (n == "hpcp_step") return options().hpcp_step;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -308,6 +310,23 @@ void ntpoly_amd_isr_chain_counts(long long out[3]) {
 int ntpoly_amd_isr_chain_step(const int* ih_X, const int* ih_X2, const int* order, const double* a, const double* b, const double* c,
                               int* ih_Out1, int* ih_Out2) {
   return ps_isr_chain_step(*get_unpacked(ih_X), *get_unpacked(ih_X2), *order, *a, *b, *c, *get_unpacked(ih_Out1), *get_unpacked(ih_Out2)) ? 1 : 0;
+}
+// HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update)
+// since start: out[0] = trace passes fused, out[1] = updates fused, out[2] = updates refused (the vocabulary calls ran instead).  A
+// step that never reaches the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled
+// slab form, alignments that differ, a WH the dot cannot read as runs -- is neither fused nor counted as refused
+void ntpoly_amd_hpcp_step_counts(long long out[3]) {
+  for (int q = 0; q < 3; ++q) out[q] = hpcp_step_counts()[q];
+}
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: one fused HPCP update on caller-held real matrices D1, DDH
+// (what the loop's product D1 (I - D1) would be), D2DH (D1 DDH) and WH.  The operands are brought into slab form, the update runs,
+// the outputs are packed into the result handles: D1out = (D1 + 2 D2DH) + (-2 sigma) DDH, DHout = I - D1out as CopyMatrix,
+// IncrementMatrix(Identity, ., -1) and ScaleMatrix(., -1) build it, *energy = DotMatrix(D1out, WH).  Returns 1 when taken, 0 when
+// refused: every handle and *energy are then as they were.
+int ntpoly_amd_hpcp_update_step(const int* ih_D1, const int* ih_DDH, const int* ih_D2DH, const double* sigma, const int* ih_WH, int* ih_D1out,
+                                int* ih_DHout, double* energy) {
+  return ps_hpcp_update_step(*get_unpacked(ih_D1), *get_unpacked(ih_DDH), *get_unpacked(ih_D2DH), *sigma, *get_unpacked(ih_WH),
+                             *get_unpacked(ih_D1out), *get_unpacked(ih_DHout), energy) ? 1 : 0;
 }
 // PM purification on a slab-form iterate (option pm_session; engine.hpp ps_pm_sigma / ps_pm_update) since start: out[0] = sigma passes
 // fused, out[1] = updates fused, out[2] = stored zeros carried beside the runs (summed over the updates), out[3] = solves that left

@@ -1082,6 +1082,27 @@ def isr_chain_step(X, X2, order, a, b, c, Out1, Out2):
     return True if ok else None
 
 
+def hpcp_step_counts():
+    """HPCP purification with its traces and its update in one pass each (option hpcp_step; csrc/slab_extra.hip k_hpcp_traces /
+    k_hpcp_update) since start: trace passes fused, updates fused, updates refused (the vocabulary calls ran instead);
+    slab_algebra_counts() counts a fused update as the four merges / copies and the two other operations it replaces.  A step kept
+    out by a gate (the option off, no open real session, a complex operand, block form, a labelled slab form, alignments that
+    differ, a WH the dot cannot read as runs) is neither fused nor counted as refused"""
+    out = (C.c_longlong * 3)()
+    lib.ntpoly_amd_hpcp_step_counts(out)
+    return dict(traces=int(out[0]), updates=int(out[1]), refused=int(out[2]))
+
+
+def hpcp_update_step(D1, DDH, D2DH, sigma, WH, D1out, DHout):
+    """DIAGNOSTIC, inside `with solver_session():` -- one fused HPCP update on caller-held real matrices (DDH, D2DH: what the
+    products D1 (I - D1) and D1 DDH would be): D1out = (D1 + 2 D2DH) + (-2 sigma) DDH, DHout = I - D1out, both as the vocabulary at
+    threshold 0 builds them.  Returns the energy dot(D1out, WH) when taken; None: refused, every matrix as it was."""
+    e = C.c_double(0.0)
+    lib.ntpoly_amd_hpcp_update_step.restype = C.c_int
+    ok = lib.ntpoly_amd_hpcp_update_step(D1.ih, DDH.ih, D2DH.ih, d(sigma), WH.ih, D1out.ih, DHout.ih, C.byref(e))
+    return float(e.value) if ok else None
+
+
 def last_grouped_stats():
     """grouped LDS-hash path of the last SpGEMM (csrc/spgemm_grouped.hip)"""
     out = (C.c_longlong * 6)()
