@@ -209,6 +209,27 @@ bool ps_hpcp_update(PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, dou
 bool ps_hpcp_update_step(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& D1out,
                          PSMatrix& DHout, double* energy);
 long long* hpcp_step_counts();   // since start: [0] trace passes fused, [1] updates fused, [2] updates refused (past the gates: a gated step counts nowhere)
+// ScaleAndFold (DensityMatrixSolversModule.F90:1049-1081) inside a real slab session, option scale_fold_step (slab_extra.hip
+// k_saf_update / k_saf_dot_trace).
+// ps_saf_update: what ps_axpby(X2, X, a, b, 0) -- ScaleMatrix(X, b); IncrementMatrix(X2, X, a) -- leaves in X, values and pattern bit
+// for bit, *dot = dot(X, WH) of that X to rounding (another summation order; it only feeds the convergence monitor) and *trace =
+// ps_trace of that X with its bits, from one pass and one read-back.  ps_saf_dot_trace: the same two numbers of X as it stands, one
+// pass over X and WH.  Counted in slab_algebra_counts() as the calls replaced (the merge, the dot, the trace).
+// Collective: past gates that are the same on every rank (the option off, no open real session, a complex operand, dimensions
+// that differ, one matrix twice, block form) each rank enters ONE reduction of {dot, trace}; across ranks a rank whose panel is
+// not taken runs the calls on it and adds the partial sums they compute, and the call still returns true.  false: nothing done
+// (an operand still in compressed columns may have been turned into slab form) -- the caller makes the calls.  On one rank that
+// is also the answer where the panel is not taken: by a gate of its own that counts nothing (a session that has given up slab
+// form, a labelled slab form, every merged operand in compressed columns, alignments that differ, a WH that is neither a zero-free
+// slab form nor a read-only view), or refused and counted so (a or b not finite, an operand the slab form cannot hold, runs far
+// apart, a scaled entry that underflows to zero).
+bool ps_saf_update(PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, double* dot, double* trace);
+bool ps_saf_dot_trace(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace);
+// DIAGNOSTICS (the C ABI's ntpoly_amd_scale_fold_update_step / _dot_trace): the operands are brought into slab form where they are,
+// one pass runs, the new X is packed into Xout; false: refused or gated, everything as it was
+bool ps_saf_update_step(const PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, PSMatrix& Xout, double* dot, double* trace);
+bool ps_saf_dot_trace_step(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace);
+long long* scale_fold_step_counts();   // since start: [0] updates fused, [1] dot-and-trace passes fused, [2] refused (past the gates: a gated step counts nowhere)
 // solvers.cpp: this loop may take a complex operand like m in slab form (FMA arithmetic, complex tile kernel, complex_sessions)
 bool complex_slab_loop(const PSMatrix& m);
 void ps_slab_leave(PSMatrix& m);   // back to compressed columns (no-op for a matrix that is not in slab form)

@@ -102,6 +102,7 @@ struct EngineOptions {
   int pm_session = 1;          // PM purification, real operands, wherever a real slab session opens (one rank and column panels across ranks): the iterate stays in slab form, the scalars of sigma come from one pass over X and X2 without forming X - X2, the update a1 X + a2 X2 + a3 X3 is one pass over the three runs, and the stored zeros that compressed columns would carry (ScaleMatrix by a1 = 0 when sigma > 1/2, unfiltered tails) travel in a per-panel zero list next to the zero-free runs (slab_extra.hip k_pm_sigma / k_pm_update); 0: the loop on compressed columns, bit for bit as before
   int isr_chain = 1;           // the Taylor square-root loop (InverseSquareRoot / SquareRoot, orders 5 and 3) inside a slab session, real operands and complex ones in a complex session, one rank and column panels: the vocabulary calls between the product X X and the next product (order 5: four merges that build Temp2 and Temp; order 3: two that build the new X) are ONE pass over the runs of X and X X (slab_extra.hip k_sa_isr_chain) -- the same values and patterns bit for bit, one host read-back instead of up to four; a step the kernel refuses runs the calls as before.  0: the calls, one by one
   int hpcp_step = 1;           // HPCP purification, real operands, inside a real slab session (one rank and column panels across ranks): the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH with one read-back (slab_extra.hip k_hpcp_traces: the bits of two MatrixTrace calls), and the two merges into D1, the energy dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update: the values and patterns of the vocabulary calls at threshold 0 bit for bit; the energy is summed in another order and only feeds the convergence monitor) -- two read-backs per iteration instead of five; an update the kernel refuses runs the calls as before.  0: the eight calls, one by one
+  int scale_fold_step = 1;     // ScaleAndFold, real operands, inside a real slab session (one rank and column panels across ranks): behind the step's one product, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update: the values and pattern of the vocabulary calls at threshold 0 and the trace of slab_trace bit for bit; the energy is summed in another order and only feeds the convergence monitor); the scale branch, whose product's result is the new X, takes the energy and the trace from one pass over X and WH (k_saf_dot_trace) -- one read-back per step instead of two or three; a step the kernel refuses runs the calls as before.  0: the three calls, one by one
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
   int plan_fused = 1;          // the maxima and prefix sums of a slab step's plan in ONE launch (k_slab_offsets: every workgroup sums what lies before its part itself) instead of four to seven; 0: separate launches
@@ -326,6 +327,15 @@ bool slab_isr_chain3(const DevMat& X, const DevMat& X2, int32_t col_offset, DevM
 bool slab_hpcp_traces(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]);
 bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, double sigma, const DevMat& WH, int32_t col_offset, DevMat& OutD1,
                       DevMat& OutDH, double* energy);
+// ScaleAndFold on slab-form matrices (slab_extra.hip; real, square or column panels with col_offset = the panel's first column).
+// slab_saf_update: Out = b X + a X2 as a fresh slab-form matrix, the values and pattern of ScaleMatrix(X, b); IncrementMatrix(X2, X, a)
+// at threshold 0 bit for bit, *dot = the LOCAL dot(Out, WH) (WH: zero-free slab form or a read-only view; another summation order
+// than slab_dot's), *trace = the LOCAL sum of Out's diagonal with the bits slab_trace gives on Out.  slab_saf_dot_trace: the same
+// two sums of X as it stands, one pass over X and WH.  One host read-back each.  false: refused (an operand not in zero-free slab
+// form, labelled, different alignments, a or b not finite, runs far apart, a scaled entry that underflows to zero), nothing changed
+bool slab_saf_update(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
+                     double* trace);
+bool slab_saf_dot_trace(const DevMat& X, const DevMat& WH, int32_t col_offset, double* dot, double* trace);
 // PM purification on a slab-form iterate (slab_extra.hip).  The rows of each column that compressed columns would hold as STORED
 // ZEROS (a1 = 0 when sigma > 1/2, unfiltered tails that underflow) travel next to the zero-free runs: rows row[off[j] .. off[j + 1])
 // of column j, ascending, disjoint from the run's non-zeros.  off.p == nullptr: no such row.

@@ -1983,6 +1983,28 @@ void ps_pairwise(const PSMatrix& A, const PSMatrix& B, PSMatrix& C) {
 // DotMatrix_psr/psc (PSMatrixAlgebraModule.F90:387-410, distributed_algebra_includes/DotMatrix.f90):
 // sum conj(A).B; fused, no Hadamard temporary.
 namespace {
+// DotMatrix of the local panels of two matrices that are not in block form: ps_dot without its sum over the ranks
+void dot_local(const PSMatrix& A, const PSMatrix& B, double out[2]) {
+  unblock({&A, &B});
+  if (slab_on() && (A.loc.expanded() || B.loc.expanded()) && !A.cplx && !B.cplx) {
+    // (a rank whose operands left slab form computes its share from compressed columns: the sum over the ranks follows either way)
+    if (slab_enter(mut(A)) && slab_enter(mut(B)) && slab_dot(A.loc, B.loc, out)) {
+      g_slab_counts[2] += 1;
+      return;
+    }
+    slab_refused({&A, &B});
+  } else {
+    slab_pack_if({&A, &B});
+  }
+  if (A.cplx != B.cplx) {
+    PSMatrix Ac, Bc;
+    ps_to_complex(A, Ac);
+    ps_to_complex(B, Bc);
+    dot(Ac.loc, Bc.loc, out);
+  } else {
+    dot(A.loc, B.loc, out);
+  }
+}
 // extra (optional): one more number summed over the ranks by the reduction the dot makes anyway
 void ps_dot_with(const PSMatrix& A, const PSMatrix& B, double out[2], double* extra) {
   CommScope cs(A.grid);
@@ -2005,26 +2027,7 @@ void ps_dot_with(const PSMatrix& A, const PSMatrix& B, double out[2], double* ex
     }
     g_block_counts[1] += 1;
   }
-  unblock({&A, &B});
-  if (slab_on() && (A.loc.expanded() || B.loc.expanded()) && !A.cplx && !B.cplx) {
-    // (a rank whose operands left slab form computes its share from compressed columns: the sum over the ranks follows either way)
-    if (slab_enter(mut(A)) && slab_enter(mut(B)) && slab_dot(A.loc, B.loc, out)) {
-      g_slab_counts[2] += 1;
-      reduce();
-      return;
-    }
-    slab_refused({&A, &B});
-  } else {
-    slab_pack_if({&A, &B});
-  }
-  if (A.cplx != B.cplx) {
-    PSMatrix Ac, Bc;
-    ps_to_complex(A, Ac);
-    ps_to_complex(B, Bc);
-    dot(Ac.loc, Bc.loc, out);
-  } else {
-    dot(A.loc, B.loc, out);
-  }
+  dot_local(A, B, out);
   reduce();
 }
 }  // namespace
@@ -2046,6 +2049,107 @@ double ps_trace(const PSMatrix& A) {
   double t = trace_local(A);
   comm_allreduce_sum(&t, 1);
   return t;
+}
+
+long long* scale_fold_step_counts() {
+  static long long counts[3] = {0, 0, 0};
+  return counts;
+}
+namespace {
+// the gates of a fused ScaleAndFold call that are the same on every rank (X2: the fold branch's second operand, or none): a call
+// they keep out is neither fused nor refused, and past them every rank enters ONE reduction
+bool saf_gates(const PSMatrix& X, const PSMatrix* X2, const PSMatrix& WH) {
+  if (options().scale_fold_step == 0 || g_slab_depth == 0 || X.cplx || WH.cplx || X.dim != WH.dim || &X == &WH || blk_any({&X, &WH})) return false;
+  if (X2 && (X2->cplx || X2->dim != X.dim || X2 == &X || X2 == &WH || blk_any({X2}))) return false;
+  return world().active() || slab_on();
+}
+// the operands into slab form where they are, as ps_axpby and ps_dot do before their kernels (hpcp_update_enter).  *gated: what
+// cannot be fused on this rank without being a refusal -- a session that has given up slab form, a labelled slab form, in_loop:
+// merged operands all in compressed columns, a WH that is neither a zero-free slab form nor a read-only view, alignments that differ
+bool saf_enter(const PSMatrix& X, const PSMatrix* X2, const PSMatrix& WH, bool in_loop, bool* gated) {
+  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
+  *gated = true;
+  if (!slab_on() || labelled(X) || labelled(WH) || (X2 && labelled(*X2)) || WH.loc.blocked()) return false;
+  if (in_loop && !X.loc.expanded() && !(X2 && X2->loc.expanded())) return false;
+  if (!slab_enter(mut(WH)) || !(WH.loc.zero_free == 1 || WH.loc.slab->origin)) return false;
+  *gated = false;
+  if (!slab_enter(mut(X)) || (X2 && !slab_enter(mut(*X2)))) return false;
+  if (X2 && X.loc.slab->row_pad != X2->loc.slab->row_pad) { *gated = true; return false; }
+  return true;
+}
+// X2 given: the fold update into `out`; none: the sums of X as it stands.  sums = {dot, trace} of this rank's panel
+bool saf_local(const PSMatrix& X, const PSMatrix* X2, double a, double b, const PSMatrix& WH, bool in_loop, DevMat& out, double sums[2]) {
+  bool gated = false;
+  const bool taken = std::isfinite(a) && std::isfinite(b) && saf_enter(X, X2, WH, in_loop, &gated) &&
+                     (X2 ? slab_saf_update(X.loc, X2->loc, a, b, WH.loc, X.c0, out, &sums[0], &sums[1])
+                         : slab_saf_dot_trace(X.loc, WH.loc, X.c0, &sums[0], &sums[1]));
+  if (taken) {
+    if (X2) g_slab_counts[1] += 1;   // the merge
+    g_slab_counts[2] += 2;           // the dot, the next step's trace
+    scale_fold_step_counts()[X2 ? 0 : 1] += 1;
+  } else if (!gated) {
+    scale_fold_step_counts()[2] += 1;
+  }
+  return taken;
+}
+}  // namespace
+bool ps_saf_update(PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, double* dot, double* trace) {
+  CommScope cs(X.grid);
+  if (!saf_gates(X, &X2, WH)) return false;
+  DevMat o;
+  double s[2] = {0.0, 0.0};
+  if (saf_local(X, &X2, a, b, WH, true, o, s)) {
+    X.loc = std::move(o);
+  } else {
+    if (!world().active()) return false;
+    // (across ranks: this rank runs the calls on its panel and brings the partial sums they compute to the one reduction)
+    ps_axpby(X2, X, a, b, 0.0);
+    dot_local(X, WH, s);
+    s[1] = trace_local(X);
+  }
+  comm_allreduce_sum(s, 2);
+  *dot = s[0];
+  *trace = s[1];
+  return true;
+}
+bool ps_saf_dot_trace(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace) {
+  CommScope cs(X.grid);
+  if (!saf_gates(X, nullptr, WH)) return false;
+  DevMat none;
+  double s[2] = {0.0, 0.0};
+  if (!saf_local(X, nullptr, 1.0, 1.0, WH, true, none, s)) {
+    if (!world().active()) return false;
+    dot_local(X, WH, s);
+    s[1] = trace_local(X);
+  }
+  comm_allreduce_sum(s, 2);
+  *dot = s[0];
+  *trace = s[1];
+  return true;
+}
+bool ps_saf_update_step(const PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, PSMatrix& Xout, double* dot, double* trace) {
+  CommScope cs(X.grid);
+  if (!saf_gates(X, &X2, WH) || &Xout == &X || &Xout == &X2 || &Xout == &WH) return false;
+  DevMat o;
+  double s[2] = {0.0, 0.0};
+  if (!saf_local(X, &X2, a, b, WH, false, o, s)) return false;
+  pack(o);
+  install(Xout, X.grid, X.dim, false, X.c0, X.c1, std::move(o));
+  comm_allreduce_sum(s, 2);
+  *dot = s[0];
+  *trace = s[1];
+  return true;
+}
+bool ps_saf_dot_trace_step(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace) {
+  CommScope cs(X.grid);
+  if (!saf_gates(X, nullptr, WH)) return false;
+  DevMat none;
+  double s[2] = {0.0, 0.0};
+  if (!saf_local(X, nullptr, 1.0, 1.0, WH, false, none, s)) return false;
+  comm_allreduce_sum(s, 2);
+  *dot = s[0];
+  *trace = s[1];
+  return true;
 }
 
 double ps_norm(const PSMatrix& A) {

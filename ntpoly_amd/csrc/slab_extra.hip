@@ -1552,6 +1552,203 @@ bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, d
   return true;
 }
 
+// ------------------------------------------------------------------ ScaleAndFold: the update, the energy and the next trace of a step
+// DensityMatrixSolversModule.F90:1049-1081 builds around its one product X2 = X X, with the vocabulary at threshold 0,
+//   fold  (trace(X) <= trace):  x = (2 alpha) x;  x = x + (-alpha^2) x2;  energy = 2 dot(x, wh);  the next step begins with trace(x)
+//   scale (trace(X) >  trace):  the product's result becomes X;           energy = 2 dot(x, wh);  likewise
+// k_saf_update is the fold branch in one pass over the runs of X, X2 and WH; k_saf_dot_trace is what follows the product of the scale
+// branch, one pass over the new X and WH.  Both leave per column the pair (sum of x wh, the new X's diagonal entry): sum_pairs_async
+// sums the members of the pairs independently, so the second sum has the bits of slab_trace on the new X -- the trace steers the
+// next branch -- and the first is the dot's terms in another fixed order.
+namespace {
+// the aligned hull of the two runs, per column (nothing where both are empty)
+__global__ void k_saf_span(HpcpRuns A, HpcpRuns B, int n, int al, int32_t* __restrict__ span) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  int f = INT_MAX, l = -1;
+  if (A.last[j] >= A.first[j]) { f = min(f, A.first[j]); l = max(l, A.last[j]); }
+  if (B.last[j] >= B.first[j]) { f = min(f, B.first[j]); l = max(l, B.last[j]); }
+  span[j] = l >= 0 ? (l / al + 1) * al - f / al * al : 0;
+}
+// chunks of 64 rows whose loads (three operands each) are all requested before the first of them is used: HPCP_KC's depth with
+// three operands instead of four -- 12 loads per lane, a hull of up to 256 aligned rows is one trip
+constexpr int SAF_KC = 4;
+// One wave per column, lanes on consecutive rows of the aligned hull [a0, a1) of the runs of A = X and B = X2.  o1 = the new X into
+// the slot at base[j]; sb = 2 alpha and sa = -alpha^2 as the host rounds them: s = sb x (ScaleMatrix), o = s + sa x2 (IncrementMatrix
+// at threshold 0: isr_merge).  part[2 j] = sum over the column of o wh, a lane-strided sum then a wave sum (fixed shapes: the same
+// value every run); part[2 j + 1] = o on the diagonal row, what k_sa_diag reads from the new X (0 where the row is absent).
+// stat |= 1: a scaled entry underflows to zero; |= 2: runs far apart or a slot beyond the output buffer -- nothing is written for
+// that column (k_hpcp_update).
+__global__ __launch_bounds__(256) void k_saf_update(int n, HpcpRuns A, HpcpRuns B, HpcpRuns W, int col_offset, double sa, double sb, int al,
+                                                    const int64_t* __restrict__ base, IsrOut o1, int64_t bound, double* __restrict__ part,
+                                                    unsigned long long* __restrict__ stat) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id();
+  const int fA = A.first[j], lA = A.last[j], fB = B.first[j], lB = B.last[j], fW = W.first[j], lW = W.last[j];
+  const int dg = j + col_offset;
+  const bool anyA = lA >= fA, anyB = lB >= fB, anyW = lW >= fW;
+  const int64_t slot = base[j];
+  int f = INT_MAX, l = -1, own = 0;   // the hull of the two runs, and the rows their own aligned slots hold
+  if (anyA) { f = min(f, fA); l = max(l, lA); own += (lA / al + 1) * al - fA / al * al; }
+  if (anyB) { f = min(f, fB); l = max(l, lB); own += (lB / al + 1) * al - fB / al * al; }
+  const int a0 = l >= 0 ? f / al * al : 0, a1 = l >= 0 ? (l / al + 1) * al : 0;
+  // (runs far apart: their hull is not bounded by the two slots and the pads between them -- refused per column)
+  if (a1 - a0 > own + 2 * al || slot + (int64_t)(a1 - a0) > bound || l < 0) {
+    if (lane == 0) {
+      o1.first[j] = INT_MAX; o1.last[j] = -1; o1.count[j] = 0; o1.off[j] = slot;
+      part[2 * (size_t)j] = 0.0; part[2 * (size_t)j + 1] = 0.0;
+      if (l >= 0) atomicOr(stat, 2ull);   // (a column empty in both operands is an empty column of the result)
+    }
+    return;
+  }
+  const double* __restrict__ pa = anyA ? A.val + (A.off[j] - fA) : A.val;
+  const double* __restrict__ pb = anyB ? B.val + (B.off[j] - fB) : B.val;
+  const double* __restrict__ pw = anyW ? W.val + (W.off[j] - fW) : W.val;
+  double* __restrict__ d1 = static_cast<double*>(o1.val) + (slot - a0);
+  int uf = 0, c1 = 0, f1 = INT_MAX, l1 = -1;
+  double e = 0.0;
+  for (int rb = a0; rb < a1; rb += SAF_KC * WAVE) {
+    double va[SAF_KC], vb[SAF_KC], vw[SAF_KC];
+#pragma unroll
+    for (int k = 0; k < SAF_KC; ++k) {
+      const int r = rb + k * WAVE + lane;
+      va[k] = (anyA && r >= fA && r <= lA) ? pa[r] : 0.0;
+      vb[k] = (anyB && r >= fB && r <= lB) ? pb[r] : 0.0;
+      vw[k] = (anyW && r >= fW && r <= lW) ? pw[r] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < SAF_KC; ++k) {
+      const int r = rb + k * WAVE + lane;
+      if (r >= a1) continue;
+      const double x = va[k], x2 = vb[k];
+      bool ho;
+      const double s = __dmul_rn(sb, x);                                                          // ScaleMatrix(X, 2 alpha)
+      const double o = isr_merge<double>(1.0, s, x != 0.0, sa, x2, x2 != 0.0, &ho, &uf);          // IncrementMatrix(X2, X, -alpha^2)
+      d1[r] = o;
+      e = __dadd_rn(e, __dmul_rn(o, vw[k]));                                                      // DotMatrix(X, WH)
+      if (r == dg) part[2 * (size_t)j + 1] = o;                                                   // MatrixTrace(X) of the next step
+      c1 += ho ? 1 : 0; f1 = min(f1, ho ? r : INT_MAX); l1 = max(l1, ho ? r : -1);
+    }
+  }
+  c1 = (int)wave_sum_i64(c1);
+  f1 = wave_min_i32(f1);
+  l1 = wave_max_i32(l1);
+  e = wave_sum_f64(e);
+  if (__ballot(uf != 0) && lane == 0) atomicOr(stat, 1ull);
+  if (lane == 0) {
+    o1.first[j] = f1; o1.last[j] = l1; o1.count[j] = c1;
+    o1.off[j] = slot + (c1 ? f1 - a0 : 0);
+    part[2 * (size_t)j] = e;
+    if (dg < a0 || dg >= a1) part[2 * (size_t)j + 1] = 0.0;   // (inside the hull the lane on the diagonal row has written it)
+  }
+}
+// One wave per column of A = the new X: part[2 j] = sum over the rows both runs hold of x wh (lane-strided, then a wave sum),
+// part[2 j + 1] = X's diagonal entry as k_sa_diag reads it.  Writes nothing else.
+__global__ __launch_bounds__(256) void k_saf_dot_trace(int n, HpcpRuns A, HpcpRuns W, int col_offset, double* __restrict__ part) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id();
+  const int fA = A.first[j], lA = A.last[j], fW = W.first[j], lW = W.last[j], dg = j + col_offset;
+  const bool anyA = lA >= fA, anyW = lW >= fW;
+  double e = 0.0;
+  if (anyA && anyW) {
+    const int lo = max(fA, fW), hi = min(lA, lW);
+    const double* __restrict__ pa = A.val + (A.off[j] - fA);
+    const double* __restrict__ pw = W.val + (W.off[j] - fW);
+    for (int rb = lo; rb <= hi; rb += SAF_KC * WAVE) {
+      double va[SAF_KC], vw[SAF_KC];
+#pragma unroll
+      for (int k = 0; k < SAF_KC; ++k) {
+        const int r = rb + k * WAVE + lane;
+        va[k] = r <= hi ? pa[r] : 0.0;
+        vw[k] = r <= hi ? pw[r] : 0.0;
+      }
+#pragma unroll
+      for (int k = 0; k < SAF_KC; ++k) e = __dadd_rn(e, __dmul_rn(va[k], vw[k]));
+    }
+  }
+  e = wave_sum_f64(e);
+  if (lane == 0) {
+    part[2 * (size_t)j] = e;
+    part[2 * (size_t)j + 1] = (anyA && dg >= fA && dg <= lA) ? A.val[A.off[j] + (dg - fA)] : 0.0;
+  }
+}
+// WH of the energy's dot: a zero-free slab form or a read-only view (a view's stored zeros add nothing to the dot)
+bool saf_wh_ok(const DevMat& WH) {
+  return WH.expanded() && !WH.cplx && !WH.slab->labelled() && (WH.rows == WH.cols || slab_panels_ok()) && (WH.zero_free == 1 || WH.slab->origin);
+}
+}  // namespace
+
+bool slab_saf_update(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
+                     double* trace) {
+  if (!hpcp_operand(X) || !hpcp_operand(X2) || !saf_wh_ok(WH) || &X == &X2 || X.cols != X2.cols || X.cols != WH.cols || X.rows != X2.rows ||
+      X.rows != WH.rows || X.slab->row_pad != X2.slab->row_pad || !std::isfinite(a) || !std::isfinite(b))
+    return false;
+  const SlabForm &fa = *X.slab, &fb = *X2.slab;
+  const int n = X.cols, al = std::max(1, fa.row_pad);
+  std::unique_ptr<SlabForm> fo(new SlabForm());
+  // (the operands' slots and per column the pads of a hull)
+  const int64_t bound = fa.slots + fb.slots + 4LL * al * n;
+  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
+  fo->val.alloc((size_t)bound + kIndexSlack);
+  const IsrOut o{fo->val.p, fo->first.p, fo->last.p, fo->count.p, fo->off.p};
+  DevBuf<int32_t> span((size_t)n);
+  DevBuf<int64_t> base((size_t)n + 1);
+  DevBuf<unsigned long long> stat(1), tot(1);
+  DevBuf<double> part((size_t)2 * n), res(2);
+  stat.zero();
+  tot.zero();
+  const HpcpRuns ra = hpcp_runs(X), rb = hpcp_runs(X2);
+  hipLaunchKernelGGL(k_saf_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, n, al, span.p);
+  scan_i32_async(span.p, base.p, (int64_t)n);
+  hipLaunchKernelGGL(k_saf_update, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, hpcp_runs(WH), col_offset, a, b, al,
+                     base.p, o, bound, part.p, stat.p);
+  hipLaunchKernelGGL(k_sa_count_sum, dim3(std::max(1, std::min(256, cdiv(n, 1024)))), dim3(256), 0, stream(), fo->count.p, n, tot.p);
+  sum_pairs_async(part.p, n, res.p);
+  int64_t nnz = 0, slots = 0;
+  unsigned long long hs = 0;
+  double sums[2] = {0.0, 0.0};
+  {
+    ScalarFetch ft;
+    ft.add(tot.p, 1, &nnz);
+    ft.add(base.p + n, 1, &slots);
+    ft.add(stat.p, 1, &hs);
+    ft.add(res.p, 2, sums);
+    ft.run();
+  }
+  if (hs != 0) {
+    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+      std::fprintf(stderr, "[scale and fold update] refused:%s%s\n", (hs & 1ull) ? " a scaled entry underflows to zero" : "", (hs & 2ull) ? " runs far apart" : "");
+    return false;
+  }
+  DevMat R;
+  fo->row_pad = al;
+  fo->slots = slots;
+  R.rows = X.rows; R.cols = n; R.cplx = false; R.nnz = nnz; R.zero_free = 1;
+  R.slab = std::move(fo);
+  bump_matrix_value_epoch();   // (the merge it replaces is in place: slab_axpby counts it so)
+  Out = std::move(R);
+  *dot = sums[0];
+  *trace = sums[1];
+  return true;
+}
+
+bool slab_saf_dot_trace(const DevMat& X, const DevMat& WH, int32_t col_offset, double* dot, double* trace) {
+  if (!hpcp_operand(X) || !saf_wh_ok(WH) || X.cols != WH.cols || X.rows != WH.rows) return false;
+  const int n = X.cols;
+  DevBuf<double> part((size_t)2 * n), res(2);
+  hipLaunchKernelGGL(k_saf_dot_trace, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, hpcp_runs(X), hpcp_runs(WH), col_offset, part.p);
+  sum_pairs_async(part.p, n, res.p);
+  double sums[2] = {0.0, 0.0};
+  ScalarFetch ft;
+  ft.add(res.p, 2, sums);
+  ft.run();
+  *dot = sums[0];
+  *trace = sums[1];
+  return true;
+}
+
 long long slab_product_count(const DevMat& A, const DevMat& B) {
   if (!A.expanded() || !B.expanded() || A.cplx || B.cplx) return 0;
   const SlabForm &fa = *A.slab, &fb = *B.slab;

@@ -658,24 +658,38 @@ void solver_scale_and_fold(const PSMatrix& H, const PSMatrix& ISQ, double trace,
   f.begin_loop();
   int II;
   SlabSession slab(!X.cplx && !WH.cplx);
+  // Option scale_fold_step, inside the real session: behind the step's one product the fold branch's update, the energy and the
+  // NEXT step's trace are one pass (ps_saf_update), and the scale branch, whose product's result is the new X, takes the energy and
+  // the trace from one pass over X and WH (ps_saf_dot_trace).  A step that is not taken runs the calls, and the next step asks for
+  // its trace again.
+  const bool step = options().scale_fold_step != 0;
+  double trace_x = std::nan("");   // trace(X) as the last fused pass returned it; NaN: not known
   for (II = 1; II <= p.max_iterations; ++II) {                     // :1049-1081
-    const double trace_value = ps_trace(X);
-    double alpha;
+    const double trace_value = std::isnan(trace_x) ? ps_trace(X) : trace_x;
+    trace_x = std::nan("");
+    double alpha, dot;
+    bool fused;
     if (trace_value > trace) {
       alpha = 2.0 / (2.0 - Beta);
       ps_axpby(IMat, X, 1.0 - alpha, alpha, 0.0);                   // ScaleMatrix(X, alpha); IncrementMatrix(I, X, 1 - alpha)
       ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
       std::swap(X.loc, X2.loc);  // CopyMatrix(X_k2, X_k); X2 is scratch
+      fused = step && ps_saf_dot_trace(X, WH, &dot, &trace_x);
       Beta = (alpha * Beta + 1 - alpha) * (alpha * Beta + 1 - alpha);
       BetaBar = (alpha * BetaBar + 1 - alpha) * (alpha * BetaBar + 1 - alpha);
     } else {
       alpha = 2.0 / (1.0 + BetaBar);
       ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
-      ps_axpby(X2, X, -1.0 * alpha * alpha, 2 * alpha, 0.0);        // ScaleMatrix(X, 2 alpha); IncrementMatrix(X2, X, -alpha^2)
+      fused = step && ps_saf_update(X, X2, -1.0 * alpha * alpha, 2 * alpha, WH, &dot, &trace_x);
+      if (!fused) ps_axpby(X2, X, -1.0 * alpha * alpha, 2 * alpha, 0.0);   // ScaleMatrix(X, 2 alpha); IncrementMatrix(X2, X, -alpha^2)
       Beta = 2.0 * alpha * Beta - alpha * alpha * Beta * Beta;
       BetaBar = 2.0 * alpha * BetaBar - alpha * alpha * BetaBar * BetaBar;
     }
-    if (f.converged(2.0 * real_dot(X, WH), trace_value > trace ? -1.0 : 1.0, X)) break;
+    if (!fused) {
+      dot = real_dot(X, WH);
+      trace_x = std::nan("");
+    }
+    if (f.converged(2.0 * dot, trace_value > trace ? -1.0 : 1.0, X)) break;
   }
   slab.close();
   ps_slab_leave(X);

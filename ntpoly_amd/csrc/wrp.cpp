@@ -199,6 +199,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "pm_session") options().pm_session = *value;
   else if (n == "isr_chain") options().isr_chain = *value;
   else if (n == "hpcp_step") options().hpcp_step = *value;
+  else if (n == "scale_fold_step") options().scale_fold_step = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -239,6 +240,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "pm_session") return options().pm_session;
   if (n == "isr_chain") return options().isr_chain;
   if (n == "hpcp_step") return options().hpcp_step;
+  if (n == "scale_fold_step") return options().scale_fold_step;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -327,6 +329,27 @@ int ntpoly_amd_hpcp_update_step(const int* ih_D1, const int* ih_DDH, const int* 
                                 int* ih_DHout, double* energy) {
   return ps_hpcp_update_step(*get_unpacked(ih_D1), *get_unpacked(ih_DDH), *get_unpacked(ih_D2DH), *sigma, *get_unpacked(ih_WH),
                              *get_unpacked(ih_D1out), *get_unpacked(ih_DHout), energy) ? 1 : 0;
+}
+// ScaleAndFold with the update, the energy and the next step's trace in one pass (option scale_fold_step; engine.hpp ps_saf_update /
+// ps_saf_dot_trace) since start: out[0] = fold updates fused, out[1] = dot-and-trace passes fused (the scale branch), out[2] = passes
+// refused (the vocabulary calls ran instead).  A step that never reaches the kernel's decision -- the option off, no open real
+// session, a complex operand, block form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs -- is
+// neither fused nor counted as refused
+void ntpoly_amd_scale_fold_step_counts(long long out[3]) {
+  for (int q = 0; q < 3; ++q) out[q] = scale_fold_step_counts()[q];
+}
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: one fused fold update on caller-held real matrices X, X2
+// (what the loop's product X X would be) and WH.  The operands are brought into slab form, the pass runs, the new X is packed into
+// the result handle: Xout = b X + a X2 as ScaleMatrix(X, b); IncrementMatrix(X2, X, a) at threshold 0 build it, *dot =
+// DotMatrix(Xout, WH), *trace = MatrixTrace(Xout).  Returns 1 when taken, 0 when refused: every handle, *dot and *trace are then
+// as they were.
+int ntpoly_amd_scale_fold_update_step(const int* ih_X, const int* ih_X2, const double* a, const double* b, const int* ih_WH, int* ih_Xout,
+                                      double* dot, double* trace) {
+  return ps_saf_update_step(*get_unpacked(ih_X), *get_unpacked(ih_X2), *a, *b, *get_unpacked(ih_WH), *get_unpacked(ih_Xout), dot, trace) ? 1 : 0;
+}
+// ... and the pass of the scale branch: *dot = DotMatrix(X, WH) and *trace = MatrixTrace(X) of X as it stands, nothing written
+int ntpoly_amd_scale_fold_dot_trace(const int* ih_X, const int* ih_WH, double* dot, double* trace) {
+  return ps_saf_dot_trace_step(*get_unpacked(ih_X), *get_unpacked(ih_WH), dot, trace) ? 1 : 0;
 }
 // PM purification on a slab-form iterate (option pm_session; engine.hpp ps_pm_sigma / ps_pm_update) since start: out[0] = sigma passes
 // fused, out[1] = updates fused, out[2] = stored zeros carried beside the runs (summed over the updates), out[3] = solves that left

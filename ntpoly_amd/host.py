@@ -627,6 +627,14 @@ class DensityMatrixSolvers:
     def HPCP(H, ISQ, trace, Density, solver_parameters):
         return DensityMatrixSolvers._run(lib.HPCP_wrp, H, ISQ, trace, Density, solver_parameters)
 
+    @staticmethod
+    def ScaleAndFold(H, ISQ, trace, Density, homo, lumo, solver_parameters):
+        """rubensson2011nonmonotonic; homo / lumo: conservative estimates of the highest occupied and the lowest unoccupied
+        eigenvalue.  Returns the energy (the method computes no chemical potential)."""
+        e = C.c_double()
+        lib.ScaleAndFold_wrp(H.ih, ISQ.ih, d(trace), Density.ih, d(homo), d(lumo), C.byref(e), solver_parameters.ih)
+        return e.value
+
 
 def trs2_step(X, X2, WH, trace, threshold, trace_x=None):
     """one TRS2 iteration (what TRS2_wrp runs inside its loop) -> (sigma, energy, trace of the new X);
@@ -1101,6 +1109,36 @@ def hpcp_update_step(D1, DDH, D2DH, sigma, WH, D1out, DHout):
     lib.ntpoly_amd_hpcp_update_step.restype = C.c_int
     ok = lib.ntpoly_amd_hpcp_update_step(D1.ih, DDH.ih, D2DH.ih, d(sigma), WH.ih, D1out.ih, DHout.ih, C.byref(e))
     return float(e.value) if ok else None
+
+
+def scale_fold_step_counts():
+    """ScaleAndFold with the update, the energy and the next step's trace in one pass (option scale_fold_step; csrc/slab_extra.hip
+    k_saf_update / k_saf_dot_trace) since start: fold updates fused, dot-and-trace passes fused (the scale branch), passes refused
+    (the vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the calls it replaces (the merge of an
+    update, the dot, the next trace).  A step kept out by a gate (the option off, no open real session, a complex operand, block
+    form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs) is neither fused nor counted as refused"""
+    out = (C.c_longlong * 3)()
+    lib.ntpoly_amd_scale_fold_step_counts(out)
+    return dict(updates=int(out[0]), dot_traces=int(out[1]), refused=int(out[2]))
+
+
+def scale_fold_update_step(X, X2, a, b, WH, Xout):
+    """DIAGNOSTIC, inside `with solver_session():` -- one fused fold update of ScaleAndFold on caller-held real matrices (X2: what
+    the product X X would be): Xout = b X + a X2 as ScaleMatrix(X, b); IncrementMatrix(X2, X, a) at threshold 0 build it.  Returns
+    (dot(Xout, WH), trace(Xout)) when taken; None: refused, every matrix as it was."""
+    dot, tr = C.c_double(0.0), C.c_double(0.0)
+    lib.ntpoly_amd_scale_fold_update_step.restype = C.c_int
+    ok = lib.ntpoly_amd_scale_fold_update_step(X.ih, X2.ih, d(a), d(b), WH.ih, Xout.ih, C.byref(dot), C.byref(tr))
+    return (float(dot.value), float(tr.value)) if ok else None
+
+
+def scale_fold_dot_trace(X, WH):
+    """DIAGNOSTIC, inside `with solver_session():` -- the pass behind the product of ScaleAndFold's scale branch: (dot(X, WH),
+    trace(X)) from one pass over X and WH; None: refused."""
+    dot, tr = C.c_double(0.0), C.c_double(0.0)
+    lib.ntpoly_amd_scale_fold_dot_trace.restype = C.c_int
+    ok = lib.ntpoly_amd_scale_fold_dot_trace(X.ih, WH.ih, C.byref(dot), C.byref(tr))
+    return (float(dot.value), float(tr.value)) if ok else None
 
 
 def last_grouped_stats():
