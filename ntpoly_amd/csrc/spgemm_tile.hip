@@ -1089,6 +1089,47 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
     tk0 = min(tk0, col_first[c]);
     tk1 = max(tk1, col_last[c]);
   }
+  // One or four rows per lane: the energy in the summation order of TWO rows per lane, so that it does not depend on the option
+  // tile_rows.  The tiles above added their terms of dot(X, D) per lane and per tile of 16 R rows; here the block goes over its
+  // window once more in tiles of 32 rows at multiples of 32 (the tiles of R = 2, whose windows start there) -- lane (q, jj) adds
+  // rows 2 (4 v + q) + m of column jj in the order (v, m), then the wave, then the tiles in order: the chain of the R = 2
+  // epilogue, term for term (an element that was not kept, or deferred, is a zero in the slots and adds +0.0 there as here).
+  // The values are read back from the slots this block has just written; the trace keeps the sums of the tiles above.
+#ifndef NTP_TILE_STATIC
+  constexpr bool ESUM2 = EPI != 0 && R != 2;
+#else
+  constexpr bool ESUM2 = false;
+#endif
+  [[maybe_unused]] double ytrace = 0.0;
+  [[maybe_unused]] int NE = 0;
+  if constexpr (ESUM2) {
+    if (tid == 64) {
+      for (int t2 = 0; t2 < T; ++t2) ytrace = __dadd_rn(ytrace, tred[2 * t2 + 1]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (this wave's stores to the slots, then everybody's)
+    __syncthreads();
+    const int e0 = lo & ~31;
+    NE = (rend - e0 + 31) >> 5;                         // (<= 2 tmax: the doubles of tred)
+    for (int te = wave; te < NE; te += TILE_NW) {
+      const int r0e = e0 + 32 * te;
+      double es = 0.0;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          const int r = r0e + 2 * (4 * v + q) + m;
+          // (a row of the window whose tile stored this column: written above, all 16 R rows of it)
+          const bool has = r >= lo && r < rend && ((colmask[min(max(r - lo, 0) / TROWS, T - 1)] >> jj) & 1u) != 0u;
+          const double o = has ? __hip_atomic_load(orun + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+          const double dval = (has && r >= df && r <= dl) ? drz[r] : 0.0;
+          es = __dadd_rn(es, o != 0.0 ? __dmul_rn(o, dval) : 0.0);
+        }
+      }
+      es = wave_sum_f64(es);
+      if (lane == 0) tred[te] = es;
+    }
+    __syncthreads();
+  }
   if constexpr (EPI != 0) {
     if (tid == 0) {
       a.otoff[b] = tbase + (tk1 >= tk0 ? (int64_t)(tk0 - lo) * SLAB_J : 0);
@@ -1108,9 +1149,14 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
         y = __dadd_rn(y, red[2 * qq + 1]);
       }
 #else
-      for (int t2 = 0; t2 < T; ++t2) {
-        x = __dadd_rn(x, tred[2 * t2]);
-        y = __dadd_rn(y, tred[2 * t2 + 1]);
+      if constexpr (ESUM2) {
+        for (int t2 = 0; t2 < NE; ++t2) x = __dadd_rn(x, tred[t2]);
+        y = ytrace;
+      } else {
+        for (int t2 = 0; t2 < T; ++t2) {
+          x = __dadd_rn(x, tred[2 * t2]);
+          y = __dadd_rn(y, tred[2 * t2 + 1]);
+        }
       }
 #endif
       if constexpr (EPI == 2) {   // kept deferred elements, in (row, column) order (ranked above)
@@ -1186,6 +1232,11 @@ __global__ __launch_bounds__(TILE_NW* WAVE) __attribute__((amdgpu_waves_per_eu(R
 // (the two-block geometry is an experiment outside the product build, csrc/experiments/spgemm_tile2.hip: declined here)
 bool launch_spgemm_tile2(const TileLaunch&, int*) { return false; }
 #endif
+
+TileLaunchInfo& last_tile_launch() {
+  static TileLaunchInfo info;
+  return info;
+}
 
 int tile_rows() {
   const int r = options().tile_rows;
@@ -1285,6 +1336,7 @@ bool launch_spgemm_tile(const TileLaunch& L) {
   a.amax = skip ? L.amax : nullptr;
   a.amax_bytes = skip ? (uint32_t)L.amax_bytes : 0u;
   a.oamax = skip ? L.oamax : nullptr;
+  TileLaunchInfo inst;   // (the instantiation that was launched, for last_tile_launch())
   auto go = [&](auto epi_tag, auto nw_tag, auto r_tag, auto lab_tag, auto off_tag) {
     constexpr int E = decltype(epi_tag)::value, NW = decltype(nw_tag)::value, RR = decltype(r_tag)::value;
     constexpr bool LB = decltype(lab_tag)::value, OF = decltype(off_tag)::value;
@@ -1295,6 +1347,7 @@ bool launch_spgemm_tile(const TileLaunch& L) {
       raised = 150 * 1024;
     }
     hipLaunchKernelGGL((k_spgemm_tile<E, NW, RR, LB, OF>), dim3(xcd_grid(L.nblocks)), dim3(NW * WAVE), lds, stream(), a);
+    inst.epi = E; inst.nw = NW; inst.rows = RR; inst.labelled = LB ? 1 : 0; inst.off32 = OF ? 1 : 0;
   };
   auto by_off = [&](auto epi_tag, auto nw_tag, auto r_tag, auto lab_tag) {
     // (32-bit offsets: the default geometries only -- four or eight waves, one or two rows per lane)
@@ -1339,6 +1392,14 @@ bool launch_spgemm_tile(const TileLaunch& L) {
     if (FILE* fp = std::fopen((std::string(f) + ".blocks").c_str(), "wb")) { std::fwrite(hb.data(), 8, hb.size(), fp); std::fclose(fp); }
   }
 #endif
+  // the record of what was launched (tests: the path they name is the path that ran) -- the kernel's own tests on its arguments:
+  // brun = brun_val != nullptr, the buffer with bbytes != 0, pairs of rows with bpair in the instantiations of four or eight waves
+  TileLaunchInfo& rec = last_tile_launch();
+  inst.launches = rec.launches + 1;
+  inst.bsrc = a.brun_val == nullptr ? 0 : a.bbytes == 0u ? 1 : (a.bpair != 0 && (inst.nw == 4 || inst.nw == 8)) ? 3 : 2;
+  inst.max_kn = L.max_kn;
+  inst.skip = a.amax != nullptr ? 1 : 0;
+  rec = inst;
   return skip;
 }
 

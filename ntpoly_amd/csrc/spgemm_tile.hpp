@@ -66,6 +66,18 @@ inline int tile_expand_align() { return 16 * tile_rows(); }
 bool spgemm_tile_skips(const TileLaunch& a);
 // true: the tile-skip test ran (TileLaunch::amax) and the result's segment maxima were written to oamax
 bool launch_spgemm_tile(const TileLaunch& a);
+// What launch_spgemm_tile chose, for tests that must prove which path they reached: written at the end of every launch from the
+// values the launch itself used (the two-block experiment, launch_spgemm_tile2, is not recorded).
+struct TileLaunchInfo {
+  long long launches = 0;            // launches of k_spgemm_tile since the last ntpoly_amd_reset_spgemm_accum
+  // the last launch: the instantiation <EPI, NW, R, LAB, OFF32> ...
+  int epi = -1, nw = 0, rows = 0, labelled = 0, off32 = 0;
+  int bsrc = -1;                     // ... where the multiplier tile came from: 0 prepared tiles, 1 the runs through 64-bit pointers
+                                     // (bbytes == 0), 2 the runs through the buffer per element, 3 the runs as pairs of rows (bpair)
+  int max_kn = 0;                    // ... TileLaunch::max_kn
+  int skip = 0;                      // ... 1: the amax pointers were passed (the tile-skip test ran)
+};
+TileLaunchInfo& last_tile_launch();
 // The same multiply in the two-block geometry (spgemm_tile2.hip: pairs of column blocks share every fragment of A, the
 // multiplier rows stream through LDS in chunks): rows == 2, the right operand given by its runs (brun_*), not labelled.
 // false: not launched (the geometry cannot fit), call launch_spgemm_tile.  true: launched -- *fail (device, zeroed by the

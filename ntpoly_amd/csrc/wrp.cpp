@@ -9,6 +9,7 @@
 
 #include "engine.hpp"
 #include "spgemm_block.hpp"
+#include "spgemm_tile.hpp"
 #include "io.hpp"
 
 using namespace ntp;
@@ -457,6 +458,15 @@ void ntpoly_amd_tile2_counts(long long* out) {
 void ntpoly_amd_tile_skip_counts(long long* out) {
   for (int q = 0; q < 2; ++q) out[q] = tile_skip_counts()[q];
 }
+// what the last launch of the MFMA tile kernel chose (spgemm_tile.hpp TileLaunchInfo): out[0] = launches since the last
+// ntpoly_amd_reset_spgemm_accum; of the last one out[1..8] = epi, waves per workgroup, rows per lane, label-aware, 32-bit
+// offsets, source of the multiplier tile (0 prepared tiles, 1 runs through 64-bit pointers, 2 runs through the buffer per
+// element, 3 runs as pairs of rows), largest k range of a block, tile-skip test carried
+void ntpoly_amd_last_tile_launch(long long* out) {
+  const TileLaunchInfo& t = last_tile_launch();
+  out[0] = t.launches; out[1] = t.epi; out[2] = t.nw; out[3] = t.rows; out[4] = t.labelled; out[5] = t.off32;
+  out[6] = t.bsrc; out[7] = t.max_kn; out[8] = t.skip;
+}
 // GatherMatrixToProcess (PSMatrixModule.F90:1704-1808, distributed_includes/GatherMatrixToProcess.f90, GatherMatrixToAll.f90):
 // the whole distributed matrix as a LOCAL matrix (Matrix_lsr / Matrix_lsc of its scalar type) -- on every process
 // (*within_slice_id < 0: the _all variants) or on the process with that rank inside its slice only (the _id variants: data
@@ -554,6 +564,7 @@ void ntpoly_amd_reset_spgemm_accum() {
   flush_spgemm_timers();
   spgemm_accum() = SpgemmAccum();
   tile_skip_counts()[0] = tile_skip_counts()[1] = 0;
+  last_tile_launch().launches = 0;
 }
 // out: calls, products, nnz_c ; dout: alg_bytes, ms_numeric, ms_total
 void ntpoly_amd_get_spgemm_accum(long long* out, double* dout) {

@@ -951,6 +951,18 @@ def tile_skip_counts():
     return (int(out[0]), int(out[1]))
 
 
+def last_tile_launch():
+    """what the last launch of the MFMA tile kernel chose (csrc/spgemm_tile.hpp TileLaunchInfo), as a dict: `launches` since
+    reset_spgemm_accum, and of the last one the instantiation `epi` (0 product, 1 X*X, 2 2X - X*X), `nw` (waves per workgroup),
+    `rows` (per lane), `labelled`, `off32` (32-bit offsets), then `bsrc` (the multiplier tile: 0 prepared tiles, 1 runs through
+    64-bit pointers, 2 runs through the buffer per element, 3 runs as pairs of rows), `max_kn` (largest k range of a block) and
+    `skip` (1: the tile-skip test ran)"""
+    out = (C.c_longlong * 9)()
+    lib.ntpoly_amd_last_tile_launch(out)
+    names = ("launches", "epi", "nw", "rows", "labelled", "off32", "bsrc", "max_kn", "skip")
+    return {k: int(out[q]) for q, k in enumerate(names)}
+
+
 def band_scope_counts():
     """(solves run in a recovered band order across ranks, operands searched for a hidden band)"""
     out = (C.c_longlong * 2)()
