@@ -145,6 +145,22 @@ void ps_increment_identity(const PSMatrix& Identity, PSMatrix& B, double alpha);
 // done, the caller runs the sequence of merges and dots): the two traces, then P = Fx + sigma Gx
 bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx);
 bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P);
+// Option complex_trs4 (one rank, inside a session that takes complex operands): the two calls above take a complex X and X2 in
+// complex slab form (slab_extra.hip k_sa_trs4_c: the real kernel's arithmetic on each part of an entry, the values and pattern of
+// the four merges at threshold 0; the traces summed in another fixed order), and
+// ps_trs4_energy: *energy = the real part of dot(X, WH) from one pass over the runs of a complex slab-form X and WH as it stands --
+// slab form, a read-only view or compressed columns, stored zeros included (slab_dot_trace_c) -- instead of a dot that packs X.
+// false: not done, nothing changed -- the caller runs the vocabulary calls.  Gates (the option off, several ranks, no complex
+// session, block form, a labelled slab form, an operand still in compressed columns, sigma == 0 for the operand) count nothing;
+// past them a pass the kernel does not take (alignments that differ, hulls beyond the output's bound) counts as refused.
+// slab_algebra_counts() counts a fused pass as the real branch does.
+bool ps_trs4_energy(const PSMatrix& X, const PSMatrix& WH, double* energy);
+// DIAGNOSTICS (the C ABI's ntpoly_amd_trs4_chain_step / _trs4_energy): X and X2 (X) are brought into slab form where they are; both
+// traces and P, packed, from caller-held matrices -- real ones in any session, complex ones under the gates above; false: gated
+// or refused, every matrix as it was
+bool ps_trs4_chain_step(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P, double* trace_fx, double* trace_gx);
+bool ps_trs4_energy_step(const PSMatrix& X, const PSMatrix& WH, double* energy);
+long long* complex_trs4_counts();   // since start: [0] trace passes fused, [1] operands fused, [2] energies fused, [3] passes refused (past the gates: a gated pass counts nowhere)
 // PM purification with the iterate X kept in slab form (zero-free runs) and the rows compressed columns would hold as stored
 // zeros in Z (kernels.hpp ZeroList; option pm_session), inside a real slab session, one rank or column panels across ranks.
 // ps_pm_sigma: trace and dot(., X) of X - X2 merged at `threshold`, X - X2 not formed.  Collective: the two sums and "some rank

@@ -1241,9 +1241,50 @@ bool ps_recurrence_step(const PSMatrix& P, const PSMatrix& Tkm2, PSMatrix& Tk, P
   return true;
 }
 
+long long* complex_trs4_counts() {
+  static long long counts[4] = {0, 0, 0, 0};
+  return counts;
+}
+namespace {
+// the gates of the complex TRS4 passes (option complex_trs4): the option, one rank, an open session that takes complex operands,
+// complex operands of one dimension that are not in block form.  A pass they keep out is neither fused nor counted as refused
+bool ctrs4_on(std::initializer_list<const PSMatrix*> ms) {
+  if (options().complex_trs4 == 0 || world().active() || !slab_on() || !session_takes(true) || blk_any(ms)) return false;
+  const PSMatrix* first = *ms.begin();
+  for (const PSMatrix* m : ms)
+    if (!m->cplx || m->dim != first->dim || m->loc.blocked() || m->loc.loose()) return false;
+  return true;
+}
+// ... and in the loop: both merged operands in complex slab form as the products left them, neither labelled
+bool ctrs4_in_slab_form(const PSMatrix& X, const PSMatrix& X2) {
+  return &X != &X2 && X.loc.expanded() && X2.loc.expanded() && !X.loc.slab->labelled() && !X2.loc.slab->labelled();
+}
+bool ctrs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx) {
+  if (!ctrs4_on({&X, &X2}) || !ctrs4_in_slab_form(X, X2)) return false;
+  if (!slab_trs4_traces_c(X.loc, X2.loc, X.c0, trace_fx, trace_gx)) {
+    complex_trs4_counts()[3] += 1;
+    return false;
+  }
+  g_slab_counts[2] += 1;
+  complex_trs4_counts()[0] += 1;
+  return true;
+}
+bool ctrs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, DevMat& R) {
+  if (!ctrs4_on({&X, &X2}) || !ctrs4_in_slab_form(X, X2) || sigma == 0.0) return false;
+  if (!slab_trs4_operand_c(X.loc, X2.loc, sigma, X.c0, R)) {
+    complex_trs4_counts()[3] += 1;
+    return false;
+  }
+  g_slab_counts[1] += 1;
+  complex_trs4_counts()[1] += 1;
+  return true;
+}
+}  // namespace
+
 bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx) {
   CommScope cs(X.grid);
   if (blk_any({&X, &X2})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
+  if (X.cplx && X2.cplx) return ctrs4_traces(X, X2, trace_fx, trace_gx);   // (option complex_trs4; one rank)
   if (world().active()) {
     // (a session across ranks: the decision is collective -- the sums and "some rank declined" in one reduction)
     if (g_slab_depth == 0 || X.cplx || X2.cplx) return false;
@@ -1265,12 +1306,70 @@ bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, dou
 bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P) {
   CommScope cs(X.grid);
   if (blk_any({&X, &X2})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
+  if (X.cplx && X2.cplx) {   // (option complex_trs4; one rank)
+    DevMat R;
+    if (!ctrs4_operand(X, X2, sigma, R)) return false;
+    install(P, X.grid, X.dim, true, X.c0, X.c1, std::move(R));
+    return true;
+  }
   if (!slab_on() || !X.loc.expanded() || !X2.loc.expanded() || X.cplx || X2.cplx || sigma == 0.0) return false;
   DevMat R;
   if (!slab_trs4_operand(X.loc, X2.loc, sigma, X.c0, R)) return false;
   install(P, X.grid, X.dim, false, X.c0, X.c1, std::move(R));
   g_slab_counts[1] += 1;
   return true;
+}
+bool ps_trs4_energy(const PSMatrix& X, const PSMatrix& WH, double* energy) {
+  CommScope cs(X.grid);
+  // (WH as it stands: complex slab form, a read-only view, or compressed columns -- stored zeros add exact zeros to the sum)
+  if (&X == &WH || !ctrs4_on({&X, &WH}) || !X.loc.expanded() || X.loc.slab->labelled() || (WH.loc.expanded() && WH.loc.slab->labelled())) return false;
+  double dot[2] = {0.0, 0.0};
+  if (!sa_operand_c(X.loc) || !slab_dot_trace_c(X.loc, &WH.loc, X.c0, dot, nullptr)) {
+    complex_trs4_counts()[3] += 1;
+    return false;
+  }
+  *energy = dot[0];
+  g_slab_counts[2] += 1;
+  complex_trs4_counts()[2] += 1;
+  return true;
+}
+bool ps_trs4_chain_step(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P, double* trace_fx, double* trace_gx) {
+  CommScope cs(X.grid);
+  if (world().active() || !slab_on() || X.cplx != X2.cplx || X.dim != X2.dim || &X == &X2 || &P == &X || &P == &X2 || sigma == 0.0) return false;
+  if (X.cplx && !ctrs4_on({&X, &X2})) return false;
+  unblock({&X, &X2});
+  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
+  if (labelled(X) || labelled(X2)) return false;
+  const SlabKind& k = slab_kind(X.cplx);
+  double t[2] = {0.0, 0.0};
+  DevMat R;
+  const bool entered = k.enter(mut(X)) && k.enter(mut(X2));
+  const bool ok = entered && (X.cplx ? slab_trs4_traces_c(X.loc, X2.loc, X.c0, &t[0], &t[1]) && slab_trs4_operand_c(X.loc, X2.loc, sigma, X.c0, R)
+                                     : slab_trs4_traces(X.loc, X2.loc, X.c0, &t[0], &t[1]) && slab_trs4_operand(X.loc, X2.loc, sigma, X.c0, R));
+  if (!ok) {
+    if (X.cplx) complex_trs4_counts()[3] += 1;
+    return false;
+  }
+  pack(R);
+  install(P, X.grid, X.dim, X.cplx, X.c0, X.c1, std::move(R));
+  *trace_fx = t[0];
+  *trace_gx = t[1];
+  g_slab_counts[1] += 1;
+  g_slab_counts[2] += 1;
+  if (X.cplx) {
+    complex_trs4_counts()[0] += 1;
+    complex_trs4_counts()[1] += 1;
+  }
+  return true;
+}
+bool ps_trs4_energy_step(const PSMatrix& X, const PSMatrix& WH, double* energy) {
+  CommScope cs(X.grid);
+  if (&X == &WH || !ctrs4_on({&X, &WH})) return false;
+  if (!X.loc.expanded() && !slab_enter_c(mut(X), nullptr, false)) {
+    complex_trs4_counts()[3] += 1;
+    return false;
+  }
+  return ps_trs4_energy(X, WH, energy);
 }
 
 long long* isr_chain_counts() {

@@ -309,6 +309,154 @@ bool slab_trs4_operand(const DevMat& X, const DevMat& X2, double sigma, int32_t 
   return true;
 }
 
+// ------------------------------------------------------------------ ... and on complex operands (option complex_trs4)
+// Every scalar of the chain (4, -3, -2, 1, sigma) is real, and a real scalar times a complex value is a componentwise product:
+// each part of an entry goes through trs4_elem on its own, the identity adding (1, 0) on the diagonal row.  The traces are the
+// real parts of DotMatrix = sum conj(x2) fx and sum conj(x2) gx, x2.re f.re + x2.im f.im with each product and each sum rounded
+// (the terms of k_sa_dot_trace_c); an entry of P exists where either part is not zero (the complex merges keep an entry by its
+// modulus at threshold 0).  Runs of double2: 16 bytes per lane, consecutive lanes on consecutive rows.  No LDS, no scratch.
+namespace {
+struct Trs4ElemC {
+  double2 fx, gx;
+};
+__device__ inline Trs4ElemC trs4_elem_c(double2 x, double2 x2, double d) {
+  const Trs4Elem re = trs4_elem(x.x, x2.x, d), im = trs4_elem(x.y, x2.y, 0.0);
+  Trs4ElemC e;
+  e.fx = make_double2(re.fx, im.fx);
+  e.gx = make_double2(re.gx, im.gx);
+  return e;
+}
+// k_sa_trs4 on runs of (re, im) pairs; base, bound and the slots of `out` count double2
+template <int MODE>
+__global__ __launch_bounds__(256) void k_sa_trs4_c(int n, const int32_t* __restrict__ fa, const int32_t* __restrict__ la,
+                                                   const int64_t* __restrict__ offa, const double2* __restrict__ va,
+                                                   const int32_t* __restrict__ fb, const int32_t* __restrict__ lb,
+                                                   const int64_t* __restrict__ offb, const double2* __restrict__ vb, int col_offset,
+                                                   double sigma, int al, const int64_t* __restrict__ base, double* __restrict__ part,
+                                                   double2* __restrict__ out, int32_t* __restrict__ ofirst, int32_t* __restrict__ olast,
+                                                   int32_t* __restrict__ ocount, int64_t* __restrict__ ooff, int64_t bound,
+                                                   unsigned long long* __restrict__ stat) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int lane = lane_id();
+  const int fA = fa[j], lA = la[j], fB = fb[j], lB = lb[j], dg = j + col_offset;
+  const bool anyA = lA >= fA, anyB = lB >= fB;
+  int f = dg, l = dg;   // (the identity's entry is always there)
+  if (anyA) { f = min(f, fA); l = max(l, lA); }
+  if (anyB) { f = min(f, fB); l = max(l, lB); }
+  const int a0 = f / al * al, a1 = (l / al + 1) * al;
+  const double2* __restrict__ pa = anyA ? va + (offa[j] - fA) : va;
+  const double2* __restrict__ pb = anyB ? vb + (offb[j] - fB) : vb;
+  const double2 zero = make_double2(0.0, 0.0);
+  if (MODE == 0) {
+    double s0 = 0.0, s1 = 0.0;
+    for (int r = a0 + lane; r < a1; r += WAVE) {
+      const double2 x = (anyA && r >= fA && r <= lA) ? pa[r] : zero;
+      const double2 x2 = (anyB && r >= fB && r <= lB) ? pb[r] : zero;
+      const Trs4ElemC e = trs4_elem_c(x, x2, r == dg ? 1.0 : 0.0);
+      s0 = __dadd_rn(s0, __dadd_rn(__dmul_rn(x2.x, e.fx.x), __dmul_rn(x2.y, e.fx.y)));
+      s1 = __dadd_rn(s1, __dadd_rn(__dmul_rn(x2.x, e.gx.x), __dmul_rn(x2.y, e.gx.y)));
+    }
+    s0 = wave_sum_f64(s0);
+    s1 = wave_sum_f64(s1);
+    if (lane == 0) { part[2 * (size_t)j] = s0; part[2 * (size_t)j + 1] = s1; }
+  } else {
+    const int64_t slot = base[j];
+    if (slot + (int64_t)(a1 - a0) > bound) {   // (runs far apart: the union extent does not fit the output -- refused by the host)
+      if (lane == 0) { ofirst[j] = INT_MAX; olast[j] = -1; ocount[j] = 0; ooff[j] = slot; atomicOr(stat, 2ull); }
+      return;
+    }
+    double2* __restrict__ dst = out + (slot - a0);
+    int cnt = 0, kf = INT_MAX, kl = -1;
+    for (int r = a0 + lane; r < a1; r += WAVE) {
+      const double2 x = (anyA && r >= fA && r <= lA) ? pa[r] : zero;
+      const double2 x2 = (anyB && r >= fB && r <= lB) ? pb[r] : zero;
+      const Trs4ElemC e = trs4_elem_c(x, x2, r == dg ? 1.0 : 0.0);
+      const double pr = __dadd_rn(e.fx.x, __dmul_rn(sigma, e.gx.x)), pi = __dadd_rn(e.fx.y, __dmul_rn(sigma, e.gx.y));
+      const bool keep = pr != 0.0 || pi != 0.0;
+      dst[r] = keep ? make_double2(pr, pi) : zero;
+      cnt += keep ? 1 : 0;
+      kf = min(kf, keep ? r : INT_MAX);
+      kl = max(kl, keep ? r : -1);
+    }
+    cnt = (int)wave_sum_i64(cnt);
+    kf = wave_min_i32(kf);
+    kl = wave_max_i32(kl);
+    if (lane == 0) {
+      ofirst[j] = kf; olast[j] = kl; ocount[j] = cnt;
+      ooff[j] = slot + (cnt ? kf - a0 : 0);
+    }
+  }
+}
+}  // namespace
+
+bool trs4_operands_c(const DevMat& X, const DevMat& X2) {
+  auto ok = [](const DevMat& M) { return sa_operand_c(M) && M.zero_free == 1; };   // (no labelled form, no read-only view)
+  return ok(X) && ok(X2) && X.cols == X2.cols && X.rows == X2.rows && X.slab->row_pad == X2.slab->row_pad;
+}
+
+bool slab_trs4_traces_c(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx) {
+  if (!trs4_operands_c(X, X2)) return false;
+  const SlabForm &fa = *X.slab, &fb = *X2.slab;
+  const int n = X.cols;
+  DevBuf<double> part((size_t)2 * n), res(2);
+  hipLaunchKernelGGL((k_sa_trs4_c<0>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
+                     reinterpret_cast<const double2*>(fa.val.p), fb.first.p, fb.last.p, fb.off.p, reinterpret_cast<const double2*>(fb.val.p),
+                     col_offset, 0.0, std::max(1, fa.row_pad), (const int64_t*)nullptr, part.p, (double2*)nullptr, (int32_t*)nullptr,
+                     (int32_t*)nullptr, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (unsigned long long*)nullptr);
+  sum_pairs_async(part.p, n, res.p);
+  unsigned long long h[2] = {0, 0};
+  ScalarFetch ft;
+  ft.add(res.p, 2, h);
+  ft.run();
+  double d[2];
+  std::memcpy(d, h, sizeof(h));
+  *trace_fx = d[0];
+  *trace_gx = d[1];
+  return true;
+}
+
+bool slab_trs4_operand_c(const DevMat& X, const DevMat& X2, double sigma, int32_t col_offset, DevMat& Out) {
+  if (!trs4_operands_c(X, X2)) return false;
+  const SlabForm &fa = *X.slab, &fb = *X2.slab;
+  const int n = X.cols, al = std::max(1, fa.row_pad);
+  std::unique_ptr<SlabForm> fo(new SlabForm());
+  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
+  DevBuf<int32_t> span((size_t)n);
+  DevBuf<int64_t> base((size_t)n + 1);
+  hipLaunchKernelGGL(k_sa_trs4_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fb.first.p, fb.last.p, n, col_offset,
+                     al, span.p);
+  scan_i32_async(span.p, base.p, (int64_t)n);
+  const int64_t bound = fa.slots + fb.slots + 4LL * al * n;   // (slots of (re, im) pairs)
+  fo->val.alloc(((size_t)bound + kIndexSlack) * 2);
+  DevBuf<unsigned long long> stat(1);
+  stat.zero();
+  hipLaunchKernelGGL((k_sa_trs4_c<1>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
+                     reinterpret_cast<const double2*>(fa.val.p), fb.first.p, fb.last.p, fb.off.p, reinterpret_cast<const double2*>(fb.val.p),
+                     col_offset, sigma, al, base.p, (double*)nullptr, reinterpret_cast<double2*>(fo->val.p), fo->first.p, fo->last.p,
+                     fo->count.p, fo->off.p, bound, stat.p);
+  DevBuf<unsigned long long> tot(1);
+  tot.zero();
+  hipLaunchKernelGGL(k_sa_count_sum, dim3(std::max(1, std::min(256, cdiv(n, 1024)))), dim3(256), 0, stream(), fo->count.p, n, tot.p);
+  int64_t nnz = 0, slots = 0;
+  unsigned long long hs = 0;
+  {
+    ScalarFetch ft;
+    ft.add(tot.p, 1, &nnz);
+    ft.add(base.p + n, 1, &slots);
+    ft.add(stat.p, 1, &hs);
+    ft.run();
+  }
+  if (hs != 0) return false;   // (a union extent beyond the output buffer: runs far apart -- the caller runs the vocabulary calls)
+  fo->row_pad = al;
+  fo->slots = slots;
+  DevMat R;
+  R.rows = X.rows; R.cols = n; R.cplx = true; R.nnz = nnz; R.zero_free = 1;
+  R.slab = std::move(fo);
+  Out = std::move(R);
+  return true;
+}
+
 // ------------------------------------------------------------------ MatrixNorm(alpha A + beta B) without the sum
 // The loops of SignFunction, Invert and the square roots build a difference (Out - Temp2, I - Temp1, I - X) only to
 // take its norm (max column abs-sum) for the convergence test.  One pass over the two runs of every column: the

@@ -403,7 +403,11 @@ void solver_trs4(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
   f.start_iterate(X);
   f.begin_loop();
   int II;
-  SlabSession slab(!X.cplx && !WH.cplx);   // (the loop's matrices stay in slab form between its operations where they can)
+  // Option complex_trs4, a complex Hamiltonian on one rank without process slices: a complex session -- the products on the complex
+  // tile kernel, the chain below on complex runs (ps_trs4_traces / ps_trs4_operand), the energy from one pass (ps_trs4_energy)
+  const bool complex_session = X.cplx && WH.cplx && complex_slab_loop(X) && options().complex_trs4 != 0 && !world().active() &&
+                               !(X.grid && X.grid->num_slices > 1);
+  SlabSession slab((!X.cplx && !WH.cplx) || complex_session, false, complex_session);   // (the loop's matrices stay in slab form between its operations where they can)
   for (II = 1; II <= p.max_iterations; ++II) {                     // :586-638
     ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
     // Fx = 4 X - 3 X2, Gx = I - 2 X + X2 and their traces against X2: in a slab session one pass over X and X2 leaves the
@@ -437,7 +441,9 @@ void solver_trs4(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
     // :630-631 IncrementMatrix(TempMat, X_k, -1) is overwritten by the copy that follows it; the copy itself is a
     // hand-over here (Temp is rebuilt in every iteration)
     std::swap(X.loc, Temp.loc);
-    if (f.converged(real_dot(X, WH), sigma_array[(size_t)II], X)) break;
+    double energy_value = 0.0;
+    if (!(complex_session && ps_trs4_energy(X, WH, &energy_value))) energy_value = real_dot(X, WH);
+    if (f.converged(energy_value, sigma_array[(size_t)II], X)) break;
   }
   const int total_iterations = II - 1;
   slab.close();

@@ -201,6 +201,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "isr_chain") options().isr_chain = *value;
   else if (n == "hpcp_step") options().hpcp_step = *value;
   else if (n == "scale_fold_step") options().scale_fold_step = *value;
+  else if (n == "complex_trs4") options().complex_trs4 = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -242,6 +243,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "isr_chain") return options().isr_chain;
   if (n == "hpcp_step") return options().hpcp_step;
   if (n == "scale_fold_step") return options().scale_fold_step;
+  if (n == "complex_trs4") return options().complex_trs4;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -351,6 +353,26 @@ int ntpoly_amd_scale_fold_update_step(const int* ih_X, const int* ih_X2, const d
 // ... and the pass of the scale branch: *dot = DotMatrix(X, WH) and *trace = MatrixTrace(X) of X as it stands, nothing written
 int ntpoly_amd_scale_fold_dot_trace(const int* ih_X, const int* ih_WH, double* dot, double* trace) {
   return ps_saf_dot_trace_step(*get_unpacked(ih_X), *get_unpacked(ih_WH), dot, trace) ? 1 : 0;
+}
+// Complex TRS4 in a complex slab session (option complex_trs4; engine.hpp ps_trs4_traces / ps_trs4_operand / ps_trs4_energy on
+// complex operands) since start: out[0] = trace passes fused, out[1] = operands Fx + sigma Gx fused, out[2] = energies fused, out[3] =
+// passes refused (the vocabulary calls ran instead).  A pass that never reaches the kernel's decision -- the option off, no open
+// complex session, several ranks, block form, a labelled slab form -- is neither fused nor counted as refused
+void ntpoly_amd_complex_trs4_counts(long long out[4]) {
+  for (int q = 0; q < 4; ++q) out[q] = complex_trs4_counts()[q];
+}
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: TRS4's chain on caller-held matrices X and X2 (what the
+// loop's product X X would be), real or -- in a session with complex_ok and option complex_trs4 -- complex.  The two operands are
+// brought into slab form, *trace_fx = dot(X2, 4 X - 3 X2) and *trace_gx = dot(X2, I - 2 X + X2) (their real parts) come from the
+// first pass, P = (4 X - 3 X2) + sigma (I - 2 X + X2) from the second and is packed into the result handle.  Returns 1 when taken,
+// 0 when refused or gated (sigma == 0 among the gates): every handle and both traces are then as they were.
+int ntpoly_amd_trs4_chain_step(const int* ih_X, const int* ih_X2, const double* sigma, int* ih_P, double* trace_fx, double* trace_gx) {
+  return ps_trs4_chain_step(*get_unpacked(ih_X), *get_unpacked(ih_X2), *sigma, *get_unpacked(ih_P), trace_fx, trace_gx) ? 1 : 0;
+}
+// ... and the energy pass of the complex loop: *energy = the real part of DotMatrix(X, WH) for a complex X, brought into slab form,
+// and a complex WH as it stands (slab form, a read-only view or compressed columns), nothing written
+int ntpoly_amd_trs4_energy(const int* ih_X, const int* ih_WH, double* energy) {
+  return ps_trs4_energy_step(*get_unpacked(ih_X), *get_unpacked(ih_WH), energy) ? 1 : 0;
 }
 // PM purification on a slab-form iterate (option pm_session; engine.hpp ps_pm_sigma / ps_pm_update) since start: out[0] = sigma passes
 // fused, out[1] = updates fused, out[2] = stored zeros carried beside the runs (summed over the updates), out[3] = solves that left

@@ -1153,6 +1153,37 @@ def scale_fold_dot_trace(X, WH):
     return (float(dot.value), float(tr.value)) if ok else None
 
 
+def complex_trs4_counts():
+    """complex TRS4 in a complex slab session (option complex_trs4; csrc/slab_extra.hip k_sa_trs4_c) since start: trace passes
+    fused, operands Fx + sigma Gx fused, energies fused, passes refused (the vocabulary calls ran instead); slab_algebra_counts()
+    counts a fused pass as the real branch does.  A pass kept out by a gate (the option off, no open complex session, several
+    ranks, block form, a labelled slab form) is neither fused nor counted as refused"""
+    out = (C.c_longlong * 4)()
+    lib.ntpoly_amd_complex_trs4_counts(out)
+    return dict(traces=int(out[0]), operands=int(out[1]), energies=int(out[2]), refused=int(out[3]))
+
+
+def trs4_chain_step(X, X2, sigma, P):
+    """DIAGNOSTIC, inside `with solver_session():` -- TRS4's chain on caller-held matrices, real or (option complex_trs4) complex
+    (X2: what the product X X would be): P = (4 X - 3 X2) + sigma (I - 2 X + X2) as the vocabulary at threshold 0 builds it.
+    Returns (dot(X2, 4 X - 3 X2), dot(X2, I - 2 X + X2)), the real parts, when taken; None: refused or gated (sigma == 0), every
+    matrix as it was."""
+    tf, tg = C.c_double(0.0), C.c_double(0.0)
+    lib.ntpoly_amd_trs4_chain_step.restype = C.c_int
+    ok = lib.ntpoly_amd_trs4_chain_step(X.ih, X2.ih, d(sigma), P.ih, C.byref(tf), C.byref(tg))
+    return (float(tf.value), float(tg.value)) if ok else None
+
+
+def trs4_energy(X, WH):
+    """DIAGNOSTIC, inside `with solver_session():` -- the energy pass of the complex TRS4 loop (option complex_trs4): the real part
+    of dot(X, WH) from one pass over the runs of a complex X and WH as it stands (slab form or compressed columns, stored zeros
+    included); None: refused or gated."""
+    e = C.c_double(0.0)
+    lib.ntpoly_amd_trs4_energy.restype = C.c_int
+    ok = lib.ntpoly_amd_trs4_energy(X.ih, WH.ih, C.byref(e))
+    return float(e.value) if ok else None
+
+
 def last_grouped_stats():
     """grouped LDS-hash path of the last SpGEMM (csrc/spgemm_grouped.hip)"""
     out = (C.c_longlong * 6)()
