@@ -224,6 +224,20 @@ bool ps_hpcp_update(PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, dou
 // the new D1 and DH are packed into D1out and DHout
 bool ps_hpcp_update_step(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& D1out,
                          PSMatrix& DHout, double* energy);
+// Option complex_hpcp (one rank, inside a session that takes complex operands): ps_hpcp_traces, ps_hpcp_update and
+// ps_hpcp_update_step take COMPLEX operands (slab_extra.hip k_hpcp_traces<double2> / k_hpcp_update<double2, .>: the traces sum the
+// real parts of the diagonals in the order of the real pass; the update is the real kernel's chain on each part of an entry, the
+// values and patterns of the vocabulary calls at threshold 0 bit for bit, *energy = Re dot(D1, WH) to rounding).  No collective.
+// Gates (complex_hpcp off -- hpcp_step is for real operands only --, several ranks, no complex session, block or loose form, a
+// labelled slab form, operands that are not all complex, of one dimension and distinct; in the loop: operands not left in slab
+// form by the products; alignments that differ, a WH that becomes neither a zero-free slab form nor a read-only view) count
+// nothing; past them a sigma that is zero or not finite, an operand the kernel's rules exclude once it is in slab form (stored
+// zeros in a merged operand) and a non-zero status (runs far apart, an underflow) count as refused in complex_hpcp_counts().
+// slab_algebra_counts() counts a fused pass as the real branch does; hpcp_step_counts() never counts a complex pass.
+long long* complex_hpcp_counts();   // since start: [0] trace passes fused, [1] updates fused, [2] passes refused
+// DIAGNOSTIC (the C ABI's ntpoly_amd_hpcp_traces_step): both matrices are brought into slab form where they are and the fused trace
+// pass runs, real (option hpcp_step) or complex (option complex_hpcp); false: gated or refused, out as it was
+bool ps_hpcp_traces_step(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]);
 long long* hpcp_step_counts();   // since start: [0] trace passes fused, [1] updates fused, [2] updates refused (past the gates: a gated step counts nowhere)
 // ScaleAndFold (DensityMatrixSolversModule.F90:1049-1081) inside a real slab session, option scale_fold_step (slab_extra.hip
 // k_saf_update / k_saf_dot_trace).

@@ -104,6 +104,7 @@ struct EngineOptions {
   int hpcp_step = 1;           // HPCP purification, real operands, inside a real slab session (one rank and column panels across ranks): the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH with one read-back (slab_extra.hip k_hpcp_traces: the bits of two MatrixTrace calls), and the two merges into D1, the energy dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update: the values and patterns of the vocabulary calls at threshold 0 bit for bit; the energy is summed in another order and only feeds the convergence monitor) -- two read-backs per iteration instead of five; an update the kernel refuses runs the calls as before.  0: the eight calls, one by one
   int scale_fold_step = 1;     // ScaleAndFold, real operands, inside a real slab session (one rank and column panels across ranks): behind the step's one product, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update: the values and pattern of the vocabulary calls at threshold 0 and the trace of slab_trace bit for bit; the energy is summed in another order and only feeds the convergence monitor); the scale branch, whose product's result is the new X, takes the energy and the trace from one pass over X and WH (k_saf_dot_trace) -- one read-back per step instead of two or three; a step the kernel refuses runs the calls as before.  0: the three calls, one by one
   int complex_trs4 = 0;        // complex TRS4 on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and the second product's operand stay runs of (re, im) pairs between the products on the complex tile kernel --, the traces dot(X2, Fx) and dot(X2, Gx) come from ONE pass over X and X X without building Fx and Gx, the operand Fx + sigma Gx from a second one (slab_extra.hip k_sa_trs4_c: the real kernel's arithmetic on each part, the values and pattern of the four merges at threshold 0), and the energy Re dot(X, WH) from one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  0 (default; measured 4.51 against 10.62 ms per iteration on configs[4]'s operand, profiles/README.md 130, but the rule that decides defaults also wants option 0 and the parent commit equal within the block spread, which one run missed by a hair): the loop on compressed columns, bit for bit as before
+  int complex_hpcp = 0;        // complex HPCP on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- D1, DH and both products stay runs of (re, im) pairs between the products on the complex tile kernel --, the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH (slab_extra.hip k_hpcp_traces<double2>: the real parts), and the two merges into D1, the energy Re dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update<double2, .>: the real kernel's chain on each part of an entry, the values and patterns of the vocabulary calls at threshold 0); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of hpcp_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
   int plan_fused = 1;          // the maxima and prefix sums of a slab step's plan in ONE launch (k_slab_offsets: every workgroup sums what lies before its part itself) instead of four to seven; 0: separate launches
@@ -335,6 +336,15 @@ bool slab_isr_chain3(const DevMat& X, const DevMat& X2, int32_t col_offset, DevM
 bool slab_hpcp_traces(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]);
 bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, double sigma, const DevMat& WH, int32_t col_offset, DevMat& OutD1,
                       DevMat& OutDH, double* energy);
+// the same two passes on COMPLEX slab-form operands (option complex_hpcp; k_hpcp_traces<double2>, k_hpcp_update<double2, .>: runs of
+// (re, im) pairs, 16 bytes per lane).  The traces are the sums of the real parts of the diagonals (MatrixTrace); every scalar of
+// the update is real, so each merge scales and adds part by part and keeps an entry where either part is not zero -- the values
+// and patterns of the vocabulary calls on complex matrices at threshold 0 bit for bit; *energy = Re dot(OutD1, WH), each product
+// and each pair's sum rounded (the terms of slab_dot_trace_c, in another fixed order).  The three merged operands: sa_operand_c and
+// zero-free; WH: zero-free or a read-only view; slots and the bound count pairs.  false: refused, nothing changed
+bool slab_hpcp_traces_c(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]);
+bool slab_hpcp_update_c(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, double sigma, const DevMat& WH, int32_t col_offset, DevMat& OutD1,
+                        DevMat& OutDH, double* energy);
 // ScaleAndFold on slab-form matrices (slab_extra.hip; real, square or column panels with col_offset = the panel's first column).
 // slab_saf_update: Out = b X + a X2 as a fresh slab-form matrix, the values and pattern of ScaleMatrix(X, b); IncrementMatrix(X2, X, a)
 // at threshold 0 bit for bit, *dot = the LOCAL dot(Out, WH) (WH: zero-free slab form or a read-only view; another summation order

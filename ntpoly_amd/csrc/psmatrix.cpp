@@ -1248,13 +1248,15 @@ long long* complex_trs4_counts() {
 namespace {
 // the gates of the complex TRS4 passes (option complex_trs4): the option, one rank, an open session that takes complex operands,
 // complex operands of one dimension that are not in block form.  A pass they keep out is neither fused nor counted as refused
-bool ctrs4_on(std::initializer_list<const PSMatrix*> ms) {
-  if (options().complex_trs4 == 0 || world().active() || !slab_on() || !session_takes(true) || blk_any(ms)) return false;
+// (option: the value of the loop's own option -- complex_trs4 here, complex_hpcp for the HPCP passes below)
+bool complex_passes_on(int option, std::initializer_list<const PSMatrix*> ms) {
+  if (option == 0 || world().active() || !slab_on() || !session_takes(true) || blk_any(ms)) return false;
   const PSMatrix* first = *ms.begin();
   for (const PSMatrix* m : ms)
     if (!m->cplx || m->dim != first->dim || m->loc.blocked() || m->loc.loose()) return false;
   return true;
 }
+bool ctrs4_on(std::initializer_list<const PSMatrix*> ms) { return complex_passes_on(options().complex_trs4, ms); }
 // ... and in the loop: both merged operands in complex slab form as the products left them, neither labelled
 bool ctrs4_in_slab_form(const PSMatrix& X, const PSMatrix& X2) {
   return &X != &X2 && X.loc.expanded() && X2.loc.expanded() && !X.loc.slab->labelled() && !X2.loc.slab->labelled();
@@ -1482,9 +1484,61 @@ bool hpcp_update_enter(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& 
   return true;
 }
 bool hpcp_sigma_ok(double sigma) { return sigma != 0.0 && std::isfinite(sigma); }
+// Option complex_hpcp: the two passes on COMPLEX operands, one rank, inside a session that takes complex operands.  The gates of
+// complex TRS4 (complex_passes_on) and: no labelled slab form, distinct operands.  A pass they keep out is neither fused nor refused
+bool chpcp_on(std::initializer_list<const PSMatrix*> ms) {
+  if (!complex_passes_on(options().complex_hpcp, ms)) return false;
+  for (auto a = ms.begin(); a != ms.end(); ++a) {
+    if ((*a)->loc.expanded() && (*a)->loc.slab->labelled()) return false;
+    for (auto b = a + 1; b != ms.end(); ++b)
+      if (*a == *b) return false;
+  }
+  return true;
+}
+// hpcp_update_enter for complex operands: WH may become a read-only view (stored zeros, option stored_zero_views), the merged
+// operands may not
+bool chpcp_update_enter(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, const PSMatrix& WH, bool* gated) {
+  *gated = false;
+  if (!slab_enter_c(mut(WH)) || !(WH.loc.zero_free == 1 || WH.loc.slab->origin)) { *gated = true; return false; }
+  if (!slab_enter_c(mut(D1), nullptr, false) || !slab_enter_c(mut(DDH), nullptr, false) || !slab_enter_c(mut(D2DH), nullptr, false)) return false;
+  if (D1.loc.slab->row_pad != DDH.loc.slab->row_pad || D1.loc.slab->row_pad != D2DH.loc.slab->row_pad) { *gated = true; return false; }
+  return true;
+}
+// the fused complex update past its gates: the new D1 and DH in slab form; false: refused (counted) or gated (*gated)
+bool chpcp_update(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, DevMat& o, DevMat& h,
+                  double* energy) {
+  bool gated = false;
+  if (!hpcp_sigma_ok(sigma) || !chpcp_update_enter(D1, DDH, D2DH, WH, &gated) ||
+      !slab_hpcp_update_c(D1.loc, DDH.loc, D2DH.loc, sigma, WH.loc, D1.c0, o, h, energy)) {
+    if (!gated) complex_hpcp_counts()[2] += 1;
+    return false;
+  }
+  g_slab_counts[1] += 4;   // (counted as the real branch counts it)
+  g_slab_counts[2] += 2;
+  complex_hpcp_counts()[1] += 1;
+  return true;
+}
+bool chpcp_traces(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]) {
+  double t[2] = {0.0, 0.0};
+  if (!slab_hpcp_traces_c(DDH.loc, D2DH.loc, DDH.c0, t)) {
+    complex_hpcp_counts()[2] += 1;
+    return false;
+  }
+  g_slab_counts[2] += 2;
+  complex_hpcp_counts()[0] += 1;
+  out[0] = t[0];
+  out[1] = t[1];
+  return true;
+}
 }  // namespace
+long long* complex_hpcp_counts() {
+  static long long counts[3] = {0, 0, 0};
+  return counts;
+}
 bool ps_hpcp_traces(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]) {
   CommScope cs(DDH.grid);
+  if (DDH.cplx || D2DH.cplx)   // (option complex_hpcp; one rank: no reduction)
+    return chpcp_on({&DDH, &D2DH}) && DDH.loc.expanded() && D2DH.loc.expanded() && chpcp_traces(DDH, D2DH, out);
   // (every gate here is the same on every rank: past them each rank enters ONE reduction, and a rank whose panels the kernel does
   // not take adds the partial sums it computes as ps_trace would)
   if (options().hpcp_step == 0 || g_slab_depth == 0 || DDH.cplx || D2DH.cplx || DDH.dim != D2DH.dim || &DDH == &D2DH || blk_any({&DDH, &D2DH}) ||
@@ -1505,7 +1559,19 @@ bool ps_hpcp_traces(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]) {
 }
 bool ps_hpcp_update(PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& DH, double* energy) {
   CommScope cs(D1.grid);
-  if (&DH == &D1 || &DH == &DDH || &DH == &D2DH || &DH == &WH || !hpcp_update_on(D1, DDH, D2DH, WH)) return false;
+  if (&DH == &D1 || &DH == &DDH || &DH == &D2DH || &DH == &WH) return false;
+  if (D1.cplx || DDH.cplx || D2DH.cplx || WH.cplx) {   // (option complex_hpcp; one rank: no reduction)
+    DevMat o, h;
+    if (!chpcp_on({&D1, &DDH, &D2DH, &WH}) || !(D1.loc.expanded() || DDH.loc.expanded() || D2DH.loc.expanded()) ||
+        !chpcp_update(D1, DDH, D2DH, sigma, WH, o, h, energy))
+      return false;
+    const ProcessGrid* grid = D1.grid;
+    const int32_t dim = D1.dim, c0 = D1.c0, c1 = D1.c1;
+    D1.loc = std::move(o);
+    install(DH, grid, dim, true, c0, c1, std::move(h));
+    return true;
+  }
+  if (!hpcp_update_on(D1, DDH, D2DH, WH)) return false;
   bool gated = false;
   DevMat o, h;
   double e[2] = {0.0, 0.0};
@@ -1529,6 +1595,18 @@ bool ps_hpcp_update(PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, dou
 bool ps_hpcp_update_step(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& D1out,
                          PSMatrix& DHout, double* energy) {
   CommScope cs(D1.grid);
+  if (D1.cplx && DDH.cplx && D2DH.cplx && WH.cplx) {   // (option complex_hpcp, under the gates of the loop's call)
+    if (&D1out == &DHout || !chpcp_on({&D1, &DDH, &D2DH, &WH})) return false;
+    for (const PSMatrix* m : {&D1, &DDH, &D2DH, &WH})
+      if (m == &D1out || m == &DHout) return false;
+    DevMat o, h;
+    if (!chpcp_update(D1, DDH, D2DH, sigma, WH, o, h, energy)) return false;
+    pack(o);
+    pack(h);
+    install(D1out, D1.grid, D1.dim, true, D1.c0, D1.c1, std::move(o));
+    install(DHout, D1.grid, D1.dim, true, D1.c0, D1.c1, std::move(h));
+    return true;
+  }
   auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
   if (options().hpcp_step == 0 || !slab_on() || D1.cplx || DDH.cplx || D2DH.cplx || WH.cplx || D1.dim != DDH.dim || D1.dim != D2DH.dim ||
       D1.dim != WH.dim || &D1 == &DDH || &D1 == &D2DH || &DDH == &D2DH || &D1out == &DHout || labelled(D1) || labelled(DDH) || labelled(D2DH) ||
@@ -1554,6 +1632,28 @@ bool ps_hpcp_update_step(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix
   g_slab_counts[1] += 4;
   g_slab_counts[2] += 2;
   hpcp_step_counts()[1] += 1;
+  return true;
+}
+bool ps_hpcp_traces_step(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]) {
+  CommScope cs(DDH.grid);
+  if (DDH.cplx || D2DH.cplx) {   // (option complex_hpcp, under the gates of the loop's call)
+    if (!chpcp_on({&DDH, &D2DH})) return false;
+    if (!slab_enter_c(mut(DDH)) || !slab_enter_c(mut(D2DH))) {
+      complex_hpcp_counts()[2] += 1;
+      return false;
+    }
+    return chpcp_traces(DDH, D2DH, out);
+  }
+  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
+  if (options().hpcp_step == 0 || !slab_on() || DDH.dim != D2DH.dim || &DDH == &D2DH || labelled(DDH) || labelled(D2DH)) return false;
+  unblock({&DDH, &D2DH});
+  double t[2] = {0.0, 0.0};
+  if (!slab_enter(mut(DDH)) || !slab_enter(mut(D2DH)) || !slab_hpcp_traces(DDH.loc, D2DH.loc, DDH.c0, t)) return false;
+  comm_allreduce_sum(t, 2);
+  out[0] = t[0];
+  out[1] = t[1];
+  g_slab_counts[2] += 2;
+  hpcp_step_counts()[0] += 1;
   return true;
 }
 

@@ -1511,13 +1511,17 @@ struct HpcpRuns {   // one operand in slab form
   const double* val;
 };
 HpcpRuns hpcp_runs(const DevMat& M) { return HpcpRuns{M.slab->first.p, M.slab->last.p, M.slab->off.p, M.slab->val.p}; }
-// one thread per column: part[2 j] = A's diagonal entry, part[2 j + 1] = B's, each read as k_sa_diag reads it
+// one thread per column: part[2 j] = A's diagonal entry, part[2 j + 1] = B's, each read as k_sa_diag reads it; T = double2 (runs of
+// (re, im) pairs): the real part, as k_sa_dot_trace_c reads it -- MatrixTrace of a complex matrix sums the real parts
+template <typename T>
 __global__ __launch_bounds__(256) void k_hpcp_traces(int n, HpcpRuns A, HpcpRuns B, int col_offset, double* __restrict__ part) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
+  const T* __restrict__ va = reinterpret_cast<const T*>(A.val);
+  const T* __restrict__ vb = reinterpret_cast<const T*>(B.val);
   const int d = j + col_offset, fA = A.first[j], lA = A.last[j], fB = B.first[j], lB = B.last[j];
-  part[2 * (size_t)j] = (lA >= fA && d >= fA && d <= lA) ? A.val[A.off[j] + (d - fA)] : 0.0;
-  part[2 * (size_t)j + 1] = (lB >= fB && d >= fB && d <= lB) ? B.val[B.off[j] + (d - fB)] : 0.0;
+  part[2 * (size_t)j] = (lA >= fA && d >= fA && d <= lA) ? Sc<T>::re(va[A.off[j] + (d - fA)]) : 0.0;
+  part[2 * (size_t)j + 1] = (lB >= fB && d >= fB && d <= lB) ? Sc<T>::re(vb[B.off[j] + (d - fB)]) : 0.0;
 }
 // the aligned hull of the three runs and the diagonal row, per column
 __global__ void k_hpcp_span(HpcpRuns A, HpcpRuns B, HpcpRuns C, int n, int col_offset, int al, int32_t* __restrict__ span) {
@@ -1532,11 +1536,24 @@ __global__ void k_hpcp_span(HpcpRuns A, HpcpRuns B, HpcpRuns C, int n, int col_o
 // chunks of 64 rows whose loads (four operands each) are all requested before the first of them is used: 16 loads per lane in 82
 // VGPRs, five waves per SIMD, no scratch -- a hull of up to 256 aligned rows is one trip (ISR_KC's depth with twice the operands)
 constexpr int HPCP_KC = 4;
+// ... and on runs of (re, im) pairs (option complex_hpcp), one 16-byte load per lane and operand: two chunks in flight are the 32
+// VGPRs of load data the real kernel's four are -- 84 VGPRs, five waves per SIMD, no scratch; a hull of up to 128 aligned rows is
+// one trip
+constexpr int HPCP_KC_C = 2;
+// the term of DotMatrix(D1, WH) one row adds: o wh, and for complex operands the real part of conj(o) wh with each product and
+// the pair's sum rounded (the terms of k_sa_dot_trace_c)
+__device__ inline double hpcp_term(double o, double w) { return __dmul_rn(o, w); }
+__device__ inline double hpcp_term(double2 o, double2 w) { return __dadd_rn(__dmul_rn(o.x, w.x), __dmul_rn(o.y, w.y)); }
+__device__ inline double hpcp_negate(double u) { return -u; }   // ScaleMatrix(., -1): exact
+__device__ inline double2 hpcp_negate(double2 u) { return Sc<double2>::scale(-1.0, u); }
 // One wave per column, lanes on consecutive rows of the aligned hull [a0, a1) of the runs of A = D1, B = DDH, C = D2DH and the
 // diagonal row.  o1 = the new D1, o2 = DH, both into the slot at base[j]; part[2 j] = sum over the column of o wh, a lane-strided
 // sum then a wave sum (fixed shapes: the same value every run).  s2 = -2 sigma as the host rounds it.
 // stat |= 1: a scaled entry underflows to zero; |= 2: runs far apart or a slot beyond the output buffer -- nothing is written for
 // that column (k_sa_isr_chain).
+// T = double2: the runs, the slots, base and bound count (re, im) pairs; every scalar of the chain is real, so isr_merge<double2>
+// scales and adds part by part and keeps an entry where either part is not zero; d = (1, 0).
+template <typename T, int KC>
 __global__ __launch_bounds__(256) void k_hpcp_update(int n, HpcpRuns A, HpcpRuns B, HpcpRuns C, HpcpRuns W, int col_offset, double s2, int al,
                                                      const int64_t* __restrict__ base, IsrOut o1, IsrOut o2, int64_t bound,
                                                      double* __restrict__ part, unsigned long long* __restrict__ stat) {
@@ -1566,36 +1583,39 @@ __global__ __launch_bounds__(256) void k_hpcp_update(int n, HpcpRuns A, HpcpRuns
     }
     return;
   }
-  const double* __restrict__ pa = anyA ? A.val + (A.off[j] - fA) : A.val;
-  const double* __restrict__ pb = anyB ? B.val + (B.off[j] - fB) : B.val;
-  const double* __restrict__ pc = anyC ? C.val + (C.off[j] - fC) : C.val;
-  const double* __restrict__ pw = anyW ? W.val + (W.off[j] - fW) : W.val;
-  double* __restrict__ d1 = static_cast<double*>(o1.val) + (slot - a0);
-  double* __restrict__ d2 = static_cast<double*>(o2.val) + (slot - a0);
+  const T *__restrict__ va0 = reinterpret_cast<const T*>(A.val), *__restrict__ vb0 = reinterpret_cast<const T*>(B.val);
+  const T *__restrict__ vc0 = reinterpret_cast<const T*>(C.val), *__restrict__ vw0 = reinterpret_cast<const T*>(W.val);
+  const T* __restrict__ pa = anyA ? va0 + (A.off[j] - fA) : va0;
+  const T* __restrict__ pb = anyB ? vb0 + (B.off[j] - fB) : vb0;
+  const T* __restrict__ pc = anyC ? vc0 + (C.off[j] - fC) : vc0;
+  const T* __restrict__ pw = anyW ? vw0 + (W.off[j] - fW) : vw0;
+  T* __restrict__ d1 = static_cast<T*>(o1.val) + (slot - a0);
+  T* __restrict__ d2 = static_cast<T*>(o2.val) + (slot - a0);
+  const T one = isr_one(T{});
   int uf = 0, c1 = 0, f1 = INT_MAX, l1 = -1, c2 = 0, f2 = INT_MAX, l2 = -1;
   double e = 0.0;
-  for (int rb = a0; rb < a1; rb += HPCP_KC * WAVE) {
-    double va[HPCP_KC], vb[HPCP_KC], vc[HPCP_KC], vw[HPCP_KC];
+  for (int rb = a0; rb < a1; rb += KC * WAVE) {
+    T va[KC], vb[KC], vc[KC], vw[KC];
 #pragma unroll
-    for (int k = 0; k < HPCP_KC; ++k) {
+    for (int k = 0; k < KC; ++k) {
       const int r = rb + k * WAVE + lane;
-      va[k] = (anyA && r >= fA && r <= lA) ? pa[r] : 0.0;
-      vb[k] = (anyB && r >= fB && r <= lB) ? pb[r] : 0.0;
-      vc[k] = (anyC && r >= fC && r <= lC) ? pc[r] : 0.0;
-      vw[k] = (anyW && r >= fW && r <= lW) ? pw[r] : 0.0;
+      va[k] = (anyA && r >= fA && r <= lA) ? pa[r] : Sc<T>::zero();
+      vb[k] = (anyB && r >= fB && r <= lB) ? pb[r] : Sc<T>::zero();
+      vc[k] = (anyC && r >= fC && r <= lC) ? pc[r] : Sc<T>::zero();
+      vw[k] = (anyW && r >= fW && r <= lW) ? pw[r] : Sc<T>::zero();
     }
 #pragma unroll
-    for (int k = 0; k < HPCP_KC; ++k) {
+    for (int k = 0; k < KC; ++k) {
       const int r = rb + k * WAVE + lane;
       if (r >= a1) continue;
-      const double x = va[k], xb = vb[k], xc = vc[k];
+      const T x = va[k], xb = vb[k], xc = vc[k];
       bool ht, ho, hu;
-      const double t = isr_merge<double>(1.0, x, x != 0.0, 2.0, xc, xc != 0.0, &ht, &uf);     // IncrementMatrix(D2DH, D1, 2)
-      const double o = isr_merge<double>(1.0, t, ht, s2, xb, xb != 0.0, &ho, &uf);             // IncrementMatrix(DDH, D1, -2 sigma)
-      const double u = isr_merge<double>(1.0, o, ho, -1.0, 1.0, r == dg, &hu, &uf);            // CopyMatrix(D1, DH); IncrementMatrix(I, DH, -1)
+      const T t = isr_merge<T>(1.0, x, !Sc<T>::is_zero(x), 2.0, xc, !Sc<T>::is_zero(xc), &ht, &uf);   // IncrementMatrix(D2DH, D1, 2)
+      const T o = isr_merge<T>(1.0, t, ht, s2, xb, !Sc<T>::is_zero(xb), &ho, &uf);                    // IncrementMatrix(DDH, D1, -2 sigma)
+      const T u = isr_merge<T>(1.0, o, ho, -1.0, one, r == dg, &hu, &uf);                             // CopyMatrix(D1, DH); IncrementMatrix(I, DH, -1)
       d1[r] = o;
-      d2[r] = hu ? -u : 0.0;                                                                   // ScaleMatrix(DH, -1)
-      e = __dadd_rn(e, __dmul_rn(o, vw[k]));                                                   // DotMatrix(D1, WH)
+      d2[r] = hu ? hpcp_negate(u) : Sc<T>::zero();                                                    // ScaleMatrix(DH, -1)
+      e = __dadd_rn(e, hpcp_term(o, vw[k]));                                                          // DotMatrix(D1, WH)
       c1 += ho ? 1 : 0; f1 = min(f1, ho ? r : INT_MAX); l1 = max(l1, ho ? r : -1);
       c2 += hu ? 1 : 0; f2 = min(f2, hu ? r : INT_MAX); l2 = max(l2, hu ? r : -1);
     }
@@ -1617,29 +1637,32 @@ __global__ __launch_bounds__(256) void k_hpcp_update(int n, HpcpRuns A, HpcpRuns
   }
 }
 // what the three merged operands must be: trs4_operands for three
-bool hpcp_operand(const DevMat& M) {
-  return M.expanded() && !M.cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1;
+// (cplx: runs of (re, im) pairs in slots aligned to 16 rows, what sa_operand_c takes)
+bool hpcp_operand(const DevMat& M, bool cplx = false) {
+  return M.expanded() && M.cplx == cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1 &&
+         (!cplx || M.slab->row_pad % 16 == 0);
 }
-}  // namespace
-
-bool slab_hpcp_traces(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]) {
-  auto ok = [](const DevMat& M) { return M.expanded() && !M.cplx && !M.slab->labelled(); };   // (what slab_trace takes)
-  if (!ok(DDH) || !ok(D2DH) || DDH.cols != D2DH.cols) return false;
+template <typename T>
+bool hpcp_traces_run(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]) {
   const int n = DDH.cols;
   DevBuf<double> part((size_t)2 * n), res(2);
-  hipLaunchKernelGGL(k_hpcp_traces, dim3(cdiv(n, 256)), dim3(256), 0, stream(), n, hpcp_runs(DDH), hpcp_runs(D2DH), col_offset, part.p);
+  hipLaunchKernelGGL(k_hpcp_traces<T>, dim3(cdiv(n, 256)), dim3(256), 0, stream(), n, hpcp_runs(DDH), hpcp_runs(D2DH), col_offset, part.p);
   sum_pairs_async(part.p, n, res.p);
   ScalarFetch ft;
   ft.add(res.p, 2, out2);
   ft.run();
   return true;
 }
-
-bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, double sigma, const DevMat& WH, int32_t col_offset, DevMat& OutD1,
-                      DevMat& OutDH, double* energy) {
-  const bool wh_ok = WH.expanded() && !WH.cplx && !WH.slab->labelled() && (WH.rows == WH.cols || slab_panels_ok()) &&
-                     (WH.zero_free == 1 || WH.slab->origin);   // (a view's stored zeros add nothing to the dot)
-  if (!hpcp_operand(D1) || !hpcp_operand(DDH) || !hpcp_operand(D2DH) || !wh_ok || &D1 == &DDH || &D1 == &D2DH || &DDH == &D2DH ||
+// the update on operands of one kind; the slots, `bound` and the outputs' buffers count entries of T
+template <typename T, int KC>
+bool hpcp_update_run(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, double sigma, const DevMat& WH, int32_t col_offset, DevMat& OutD1,
+                     DevMat& OutDH, double* energy) {
+  constexpr bool cplx = Sc<T>::cplx;
+  const bool wh_ok = WH.expanded() && WH.cplx == cplx && !WH.slab->labelled() && (WH.rows == WH.cols || slab_panels_ok()) &&
+                     (WH.zero_free == 1 || WH.slab->origin) &&   // (a view's stored zeros add nothing to the dot)
+                     (!cplx || sa_readable_c(WH));
+  auto ok = [](const DevMat& M) { return hpcp_operand(M, cplx); };
+  if (!ok(D1) || !ok(DDH) || !ok(D2DH) || !wh_ok || &D1 == &DDH || &D1 == &D2DH || &DDH == &D2DH ||
       &OutD1 == &OutDH || D1.cols != DDH.cols || D1.cols != D2DH.cols || D1.cols != WH.cols || D1.rows != DDH.rows || D1.rows != D2DH.rows ||
       D1.rows != WH.rows || D1.slab->row_pad != DDH.slab->row_pad || D1.slab->row_pad != D2DH.slab->row_pad)
     return false;
@@ -1652,7 +1675,7 @@ bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, d
   for (int q = 0; q < 2; ++q) {
     fo[q].reset(new SlabForm());
     fo[q]->first.alloc((size_t)n); fo[q]->last.alloc((size_t)n); fo[q]->count.alloc((size_t)n); fo[q]->off.alloc((size_t)n + 1);
-    fo[q]->val.alloc((size_t)bound + kIndexSlack);
+    fo[q]->val.alloc(((size_t)bound + kIndexSlack) * (cplx ? 2 : 1));
     o[q] = IsrOut{fo[q]->val.p, fo[q]->first.p, fo[q]->last.p, fo[q]->count.p, fo[q]->off.p};
   }
   DevBuf<int32_t> span((size_t)n);
@@ -1664,7 +1687,7 @@ bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, d
   const HpcpRuns ra = hpcp_runs(D1), rb = hpcp_runs(DDH), rc = hpcp_runs(D2DH);
   hipLaunchKernelGGL(k_hpcp_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, rc, n, col_offset, al, span.p);
   scan_i32_async(span.p, base.p, (int64_t)n);
-  hipLaunchKernelGGL(k_hpcp_update, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, rc, hpcp_runs(WH), col_offset,
+  hipLaunchKernelGGL((k_hpcp_update<T, KC>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, rc, hpcp_runs(WH), col_offset,
                      -1.0 * 2.0 * sigma, al, base.p, o[0], o[1], bound, part.p, stat.p);
   const dim3 sum_grid(std::max(1, std::min(256, cdiv(n, 1024))));
   for (int q = 0; q < 2; ++q) hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), fo[q]->count.p, n, tot.p + q);
@@ -1689,7 +1712,7 @@ bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, d
   for (int q = 0; q < 2; ++q) {
     fo[q]->row_pad = al;
     fo[q]->slots = slots;
-    R[q].rows = D1.rows; R[q].cols = n; R[q].cplx = false; R[q].nnz = nnz[q]; R[q].zero_free = 1;
+    R[q].rows = D1.rows; R[q].cols = n; R[q].cplx = cplx; R[q].nnz = nnz[q]; R[q].zero_free = 1;
     R[q].slab = std::move(fo[q]);
   }
   bump_matrix_value_epoch();   // (of the calls it replaces, the two merges into D1 are in place: slab_axpby counts them so)
@@ -1698,6 +1721,27 @@ bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, d
   OutDH = std::move(R[1]);
   *energy = e;
   return true;
+}
+}  // namespace
+
+bool slab_hpcp_traces(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]) {
+  auto ok = [](const DevMat& M) { return M.expanded() && !M.cplx && !M.slab->labelled(); };   // (what slab_trace takes)
+  if (!ok(DDH) || !ok(D2DH) || DDH.cols != D2DH.cols) return false;
+  return hpcp_traces_run<double>(DDH, D2DH, col_offset, out2);
+}
+bool slab_hpcp_traces_c(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]) {
+  // (what slab_dot_trace_c takes for its trace: a read-only view's stored zeros are zeros of the run)
+  if (!sa_readable_c(DDH) || !sa_readable_c(D2DH) || DDH.cols != D2DH.cols) return false;
+  return hpcp_traces_run<double2>(DDH, D2DH, col_offset, out2);
+}
+
+bool slab_hpcp_update(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, double sigma, const DevMat& WH, int32_t col_offset, DevMat& OutD1,
+                      DevMat& OutDH, double* energy) {
+  return hpcp_update_run<double, HPCP_KC>(D1, DDH, D2DH, sigma, WH, col_offset, OutD1, OutDH, energy);
+}
+bool slab_hpcp_update_c(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, double sigma, const DevMat& WH, int32_t col_offset, DevMat& OutD1,
+                        DevMat& OutDH, double* energy) {
+  return hpcp_update_run<double2, HPCP_KC_C>(D1, DDH, D2DH, sigma, WH, col_offset, OutD1, OutDH, energy);
 }
 
 // ------------------------------------------------------------------ ScaleAndFold: the update, the energy and the next trace of a step

@@ -600,11 +600,16 @@ void solver_hpcp(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix&
   f.begin_loop();
   double trace_value = 0.0;
   int II;
-  SlabSession slab(!D1.cplx && !WH.cplx);
+  // Option complex_hpcp, a complex Hamiltonian on one rank without process slices: a complex session, as solver_trs4 opens it -- the
+  // products on the complex tile kernel, the two fused calls below on complex runs
+  const bool complex_session = D1.cplx && WH.cplx && complex_slab_loop(D1) && options().complex_hpcp != 0 && !world().active() &&
+                               !(D1.grid && D1.grid->num_slices > 1);
+  SlabSession slab((!D1.cplx && !WH.cplx) || complex_session, false, complex_session);
   // Option hpcp_step, inside the real session: the two traces in one pass behind the second product (ps_hpcp_traces: the bits of
   // the two calls), and the two merges, the energy and the NEXT iteration's DH in one pass over the three runs (ps_hpcp_update).
   // An update that is not taken runs the calls of this iteration, and the next DH is built by the three calls again.
-  const bool step = options().hpcp_step != 0;
+  // (hpcp_step is the real loop's option: complex operands outside a complex session are declined by both calls, as before)
+  const bool step = options().hpcp_step != 0 || complex_session;
   bool have_dh = false;   // DH = I - D1 came out of the last update
   for (II = 1; II <= p.max_iterations; ++II) {                     // :836-872
     if (!have_dh) {

@@ -202,6 +202,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "hpcp_step") options().hpcp_step = *value;
   else if (n == "scale_fold_step") options().scale_fold_step = *value;
   else if (n == "complex_trs4") options().complex_trs4 = *value;
+  else if (n == "complex_hpcp") options().complex_hpcp = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -244,6 +245,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "hpcp_step") return options().hpcp_step;
   if (n == "scale_fold_step") return options().scale_fold_step;
   if (n == "complex_trs4") return options().complex_trs4;
+  if (n == "complex_hpcp") return options().complex_hpcp;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -332,6 +334,22 @@ int ntpoly_amd_hpcp_update_step(const int* ih_D1, const int* ih_DDH, const int* 
                                 int* ih_DHout, double* energy) {
   return ps_hpcp_update_step(*get_unpacked(ih_D1), *get_unpacked(ih_DDH), *get_unpacked(ih_D2DH), *sigma, *get_unpacked(ih_WH),
                              *get_unpacked(ih_D1out), *get_unpacked(ih_DHout), energy) ? 1 : 0;
+}
+// Complex HPCP in a complex slab session (option complex_hpcp; engine.hpp ps_hpcp_traces / ps_hpcp_update on complex operands)
+// since start: out[0] = trace passes fused, out[1] = updates fused, out[2] = passes refused (the vocabulary calls ran instead).  A
+// pass that never reaches the kernel's decision -- the option off, no open complex session, several ranks, block form, a labelled
+// slab form, alignments that differ, a WH the dot cannot read as runs -- is neither fused nor counted as refused.  Real operands
+// count in ntpoly_amd_hpcp_step_counts only, complex ones here only.  With the option on, ntpoly_amd_hpcp_update_step takes four
+// complex matrices in a session with complex_ok: the chain on each part of an entry, *energy = the real part of DotMatrix
+void ntpoly_amd_complex_hpcp_counts(long long out[3]) {
+  for (int q = 0; q < 3; ++q) out[q] = complex_hpcp_counts()[q];
+}
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: the fused trace pass of the HPCP loop on caller-held
+// matrices, real (option hpcp_step) or complex (option complex_hpcp).  Both are brought into slab form where they are; out[0] =
+// MatrixTrace(DDH), out[1] = MatrixTrace(D2DH) from one pass and one read-back.  Returns 1 when taken, 0 when refused or gated: out
+// is then as it was.
+int ntpoly_amd_hpcp_traces_step(const int* ih_DDH, const int* ih_D2DH, double out[2]) {
+  return ps_hpcp_traces_step(*get_unpacked(ih_DDH), *get_unpacked(ih_D2DH), out) ? 1 : 0;
 }
 // ScaleAndFold with the update, the energy and the next step's trace in one pass (option scale_fold_step; engine.hpp ps_saf_update /
 // ps_saf_dot_trace) since start: out[0] = fold updates fused, out[1] = dot-and-trace passes fused (the scale branch), out[2] = passes

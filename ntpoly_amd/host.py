@@ -1114,13 +1114,34 @@ def hpcp_step_counts():
 
 
 def hpcp_update_step(D1, DDH, D2DH, sigma, WH, D1out, DHout):
-    """DIAGNOSTIC, inside `with solver_session():` -- one fused HPCP update on caller-held real matrices (DDH, D2DH: what the
-    products D1 (I - D1) and D1 DDH would be): D1out = (D1 + 2 D2DH) + (-2 sigma) DDH, DHout = I - D1out, both as the vocabulary at
-    threshold 0 builds them.  Returns the energy dot(D1out, WH) when taken; None: refused, every matrix as it was."""
+    """DIAGNOSTIC, inside `with solver_session():` -- one fused HPCP update on caller-held matrices, all real (option hpcp_step) or
+    all complex (option complex_hpcp, one rank) (DDH, D2DH: what the products D1 (I - D1) and D1 DDH would be): D1out = (D1 + 2
+    D2DH) + (-2 sigma) DDH, DHout = I - D1out, both as the vocabulary at threshold 0 builds them.  Returns the energy dot(D1out, WH)
+    (complex: its real part) when taken; None: refused or gated, every matrix as it was."""
     e = C.c_double(0.0)
     lib.ntpoly_amd_hpcp_update_step.restype = C.c_int
     ok = lib.ntpoly_amd_hpcp_update_step(D1.ih, DDH.ih, D2DH.ih, d(sigma), WH.ih, D1out.ih, DHout.ih, C.byref(e))
     return float(e.value) if ok else None
+
+
+def complex_hpcp_counts():
+    """complex HPCP in a complex slab session (option complex_hpcp; csrc/slab_extra.hip k_hpcp_traces / k_hpcp_update on runs of
+    (re, im) pairs) since start: trace passes fused, updates fused, passes refused (the vocabulary calls ran instead);
+    slab_algebra_counts() counts a fused pass as the real branch does.  A pass kept out by a gate (the option off, no open complex
+    session, several ranks, block form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs) is neither
+    fused nor counted as refused; real operands count in hpcp_step_counts() only"""
+    out = (C.c_longlong * 3)()
+    lib.ntpoly_amd_complex_hpcp_counts(out)
+    return dict(traces=int(out[0]), updates=int(out[1]), refused=int(out[2]))
+
+
+def hpcp_traces_step(DDH, D2DH):
+    """DIAGNOSTIC, inside `with solver_session():` -- the fused trace pass of the HPCP loop on caller-held matrices, real (option
+    hpcp_step) or complex (option complex_hpcp): returns (trace(DDH), trace(D2DH)) from one pass; None: refused or gated."""
+    out = (C.c_double * 2)()
+    lib.ntpoly_amd_hpcp_traces_step.restype = C.c_int
+    ok = lib.ntpoly_amd_hpcp_traces_step(DDH.ih, D2DH.ih, out)
+    return (float(out[0]), float(out[1])) if ok else None
 
 
 def scale_fold_step_counts():
