@@ -146,7 +146,7 @@ void ps_increment_identity(const PSMatrix& Identity, PSMatrix& B, double alpha);
 bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx);
 bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P);
 // Option complex_trs4 (one rank, inside a session that takes complex operands): the two calls above take a complex X and X2 in
-// complex slab form (slab_extra.hip k_sa_trs4_c: the real kernel's arithmetic on each part of an entry, the values and pattern of
+// complex slab form (slab_extra.hip k_sa_trs4<double2, .>: the real kernel's arithmetic on each part of an entry, the values and pattern of
 // the four merges at threshold 0; the traces summed in another fixed order), and
 // ps_trs4_energy: *energy = the real part of dot(X, WH) from one pass over the runs of a complex slab-form X and WH as it stands --
 // slab form, a read-only view or compressed columns, stored zeros included (slab_dot_trace_c) -- instead of a dot that packs X.

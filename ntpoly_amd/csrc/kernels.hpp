@@ -103,7 +103,7 @@ struct EngineOptions {
   int isr_chain = 1;           // the Taylor square-root loop (InverseSquareRoot / SquareRoot, orders 5 and 3) inside a slab session, real operands and complex ones in a complex session, one rank and column panels: the vocabulary calls between the product X X and the next product (order 5: four merges that build Temp2 and Temp; order 3: two that build the new X) are ONE pass over the runs of X and X X (slab_extra.hip k_sa_isr_chain) -- the same values and patterns bit for bit, one host read-back instead of up to four; a step the kernel refuses runs the calls as before.  0: the calls, one by one
   int hpcp_step = 1;           // HPCP purification, real operands, inside a real slab session (one rank and column panels across ranks): the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH with one read-back (slab_extra.hip k_hpcp_traces: the bits of two MatrixTrace calls), and the two merges into D1, the energy dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update: the values and patterns of the vocabulary calls at threshold 0 bit for bit; the energy is summed in another order and only feeds the convergence monitor) -- two read-backs per iteration instead of five; an update the kernel refuses runs the calls as before.  0: the eight calls, one by one
   int scale_fold_step = 1;     // ScaleAndFold, real operands, inside a real slab session (one rank and column panels across ranks): behind the step's one product, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update: the values and pattern of the vocabulary calls at threshold 0 and the trace of slab_trace bit for bit; the energy is summed in another order and only feeds the convergence monitor); the scale branch, whose product's result is the new X, takes the energy and the trace from one pass over X and WH (k_saf_dot_trace) -- one read-back per step instead of two or three; a step the kernel refuses runs the calls as before.  0: the three calls, one by one
-  int complex_trs4 = 0;        // complex TRS4 on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and the second product's operand stay runs of (re, im) pairs between the products on the complex tile kernel --, the traces dot(X2, Fx) and dot(X2, Gx) come from ONE pass over X and X X without building Fx and Gx, the operand Fx + sigma Gx from a second one (slab_extra.hip k_sa_trs4_c: the real kernel's arithmetic on each part, the values and pattern of the four merges at threshold 0), and the energy Re dot(X, WH) from one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  0 (default; measured 4.51 against 10.62 ms per iteration on configs[4]'s operand, profiles/README.md 130, but the rule that decides defaults also wants option 0 and the parent commit equal within the block spread, which one run missed by a hair): the loop on compressed columns, bit for bit as before
+  int complex_trs4 = 0;        // complex TRS4 on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and the second product's operand stay runs of (re, im) pairs between the products on the complex tile kernel --, the traces dot(X2, Fx) and dot(X2, Gx) come from ONE pass over X and X X without building Fx and Gx, the operand Fx + sigma Gx from a second one (slab_extra.hip k_sa_trs4<double2, .>: the real kernel's arithmetic on each part, the values and pattern of the four merges at threshold 0), and the energy Re dot(X, WH) from one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  0 (default; measured 4.51 against 10.62 ms per iteration on configs[4]'s operand, profiles/README.md 130, but the rule that decides defaults also wants option 0 and the parent commit equal within the block spread, which one run missed by a hair): the loop on compressed columns, bit for bit as before
   int complex_hpcp = 0;        // complex HPCP on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- D1, DH and both products stay runs of (re, im) pairs between the products on the complex tile kernel --, the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH (slab_extra.hip k_hpcp_traces<double2>: the real parts), and the two merges into D1, the energy Re dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update<double2, .>: the real kernel's chain on each part of an entry, the values and patterns of the vocabulary calls at threshold 0); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of hpcp_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
@@ -312,7 +312,7 @@ bool slab_add_diagonal(DevMat& B, double alpha, int32_t col_offset);   // B <- B
 // operand (4X - 3X2) + sigma (I - 2X + X2) of the iteration's second product
 bool slab_trs4_traces(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx);
 bool slab_trs4_operand(const DevMat& X, const DevMat& X2, double sigma, int32_t col_offset, DevMat& Out);
-// the same two passes on COMPLEX slab-form X and X2 (k_sa_trs4_c: every scalar of the chain is real, so each part of an entry goes
+// the same two passes on COMPLEX slab-form X and X2 (k_sa_trs4<double2, .>: every scalar of the chain is real, so each part of an entry goes
 // through the real kernel's arithmetic on its own; the traces are Re sum conj(x2) fx and Re sum conj(x2) gx; an entry of the
 // operand exists where either part is not zero).  false: not taken (trs4_operands_c) or, for the operand, hulls beyond the
 // output's bound -- nothing changed

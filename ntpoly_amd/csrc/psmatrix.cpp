@@ -277,6 +277,26 @@ bool blk_any(std::initializer_list<const PSMatrix*> ms) {
     if (m->loc.blocked()) return true;
   return false;
 }
+// a slab form under a relabelling (a relabelled band): the fused passes walk rows in the caller's order and leave it alone
+bool labelled(const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); }
+// no matrix is named twice
+bool all_distinct(std::initializer_list<const PSMatrix*> ms) {
+  for (auto a = ms.begin(); a != ms.end(); ++a)
+    for (auto b = a + 1; b != ms.end(); ++b)
+      if (*a == *b) return false;
+  return true;
+}
+bool same_dim(std::initializer_list<const PSMatrix*> ms) {
+  for (const PSMatrix* m : ms)
+    if (m->dim != (*ms.begin())->dim) return false;
+  return true;
+}
+// install with the header of X (read before the move: Out may be X)
+void install_like(PSMatrix& Out, const PSMatrix& X, bool cplx, DevMat&& loc) {
+  const ProcessGrid* grid = X.grid;
+  const int32_t dim = X.dim, c0 = X.c0, c1 = X.c1;
+  install(Out, grid, dim, cplx, c0, c1, std::move(loc));
+}
 // complex operands stay in block form (complex products and the complex block algebra, spgemm_block.hpp) inside a session on
 // one rank where complex sessions and the complex block path are both allowed -- a solver's complex session or a one-call
 // session of the C ABI
@@ -1259,34 +1279,38 @@ bool complex_passes_on(int option, std::initializer_list<const PSMatrix*> ms) {
 bool ctrs4_on(std::initializer_list<const PSMatrix*> ms) { return complex_passes_on(options().complex_trs4, ms); }
 // ... and in the loop: both merged operands in complex slab form as the products left them, neither labelled
 bool ctrs4_in_slab_form(const PSMatrix& X, const PSMatrix& X2) {
-  return &X != &X2 && X.loc.expanded() && X2.loc.expanded() && !X.loc.slab->labelled() && !X2.loc.slab->labelled();
+  return &X != &X2 && X.loc.expanded() && X2.loc.expanded() && !labelled(X) && !labelled(X2);
 }
-bool ctrs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx) {
-  if (!ctrs4_on({&X, &X2}) || !ctrs4_in_slab_form(X, X2)) return false;
-  if (!slab_trs4_traces_c(X.loc, X2.loc, X.c0, trace_fx, trace_gx)) {
-    complex_trs4_counts()[3] += 1;
-    return false;
-  }
-  g_slab_counts[2] += 1;
-  complex_trs4_counts()[0] += 1;
-  return true;
+// the loop's gates on one rank: both operands of one kind in slab form -- complex ones under ctrs4_on, real ones in any session
+bool trs4_in_loop(const PSMatrix& X, const PSMatrix& X2) {
+  if (X.cplx && X2.cplx) return ctrs4_on({&X, &X2}) && ctrs4_in_slab_form(X, X2);   // (option complex_trs4; one rank)
+  return slab_on() && X.loc.expanded() && X2.loc.expanded() && !X.cplx && !X2.cplx;
 }
-bool ctrs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, DevMat& R) {
-  if (!ctrs4_on({&X, &X2}) || !ctrs4_in_slab_form(X, X2) || sigma == 0.0) return false;
-  if (!slab_trs4_operand_c(X.loc, X2.loc, sigma, X.c0, R)) {
+// the two passes past their gates, on operands of one kind in slab form
+bool trs4_traces_local(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx) {
+  return X.cplx ? slab_trs4_traces_c(X.loc, X2.loc, X.c0, trace_fx, trace_gx) : slab_trs4_traces(X.loc, X2.loc, X.c0, trace_fx, trace_gx);
+}
+bool trs4_operand_local(const PSMatrix& X, const PSMatrix& X2, double sigma, DevMat& R) {
+  return X.cplx ? slab_trs4_operand_c(X.loc, X2.loc, sigma, X.c0, R) : slab_trs4_operand(X.loc, X2.loc, sigma, X.c0, R);
+}
+// ... and their books (pass 0: the traces, 1: the operand): slab_algebra_counts() counts a fused pass of either kind,
+// complex_trs4_counts() the complex ones -- and a complex pass the kernel does not take as refused.  Returns ok
+bool trs4_counted(bool cplx, int pass, bool ok) {
+  if (ok) {
+    g_slab_counts[pass == 0 ? 2 : 1] += 1;
+    if (cplx) complex_trs4_counts()[pass] += 1;
+  } else if (cplx) {
     complex_trs4_counts()[3] += 1;
-    return false;
   }
-  g_slab_counts[1] += 1;
-  complex_trs4_counts()[1] += 1;
-  return true;
+  return ok;
 }
 }  // namespace
 
 bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, double* trace_gx) {
   CommScope cs(X.grid);
   if (blk_any({&X, &X2})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
-  if (X.cplx && X2.cplx) return ctrs4_traces(X, X2, trace_fx, trace_gx);   // (option complex_trs4; one rank)
+  if (X.cplx && X2.cplx)   // (option complex_trs4; one rank)
+    return trs4_in_loop(X, X2) && trs4_counted(true, 0, trs4_traces_local(X, X2, trace_fx, trace_gx));
   if (world().active()) {
     // (a session across ranks: the decision is collective -- the sums and "some rank declined" in one reduction)
     if (g_slab_depth == 0 || X.cplx || X2.cplx) return false;
@@ -1300,31 +1324,20 @@ bool ps_trs4_traces(const PSMatrix& X, const PSMatrix& X2, double* trace_fx, dou
     g_slab_counts[2] += 1;
     return true;
   }
-  if (!slab_on() || !X.loc.expanded() || !X2.loc.expanded() || X.cplx || X2.cplx) return false;
-  if (!slab_trs4_traces(X.loc, X2.loc, X.c0, trace_fx, trace_gx)) return false;
-  g_slab_counts[2] += 1;
-  return true;
+  return trs4_in_loop(X, X2) && trs4_counted(false, 0, trs4_traces_local(X, X2, trace_fx, trace_gx));
 }
 bool ps_trs4_operand(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P) {
   CommScope cs(X.grid);
   if (blk_any({&X, &X2})) return false;   // (the caller spells it with the vocabulary, which knows the block form)
-  if (X.cplx && X2.cplx) {   // (option complex_trs4; one rank)
-    DevMat R;
-    if (!ctrs4_operand(X, X2, sigma, R)) return false;
-    install(P, X.grid, X.dim, true, X.c0, X.c1, std::move(R));
-    return true;
-  }
-  if (!slab_on() || !X.loc.expanded() || !X2.loc.expanded() || X.cplx || X2.cplx || sigma == 0.0) return false;
   DevMat R;
-  if (!slab_trs4_operand(X.loc, X2.loc, sigma, X.c0, R)) return false;
-  install(P, X.grid, X.dim, false, X.c0, X.c1, std::move(R));
-  g_slab_counts[1] += 1;
+  if (!trs4_in_loop(X, X2) || sigma == 0.0 || !trs4_counted(X.cplx, 1, trs4_operand_local(X, X2, sigma, R))) return false;
+  install_like(P, X, X.cplx, std::move(R));
   return true;
 }
 bool ps_trs4_energy(const PSMatrix& X, const PSMatrix& WH, double* energy) {
   CommScope cs(X.grid);
   // (WH as it stands: complex slab form, a read-only view, or compressed columns -- stored zeros add exact zeros to the sum)
-  if (&X == &WH || !ctrs4_on({&X, &WH}) || !X.loc.expanded() || X.loc.slab->labelled() || (WH.loc.expanded() && WH.loc.slab->labelled())) return false;
+  if (&X == &WH || !ctrs4_on({&X, &WH}) || !X.loc.expanded() || labelled(X) || labelled(WH)) return false;
   double dot[2] = {0.0, 0.0};
   if (!sa_operand_c(X.loc) || !slab_dot_trace_c(X.loc, &WH.loc, X.c0, dot, nullptr)) {
     complex_trs4_counts()[3] += 1;
@@ -1337,32 +1350,20 @@ bool ps_trs4_energy(const PSMatrix& X, const PSMatrix& WH, double* energy) {
 }
 bool ps_trs4_chain_step(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P, double* trace_fx, double* trace_gx) {
   CommScope cs(X.grid);
-  if (world().active() || !slab_on() || X.cplx != X2.cplx || X.dim != X2.dim || &X == &X2 || &P == &X || &P == &X2 || sigma == 0.0) return false;
+  if (world().active() || !slab_on() || X.cplx != X2.cplx || !same_dim({&X, &X2}) || !all_distinct({&X, &X2, &P}) || sigma == 0.0) return false;
   if (X.cplx && !ctrs4_on({&X, &X2})) return false;
   unblock({&X, &X2});
-  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
   if (labelled(X) || labelled(X2)) return false;
   const SlabKind& k = slab_kind(X.cplx);
   double t[2] = {0.0, 0.0};
   DevMat R;
-  const bool entered = k.enter(mut(X)) && k.enter(mut(X2));
-  const bool ok = entered && (X.cplx ? slab_trs4_traces_c(X.loc, X2.loc, X.c0, &t[0], &t[1]) && slab_trs4_operand_c(X.loc, X2.loc, sigma, X.c0, R)
-                                     : slab_trs4_traces(X.loc, X2.loc, X.c0, &t[0], &t[1]) && slab_trs4_operand(X.loc, X2.loc, sigma, X.c0, R));
-  if (!ok) {
-    if (X.cplx) complex_trs4_counts()[3] += 1;
-    return false;
-  }
+  if (!(k.enter(mut(X)) && k.enter(mut(X2)) && trs4_traces_local(X, X2, &t[0], &t[1]) && trs4_operand_local(X, X2, sigma, R)))
+    return trs4_counted(X.cplx, 0, false);   // (one refusal, whichever of them declined)
   pack(R);
-  install(P, X.grid, X.dim, X.cplx, X.c0, X.c1, std::move(R));
+  install_like(P, X, X.cplx, std::move(R));
   *trace_fx = t[0];
   *trace_gx = t[1];
-  g_slab_counts[1] += 1;
-  g_slab_counts[2] += 1;
-  if (X.cplx) {
-    complex_trs4_counts()[0] += 1;
-    complex_trs4_counts()[1] += 1;
-  }
-  return true;
+  return trs4_counted(X.cplx, 0, true) && trs4_counted(X.cplx, 1, true);
 }
 bool ps_trs4_energy_step(const PSMatrix& X, const PSMatrix& WH, double* energy) {
   CommScope cs(X.grid);
@@ -1385,65 +1386,53 @@ namespace {
 // relabelled band: the kernel walks rows in the caller's order).  A step the gates keep out is neither fused nor counted as refused
 bool isr_chain_on(const PSMatrix& X, const PSMatrix& X2) {
   return options().isr_chain != 0 && slab_on() && X.cplx == X2.cplx && session_takes(X.cplx) && X.dim == X2.dim && &X != &X2 &&
-         !blk_any({&X, &X2}) && (X.loc.expanded() || X2.loc.expanded()) && !(X.loc.expanded() && X.loc.slab->labelled()) &&
-         !(X2.loc.expanded() && X2.loc.slab->labelled());
+         !blk_any({&X, &X2}) && (X.loc.expanded() || X2.loc.expanded()) && !labelled(X) && !labelled(X2);
 }
-// (an operand still in compressed columns is turned into slab form where it is, as ps_axpby does before a merge)
-bool isr_chain_enter(const PSMatrix& X, const PSMatrix& X2) {
+// the chain past its gates: an operand still in compressed columns is turned into slab form where it is, as ps_axpby does before
+// a merge, and one chain of the given order leaves q (and p, order 5).  Counted as fused -- in slab_algebra_counts() as the merges
+// replaced -- or as refused
+bool isr_chain_local(const PSMatrix& X, const PSMatrix& X2, int order, double a, double b, double c, DevMat& q, DevMat& p) {
   const SlabKind& k = slab_kind(X.cplx);
-  return k.enter(mut(X)) && k.enter(mut(X2));
+  if (!(k.enter(mut(X)) && k.enter(mut(X2)) &&
+        (order == 5 ? slab_isr_chain5(X.loc, X2.loc, a, b, c, X.c0, q, p) : slab_isr_chain3(X.loc, X2.loc, X.c0, q)))) {
+    isr_chain_counts()[2] += 1;
+    return false;
+  }
+  g_slab_counts[1] += order == 5 ? 4 : 2;
+  isr_chain_counts()[order == 5 ? 0 : 1] += 1;
+  return true;
 }
 }  // namespace
 bool ps_isr_chain5(const PSMatrix& X, const PSMatrix& X2, double a, double b, double c, PSMatrix& Temp2, PSMatrix& Temp) {
   CommScope cs(X.grid);
-  if (!isr_chain_on(X, X2)) return false;
   DevMat q, p;
-  if (!isr_chain_enter(X, X2) || !slab_isr_chain5(X.loc, X2.loc, a, b, c, X.c0, q, p)) {
-    isr_chain_counts()[2] += 1;
-    return false;
-  }
-  const ProcessGrid* grid = X.grid;
-  const int32_t dim = X.dim, c0 = X.c0, c1 = X.c1;
+  if (!isr_chain_on(X, X2) || !isr_chain_local(X, X2, 5, a, b, c, q, p)) return false;
   const bool cplx = X.cplx;
-  install(Temp2, grid, dim, cplx, c0, c1, std::move(q));
-  install(Temp, grid, dim, cplx, c0, c1, std::move(p));
-  g_slab_counts[1] += 4;
-  isr_chain_counts()[0] += 1;
+  install_like(Temp2, X, cplx, std::move(q));
+  install_like(Temp, X, cplx, std::move(p));
   return true;
 }
 bool ps_isr_chain3(PSMatrix& X, const PSMatrix& X2) {
   CommScope cs(X.grid);
-  if (!isr_chain_on(X, X2)) return false;
-  DevMat o;
-  if (!isr_chain_enter(X, X2) || !slab_isr_chain3(X.loc, X2.loc, X.c0, o)) {
-    isr_chain_counts()[2] += 1;
-    return false;
-  }
+  DevMat o, none;
+  if (!isr_chain_on(X, X2) || !isr_chain_local(X, X2, 3, 0.0, 0.0, 0.0, o, none)) return false;
   X.loc = std::move(o);
-  g_slab_counts[1] += 2;
-  isr_chain_counts()[1] += 1;
   return true;
 }
 bool ps_isr_chain_step(const PSMatrix& X, const PSMatrix& X2, int order, double a, double b, double c, PSMatrix& Out1, PSMatrix& Out2) {
   CommScope cs(X.grid);
-  if ((order != 5 && order != 3) || options().isr_chain == 0 || !slab_on() || X.cplx != X2.cplx || !session_takes(X.cplx) || X.dim != X2.dim ||
-      &X == &X2 || &Out1 == &X || &Out1 == &X2 || &Out2 == &X || &Out2 == &X2 || &Out1 == &Out2)
+  if ((order != 5 && order != 3) || options().isr_chain == 0 || !slab_on() || X.cplx != X2.cplx || !session_takes(X.cplx) || !same_dim({&X, &X2}) ||
+      !all_distinct({&X, &X2, &Out1, &Out2}))
     return false;
   unblock({&X, &X2});
   DevMat q, p;
-  const bool ok = isr_chain_enter(X, X2) && (order == 5 ? slab_isr_chain5(X.loc, X2.loc, a, b, c, X.c0, q, p) : slab_isr_chain3(X.loc, X2.loc, X.c0, q));
-  if (!ok) {
-    isr_chain_counts()[2] += 1;
-    return false;
-  }
+  if (!isr_chain_local(X, X2, order, a, b, c, q, p)) return false;
   pack(q);
-  install(Out1, X.grid, X.dim, X.cplx, X.c0, X.c1, std::move(q));
+  install_like(Out1, X, X.cplx, std::move(q));
   if (order == 5) {
     pack(p);
-    install(Out2, X.grid, X.dim, X.cplx, X.c0, X.c1, std::move(p));
+    install_like(Out2, X, X.cplx, std::move(p));
   }
-  g_slab_counts[1] += order == 5 ? 4 : 2;
-  isr_chain_counts()[order == 5 ? 0 : 1] += 1;
   return true;
 }
 
@@ -1469,17 +1458,18 @@ double trace_local(const PSMatrix& A) {
 }
 // the gates of the fused update (isr_chain_on for three merged operands and WH): a step they keep out is neither fused nor refused
 bool hpcp_update_on(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, const PSMatrix& WH) {
-  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
-  return options().hpcp_step != 0 && slab_on() && !D1.cplx && !DDH.cplx && !D2DH.cplx && !WH.cplx && D1.dim == DDH.dim && D1.dim == D2DH.dim &&
-         D1.dim == WH.dim && &D1 != &DDH && &D1 != &D2DH && &DDH != &D2DH && !blk_any({&D1, &DDH, &D2DH, &WH}) && !WH.loc.blocked() &&
+  return options().hpcp_step != 0 && slab_on() && !D1.cplx && !DDH.cplx && !D2DH.cplx && !WH.cplx && same_dim({&D1, &DDH, &D2DH, &WH}) &&
+         all_distinct({&D1, &DDH, &D2DH}) && !blk_any({&D1, &DDH, &D2DH, &WH}) && !WH.loc.blocked() &&
          (D1.loc.expanded() || DDH.loc.expanded() || D2DH.loc.expanded()) && !labelled(D1) && !labelled(DDH) && !labelled(D2DH) && !labelled(WH);
 }
 // the operands into slab form where they are, as ps_axpby and ps_dot do before their kernels.  *gated: what cannot be fused without
-// being a refusal -- alignments that differ, a WH that is neither a zero-free slab form nor a read-only view
-bool hpcp_update_enter(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, const PSMatrix& WH, bool* gated) {
+// being a refusal -- alignments that differ, a WH that is neither a zero-free slab form nor a read-only view.  Complex operands:
+// WH may become a read-only view (stored zeros, option stored_zero_views), the merged operands may not
+bool hpcp_enter(bool cplx, const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, const PSMatrix& WH, bool* gated) {
+  auto merged = [cplx](const PSMatrix& M) { return cplx ? slab_enter_c(mut(M), nullptr, false) : slab_enter(mut(M)); };
   *gated = false;
-  if (!slab_enter(mut(WH)) || !(WH.loc.zero_free == 1 || WH.loc.slab->origin)) { *gated = true; return false; }
-  if (!slab_enter(mut(D1)) || !slab_enter(mut(DDH)) || !slab_enter(mut(D2DH))) return false;
+  if (!(cplx ? slab_enter_c(mut(WH)) : slab_enter(mut(WH))) || !(WH.loc.zero_free == 1 || WH.loc.slab->origin)) { *gated = true; return false; }
+  if (!merged(D1) || !merged(DDH) || !merged(D2DH)) return false;
   if (D1.loc.slab->row_pad != DDH.loc.slab->row_pad || D1.loc.slab->row_pad != D2DH.loc.slab->row_pad) { *gated = true; return false; }
   return true;
 }
@@ -1487,35 +1477,25 @@ bool hpcp_sigma_ok(double sigma) { return sigma != 0.0 && std::isfinite(sigma); 
 // Option complex_hpcp: the two passes on COMPLEX operands, one rank, inside a session that takes complex operands.  The gates of
 // complex TRS4 (complex_passes_on) and: no labelled slab form, distinct operands.  A pass they keep out is neither fused nor refused
 bool chpcp_on(std::initializer_list<const PSMatrix*> ms) {
-  if (!complex_passes_on(options().complex_hpcp, ms)) return false;
-  for (auto a = ms.begin(); a != ms.end(); ++a) {
-    if ((*a)->loc.expanded() && (*a)->loc.slab->labelled()) return false;
-    for (auto b = a + 1; b != ms.end(); ++b)
-      if (*a == *b) return false;
-  }
+  if (!complex_passes_on(options().complex_hpcp, ms) || !all_distinct(ms)) return false;
+  for (const PSMatrix* m : ms)
+    if (labelled(*m)) return false;
   return true;
 }
-// hpcp_update_enter for complex operands: WH may become a read-only view (stored zeros, option stored_zero_views), the merged
-// operands may not
-bool chpcp_update_enter(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, const PSMatrix& WH, bool* gated) {
-  *gated = false;
-  if (!slab_enter_c(mut(WH)) || !(WH.loc.zero_free == 1 || WH.loc.slab->origin)) { *gated = true; return false; }
-  if (!slab_enter_c(mut(D1), nullptr, false) || !slab_enter_c(mut(DDH), nullptr, false) || !slab_enter_c(mut(D2DH), nullptr, false)) return false;
-  if (D1.loc.slab->row_pad != DDH.loc.slab->row_pad || D1.loc.slab->row_pad != D2DH.loc.slab->row_pad) { *gated = true; return false; }
-  return true;
-}
-// the fused complex update past its gates: the new D1 and DH in slab form; false: refused (counted) or gated (*gated)
-bool chpcp_update(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, DevMat& o, DevMat& h,
-                  double* energy) {
+// the fused update past its gates, operands of one kind: the new D1 and DH in slab form and this rank's energy in e[0]; false: refused
+// (counted) or gated.  A complex update counts in complex_hpcp_counts(), a real one in hpcp_step_counts()
+bool hpcp_update_local(bool cplx, const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, DevMat& o,
+                       DevMat& h, double e[2]) {
+  long long* counts = cplx ? complex_hpcp_counts() : hpcp_step_counts();
   bool gated = false;
-  if (!hpcp_sigma_ok(sigma) || !chpcp_update_enter(D1, DDH, D2DH, WH, &gated) ||
-      !slab_hpcp_update_c(D1.loc, DDH.loc, D2DH.loc, sigma, WH.loc, D1.c0, o, h, energy)) {
-    if (!gated) complex_hpcp_counts()[2] += 1;
+  if (!hpcp_sigma_ok(sigma) || !hpcp_enter(cplx, D1, DDH, D2DH, WH, &gated) ||
+      !(cplx ? slab_hpcp_update_c : slab_hpcp_update)(D1.loc, DDH.loc, D2DH.loc, sigma, WH.loc, D1.c0, o, h, &e[0])) {
+    if (!gated) counts[2] += 1;
     return false;
   }
-  g_slab_counts[1] += 4;   // (counted as the real branch counts it)
-  g_slab_counts[2] += 2;
-  complex_hpcp_counts()[1] += 1;
+  g_slab_counts[1] += 4;   // two merges into D1; the copy and the identity's merge of DH (a complex update counts as the real one)
+  g_slab_counts[2] += 2;   // the scaling of DH, the dot
+  counts[1] += 1;
   return true;
 }
 bool chpcp_traces(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]) {
@@ -1560,78 +1540,42 @@ bool ps_hpcp_traces(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]) {
 bool ps_hpcp_update(PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& DH, double* energy) {
   CommScope cs(D1.grid);
   if (&DH == &D1 || &DH == &DDH || &DH == &D2DH || &DH == &WH) return false;
-  if (D1.cplx || DDH.cplx || D2DH.cplx || WH.cplx) {   // (option complex_hpcp; one rank: no reduction)
-    DevMat o, h;
-    if (!chpcp_on({&D1, &DDH, &D2DH, &WH}) || !(D1.loc.expanded() || DDH.loc.expanded() || D2DH.loc.expanded()) ||
-        !chpcp_update(D1, DDH, D2DH, sigma, WH, o, h, energy))
-      return false;
-    const ProcessGrid* grid = D1.grid;
-    const int32_t dim = D1.dim, c0 = D1.c0, c1 = D1.c1;
-    D1.loc = std::move(o);
-    install(DH, grid, dim, true, c0, c1, std::move(h));
-    return true;
-  }
-  if (!hpcp_update_on(D1, DDH, D2DH, WH)) return false;
-  bool gated = false;
+  const bool cplx = D1.cplx || DDH.cplx || D2DH.cplx || WH.cplx;   // (option complex_hpcp; one rank: no reduction)
+  if (cplx ? !chpcp_on({&D1, &DDH, &D2DH, &WH}) || !(D1.loc.expanded() || DDH.loc.expanded() || D2DH.loc.expanded())
+           : !hpcp_update_on(D1, DDH, D2DH, WH))
+    return false;
   DevMat o, h;
   double e[2] = {0.0, 0.0};
-  if (!hpcp_sigma_ok(sigma) || !hpcp_update_enter(D1, DDH, D2DH, WH, &gated) ||
-      !slab_hpcp_update(D1.loc, DDH.loc, D2DH.loc, sigma, WH.loc, D1.c0, o, h, &e[0])) {
-    if (!gated) hpcp_step_counts()[2] += 1;
-    return false;
-  }
-  const ProcessGrid* grid = D1.grid;
-  const int32_t dim = D1.dim, c0 = D1.c0, c1 = D1.c1;
+  if (!hpcp_update_local(cplx, D1, DDH, D2DH, sigma, WH, o, h, e)) return false;
+  install_like(DH, D1, cplx, std::move(h));
   D1.loc = std::move(o);
-  install(DH, grid, dim, false, c0, c1, std::move(h));
   // (the reduction of the dot this replaces, entry for entry: a rank that refused is in ps_dot's with its own partial sum)
-  comm_allreduce_sum(e, 2);
+  if (!cplx) comm_allreduce_sum(e, 2);
   *energy = e[0];
-  g_slab_counts[1] += 4;   // two merges into D1; the copy and the identity's merge of DH
-  g_slab_counts[2] += 2;   // the scaling of DH, the dot
-  hpcp_step_counts()[1] += 1;
   return true;
 }
 bool ps_hpcp_update_step(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix& D2DH, double sigma, const PSMatrix& WH, PSMatrix& D1out,
                          PSMatrix& DHout, double* energy) {
   CommScope cs(D1.grid);
-  if (D1.cplx && DDH.cplx && D2DH.cplx && WH.cplx) {   // (option complex_hpcp, under the gates of the loop's call)
-    if (&D1out == &DHout || !chpcp_on({&D1, &DDH, &D2DH, &WH})) return false;
-    for (const PSMatrix* m : {&D1, &DDH, &D2DH, &WH})
-      if (m == &D1out || m == &DHout) return false;
-    DevMat o, h;
-    if (!chpcp_update(D1, DDH, D2DH, sigma, WH, o, h, energy)) return false;
-    pack(o);
-    pack(h);
-    install(D1out, D1.grid, D1.dim, true, D1.c0, D1.c1, std::move(o));
-    install(DHout, D1.grid, D1.dim, true, D1.c0, D1.c1, std::move(h));
-    return true;
+  if (!all_distinct({&D1, &DDH, &D2DH, &D1out, &DHout}) || !all_distinct({&WH, &D1out, &DHout})) return false;
+  const bool cplx = D1.cplx && DDH.cplx && D2DH.cplx && WH.cplx;   // (option complex_hpcp, under the gates of the loop's call)
+  if (cplx) {
+    if (!chpcp_on({&D1, &DDH, &D2DH, &WH})) return false;
+  } else {
+    if (options().hpcp_step == 0 || !slab_on() || D1.cplx || DDH.cplx || D2DH.cplx || WH.cplx || !same_dim({&D1, &DDH, &D2DH, &WH}) || labelled(D1) ||
+        labelled(DDH) || labelled(D2DH) || labelled(WH))
+      return false;
+    unblock({&D1, &DDH, &D2DH, &WH});
   }
-  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
-  if (options().hpcp_step == 0 || !slab_on() || D1.cplx || DDH.cplx || D2DH.cplx || WH.cplx || D1.dim != DDH.dim || D1.dim != D2DH.dim ||
-      D1.dim != WH.dim || &D1 == &DDH || &D1 == &D2DH || &DDH == &D2DH || &D1out == &DHout || labelled(D1) || labelled(DDH) || labelled(D2DH) ||
-      labelled(WH))
-    return false;
-  for (const PSMatrix* m : {&D1, &DDH, &D2DH, &WH})
-    if (m == &D1out || m == &DHout) return false;
-  unblock({&D1, &DDH, &D2DH, &WH});
-  bool gated = false;
   DevMat o, h;
   double e[2] = {0.0, 0.0};
-  if (!hpcp_sigma_ok(sigma) || !hpcp_update_enter(D1, DDH, D2DH, WH, &gated) ||
-      !slab_hpcp_update(D1.loc, DDH.loc, D2DH.loc, sigma, WH.loc, D1.c0, o, h, &e[0])) {
-    if (!gated) hpcp_step_counts()[2] += 1;
-    return false;
-  }
+  if (!hpcp_update_local(cplx, D1, DDH, D2DH, sigma, WH, o, h, e)) return false;
   pack(o);
   pack(h);
-  install(D1out, D1.grid, D1.dim, false, D1.c0, D1.c1, std::move(o));
-  install(DHout, D1.grid, D1.dim, false, D1.c0, D1.c1, std::move(h));
-  comm_allreduce_sum(e, 2);
+  install_like(D1out, D1, cplx, std::move(o));
+  install_like(DHout, D1, cplx, std::move(h));
+  if (!cplx) comm_allreduce_sum(e, 2);
   *energy = e[0];
-  g_slab_counts[1] += 4;
-  g_slab_counts[2] += 2;
-  hpcp_step_counts()[1] += 1;
   return true;
 }
 bool ps_hpcp_traces_step(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]) {
@@ -1644,8 +1588,7 @@ bool ps_hpcp_traces_step(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2
     }
     return chpcp_traces(DDH, D2DH, out);
   }
-  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
-  if (options().hpcp_step == 0 || !slab_on() || DDH.dim != D2DH.dim || &DDH == &D2DH || labelled(DDH) || labelled(D2DH)) return false;
+  if (options().hpcp_step == 0 || !slab_on() || !same_dim({&DDH, &D2DH}) || &DDH == &D2DH || labelled(DDH) || labelled(D2DH)) return false;
   unblock({&DDH, &D2DH});
   double t[2] = {0.0, 0.0};
   if (!slab_enter(mut(DDH)) || !slab_enter(mut(D2DH)) || !slab_hpcp_traces(DDH.loc, D2DH.loc, DDH.c0, t)) return false;
@@ -2266,7 +2209,6 @@ bool saf_gates(const PSMatrix& X, const PSMatrix* X2, const PSMatrix& WH) {
 // cannot be fused on this rank without being a refusal -- a session that has given up slab form, a labelled slab form, in_loop:
 // merged operands all in compressed columns, a WH that is neither a zero-free slab form nor a read-only view, alignments that differ
 bool saf_enter(const PSMatrix& X, const PSMatrix* X2, const PSMatrix& WH, bool in_loop, bool* gated) {
-  auto labelled = [](const PSMatrix& M) { return M.loc.expanded() && M.loc.slab->labelled(); };
   *gated = true;
   if (!slab_on() || labelled(X) || labelled(WH) || (X2 && labelled(*X2)) || WH.loc.blocked()) return false;
   if (in_loop && !X.loc.expanded() && !(X2 && X2->loc.expanded())) return false;

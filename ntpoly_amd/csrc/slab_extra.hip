@@ -116,25 +116,49 @@ bool slab_add_diagonal(DevMat& B, double alpha, int32_t col_offset) {
 // are those of the sequence of merges; an entry of the result is where the value is not zero).  Pass 1 reads X and X2
 // and leaves the two dots; pass 2 reads them again and writes P -- instead of four merges and two dots over
 // materialised Fx and Gx.
+// On complex operands (option complex_trs4) every scalar of the chain (4, -3, -2, 1, sigma) is still real, and a real scalar
+// times a complex value is a componentwise product: each part of an entry goes through the real trs4_elem on its own, the
+// identity adding (1, 0) on the diagonal row.  The traces are the real parts of DotMatrix = sum conj(x2) fx and sum conj(x2) gx,
+// x2.re f.re + x2.im f.im with each product and each sum rounded (the terms of k_sa_dot_trace_c); an entry of P exists where
+// either part is not zero (the complex merges keep an entry by its modulus at threshold 0).  Runs of double2: 16 bytes per
+// lane, consecutive lanes on consecutive rows.  No LDS, no scratch, either kind.
 namespace {
+template <typename T>
 struct Trs4Elem {
-  double fx, gx;
+  T fx, gx;
 };
-__device__ inline Trs4Elem trs4_elem(double x, double x2, double d) {
-  Trs4Elem e;
+__device__ inline Trs4Elem<double> trs4_elem(double x, double x2, double d) {
+  Trs4Elem<double> e;
   e.fx = __dadd_rn(__dmul_rn(4.0, x), __dmul_rn(-3.0, x2));
   e.gx = __dadd_rn(x2, __dadd_rn(__dmul_rn(-2.0, x), d));
   return e;
 }
+__device__ inline Trs4Elem<double2> trs4_elem(double2 x, double2 x2, double d) {
+  const Trs4Elem<double> re = trs4_elem(x.x, x2.x, d), im = trs4_elem(x.y, x2.y, 0.0);
+  Trs4Elem<double2> e;
+  e.fx = make_double2(re.fx, im.fx);
+  e.gx = make_double2(re.gx, im.gx);
+  return e;
+}
+// one term of dot(X2, F): the real part of conj(x2) f
+__device__ inline double trs4_dot(double x2, double f) { return __dmul_rn(x2, f); }
+__device__ inline double trs4_dot(double2 x2, double2 f) { return __dadd_rn(__dmul_rn(x2.x, f.x), __dmul_rn(x2.y, f.y)); }
+// fx + sigma gx (complex: each part on its own, the product and the sum of one part before the other's)
+__device__ inline double trs4_p(double fx, double sigma, double gx) { return __dadd_rn(fx, __dmul_rn(sigma, gx)); }
+__device__ inline double2 trs4_p(double2 fx, double sigma, double2 gx) { return make_double2(trs4_p(fx.x, sigma, gx.x), trs4_p(fx.y, sigma, gx.y)); }
+// what is stored for p: p where it is an entry, zero elsewhere (the pair rebuilt, not selected: the code of both kinds stays what it was)
+__device__ inline double trs4_stored(bool keep, double p, double zero) { return keep ? p : zero; }
+__device__ inline double2 trs4_stored(bool keep, double2 p, double2 zero) { return keep ? make_double2(p.x, p.y) : zero; }
+// T = double, or double2 on runs of (re, im) pairs: base, bound and the slots of `out` count entries of T.
 // MODE 0: part[2 j] = sum x2 fx, part[2 j + 1] = sum x2 gx of column j (summed by k_sa_sum_pairs).  MODE 1: out = fx + sigma gx into the slot at
 // base[j] (aligned union of the runs and the diagonal), kept count / first / last per column.
-template <int MODE>
+template <typename T, int MODE>
 __global__ __launch_bounds__(256) void k_sa_trs4(int n, const int32_t* __restrict__ fa, const int32_t* __restrict__ la,
-                                                 const int64_t* __restrict__ offa, const double* __restrict__ va,
+                                                 const int64_t* __restrict__ offa, const T* __restrict__ va,
                                                  const int32_t* __restrict__ fb, const int32_t* __restrict__ lb,
-                                                 const int64_t* __restrict__ offb, const double* __restrict__ vb, int col_offset,
+                                                 const int64_t* __restrict__ offb, const T* __restrict__ vb, int col_offset,
                                                  double sigma, int al, const int64_t* __restrict__ base, double* __restrict__ part,
-                                                 double* __restrict__ out, int32_t* __restrict__ ofirst, int32_t* __restrict__ olast,
+                                                 T* __restrict__ out, int32_t* __restrict__ ofirst, int32_t* __restrict__ olast,
                                                  int32_t* __restrict__ ocount, int64_t* __restrict__ ooff, int64_t bound,
                                                  unsigned long long* __restrict__ stat) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
@@ -146,16 +170,17 @@ __global__ __launch_bounds__(256) void k_sa_trs4(int n, const int32_t* __restric
   if (anyA) { f = min(f, fA); l = max(l, lA); }
   if (anyB) { f = min(f, fB); l = max(l, lB); }
   const int a0 = f / al * al, a1 = (l / al + 1) * al;
-  const double* __restrict__ pa = anyA ? va + (offa[j] - fA) : va;
-  const double* __restrict__ pb = anyB ? vb + (offb[j] - fB) : vb;
+  const T* __restrict__ pa = anyA ? va + (offa[j] - fA) : va;
+  const T* __restrict__ pb = anyB ? vb + (offb[j] - fB) : vb;
+  const T zero = Sc<T>::zero();
   if (MODE == 0) {
     double s0 = 0.0, s1 = 0.0;
     for (int r = a0 + lane; r < a1; r += WAVE) {
-      const double x = (anyA && r >= fA && r <= lA) ? pa[r] : 0.0;
-      const double x2 = (anyB && r >= fB && r <= lB) ? pb[r] : 0.0;
-      const Trs4Elem e = trs4_elem(x, x2, r == dg ? 1.0 : 0.0);
-      s0 = __dadd_rn(s0, __dmul_rn(x2, e.fx));
-      s1 = __dadd_rn(s1, __dmul_rn(x2, e.gx));
+      const T x = (anyA && r >= fA && r <= lA) ? pa[r] : zero;
+      const T x2 = (anyB && r >= fB && r <= lB) ? pb[r] : zero;
+      const Trs4Elem<T> e = trs4_elem(x, x2, r == dg ? 1.0 : 0.0);
+      s0 = __dadd_rn(s0, trs4_dot(x2, e.fx));
+      s1 = __dadd_rn(s1, trs4_dot(x2, e.gx));
     }
     s0 = wave_sum_f64(s0);
     s1 = wave_sum_f64(s1);
@@ -166,15 +191,15 @@ __global__ __launch_bounds__(256) void k_sa_trs4(int n, const int32_t* __restric
       if (lane == 0) { ofirst[j] = INT_MAX; olast[j] = -1; ocount[j] = 0; ooff[j] = slot; atomicOr(stat, 2ull); }
       return;
     }
-    double* __restrict__ dst = out + (slot - a0);
+    T* __restrict__ dst = out + (slot - a0);
     int cnt = 0, kf = INT_MAX, kl = -1;
     for (int r = a0 + lane; r < a1; r += WAVE) {
-      const double x = (anyA && r >= fA && r <= lA) ? pa[r] : 0.0;
-      const double x2 = (anyB && r >= fB && r <= lB) ? pb[r] : 0.0;
-      const Trs4Elem e = trs4_elem(x, x2, r == dg ? 1.0 : 0.0);
-      const double p = __dadd_rn(e.fx, __dmul_rn(sigma, e.gx));
-      const bool keep = p != 0.0;
-      dst[r] = keep ? p : 0.0;
+      const T x = (anyA && r >= fA && r <= lA) ? pa[r] : zero;
+      const T x2 = (anyB && r >= fB && r <= lB) ? pb[r] : zero;
+      const Trs4Elem<T> e = trs4_elem(x, x2, r == dg ? 1.0 : 0.0);
+      const T p = trs4_p(e.fx, sigma, e.gx);
+      const bool keep = !Sc<T>::is_zero(p);   // (complex: where either part is not zero)
+      dst[r] = trs4_stored(keep, p, zero);
       cnt += keep ? 1 : 0;
       kf = min(kf, keep ? r : INT_MAX);
       kl = max(kl, keep ? r : -1);
@@ -240,153 +265,117 @@ void sum_pairs_async(const double* part, int n, double* out2) {
   hipLaunchKernelGGL(k_sa_sum_pairs, dim3(g), dim3(256), 0, stream(), part, n, chunk, lvl.p);
   hipLaunchKernelGGL(k_sa_sum_pairs, dim3(1), dim3(256), 0, stream(), lvl.p, g, g, out2);
 }
+// the tail of a traces-style pass: the n pairs of `part` summed member by member, both sums fetched in the pass's one host wait
+void fetch_pair_sums(const DevBuf<double>& part, int n, double out2[2]) {
+  DevBuf<double> res(2);
+  sum_pairs_async(part.p, n, res.p);
+  ScalarFetch ft;
+  ft.add(res.p, 2, out2);
+  ft.run();
+}
+struct IsrOut {   // one output: values into the slot at base[j], the kept extent and count per column
+  void* val;
+  int32_t* first;
+  int32_t* last;
+  int32_t* count;
+  int64_t* off;
+};
+// The scaffold of a pass that writes one or two fresh slab-form matrices of n columns, `bound` entries (+ kIndexSlack) each.
+// The pass launches its span kernel into `span`, calls scan(), launches its chain kernel on out(q), base, stat (and part, with
+// sums), then finish(): the kept counts summed per output, the pairs of `part` summed, and the pass's one host wait.
+struct FreshSlabs {
+  const int n, outs;
+  const bool cplx;
+  std::unique_ptr<SlabForm> fo[2];
+  DevBuf<int32_t> span;
+  DevBuf<int64_t> base;
+  DevBuf<unsigned long long> stat, tot;
+  DevBuf<double> part, res;   // (with sums only)
+  FreshSlabs(int n_, int outs_, int64_t bound, bool cplx_, bool sums)
+      : n(n_), outs(outs_), cplx(cplx_), span((size_t)n_), base((size_t)n_ + 1), stat(1), tot((size_t)outs_) {
+    for (int q = 0; q < outs; ++q) {
+      fo[q].reset(new SlabForm());
+      fo[q]->first.alloc((size_t)n); fo[q]->last.alloc((size_t)n); fo[q]->count.alloc((size_t)n); fo[q]->off.alloc((size_t)n + 1);
+      fo[q]->val.alloc(((size_t)bound + kIndexSlack) * (cplx ? 2 : 1));
+    }
+    if (sums) { part.alloc((size_t)2 * n); res.alloc(2); }
+    stat.zero();
+    tot.zero();
+  }
+  IsrOut out(int q) const {
+    if (q >= outs) return IsrOut{nullptr, nullptr, nullptr, nullptr, nullptr};
+    return IsrOut{fo[q]->val.p, fo[q]->first.p, fo[q]->last.p, fo[q]->count.p, fo[q]->off.p};
+  }
+  void scan() { scan_i32_async(span.p, base.p, (int64_t)n); }
+  // R[q]: the finished outputs of `rows` rows in slots aligned to `al`; sums: the first nsums sums of part's pairs.
+  // false: the chain kernel set stat (1: a scaled entry underflows to zero, 2: a union extent beyond `bound`) -- nothing returned
+  bool finish(const char* tag, int32_t rows, int al, DevMat* R, double* sums = nullptr, int nsums = 0) {
+    const dim3 sum_grid(std::max(1, std::min(256, cdiv(n, 1024))));
+    for (int q = 0; q < outs; ++q) hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), fo[q]->count.p, n, tot.p + q);
+    if (nsums) sum_pairs_async(part.p, n, res.p);
+    int64_t nnz[2] = {0, 0}, slots = 0;
+    unsigned long long hs = 0;
+    {
+      ScalarFetch ft;
+      ft.add(tot.p, outs, nnz);
+      ft.add(base.p + n, 1, &slots);
+      ft.add(stat.p, 1, &hs);
+      if (nsums) ft.add(res.p, nsums, sums);
+      ft.run();
+    }
+    if (hs != 0) {   // (the caller takes the vocabulary calls)
+      if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+        std::fprintf(stderr, "[%s] refused:%s%s\n", tag, (hs & 1ull) ? " a scaled entry underflows to zero" : "", (hs & 2ull) ? " runs far apart" : "");
+      return false;
+    }
+    for (int q = 0; q < outs; ++q) {
+      fo[q]->row_pad = al;
+      fo[q]->slots = slots;
+      R[q].rows = rows; R[q].cols = n; R[q].cplx = cplx; R[q].nnz = nnz[q]; R[q].zero_free = 1;
+      R[q].slab = std::move(fo[q]);
+    }
+    return true;
+  }
+};
 bool trs4_operands(const DevMat& X, const DevMat& X2) {
   auto ok = [](const DevMat& M) {
     return M.expanded() && !M.cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1;
   };
   return ok(X) && ok(X2) && X.cols == X2.cols && X.slab->row_pad == X2.slab->row_pad;
 }
-}  // namespace
-
-bool slab_trs4_traces(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx) {
-  if (!trs4_operands(X, X2)) return false;
+template <typename T>
+bool trs4_traces_run(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx) {
   const SlabForm &fa = *X.slab, &fb = *X2.slab;
   const int n = X.cols;
-  DevBuf<double> part((size_t)2 * n), res(2);
-  hipLaunchKernelGGL((k_sa_trs4<0>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p, fa.val.p,
-                     fb.first.p, fb.last.p, fb.off.p, fb.val.p, col_offset, 0.0, std::max(1, fa.row_pad), (const int64_t*)nullptr, part.p,
-                     (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0,
-                     (unsigned long long*)nullptr);
-  sum_pairs_async(part.p, n, res.p);
-  unsigned long long h[2] = {0, 0};
-  ScalarFetch ft;
-  ft.add(res.p, 2, h);
-  ft.run();
-  double d[2];
-  std::memcpy(d, h, sizeof(h));
+  DevBuf<double> part((size_t)2 * n);
+  hipLaunchKernelGGL((k_sa_trs4<T, 0>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
+                     reinterpret_cast<const T*>(fa.val.p), fb.first.p, fb.last.p, fb.off.p, reinterpret_cast<const T*>(fb.val.p), col_offset, 0.0,
+                     std::max(1, fa.row_pad), (const int64_t*)nullptr, part.p, (T*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
+                     (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (unsigned long long*)nullptr);
+  double d[2] = {0.0, 0.0};
+  fetch_pair_sums(part, n, d);
   *trace_fx = d[0];
   *trace_gx = d[1];
   return true;
 }
-
-bool slab_trs4_operand(const DevMat& X, const DevMat& X2, double sigma, int32_t col_offset, DevMat& Out) {
-  if (!trs4_operands(X, X2)) return false;
+// P as a fresh slab-form matrix; false: a union extent beyond the output buffer (runs far apart) -- the caller takes the vocabulary calls
+template <typename T>
+bool trs4_operand_run(const DevMat& X, const DevMat& X2, double sigma, int32_t col_offset, DevMat& Out) {
   const SlabForm &fa = *X.slab, &fb = *X2.slab;
   const int n = X.cols, al = std::max(1, fa.row_pad);
-  std::unique_ptr<SlabForm> fo(new SlabForm());
-  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
-  DevBuf<int32_t> span((size_t)n);
-  DevBuf<int64_t> base((size_t)n + 1);
+  const int64_t bound = fa.slots + fb.slots + 4LL * al * n;   // (slots of T)
+  FreshSlabs fs(n, 1, bound, Sc<T>::cplx, false);
   hipLaunchKernelGGL(k_sa_trs4_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fb.first.p, fb.last.p, n, col_offset,
-                     al, span.p);
-  scan_i32_async(span.p, base.p, (int64_t)n);
-  const int64_t bound = fa.slots + fb.slots + 4LL * al * n;
-  fo->val.alloc((size_t)bound + kIndexSlack);
-  DevBuf<unsigned long long> stat(1);
-  stat.zero();
-  hipLaunchKernelGGL((k_sa_trs4<1>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p, fa.val.p,
-                     fb.first.p, fb.last.p, fb.off.p, fb.val.p, col_offset, sigma, al, base.p, (double*)nullptr, fo->val.p, fo->first.p,
-                     fo->last.p, fo->count.p, fo->off.p, bound, stat.p);
-  DevBuf<unsigned long long> tot(1);
-  tot.zero();
-  hipLaunchKernelGGL(k_sa_count_sum, dim3(std::max(1, std::min(256, cdiv(n, 1024)))), dim3(256), 0, stream(), fo->count.p, n, tot.p);
-  int64_t nnz = 0, slots = 0;
-  unsigned long long hs = 0;
-  {
-    ScalarFetch ft;
-    ft.add(tot.p, 1, &nnz);
-    ft.add(base.p + n, 1, &slots);
-    ft.add(stat.p, 1, &hs);
-    ft.run();
-  }
-  if (hs != 0) return false;   // (a union extent beyond the output buffer: runs far apart -- the caller takes compressed columns)
-  fo->row_pad = al;
-  fo->slots = slots;
+                     al, fs.span.p);
+  fs.scan();
+  const IsrOut o = fs.out(0);
+  hipLaunchKernelGGL((k_sa_trs4<T, 1>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
+                     reinterpret_cast<const T*>(fa.val.p), fb.first.p, fb.last.p, fb.off.p, reinterpret_cast<const T*>(fb.val.p), col_offset, sigma,
+                     al, fs.base.p, (double*)nullptr, static_cast<T*>(o.val), o.first, o.last, o.count, o.off, bound, fs.stat.p);
   DevMat R;
-  R.rows = X.rows; R.cols = n; R.cplx = false; R.nnz = nnz; R.zero_free = 1;
-  R.slab = std::move(fo);
+  if (!fs.finish("trs4 operand", X.rows, al, &R)) return false;
   Out = std::move(R);
   return true;
-}
-
-// ------------------------------------------------------------------ ... and on complex operands (option complex_trs4)
-// Every scalar of the chain (4, -3, -2, 1, sigma) is real, and a real scalar times a complex value is a componentwise product:
-// each part of an entry goes through trs4_elem on its own, the identity adding (1, 0) on the diagonal row.  The traces are the
-// real parts of DotMatrix = sum conj(x2) fx and sum conj(x2) gx, x2.re f.re + x2.im f.im with each product and each sum rounded
-// (the terms of k_sa_dot_trace_c); an entry of P exists where either part is not zero (the complex merges keep an entry by its
-// modulus at threshold 0).  Runs of double2: 16 bytes per lane, consecutive lanes on consecutive rows.  No LDS, no scratch.
-namespace {
-struct Trs4ElemC {
-  double2 fx, gx;
-};
-__device__ inline Trs4ElemC trs4_elem_c(double2 x, double2 x2, double d) {
-  const Trs4Elem re = trs4_elem(x.x, x2.x, d), im = trs4_elem(x.y, x2.y, 0.0);
-  Trs4ElemC e;
-  e.fx = make_double2(re.fx, im.fx);
-  e.gx = make_double2(re.gx, im.gx);
-  return e;
-}
-// k_sa_trs4 on runs of (re, im) pairs; base, bound and the slots of `out` count double2
-template <int MODE>
-__global__ __launch_bounds__(256) void k_sa_trs4_c(int n, const int32_t* __restrict__ fa, const int32_t* __restrict__ la,
-                                                   const int64_t* __restrict__ offa, const double2* __restrict__ va,
-                                                   const int32_t* __restrict__ fb, const int32_t* __restrict__ lb,
-                                                   const int64_t* __restrict__ offb, const double2* __restrict__ vb, int col_offset,
-                                                   double sigma, int al, const int64_t* __restrict__ base, double* __restrict__ part,
-                                                   double2* __restrict__ out, int32_t* __restrict__ ofirst, int32_t* __restrict__ olast,
-                                                   int32_t* __restrict__ ocount, int64_t* __restrict__ ooff, int64_t bound,
-                                                   unsigned long long* __restrict__ stat) {
-  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-  if (j >= n) return;
-  const int lane = lane_id();
-  const int fA = fa[j], lA = la[j], fB = fb[j], lB = lb[j], dg = j + col_offset;
-  const bool anyA = lA >= fA, anyB = lB >= fB;
-  int f = dg, l = dg;   // (the identity's entry is always there)
-  if (anyA) { f = min(f, fA); l = max(l, lA); }
-  if (anyB) { f = min(f, fB); l = max(l, lB); }
-  const int a0 = f / al * al, a1 = (l / al + 1) * al;
-  const double2* __restrict__ pa = anyA ? va + (offa[j] - fA) : va;
-  const double2* __restrict__ pb = anyB ? vb + (offb[j] - fB) : vb;
-  const double2 zero = make_double2(0.0, 0.0);
-  if (MODE == 0) {
-    double s0 = 0.0, s1 = 0.0;
-    for (int r = a0 + lane; r < a1; r += WAVE) {
-      const double2 x = (anyA && r >= fA && r <= lA) ? pa[r] : zero;
-      const double2 x2 = (anyB && r >= fB && r <= lB) ? pb[r] : zero;
-      const Trs4ElemC e = trs4_elem_c(x, x2, r == dg ? 1.0 : 0.0);
-      s0 = __dadd_rn(s0, __dadd_rn(__dmul_rn(x2.x, e.fx.x), __dmul_rn(x2.y, e.fx.y)));
-      s1 = __dadd_rn(s1, __dadd_rn(__dmul_rn(x2.x, e.gx.x), __dmul_rn(x2.y, e.gx.y)));
-    }
-    s0 = wave_sum_f64(s0);
-    s1 = wave_sum_f64(s1);
-    if (lane == 0) { part[2 * (size_t)j] = s0; part[2 * (size_t)j + 1] = s1; }
-  } else {
-    const int64_t slot = base[j];
-    if (slot + (int64_t)(a1 - a0) > bound) {   // (runs far apart: the union extent does not fit the output -- refused by the host)
-      if (lane == 0) { ofirst[j] = INT_MAX; olast[j] = -1; ocount[j] = 0; ooff[j] = slot; atomicOr(stat, 2ull); }
-      return;
-    }
-    double2* __restrict__ dst = out + (slot - a0);
-    int cnt = 0, kf = INT_MAX, kl = -1;
-    for (int r = a0 + lane; r < a1; r += WAVE) {
-      const double2 x = (anyA && r >= fA && r <= lA) ? pa[r] : zero;
-      const double2 x2 = (anyB && r >= fB && r <= lB) ? pb[r] : zero;
-      const Trs4ElemC e = trs4_elem_c(x, x2, r == dg ? 1.0 : 0.0);
-      const double pr = __dadd_rn(e.fx.x, __dmul_rn(sigma, e.gx.x)), pi = __dadd_rn(e.fx.y, __dmul_rn(sigma, e.gx.y));
-      const bool keep = pr != 0.0 || pi != 0.0;
-      dst[r] = keep ? make_double2(pr, pi) : zero;
-      cnt += keep ? 1 : 0;
-      kf = min(kf, keep ? r : INT_MAX);
-      kl = max(kl, keep ? r : -1);
-    }
-    cnt = (int)wave_sum_i64(cnt);
-    kf = wave_min_i32(kf);
-    kl = wave_max_i32(kl);
-    if (lane == 0) {
-      ofirst[j] = kf; olast[j] = kl; ocount[j] = cnt;
-      ooff[j] = slot + (cnt ? kf - a0 : 0);
-    }
-  }
 }
 }  // namespace
 
@@ -395,66 +384,17 @@ bool trs4_operands_c(const DevMat& X, const DevMat& X2) {
   return ok(X) && ok(X2) && X.cols == X2.cols && X.rows == X2.rows && X.slab->row_pad == X2.slab->row_pad;
 }
 
-bool slab_trs4_traces_c(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx) {
-  if (!trs4_operands_c(X, X2)) return false;
-  const SlabForm &fa = *X.slab, &fb = *X2.slab;
-  const int n = X.cols;
-  DevBuf<double> part((size_t)2 * n), res(2);
-  hipLaunchKernelGGL((k_sa_trs4_c<0>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
-                     reinterpret_cast<const double2*>(fa.val.p), fb.first.p, fb.last.p, fb.off.p, reinterpret_cast<const double2*>(fb.val.p),
-                     col_offset, 0.0, std::max(1, fa.row_pad), (const int64_t*)nullptr, part.p, (double2*)nullptr, (int32_t*)nullptr,
-                     (int32_t*)nullptr, (int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (unsigned long long*)nullptr);
-  sum_pairs_async(part.p, n, res.p);
-  unsigned long long h[2] = {0, 0};
-  ScalarFetch ft;
-  ft.add(res.p, 2, h);
-  ft.run();
-  double d[2];
-  std::memcpy(d, h, sizeof(h));
-  *trace_fx = d[0];
-  *trace_gx = d[1];
-  return true;
+bool slab_trs4_traces(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx) {
+  return trs4_operands(X, X2) && trs4_traces_run<double>(X, X2, col_offset, trace_fx, trace_gx);
 }
-
+bool slab_trs4_traces_c(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx) {
+  return trs4_operands_c(X, X2) && trs4_traces_run<double2>(X, X2, col_offset, trace_fx, trace_gx);
+}
+bool slab_trs4_operand(const DevMat& X, const DevMat& X2, double sigma, int32_t col_offset, DevMat& Out) {
+  return trs4_operands(X, X2) && trs4_operand_run<double>(X, X2, sigma, col_offset, Out);
+}
 bool slab_trs4_operand_c(const DevMat& X, const DevMat& X2, double sigma, int32_t col_offset, DevMat& Out) {
-  if (!trs4_operands_c(X, X2)) return false;
-  const SlabForm &fa = *X.slab, &fb = *X2.slab;
-  const int n = X.cols, al = std::max(1, fa.row_pad);
-  std::unique_ptr<SlabForm> fo(new SlabForm());
-  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
-  DevBuf<int32_t> span((size_t)n);
-  DevBuf<int64_t> base((size_t)n + 1);
-  hipLaunchKernelGGL(k_sa_trs4_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fb.first.p, fb.last.p, n, col_offset,
-                     al, span.p);
-  scan_i32_async(span.p, base.p, (int64_t)n);
-  const int64_t bound = fa.slots + fb.slots + 4LL * al * n;   // (slots of (re, im) pairs)
-  fo->val.alloc(((size_t)bound + kIndexSlack) * 2);
-  DevBuf<unsigned long long> stat(1);
-  stat.zero();
-  hipLaunchKernelGGL((k_sa_trs4_c<1>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
-                     reinterpret_cast<const double2*>(fa.val.p), fb.first.p, fb.last.p, fb.off.p, reinterpret_cast<const double2*>(fb.val.p),
-                     col_offset, sigma, al, base.p, (double*)nullptr, reinterpret_cast<double2*>(fo->val.p), fo->first.p, fo->last.p,
-                     fo->count.p, fo->off.p, bound, stat.p);
-  DevBuf<unsigned long long> tot(1);
-  tot.zero();
-  hipLaunchKernelGGL(k_sa_count_sum, dim3(std::max(1, std::min(256, cdiv(n, 1024)))), dim3(256), 0, stream(), fo->count.p, n, tot.p);
-  int64_t nnz = 0, slots = 0;
-  unsigned long long hs = 0;
-  {
-    ScalarFetch ft;
-    ft.add(tot.p, 1, &nnz);
-    ft.add(base.p + n, 1, &slots);
-    ft.add(stat.p, 1, &hs);
-    ft.run();
-  }
-  if (hs != 0) return false;   // (a union extent beyond the output buffer: runs far apart -- the caller runs the vocabulary calls)
-  fo->row_pad = al;
-  fo->slots = slots;
-  DevMat R;
-  R.rows = X.rows; R.cols = n; R.cplx = true; R.nnz = nnz; R.zero_free = 1;
-  R.slab = std::move(fo);
-  Out = std::move(R);
-  return true;
+  return trs4_operands_c(X, X2) && trs4_operand_run<double2>(X, X2, sigma, col_offset, Out);
 }
 
 // ------------------------------------------------------------------ MatrixNorm(alpha A + beta B) without the sum
@@ -1189,15 +1129,10 @@ __global__ __launch_bounds__(256) void k_insert_zeros(Csc A, const int64_t* __re
 bool slab_pm_sigma(const DevMat& X, const ZeroList& Z, const DevMat& X2, double thr, int32_t col_offset, double out2[2]) {
   if (!pm_operands(X, X2, nullptr)) return false;
   const int n = X.cols;
-  DevBuf<double> part((size_t)2 * n), res(2);
+  DevBuf<double> part((size_t)2 * n);
   hipLaunchKernelGGL(k_pm_sigma, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, pm_runs(X), Z.count ? Z.off.p : nullptr, Z.row.p,
                      pm_runs(X2), col_offset, std::max(1, X.slab->row_pad), thr, part.p);
-  sum_pairs_async(part.p, n, res.p);
-  unsigned long long h[2] = {0, 0};
-  ScalarFetch ft;
-  ft.add(res.p, 2, h);
-  ft.run();
-  std::memcpy(out2, h, sizeof(h));
+  fetch_pair_sums(part, n, out2);
   return true;
 }
 
@@ -1310,13 +1245,6 @@ __device__ inline T isr_merge(double sa, T a, bool ha, double sb, T b, bool hb, 
   *present = (ha || hb) && Sc<T>::mag(o) > 0.0;
   return *present ? o : Sc<T>::zero();
 }
-struct IsrOut {   // one output: values into the slot at base[j], the kept extent and count per column
-  void* val;
-  int32_t* first;
-  int32_t* last;
-  int32_t* count;
-  int64_t* off;
-};
 constexpr int ISR_KC = 4;   // chunks of 64 rows whose loads are all requested before the first of them is used
 // One wave per column, lanes on consecutive rows of the aligned union [a0, a1) of the two runs and the diagonal row.
 // ORDER 5: o1 = Temp2 (q), o2 = Temp (p); ORDER 3: o1 = the new X, s1 = -1/2, s2 = 0.375, o2 unused.
@@ -1429,52 +1357,18 @@ bool isr_operands(const DevMat& X, const DevMat& X2) {
 template <typename T, int ORDER>
 bool isr_chain_run(const DevMat& X, const DevMat& X2, double s1, double s2, double s3, int32_t col_offset, DevMat& Out1, DevMat* Out2) {
   const SlabForm &fa = *X.slab, &fb = *X2.slab;
-  const int n = X.cols, al = std::max(1, fa.row_pad), outs = ORDER == 5 ? 2 : 1;
-  const size_t w = Sc<T>::cplx ? 2 : 1;
-  std::unique_ptr<SlabForm> fo[2];
-  IsrOut o[2] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};
+  const int n = X.cols, al = std::max(1, fa.row_pad);
   // (the operands' slots, and per column the diagonal's slot and the pads of a union -- with room for diagonals away from their runs)
   const int64_t bound = fa.slots + fb.slots + 4LL * al * n;
-  for (int q = 0; q < outs; ++q) {
-    fo[q].reset(new SlabForm());
-    fo[q]->first.alloc((size_t)n); fo[q]->last.alloc((size_t)n); fo[q]->count.alloc((size_t)n); fo[q]->off.alloc((size_t)n + 1);
-    fo[q]->val.alloc(((size_t)bound + kIndexSlack) * w);
-    o[q] = IsrOut{fo[q]->val.p, fo[q]->first.p, fo[q]->last.p, fo[q]->count.p, fo[q]->off.p};
-  }
-  DevBuf<int32_t> span((size_t)n);
-  DevBuf<int64_t> base((size_t)n + 1);
-  DevBuf<unsigned long long> stat(1), tot(2);
-  stat.zero();
-  tot.zero();
+  FreshSlabs fs(n, ORDER == 5 ? 2 : 1, bound, Sc<T>::cplx, false);
   hipLaunchKernelGGL(k_sa_trs4_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), fa.first.p, fa.last.p, fb.first.p, fb.last.p, n, col_offset,
-                     al, span.p);
-  scan_i32_async(span.p, base.p, (int64_t)n);
+                     al, fs.span.p);
+  fs.scan();
   hipLaunchKernelGGL((k_sa_isr_chain<T, ORDER>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p,
                      reinterpret_cast<const T*>(fa.val.p), fb.first.p, fb.last.p, fb.off.p, reinterpret_cast<const T*>(fb.val.p), col_offset, s1,
-                     s2, s3, al, base.p, o[0], o[1], bound, stat.p);
-  const dim3 sum_grid(std::max(1, std::min(256, cdiv(n, 1024))));
-  for (int q = 0; q < outs; ++q) hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), fo[q]->count.p, n, tot.p + q);
-  int64_t nnz[2] = {0, 0}, slots = 0;
-  unsigned long long hs = 0;
-  {
-    ScalarFetch ft;
-    ft.add(tot.p, 2, nnz);
-    ft.add(base.p + n, 1, &slots);
-    ft.add(stat.p, 1, &hs);
-    ft.run();
-  }
-  if (hs != 0) {
-    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
-      std::fprintf(stderr, "[isr chain] refused:%s%s\n", (hs & 1ull) ? " a scaled entry underflows to zero" : "", (hs & 2ull) ? " runs far apart" : "");
-    return false;
-  }
+                     s2, s3, al, fs.base.p, fs.out(0), fs.out(1), bound, fs.stat.p);
   DevMat R[2];
-  for (int q = 0; q < outs; ++q) {
-    fo[q]->row_pad = al;
-    fo[q]->slots = slots;
-    R[q].rows = X.rows; R[q].cols = n; R[q].cplx = Sc<T>::cplx; R[q].nnz = nnz[q]; R[q].zero_free = 1;
-    R[q].slab = std::move(fo[q]);
-  }
+  if (!fs.finish("isr chain", X.rows, al, R)) return false;
   bump_matrix_value_epoch();   // (of the calls it replaces, two are merges in place: slab_axpby counts them so)
   bump_matrix_value_epoch();
   Out1 = std::move(R[0]);
@@ -1645,12 +1539,9 @@ bool hpcp_operand(const DevMat& M, bool cplx = false) {
 template <typename T>
 bool hpcp_traces_run(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]) {
   const int n = DDH.cols;
-  DevBuf<double> part((size_t)2 * n), res(2);
+  DevBuf<double> part((size_t)2 * n);
   hipLaunchKernelGGL(k_hpcp_traces<T>, dim3(cdiv(n, 256)), dim3(256), 0, stream(), n, hpcp_runs(DDH), hpcp_runs(D2DH), col_offset, part.p);
-  sum_pairs_async(part.p, n, res.p);
-  ScalarFetch ft;
-  ft.add(res.p, 2, out2);
-  ft.run();
+  fetch_pair_sums(part, n, out2);
   return true;
 }
 // the update on operands of one kind; the slots, `bound` and the outputs' buffers count entries of T
@@ -1668,53 +1559,17 @@ bool hpcp_update_run(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, do
     return false;
   const SlabForm &fa = *D1.slab, &fb = *DDH.slab, &fc = *D2DH.slab;
   const int n = D1.cols, al = std::max(1, fa.row_pad);
-  std::unique_ptr<SlabForm> fo[2];
-  IsrOut o[2];
   // (the operands' slots, and per column the diagonal's slot and the pads of a hull -- with room for diagonals away from their runs)
   const int64_t bound = fa.slots + fb.slots + fc.slots + 6LL * al * n;
-  for (int q = 0; q < 2; ++q) {
-    fo[q].reset(new SlabForm());
-    fo[q]->first.alloc((size_t)n); fo[q]->last.alloc((size_t)n); fo[q]->count.alloc((size_t)n); fo[q]->off.alloc((size_t)n + 1);
-    fo[q]->val.alloc(((size_t)bound + kIndexSlack) * (cplx ? 2 : 1));
-    o[q] = IsrOut{fo[q]->val.p, fo[q]->first.p, fo[q]->last.p, fo[q]->count.p, fo[q]->off.p};
-  }
-  DevBuf<int32_t> span((size_t)n);
-  DevBuf<int64_t> base((size_t)n + 1);
-  DevBuf<unsigned long long> stat(1), tot(2);
-  DevBuf<double> part((size_t)2 * n), res(2);
-  stat.zero();
-  tot.zero();
+  FreshSlabs fs(n, 2, bound, cplx, true);
   const HpcpRuns ra = hpcp_runs(D1), rb = hpcp_runs(DDH), rc = hpcp_runs(D2DH);
-  hipLaunchKernelGGL(k_hpcp_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, rc, n, col_offset, al, span.p);
-  scan_i32_async(span.p, base.p, (int64_t)n);
+  hipLaunchKernelGGL(k_hpcp_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, rc, n, col_offset, al, fs.span.p);
+  fs.scan();
   hipLaunchKernelGGL((k_hpcp_update<T, KC>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, rc, hpcp_runs(WH), col_offset,
-                     -1.0 * 2.0 * sigma, al, base.p, o[0], o[1], bound, part.p, stat.p);
-  const dim3 sum_grid(std::max(1, std::min(256, cdiv(n, 1024))));
-  for (int q = 0; q < 2; ++q) hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), fo[q]->count.p, n, tot.p + q);
-  sum_pairs_async(part.p, n, res.p);
-  int64_t nnz[2] = {0, 0}, slots = 0;
-  unsigned long long hs = 0;
-  double e = 0.0;
-  {
-    ScalarFetch ft;
-    ft.add(tot.p, 2, nnz);
-    ft.add(base.p + n, 1, &slots);
-    ft.add(stat.p, 1, &hs);
-    ft.add(res.p, 1, &e);
-    ft.run();
-  }
-  if (hs != 0) {
-    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
-      std::fprintf(stderr, "[hpcp update] refused:%s%s\n", (hs & 1ull) ? " a scaled entry underflows to zero" : "", (hs & 2ull) ? " runs far apart" : "");
-    return false;
-  }
+                     -1.0 * 2.0 * sigma, al, fs.base.p, fs.out(0), fs.out(1), bound, fs.part.p, fs.stat.p);
   DevMat R[2];
-  for (int q = 0; q < 2; ++q) {
-    fo[q]->row_pad = al;
-    fo[q]->slots = slots;
-    R[q].rows = D1.rows; R[q].cols = n; R[q].cplx = cplx; R[q].nnz = nnz[q]; R[q].zero_free = 1;
-    R[q].slab = std::move(fo[q]);
-  }
+  double e = 0.0;
+  if (!fs.finish("hpcp update", D1.rows, al, R, &e, 1)) return false;
   bump_matrix_value_epoch();   // (of the calls it replaces, the two merges into D1 are in place: slab_axpby counts them so)
   bump_matrix_value_epoch();
   OutD1 = std::move(R[0]);
@@ -1879,46 +1734,17 @@ bool slab_saf_update(const DevMat& X, const DevMat& X2, double a, double b, cons
     return false;
   const SlabForm &fa = *X.slab, &fb = *X2.slab;
   const int n = X.cols, al = std::max(1, fa.row_pad);
-  std::unique_ptr<SlabForm> fo(new SlabForm());
   // (the operands' slots and per column the pads of a hull)
   const int64_t bound = fa.slots + fb.slots + 4LL * al * n;
-  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
-  fo->val.alloc((size_t)bound + kIndexSlack);
-  const IsrOut o{fo->val.p, fo->first.p, fo->last.p, fo->count.p, fo->off.p};
-  DevBuf<int32_t> span((size_t)n);
-  DevBuf<int64_t> base((size_t)n + 1);
-  DevBuf<unsigned long long> stat(1), tot(1);
-  DevBuf<double> part((size_t)2 * n), res(2);
-  stat.zero();
-  tot.zero();
+  FreshSlabs fs(n, 1, bound, false, true);
   const HpcpRuns ra = hpcp_runs(X), rb = hpcp_runs(X2);
-  hipLaunchKernelGGL(k_saf_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, n, al, span.p);
-  scan_i32_async(span.p, base.p, (int64_t)n);
+  hipLaunchKernelGGL(k_saf_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, n, al, fs.span.p);
+  fs.scan();
   hipLaunchKernelGGL(k_saf_update, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, hpcp_runs(WH), col_offset, a, b, al,
-                     base.p, o, bound, part.p, stat.p);
-  hipLaunchKernelGGL(k_sa_count_sum, dim3(std::max(1, std::min(256, cdiv(n, 1024)))), dim3(256), 0, stream(), fo->count.p, n, tot.p);
-  sum_pairs_async(part.p, n, res.p);
-  int64_t nnz = 0, slots = 0;
-  unsigned long long hs = 0;
-  double sums[2] = {0.0, 0.0};
-  {
-    ScalarFetch ft;
-    ft.add(tot.p, 1, &nnz);
-    ft.add(base.p + n, 1, &slots);
-    ft.add(stat.p, 1, &hs);
-    ft.add(res.p, 2, sums);
-    ft.run();
-  }
-  if (hs != 0) {
-    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
-      std::fprintf(stderr, "[scale and fold update] refused:%s%s\n", (hs & 1ull) ? " a scaled entry underflows to zero" : "", (hs & 2ull) ? " runs far apart" : "");
-    return false;
-  }
+                     fs.base.p, fs.out(0), bound, fs.part.p, fs.stat.p);
   DevMat R;
-  fo->row_pad = al;
-  fo->slots = slots;
-  R.rows = X.rows; R.cols = n; R.cplx = false; R.nnz = nnz; R.zero_free = 1;
-  R.slab = std::move(fo);
+  double sums[2] = {0.0, 0.0};
+  if (!fs.finish("scale and fold update", X.rows, al, &R, sums, 2)) return false;
   bump_matrix_value_epoch();   // (the merge it replaces is in place: slab_axpby counts it so)
   Out = std::move(R);
   *dot = sums[0];
@@ -1929,13 +1755,10 @@ bool slab_saf_update(const DevMat& X, const DevMat& X2, double a, double b, cons
 bool slab_saf_dot_trace(const DevMat& X, const DevMat& WH, int32_t col_offset, double* dot, double* trace) {
   if (!hpcp_operand(X) || !saf_wh_ok(WH) || X.cols != WH.cols || X.rows != WH.rows) return false;
   const int n = X.cols;
-  DevBuf<double> part((size_t)2 * n), res(2);
+  DevBuf<double> part((size_t)2 * n);
   hipLaunchKernelGGL(k_saf_dot_trace, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, hpcp_runs(X), hpcp_runs(WH), col_offset, part.p);
-  sum_pairs_async(part.p, n, res.p);
   double sums[2] = {0.0, 0.0};
-  ScalarFetch ft;
-  ft.add(res.p, 2, sums);
-  ft.run();
+  fetch_pair_sums(part, n, sums);
   *dot = sums[0];
   *trace = sums[1];
   return true;

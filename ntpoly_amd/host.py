@@ -1175,7 +1175,7 @@ def scale_fold_dot_trace(X, WH):
 
 
 def complex_trs4_counts():
-    """complex TRS4 in a complex slab session (option complex_trs4; csrc/slab_extra.hip k_sa_trs4_c) since start: trace passes
+    """complex TRS4 in a complex slab session (option complex_trs4; csrc/slab_extra.hip k_sa_trs4<double2, .>) since start: trace passes
     fused, operands Fx + sigma Gx fused, energies fused, passes refused (the vocabulary calls ran instead); slab_algebra_counts()
     counts a fused pass as the real branch does.  A pass kept out by a gate (the option off, no open complex session, several
     ranks, block form, a labelled slab form) is neither fused nor counted as refused"""

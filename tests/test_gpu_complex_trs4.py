@@ -1,4 +1,4 @@
-"""GPU: complex TRS4 in a complex slab session (option complex_trs4; csrc/slab_extra.hip k_sa_trs4_c, engine.hpp ps_trs4_traces /
+"""GPU: complex TRS4 in a complex slab session (option complex_trs4; csrc/slab_extra.hip k_sa_trs4<double2, .>, engine.hpp ps_trs4_traces /
 ps_trs4_operand / ps_trs4_energy).  Behind its product X X -> X2 an iteration builds, with the vocabulary at threshold 0,
 Fx = 4 X - 3 X2 and Gx = I - 2 X + X2, takes dot(X2, Fx) and dot(X2, Gx), and multiplies X2 by Fx + sigma Gx; the fused passes read
 the runs of X and X2 twice and never build Fx and Gx, and the energy Re dot(X, WH) comes from one pass over X's runs.
