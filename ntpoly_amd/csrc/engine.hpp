@@ -260,6 +260,19 @@ bool ps_saf_dot_trace(const PSMatrix& X, const PSMatrix& WH, double* dot, double
 bool ps_saf_update_step(const PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, PSMatrix& Xout, double* dot, double* trace);
 bool ps_saf_dot_trace_step(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace);
 long long* scale_fold_step_counts();   // since start: [0] updates fused, [1] dot-and-trace passes fused, [2] refused (past the gates: a gated step counts nowhere)
+// Option complex_scale_fold (one rank, inside a session that takes complex operands): the four calls above take COMPLEX operands
+// (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of
+// the vocabulary calls at threshold 0 bit for bit; the scale branch's pass is slab_dot_trace_c over X and WH as it stands -- slab
+// form, a read-only view or compressed columns).  *dot = Re dot(X, WH) to rounding, *trace = the sum of the real parts of the
+// diagonal with the bits of slab_dot_trace_c -- which, with the option on, is what ps_trace returns for a complex slab-form matrix
+// in a complex session (trace_local; with the option at 0, and for compressed columns, k_trace as before).  No collective.  Gates (complex_scale_fold off -- scale_fold_step is for real
+// operands only --, several ranks, no complex session, block or loose form, a labelled slab form, operands that are not all
+// complex, of one dimension and distinct; in the loop: X not left in slab form by the product; alignments that differ, a WH that
+// becomes neither a zero-free slab form nor a read-only view) count nothing; past them factors that are not finite, an operand the
+// kernel's rules exclude once it is in slab form (stored zeros in a merged operand) and a non-zero status (runs far apart, an
+// underflow) count as refused in complex_scale_fold_counts().  slab_algebra_counts() counts a fused pass as the real branch does;
+// scale_fold_step_counts() never counts a complex pass.
+long long* complex_scale_fold_counts();   // since start: [0] fold updates fused, [1] dot-and-trace passes fused, [2] passes refused
 // solvers.cpp: this loop may take a complex operand like m in slab form (FMA arithmetic, complex tile kernel, complex_sessions)
 bool complex_slab_loop(const PSMatrix& m);
 void ps_slab_leave(PSMatrix& m);   // back to compressed columns (no-op for a matrix that is not in slab form)

@@ -2721,6 +2721,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_SCALE_FOLD_STEP")) e->scale_fold_step = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_TRS4")) e->complex_trs4 = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_HPCP")) e->complex_hpcp = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_SCALE_FOLD")) e->complex_scale_fold = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_DENSITY")) e->complex_density = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_SCOPE_COMPLEX")) e->block_scope_complex = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_UNFUSED")) e->block_unfused = std::atoi(v);

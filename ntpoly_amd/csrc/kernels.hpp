@@ -105,6 +105,7 @@ struct EngineOptions {
   int scale_fold_step = 1;     // ScaleAndFold, real operands, inside a real slab session (one rank and column panels across ranks): behind the step's one product, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update: the values and pattern of the vocabulary calls at threshold 0 and the trace of slab_trace bit for bit; the energy is summed in another order and only feeds the convergence monitor); the scale branch, whose product's result is the new X, takes the energy and the trace from one pass over X and WH (k_saf_dot_trace) -- one read-back per step instead of two or three; a step the kernel refuses runs the calls as before.  0: the three calls, one by one
   int complex_trs4 = 0;        // complex TRS4 on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and the second product's operand stay runs of (re, im) pairs between the products on the complex tile kernel --, the traces dot(X2, Fx) and dot(X2, Gx) come from ONE pass over X and X X without building Fx and Gx, the operand Fx + sigma Gx from a second one (slab_extra.hip k_sa_trs4<double2, .>: the real kernel's arithmetic on each part, the values and pattern of the four merges at threshold 0), and the energy Re dot(X, WH) from one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  0 (default; measured 4.51 against 10.62 ms per iteration on configs[4]'s operand, profiles/README.md 130, but the rule that decides defaults also wants option 0 and the parent commit equal within the block spread, which one run missed by a hair): the loop on compressed columns, bit for bit as before
   int complex_hpcp = 0;        // complex HPCP on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- D1, DH and both products stay runs of (re, im) pairs between the products on the complex tile kernel --, the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH (slab_extra.hip k_hpcp_traces<double2>: the real parts), and the two merges into D1, the energy Re dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update<double2, .>: the real kernel's chain on each part of an entry, the values and patterns of the vocabulary calls at threshold 0); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of hpcp_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
+  int complex_scale_fold = 0;  // complex ScaleAndFold on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X and its square stay runs of (re, im) pairs around the one product on the complex tile kernel --, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy Re dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of the vocabulary calls at threshold 0, the trace with the bits of k_sa_dot_trace_c, which with the option on is also MatrixTrace of a complex slab-form matrix in a complex session), and the scale branch takes the energy and the trace from one pass over X and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of scale_fold_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
   int plan_fused = 1;          // the maxima and prefix sums of a slab step's plan in ONE launch (k_slab_offsets: every workgroup sums what lies before its part itself) instead of four to seven; 0: separate launches
@@ -354,6 +355,14 @@ bool slab_hpcp_update_c(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH,
 bool slab_saf_update(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
                      double* trace);
 bool slab_saf_dot_trace(const DevMat& X, const DevMat& WH, int32_t col_offset, double* dot, double* trace);
+// the fold update on COMPLEX slab-form operands (option complex_scale_fold; k_saf_update<double2, .>: runs of (re, im) pairs, 16
+// bytes per lane).  Both factors are real, so the scaling and the merge work part by part and keep an entry where either part is
+// not zero -- the values and pattern of the two vocabulary calls on complex matrices at threshold 0 bit for bit; *dot = Re dot(Out,
+// WH), each product and each pair's sum rounded (the terms of slab_dot_trace_c, in another fixed order), *trace = the sum of the
+// real parts of Out's diagonal with the bits slab_dot_trace_c gives on Out.  X and X2: sa_operand_c and zero-free; WH: zero-free or
+// a read-only view; slots and the bound count pairs.  The scale branch's pass on complex operands is slab_dot_trace_c itself
+bool slab_saf_update_c(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
+                       double* trace);
 // PM purification on a slab-form iterate (slab_extra.hip).  The rows of each column that compressed columns would hold as STORED
 // ZEROS (a1 = 0 when sigma > 1/2, unfiltered tails that underflow) travel next to the zero-free runs: rows row[off[j] .. off[j + 1])
 // of column j, ascending, disjoint from the run's non-zeros.  off.p == nullptr: no such row.

@@ -1451,6 +1451,15 @@ double trace_local(const PSMatrix& A) {
       return v;
     }
     slab_refused({&A});
+  } else if (complex_passes_on(options().complex_scale_fold, {&A}) && A.loc.expanded() && !labelled(A)) {
+    // (option complex_scale_fold: MatrixTrace of a complex slab-form matrix in a complex session is the pass over its runs, the sum
+    // the loop's fused passes return -- every trace(X) of the loop on an X in slab form is then summed in one order, fused or not)
+    double v = 0.0;
+    if (slab_dot_trace_c(A.loc, nullptr, A.c0, nullptr, &v)) {
+      g_slab_counts[2] += 1;
+      return v;
+    }
+    slab_pack_if({&A});
   } else {
     slab_pack_if({&A});
   }
@@ -2233,9 +2242,63 @@ bool saf_local(const PSMatrix& X, const PSMatrix* X2, double a, double b, const 
   }
   return taken;
 }
+// Option complex_scale_fold: the two passes on COMPLEX operands, one rank, inside a session that takes complex operands.  The gates
+// of complex TRS4 (complex_passes_on) and: no labelled slab form, distinct operands.  A pass they keep out is neither fused nor refused
+bool csaf_on(const PSMatrix& X, const PSMatrix* X2, const PSMatrix& WH) {
+  const bool on = X2 ? complex_passes_on(options().complex_scale_fold, {&X, X2, &WH}) && all_distinct({&X, X2, &WH})
+                     : complex_passes_on(options().complex_scale_fold, {&X, &WH}) && &X != &WH;
+  return on && !labelled(X) && !labelled(WH) && !(X2 && labelled(*X2));
+}
+// the complex fold update past its gates (what the complex HPCP update takes: WH may become a read-only view, the merged operands
+// may not), sums = {Re dot, trace}; false: refused (counted) or gated
+bool csaf_update_local(const PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, DevMat& out, double sums[2]) {
+  bool gated = false;
+  const bool taken = [&] {
+    if (!std::isfinite(a) || !std::isfinite(b)) return false;   // (refused before any operand is touched, as saf_local does)
+    if (!slab_enter_c(mut(WH)) || !(WH.loc.zero_free == 1 || WH.loc.slab->origin)) { gated = true; return false; }
+    if (!slab_enter_c(mut(X), nullptr, false) || !slab_enter_c(mut(X2), nullptr, false)) return false;
+    if (X.loc.slab->row_pad != X2.loc.slab->row_pad) { gated = true; return false; }
+    return slab_saf_update_c(X.loc, X2.loc, a, b, WH.loc, X.c0, out, &sums[0], &sums[1]);
+  }();
+  if (taken) {
+    g_slab_counts[1] += 1;   // the merge (a complex update counts as the real one)
+    g_slab_counts[2] += 2;   // the dot, the next step's trace
+    complex_scale_fold_counts()[0] += 1;
+  } else if (!gated) {
+    complex_scale_fold_counts()[2] += 1;
+  }
+  return taken;
+}
+// the scale branch's pass on a complex X in slab form and WH as it stands (what ps_trs4_energy takes: complex slab form, a
+// read-only view, or compressed columns -- stored zeros add exact zeros to the sum); false: refused (counted)
+bool csaf_dot_trace_local(const PSMatrix& X, const PSMatrix& WH, double sums[2]) {
+  double dot[2] = {0.0, 0.0}, t = 0.0;
+  if (!sa_operand_c(X.loc) || !slab_dot_trace_c(X.loc, &WH.loc, X.c0, dot, &t)) {
+    complex_scale_fold_counts()[2] += 1;
+    return false;
+  }
+  g_slab_counts[2] += 2;   // the dot, the next step's trace
+  complex_scale_fold_counts()[1] += 1;
+  sums[0] = dot[0];
+  sums[1] = t;
+  return true;
+}
 }  // namespace
+long long* complex_scale_fold_counts() {
+  static long long counts[3] = {0, 0, 0};
+  return counts;
+}
 bool ps_saf_update(PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, double* dot, double* trace) {
   CommScope cs(X.grid);
+  if (X.cplx || X2.cplx || WH.cplx) {   // (option complex_scale_fold; one rank: no reduction)
+    DevMat o;
+    double s[2] = {0.0, 0.0};
+    if (!csaf_on(X, &X2, WH) || !(X.loc.expanded() || X2.loc.expanded()) || !csaf_update_local(X, X2, a, b, WH, o, s)) return false;
+    X.loc = std::move(o);
+    *dot = s[0];
+    *trace = s[1];
+    return true;
+  }
   if (!saf_gates(X, &X2, WH)) return false;
   DevMat o;
   double s[2] = {0.0, 0.0};
@@ -2255,6 +2318,13 @@ bool ps_saf_update(PSMatrix& X, const PSMatrix& X2, double a, double b, const PS
 }
 bool ps_saf_dot_trace(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace) {
   CommScope cs(X.grid);
+  if (X.cplx || WH.cplx) {   // (option complex_scale_fold; one rank: no reduction)
+    double s[2] = {0.0, 0.0};
+    if (!csaf_on(X, nullptr, WH) || !X.loc.expanded() || !csaf_dot_trace_local(X, WH, s)) return false;
+    *dot = s[0];
+    *trace = s[1];
+    return true;
+  }
   if (!saf_gates(X, nullptr, WH)) return false;
   DevMat none;
   double s[2] = {0.0, 0.0};
@@ -2270,6 +2340,16 @@ bool ps_saf_dot_trace(const PSMatrix& X, const PSMatrix& WH, double* dot, double
 }
 bool ps_saf_update_step(const PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, PSMatrix& Xout, double* dot, double* trace) {
   CommScope cs(X.grid);
+  if (X.cplx || X2.cplx || WH.cplx) {   // (option complex_scale_fold, under the gates of the loop's call)
+    DevMat o;
+    double s[2] = {0.0, 0.0};
+    if (!csaf_on(X, &X2, WH) || &Xout == &X || &Xout == &X2 || &Xout == &WH || !csaf_update_local(X, X2, a, b, WH, o, s)) return false;
+    pack(o);
+    install_like(Xout, X, true, std::move(o));
+    *dot = s[0];
+    *trace = s[1];
+    return true;
+  }
   if (!saf_gates(X, &X2, WH) || &Xout == &X || &Xout == &X2 || &Xout == &WH) return false;
   DevMat o;
   double s[2] = {0.0, 0.0};
@@ -2283,6 +2363,18 @@ bool ps_saf_update_step(const PSMatrix& X, const PSMatrix& X2, double a, double 
 }
 bool ps_saf_dot_trace_step(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace) {
   CommScope cs(X.grid);
+  if (X.cplx || WH.cplx) {   // (option complex_scale_fold, under the gates of the loop's call)
+    double s[2] = {0.0, 0.0};
+    if (!csaf_on(X, nullptr, WH)) return false;
+    if (!X.loc.expanded() && !slab_enter_c(mut(X), nullptr, false)) {
+      complex_scale_fold_counts()[2] += 1;
+      return false;
+    }
+    if (!csaf_dot_trace_local(X, WH, s)) return false;
+    *dot = s[0];
+    *trace = s[1];
+    return true;
+  }
   if (!saf_gates(X, nullptr, WH)) return false;
   DevMat none;
   double s[2] = {0.0, 0.0};

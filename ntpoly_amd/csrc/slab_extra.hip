@@ -1620,12 +1620,19 @@ __global__ void k_saf_span(HpcpRuns A, HpcpRuns B, int n, int al, int32_t* __res
 // chunks of 64 rows whose loads (three operands each) are all requested before the first of them is used: HPCP_KC's depth with
 // three operands instead of four -- 12 loads per lane, a hull of up to 256 aligned rows is one trip
 constexpr int SAF_KC = 4;
+// ... and on runs of (re, im) pairs (option complex_scale_fold), one 16-byte load per lane and operand: two chunks in flight are
+// the 24 VGPRs of load data the real kernel's four are; a hull of up to 128 aligned rows is one trip
+constexpr int SAF_KC_C = 2;
 // One wave per column, lanes on consecutive rows of the aligned hull [a0, a1) of the runs of A = X and B = X2.  o1 = the new X into
 // the slot at base[j]; sb = 2 alpha and sa = -alpha^2 as the host rounds them: s = sb x (ScaleMatrix), o = s + sa x2 (IncrementMatrix
 // at threshold 0: isr_merge).  part[2 j] = sum over the column of o wh, a lane-strided sum then a wave sum (fixed shapes: the same
 // value every run); part[2 j + 1] = o on the diagonal row, what k_sa_diag reads from the new X (0 where the row is absent).
 // stat |= 1: a scaled entry underflows to zero; |= 2: runs far apart or a slot beyond the output buffer -- nothing is written for
 // that column (k_hpcp_update).
+// T = double2: the runs, the slots, base and bound count (re, im) pairs; both factors are real, so the scaling and the merge work
+// part by part and keep an entry where either part is not zero; the dot's term is Re conj(o) wh (hpcp_term) and the diagonal's
+// the real part, as k_sa_dot_trace_c reads them.
+template <typename T, int KC>
 __global__ __launch_bounds__(256) void k_saf_update(int n, HpcpRuns A, HpcpRuns B, HpcpRuns W, int col_offset, double sa, double sb, int al,
                                                     const int64_t* __restrict__ base, IsrOut o1, int64_t bound, double* __restrict__ part,
                                                     unsigned long long* __restrict__ stat) {
@@ -1649,32 +1656,34 @@ __global__ __launch_bounds__(256) void k_saf_update(int n, HpcpRuns A, HpcpRuns 
     }
     return;
   }
-  const double* __restrict__ pa = anyA ? A.val + (A.off[j] - fA) : A.val;
-  const double* __restrict__ pb = anyB ? B.val + (B.off[j] - fB) : B.val;
-  const double* __restrict__ pw = anyW ? W.val + (W.off[j] - fW) : W.val;
-  double* __restrict__ d1 = static_cast<double*>(o1.val) + (slot - a0);
+  const T *__restrict__ va0 = reinterpret_cast<const T*>(A.val), *__restrict__ vb0 = reinterpret_cast<const T*>(B.val);
+  const T* __restrict__ vw0 = reinterpret_cast<const T*>(W.val);
+  const T* __restrict__ pa = anyA ? va0 + (A.off[j] - fA) : va0;
+  const T* __restrict__ pb = anyB ? vb0 + (B.off[j] - fB) : vb0;
+  const T* __restrict__ pw = anyW ? vw0 + (W.off[j] - fW) : vw0;
+  T* __restrict__ d1 = static_cast<T*>(o1.val) + (slot - a0);
   int uf = 0, c1 = 0, f1 = INT_MAX, l1 = -1;
   double e = 0.0;
-  for (int rb = a0; rb < a1; rb += SAF_KC * WAVE) {
-    double va[SAF_KC], vb[SAF_KC], vw[SAF_KC];
+  for (int rb = a0; rb < a1; rb += KC * WAVE) {
+    T va[KC], vb[KC], vw[KC];
 #pragma unroll
-    for (int k = 0; k < SAF_KC; ++k) {
+    for (int k = 0; k < KC; ++k) {
       const int r = rb + k * WAVE + lane;
-      va[k] = (anyA && r >= fA && r <= lA) ? pa[r] : 0.0;
-      vb[k] = (anyB && r >= fB && r <= lB) ? pb[r] : 0.0;
-      vw[k] = (anyW && r >= fW && r <= lW) ? pw[r] : 0.0;
+      va[k] = (anyA && r >= fA && r <= lA) ? pa[r] : Sc<T>::zero();
+      vb[k] = (anyB && r >= fB && r <= lB) ? pb[r] : Sc<T>::zero();
+      vw[k] = (anyW && r >= fW && r <= lW) ? pw[r] : Sc<T>::zero();
     }
 #pragma unroll
-    for (int k = 0; k < SAF_KC; ++k) {
+    for (int k = 0; k < KC; ++k) {
       const int r = rb + k * WAVE + lane;
       if (r >= a1) continue;
-      const double x = va[k], x2 = vb[k];
+      const T x = va[k], x2 = vb[k];
       bool ho;
-      const double s = __dmul_rn(sb, x);                                                          // ScaleMatrix(X, 2 alpha)
-      const double o = isr_merge<double>(1.0, s, x != 0.0, sa, x2, x2 != 0.0, &ho, &uf);          // IncrementMatrix(X2, X, -alpha^2)
+      const T s = Sc<T>::scale(sb, x);                                                                  // ScaleMatrix(X, 2 alpha)
+      const T o = isr_merge<T>(1.0, s, !Sc<T>::is_zero(x), sa, x2, !Sc<T>::is_zero(x2), &ho, &uf);      // IncrementMatrix(X2, X, -alpha^2)
       d1[r] = o;
-      e = __dadd_rn(e, __dmul_rn(o, vw[k]));                                                      // DotMatrix(X, WH)
-      if (r == dg) part[2 * (size_t)j + 1] = o;                                                   // MatrixTrace(X) of the next step
+      e = __dadd_rn(e, hpcp_term(o, vw[k]));                                                            // DotMatrix(X, WH)
+      if (r == dg) part[2 * (size_t)j + 1] = Sc<T>::re(o);                                              // MatrixTrace(X) of the next step
       c1 += ho ? 1 : 0; f1 = min(f1, ho ? r : INT_MAX); l1 = max(l1, ho ? r : -1);
     }
   }
@@ -1725,23 +1734,25 @@ __global__ __launch_bounds__(256) void k_saf_dot_trace(int n, HpcpRuns A, HpcpRu
 bool saf_wh_ok(const DevMat& WH) {
   return WH.expanded() && !WH.cplx && !WH.slab->labelled() && (WH.rows == WH.cols || slab_panels_ok()) && (WH.zero_free == 1 || WH.slab->origin);
 }
-}  // namespace
-
-bool slab_saf_update(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
-                     double* trace) {
-  if (!hpcp_operand(X) || !hpcp_operand(X2) || !saf_wh_ok(WH) || &X == &X2 || X.cols != X2.cols || X.cols != WH.cols || X.rows != X2.rows ||
+// the fold update on operands of one kind; the slots, `bound` and the output's buffer count entries of T
+template <typename T, int KC>
+bool saf_update_run(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
+                    double* trace) {
+  constexpr bool cplx = Sc<T>::cplx;
+  const bool wh_ok = cplx ? WH.cplx && sa_readable_c(WH) && (WH.zero_free == 1 || WH.slab->origin) : saf_wh_ok(WH);
+  if (!hpcp_operand(X, cplx) || !hpcp_operand(X2, cplx) || !wh_ok || &X == &X2 || X.cols != X2.cols || X.cols != WH.cols || X.rows != X2.rows ||
       X.rows != WH.rows || X.slab->row_pad != X2.slab->row_pad || !std::isfinite(a) || !std::isfinite(b))
     return false;
   const SlabForm &fa = *X.slab, &fb = *X2.slab;
   const int n = X.cols, al = std::max(1, fa.row_pad);
   // (the operands' slots and per column the pads of a hull)
   const int64_t bound = fa.slots + fb.slots + 4LL * al * n;
-  FreshSlabs fs(n, 1, bound, false, true);
+  FreshSlabs fs(n, 1, bound, cplx, true);
   const HpcpRuns ra = hpcp_runs(X), rb = hpcp_runs(X2);
   hipLaunchKernelGGL(k_saf_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, n, al, fs.span.p);
   fs.scan();
-  hipLaunchKernelGGL(k_saf_update, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, hpcp_runs(WH), col_offset, a, b, al,
-                     fs.base.p, fs.out(0), bound, fs.part.p, fs.stat.p);
+  hipLaunchKernelGGL((k_saf_update<T, KC>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, hpcp_runs(WH), col_offset, a, b,
+                     al, fs.base.p, fs.out(0), bound, fs.part.p, fs.stat.p);
   DevMat R;
   double sums[2] = {0.0, 0.0};
   if (!fs.finish("scale and fold update", X.rows, al, &R, sums, 2)) return false;
@@ -1750,6 +1761,16 @@ bool slab_saf_update(const DevMat& X, const DevMat& X2, double a, double b, cons
   *dot = sums[0];
   *trace = sums[1];
   return true;
+}
+}  // namespace
+
+bool slab_saf_update(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
+                     double* trace) {
+  return saf_update_run<double, SAF_KC>(X, X2, a, b, WH, col_offset, Out, dot, trace);
+}
+bool slab_saf_update_c(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
+                       double* trace) {
+  return saf_update_run<double2, SAF_KC_C>(X, X2, a, b, WH, col_offset, Out, dot, trace);
 }
 
 bool slab_saf_dot_trace(const DevMat& X, const DevMat& WH, int32_t col_offset, double* dot, double* trace) {

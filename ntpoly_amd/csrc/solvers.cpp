@@ -668,12 +668,17 @@ void solver_scale_and_fold(const PSMatrix& H, const PSMatrix& ISQ, double trace,
   double BetaBar = (e_max - homo) / (e_max - e_min);
   f.begin_loop();
   int II;
-  SlabSession slab(!X.cplx && !WH.cplx);
+  // Option complex_scale_fold, a complex Hamiltonian on one rank without process slices: a complex session, as solver_trs4 opens it
+  // -- the product on the complex tile kernel, the two fused calls below on complex runs
+  const bool complex_session = X.cplx && WH.cplx && complex_slab_loop(X) && options().complex_scale_fold != 0 && !world().active() &&
+                               !(X.grid && X.grid->num_slices > 1);
+  SlabSession slab((!X.cplx && !WH.cplx) || complex_session, false, complex_session);
   // Option scale_fold_step, inside the real session: behind the step's one product the fold branch's update, the energy and the
   // NEXT step's trace are one pass (ps_saf_update), and the scale branch, whose product's result is the new X, takes the energy and
   // the trace from one pass over X and WH (ps_saf_dot_trace).  A step that is not taken runs the calls, and the next step asks for
   // its trace again.
-  const bool step = options().scale_fold_step != 0;
+  // (scale_fold_step is the real loop's option: complex operands outside a complex session are declined by both calls, as before)
+  const bool step = options().scale_fold_step != 0 || complex_session;
   double trace_x = std::nan("");   // trace(X) as the last fused pass returned it; NaN: not known
   for (II = 1; II <= p.max_iterations; ++II) {                     // :1049-1081
     const double trace_value = std::isnan(trace_x) ? ps_trace(X) : trace_x;

@@ -203,6 +203,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "scale_fold_step") options().scale_fold_step = *value;
   else if (n == "complex_trs4") options().complex_trs4 = *value;
   else if (n == "complex_hpcp") options().complex_hpcp = *value;
+  else if (n == "complex_scale_fold") options().complex_scale_fold = *value;
   else if (n == "column_fused") options().column_fused = *value;
   else if (n == "complex_sessions") options().complex_sessions = *value;
   else NTP_FATAL("unknown option " + n);
@@ -246,6 +247,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "scale_fold_step") return options().scale_fold_step;
   if (n == "complex_trs4") return options().complex_trs4;
   if (n == "complex_hpcp") return options().complex_hpcp;
+  if (n == "complex_scale_fold") return options().complex_scale_fold;
   if (n == "column_fused") return options().column_fused;
   if (n == "complex_sessions") return options().complex_sessions;
   NTP_FATAL("unknown option " + n);
@@ -371,6 +373,15 @@ int ntpoly_amd_scale_fold_update_step(const int* ih_X, const int* ih_X2, const d
 // ... and the pass of the scale branch: *dot = DotMatrix(X, WH) and *trace = MatrixTrace(X) of X as it stands, nothing written
 int ntpoly_amd_scale_fold_dot_trace(const int* ih_X, const int* ih_WH, double* dot, double* trace) {
   return ps_saf_dot_trace_step(*get_unpacked(ih_X), *get_unpacked(ih_WH), dot, trace) ? 1 : 0;
+}
+// Complex ScaleAndFold in a complex slab session (option complex_scale_fold; engine.hpp ps_saf_update / ps_saf_dot_trace on complex
+// operands) since start: out[0] = fold updates fused, out[1] = dot-and-trace passes fused (the scale branch), out[2] = passes refused
+// (the vocabulary calls ran instead).  A pass that never reaches the kernel's decision -- the option off, no open complex session,
+// several ranks, block form, a labelled slab form, alignments that differ, a WH the dot cannot read -- is neither fused nor counted
+// as refused.  Real operands count in ntpoly_amd_scale_fold_step_counts only, complex ones here only.  With the option on, the two
+// diagnostics above take complex matrices in a session with complex_ok: *dot = the real part of DotMatrix, *trace = MatrixTrace
+void ntpoly_amd_complex_scale_fold_counts(long long out[3]) {
+  for (int q = 0; q < 3; ++q) out[q] = complex_scale_fold_counts()[q];
 }
 // Complex TRS4 in a complex slab session (option complex_trs4; engine.hpp ps_trs4_traces / ps_trs4_operand / ps_trs4_energy on
 // complex operands) since start: out[0] = trace passes fused, out[1] = operands Fx + sigma Gx fused, out[2] = energies fused, out[3] =

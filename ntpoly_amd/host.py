@@ -1156,9 +1156,10 @@ def scale_fold_step_counts():
 
 
 def scale_fold_update_step(X, X2, a, b, WH, Xout):
-    """DIAGNOSTIC, inside `with solver_session():` -- one fused fold update of ScaleAndFold on caller-held real matrices (X2: what
-    the product X X would be): Xout = b X + a X2 as ScaleMatrix(X, b); IncrementMatrix(X2, X, a) at threshold 0 build it.  Returns
-    (dot(Xout, WH), trace(Xout)) when taken; None: refused, every matrix as it was."""
+    """DIAGNOSTIC, inside `with solver_session():` -- one fused fold update of ScaleAndFold on caller-held matrices, all real (option
+    scale_fold_step) or all complex (option complex_scale_fold, one rank) (X2: what the product X X would be): Xout = b X + a X2 as
+    ScaleMatrix(X, b); IncrementMatrix(X2, X, a) at threshold 0 build it.  Returns (dot(Xout, WH), trace(Xout)) (complex: the real
+    part of the dot, the sum of the real parts of the diagonal) when taken; None: refused or gated, every matrix as it was."""
     dot, tr = C.c_double(0.0), C.c_double(0.0)
     lib.ntpoly_amd_scale_fold_update_step.restype = C.c_int
     ok = lib.ntpoly_amd_scale_fold_update_step(X.ih, X2.ih, d(a), d(b), WH.ih, Xout.ih, C.byref(dot), C.byref(tr))
@@ -1166,12 +1167,25 @@ def scale_fold_update_step(X, X2, a, b, WH, Xout):
 
 
 def scale_fold_dot_trace(X, WH):
-    """DIAGNOSTIC, inside `with solver_session():` -- the pass behind the product of ScaleAndFold's scale branch: (dot(X, WH),
-    trace(X)) from one pass over X and WH; None: refused."""
+    """DIAGNOSTIC, inside `with solver_session():` -- the pass behind the product of ScaleAndFold's scale branch, on real matrices
+    (option scale_fold_step) or complex ones (option complex_scale_fold, one rank; WH as it stands: slab form, a read-only view or
+    compressed columns): (dot(X, WH), trace(X)) (complex: the real part of the dot) from one pass over X and WH; None: refused or
+    gated."""
     dot, tr = C.c_double(0.0), C.c_double(0.0)
     lib.ntpoly_amd_scale_fold_dot_trace.restype = C.c_int
     ok = lib.ntpoly_amd_scale_fold_dot_trace(X.ih, WH.ih, C.byref(dot), C.byref(tr))
     return (float(dot.value), float(tr.value)) if ok else None
+
+
+def complex_scale_fold_counts():
+    """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
+    pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
+    vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the real branch does.  A pass kept out by a gate (the
+    option off, no open complex session, several ranks, block form, a labelled slab form, alignments that differ, a WH the dot
+    cannot read) is neither fused nor counted as refused; real operands count in scale_fold_step_counts() only"""
+    out = (C.c_longlong * 3)()
+    lib.ntpoly_amd_complex_scale_fold_counts(out)
+    return dict(updates=int(out[0]), dot_traces=int(out[1]), refused=int(out[2]))
 
 
 def complex_trs4_counts():
