@@ -170,10 +170,21 @@ long long* complex_trs4_counts();   // since start: [0] trace passes fused, [1] 
 // hands that to ps_pm_energy, whose reduction tells every rank.
 // ps_pm_energy: dot(X, WH) as ps_dot, with "this rank left the fused path" carried by the same reduction; *some_refused: on any rank.
 // ps_pm_materialise: X to compressed columns with Z's rows inserted as stored zeros -- what the loop on compressed columns holds.
-bool ps_pm_sigma(const PSMatrix& X, const ZeroList& Z, const PSMatrix& X2, double threshold, double* trace_value, double* dot_value);
+// Option complex_pm (one rank, inside a session that takes complex operands): the four calls take COMPLEX operands (slab_extra.hip
+// k_pm_sigma<double2>, k_pm_update<double2, ., .>: the real kernels' rules on each part of an entry, the threshold on the modulus as the
+// merge on compressed columns takes it -- the values, pattern and stored zeros of the vocabulary calls bit for bit; *trace_value =
+// the real parts of the diagonal summed, *dot_value = Re dot(X - X2, X); ps_pm_energy = Re dot(X, WH) from one pass over X's runs
+// and WH as it stands: slab_dot_trace_c).  No collective.  *gated (optional): ps_pm_sigma returned false at a gate -- the option
+// off, several ranks, no complex session, block or loose form, a labelled slab form, operands that are not all complex and of one
+// dimension --, which counts nothing; past the gates an operand that is no zero-free complex slab form (a read-only view, compressed
+// columns) or runs far apart refuse.  complex_pm_counts() keeps these books; pm_session_counts() never counts a complex pass,
+// slab_algebra_counts() counts a fused pass as the real branch does.
+bool ps_pm_sigma(const PSMatrix& X, const ZeroList& Z, const PSMatrix& X2, double threshold, double* trace_value, double* dot_value,
+                 bool* gated = nullptr);
 bool ps_pm_update(PSMatrix& X, ZeroList& Z, const PSMatrix& X2, const PSMatrix& X3, double a1, double a2, double a3, double threshold);
 double ps_pm_energy(const PSMatrix& X, const PSMatrix& WH, bool refused_here, bool* some_refused);
 void ps_pm_materialise(PSMatrix& X, ZeroList& Z);
+long long* complex_pm_counts();   // since start: [0] sigma passes fused, [1] updates fused, [2] stored zeros carried (summed over the updates), [3] solves that left the fused path (past the gates: a gated solve counts nowhere)
 long long* pm_session_counts();   // since start: [0] sigma passes fused, [1] updates fused, [2] stored zeros carried (summed over the updates), [3] solves that left the fused path; [4] the longest zero list an update left on this rank
 // MatrixNorm of alpha A + beta B (ScaleMatrix(B, beta); IncrementMatrix(A, B, alpha, 0); MatrixNorm(B)) for the loops
 // that build the sum only for its norm; false: not done (outside a slab session, operands in compressed columns ...)

@@ -2716,6 +2716,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_POLY_SESSIONS")) e->complex_poly_sessions = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_STORED_ZERO_VIEWS")) e->stored_zero_views = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_PM_SESSION")) e->pm_session = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PM")) e->complex_pm = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_ISR_CHAIN")) e->isr_chain = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_HPCP_STEP")) e->hpcp_step = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_SCALE_FOLD_STEP")) e->scale_fold_step = std::atoi(v);

@@ -105,6 +105,7 @@ struct EngineOptions {
   int scale_fold_step = 1;     // ScaleAndFold, real operands, inside a real slab session (one rank and column panels across ranks): behind the step's one product, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update: the values and pattern of the vocabulary calls at threshold 0 and the trace of slab_trace bit for bit; the energy is summed in another order and only feeds the convergence monitor); the scale branch, whose product's result is the new X, takes the energy and the trace from one pass over X and WH (k_saf_dot_trace) -- one read-back per step instead of two or three; a step the kernel refuses runs the calls as before.  0: the three calls, one by one
   int complex_trs4 = 0;        // complex TRS4 on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and the second product's operand stay runs of (re, im) pairs between the products on the complex tile kernel --, the traces dot(X2, Fx) and dot(X2, Gx) come from ONE pass over X and X X without building Fx and Gx, the operand Fx + sigma Gx from a second one (slab_extra.hip k_sa_trs4<double2, .>: the real kernel's arithmetic on each part, the values and pattern of the four merges at threshold 0), and the energy Re dot(X, WH) from one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  0 (default; measured 4.51 against 10.62 ms per iteration on configs[4]'s operand, profiles/README.md 130, but the rule that decides defaults also wants option 0 and the parent commit equal within the block spread, which one run missed by a hair): the loop on compressed columns, bit for bit as before
   int complex_hpcp = 0;        // complex HPCP on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- D1, DH and both products stay runs of (re, im) pairs between the products on the complex tile kernel --, the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH (slab_extra.hip k_hpcp_traces<double2>: the real parts), and the two merges into D1, the energy Re dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update<double2, .>: the real kernel's chain on each part of an entry, the values and patterns of the vocabulary calls at threshold 0); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of hpcp_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
+  int complex_pm = 0;          // complex PM on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and X X X stay runs of (re, im) pairs between the products on the complex tile kernel, the rows that compressed columns would hold as stored (0, 0) entries travel in the ZeroList beside a zero-free X, as in the real session --, sigma's trace and dot are ONE pass over X and X X (slab_extra.hip k_pm_sigma<double2>), the scaling and both merges at the solver's threshold another (k_pm_update<double2, ., 2>: the real kernel's rules on each part of an entry, the threshold on the modulus as the merge on compressed columns takes it), and the energy Re dot(X, WH) is one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses leaves the fused path for the rest of the solve, as the real session does; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of pm_session, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
   int complex_scale_fold = 0;  // complex ScaleAndFold on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X and its square stay runs of (re, im) pairs around the one product on the complex tile kernel --, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy Re dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of the vocabulary calls at threshold 0, the trace with the bits of k_sa_dot_trace_c, which with the option on is also MatrixTrace of a complex slab-form matrix in a complex session), and the scale branch takes the energy and the trace from one pass over X and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of scale_fold_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
@@ -378,11 +379,21 @@ bool slab_pm_sigma(const DevMat& X, const ZeroList& Z, const DevMat& X2, double 
 // false: refused (operands not in slab form / labelled / a view, or a union extent beyond the output), nothing changed
 bool slab_pm_update(const DevMat& X, const ZeroList& Z, const DevMat& X2, const DevMat& X3, double a1, double a2, double a3, double thr,
                     DevMat& Out, ZeroList& Zout);
-// compressed columns with the list's rows inserted as stored zeros (M packed, real); every entry of both is kept
+// the two passes on COMPLEX slab-form operands (option complex_pm; k_pm_sigma<double2>, k_pm_update<double2, ., .>: runs of (re, im)
+// pairs, 16 bytes per lane; slots and the bound count pairs).  Every scalar is real, so scalings and sums work part by part; an
+// entry is present where either part is not zero or its row is listed, kept where its modulus (Sc<double2>::mag, as the merge on
+// compressed columns takes it) exceeds thr or in a tail, and a kept (0, 0) goes to Zout -- the values and pattern of the vocabulary
+// calls on complex matrices bit for bit.  out2 = (the real parts of Temp's diagonal summed, Re dot(Temp, X)).  Operands:
+// sa_operand_c and zero-free
+bool slab_pm_sigma_c(const DevMat& X, const ZeroList& Z, const DevMat& X2, double thr, int32_t col_offset, double out2[2]);
+bool slab_pm_update_c(const DevMat& X, const ZeroList& Z, const DevMat& X2, const DevMat& X3, double a1, double a2, double a3, double thr,
+                      DevMat& Out, ZeroList& Zout);
+// compressed columns with the list's rows inserted as stored zeros (M packed, real or complex); every entry of both is kept
 void insert_stored_zeros(DevMat& M, const ZeroList& Z);
 // the stored pattern of a packed matrix as a zero list (the diagnostic entry point's Z), and a list as a matrix of stored zeros
+// of either kind
 void zero_list_from_pattern(const DevMat& M, ZeroList& Z);
-DevMat zero_list_matrix(const ZeroList& Z, int32_t rows, int32_t cols);
+DevMat zero_list_matrix(const ZeroList& Z, int32_t rows, int32_t cols, bool cplx = false);
 bool slab_trace(const DevMat& A, int32_t col_offset, double* out);   // sum of the diagonal entries held by the local columns
 int64_t slab_span_sum(const DevMat& M);   // rows covered by the runs (cached in the form)
 long long slab_product_count(const DevMat& A, const DevMat& B);   // statistics (slab_extra.hip): intermediate products of A B

@@ -1613,8 +1613,38 @@ long long* pm_session_counts() {
   static long long counts[5] = {0, 0, 0, 0, 0};
   return counts;
 }
-bool ps_pm_sigma(const PSMatrix& X, const ZeroList& Z, const PSMatrix& X2, double threshold, double* trace_value, double* dot_value) {
+long long* complex_pm_counts() {
+  static long long counts[4] = {0, 0, 0, 0};
+  return counts;
+}
+namespace {
+// Option complex_pm: the PM passes on COMPLEX operands, one rank, inside a session that takes complex operands.  The gates of
+// complex TRS4 (complex_passes_on) and: distinct operands, none labelled.  A pass they keep out is neither fused nor refused
+bool cpm_on(std::initializer_list<const PSMatrix*> ms) {
+  if (!complex_passes_on(options().complex_pm, ms) || !all_distinct(ms)) return false;
+  for (const PSMatrix* m : ms)
+    if (labelled(*m)) return false;
+  return true;
+}
+}  // namespace
+bool ps_pm_sigma(const PSMatrix& X, const ZeroList& Z, const PSMatrix& X2, double threshold, double* trace_value, double* dot_value,
+                 bool* gated) {
   CommScope cs(X.grid);
+  if (gated) *gated = false;
+  if (X.cplx || X2.cplx) {   // (option complex_pm; one rank: no reduction)
+    if (!cpm_on({&X, &X2})) {
+      if (gated) *gated = true;
+      return false;
+    }
+    // (a read-only view -- a starting iterate that stores a zero -- and an iterate a product left in compressed columns are refused)
+    double s[2] = {0.0, 0.0};
+    if (!X.loc.expanded() || !X2.loc.expanded() || !slab_pm_sigma_c(X.loc, Z, X2.loc, threshold, X.c0, s)) return false;
+    *trace_value = s[0];
+    *dot_value = s[1];
+    g_slab_counts[2] += 1;
+    complex_pm_counts()[0] += 1;
+    return true;
+  }
   double t[3] = {0.0, 0.0, 0.0};
   const bool ok = slab_on() && !X.cplx && !X2.cplx && !blk_any({&X, &X2}) && X.loc.expanded() && X2.loc.expanded() &&
                   slab_pm_sigma(X.loc, Z, X2.loc, threshold, X.c0, t);
@@ -1636,8 +1666,19 @@ bool ps_pm_update(PSMatrix& X, ZeroList& Z, const PSMatrix& X2, const PSMatrix& 
   CommScope cs(X.grid);
   DevMat R;
   ZeroList zn;
-  if (slab_on() && !X.cplx && !X2.cplx && !X3.cplx && !blk_any({&X, &X2, &X3}) && X.loc.expanded() && X2.loc.expanded() && X3.loc.expanded() &&
-      slab_pm_update(X.loc, Z, X2.loc, X3.loc, a1, a2, a3, threshold, R, zn)) {
+  if (X.cplx || X2.cplx || X3.cplx) {   // (option complex_pm; one rank.  Its own books: pm_session_counts() never counts a complex pass)
+    if (cpm_on({&X, &X2, &X3}) && X.loc.expanded() && X2.loc.expanded() && X3.loc.expanded() &&
+        slab_pm_update_c(X.loc, Z, X2.loc, X3.loc, a1, a2, a3, threshold, R, zn)) {
+      X.loc = std::move(R);
+      Z = std::move(zn);
+      bump_matrix_value_epoch();
+      g_slab_counts[1] += 2;
+      complex_pm_counts()[1] += 1;
+      complex_pm_counts()[2] += Z.count;
+      return true;
+    }
+  } else if (slab_on() && !blk_any({&X, &X2, &X3}) && X.loc.expanded() && X2.loc.expanded() && X3.loc.expanded() &&
+             slab_pm_update(X.loc, Z, X2.loc, X3.loc, a1, a2, a3, threshold, R, zn)) {
     X.loc = std::move(R);
     Z = std::move(zn);
     bump_matrix_value_epoch();
@@ -2184,6 +2225,17 @@ void ps_dot_with(const PSMatrix& A, const PSMatrix& B, double out[2], double* ex
 }  // namespace
 void ps_dot(const PSMatrix& A, const PSMatrix& B, double out[2]) { ps_dot_with(A, B, out, nullptr); }
 double ps_pm_energy(const PSMatrix& X, const PSMatrix& WH, bool refused_here, bool* some_refused) {
+  if (X.cplx && WH.cplx && !refused_here && &X != &WH && cpm_on({&X, &WH}) && X.loc.expanded() && sa_operand_c(X.loc)) {
+    // (option complex_pm; one rank: one pass over X's runs and WH as it stands -- complex slab form, a read-only view, or compressed
+    // columns --, as ps_trs4_energy takes it, where the dot below would pack X first)
+    CommScope cs(X.grid);
+    double dot[2] = {0.0, 0.0};
+    if (slab_dot_trace_c(X.loc, &WH.loc, X.c0, dot, nullptr)) {
+      g_slab_counts[2] += 1;
+      *some_refused = false;
+      return dot[0];
+    }
+  }
   double out[2], flag = refused_here ? 1.0 : 0.0;
   ps_dot_with(X, WH, out, &flag);
   *some_refused = flag != 0.0;

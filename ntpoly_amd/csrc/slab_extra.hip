@@ -893,26 +893,37 @@ int64_t slab_span_sum(const DevMat& M) {
 // row steers the tail rule of the merges that follow.  The runs of a slab form read a zero as "no entry", so those rows
 // travel in a ZeroList next to zero-free runs.  "Present" below: a non-zero of the run or a row of the list; exh = last
 // present row of a column.  Element arithmetic: __dmul_rn / __dadd_rn in the order of the vocabulary calls.
+// T = double2 (option complex_pm): runs of (re, im) pairs -- off, the slots, base and bound count pairs.  Every scalar of the loop
+// is real, so scalings and sums work part by part (Sc<double2>::scale / add); an entry is a non-zero where either part is, a stored
+// zero where both are zero; the threshold is on the modulus, Sc<double2>::mag, the function the merge on compressed columns calls
+// (kernels.hip inc_decide), so the kept pattern is that merge's.
 namespace {
-struct PmRuns {   // the runs of one slab-form operand
+struct PmRuns {   // the runs of one slab-form operand (val: entries of T)
   const int32_t* __restrict__ first;
   const int32_t* __restrict__ last;
   const int64_t* __restrict__ off;
   const double* __restrict__ val;
 };
 PmRuns pm_runs(const DevMat& M) { return PmRuns{M.slab->first.p, M.slab->last.p, M.slab->off.p, M.slab->val.p}; }
+template <typename T>
 struct PmCol {    // one column of it: rows f .. l (l < f: empty) at p[r]
   int f, l;
-  const double* __restrict__ p;
-  __device__ double at(int r) const { return (r >= f && r <= l) ? p[r] : 0.0; }
+  const T* __restrict__ p;
+  __device__ T at(int r) const { return (r >= f && r <= l) ? p[r] : Sc<T>::zero(); }
 };
-__device__ inline PmCol pm_col(const PmRuns& m, int j) {
-  PmCol c;
+template <typename T>
+__device__ inline PmCol<T> pm_col(const PmRuns& m, int j) {
+  PmCol<T> c;
+  const T* __restrict__ v = reinterpret_cast<const T*>(m.val);
   c.f = m.first[j]; c.l = m.last[j];
-  c.p = c.l >= c.f ? m.val + (m.off[j] - c.f) : m.val;
+  c.p = c.l >= c.f ? v + (m.off[j] - c.f) : v;
   if (c.l < c.f) { c.f = INT_MAX; c.l = -1; }
   return c;
 }
+// the term of a dot one row adds: o w, and for complex operands the real part of conj(o) w with each product and the pair's sum
+// rounded (the terms of k_sa_dot_trace_c)
+__device__ inline double hpcp_term(double o, double w) { return __dmul_rn(o, w); }
+__device__ inline double hpcp_term(double2 o, double2 w) { return __dadd_rn(__dmul_rn(o.x, w.x), __dmul_rn(o.y, w.y)); }
 // row r among the (few, ascending) listed rows zrow[z0 .. z1) of the column: the loop is uniform over the wave
 __device__ inline bool pm_listed(const int32_t* __restrict__ zrow, int64_t z0, int64_t z1, int r) {
   bool in = false;
@@ -922,20 +933,23 @@ __device__ inline bool pm_listed(const int32_t* __restrict__ zrow, int64_t z0, i
 // one row of o = alpha a + b by the AddSparseVectors rules (kernels.hip inc_decide): ha / hb = present, wa = alpha a and b as they
 // enter the sum, amax / bmax = last present row of the column of a / of b.  Returns "kept"; *o = the value (may be exactly zero
 // where a tail is copied unfiltered)
-__device__ inline bool pm_merge(bool ha, bool hb, double wa, double b, int r, int amax, int bmax, double thr, double* o) {
-  if (ha && hb) { *o = __dadd_rn(wa, b); return fabs(*o) > thr; }
-  if (ha) { *o = wa; return (r > bmax) ? true : (fabs(wa) > thr); }
-  if (hb) { *o = b; return (r > amax) ? true : (fabs(b) > thr); }
-  *o = 0.0;
+template <typename T>
+__device__ inline bool pm_merge(bool ha, bool hb, T wa, T b, int r, int amax, int bmax, double thr, T* o) {
+  if (ha && hb) { *o = Sc<T>::add(wa, b); return Sc<T>::mag(*o) > thr; }
+  if (ha) { *o = wa; return (r > bmax) ? true : (Sc<T>::mag(wa) > thr); }
+  if (hb) { *o = b; return (r > amax) ? true : (Sc<T>::mag(b) > thr); }
+  *o = Sc<T>::zero();
   return false;
 }
-// part[2 j] = trace, part[2 j + 1] = dot(., X) of column j of Temp = X - X2 (merged at thr), Temp itself not formed
+// part[2 j] = trace, part[2 j + 1] = dot(., X) of column j of Temp = X - X2 (merged at thr), Temp itself not formed (complex: the real
+// part of the diagonal entry, as MatrixTrace sums it, and the real part of DotMatrix(Temp, X): hpcp_term)
+template <typename T>
 __global__ __launch_bounds__(256) void k_pm_sigma(int n, PmRuns X, const int64_t* __restrict__ zoff, const int32_t* __restrict__ zrow,
                                                   PmRuns X2, int col_offset, int al, double thr, double* __restrict__ part) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= n) return;
   const int lane = lane_id(), dg = j + col_offset;
-  const PmCol cx = pm_col(X, j), c2 = pm_col(X2, j);
+  const PmCol<T> cx = pm_col<T>(X, j), c2 = pm_col<T>(X2, j);
   const int64_t z0 = zoff ? zoff[j] : 0, z1 = zoff ? zoff[j + 1] : 0;
   const int exhx = max(cx.l, z1 > z0 ? zrow[z1 - 1] : -1);
   // (a listed row outside both runs merges to an exact zero: it adds nothing to either sum)
@@ -944,13 +958,13 @@ __global__ __launch_bounds__(256) void k_pm_sigma(int n, PmRuns X, const int64_t
   if (hi >= lo) {
     const int r0 = lo / al * al, r1 = (hi / al + 1) * al;
     for (int r = r0 + lane; r < r1; r += WAVE) {
-      const double x = cx.at(r), x2 = c2.at(r);
-      const bool px = x != 0.0 || pm_listed(zrow, z0, z1, r);
-      double o;
-      const bool keep = pm_merge(x2 != 0.0, px, __dmul_rn(-1.0, x2), x, r, c2.l, exhx, thr, &o);
+      const T x = cx.at(r), x2 = c2.at(r);
+      const bool px = !Sc<T>::is_zero(x) || pm_listed(zrow, z0, z1, r);
+      T o;
+      const bool keep = pm_merge<T>(!Sc<T>::is_zero(x2), px, Sc<T>::scale(-1.0, x2), x, r, c2.l, exhx, thr, &o);
       if (keep) {
-        if (r == dg) st = __dadd_rn(st, o);
-        sd = __dadd_rn(sd, __dmul_rn(o, x));
+        if (r == dg) st = __dadd_rn(st, Sc<T>::re(o));
+        sd = __dadd_rn(sd, hpcp_term(o, x));
       }
     }
   }
@@ -971,16 +985,18 @@ __global__ void k_pm_span(const int32_t* __restrict__ fa, const int32_t* __restr
   span[j] = l >= f ? (l / al + 1) * al - f / al * al : 0;
 }
 // One wave per column.  Loop 1: Y = a2 X2 + a1 X (kept rows, values may be zero) only to find exh(Y); loop 2: Y again and
-// o = a3 X3 + Y.  Columns of up to PM_KC * 64 rows keep x, x2 and x3 in registers between the loops (every load of the column is
-// requested before the first use); longer ones read the runs again.
+// o = a3 X3 + Y.  Columns of up to KC * 64 rows keep x, x2 and x3 in registers between the loops (every load of the column is
+// requested before the first use); longer ones read the runs again.  KC = PM_KC for double; PM_KC_C for double2, one 16-byte load
+// per lane and operand: the same twelve doubles of x, x2 and x3 per lane between the loops.
 // MODE 0: kept non-zeros into the slot at base[j] (row r at base + r - a0, pads and dropped rows zero), first / last / count / offset
 //         as k_sa_axpby writes them; zcnt[j] = kept rows whose value is exactly zero.  stat |= 2: a union extent beyond the output.
 // MODE 1: those rows, ascending, to zout[nzoff[j] ...] (columns with none return at once).
 constexpr int PM_KC = 4;
-template <int MODE>
+constexpr int PM_KC_C = 2;
+template <typename T, int MODE, int KC>
 __global__ __launch_bounds__(256) void k_pm_update(int n, PmRuns X, const int64_t* __restrict__ zoff, const int32_t* __restrict__ zrow,
                                                    PmRuns X2, PmRuns X3, double a1, double a2, double a3, double thr, int al,
-                                                   const int64_t* __restrict__ base, double* __restrict__ out, int32_t* __restrict__ ofirst,
+                                                   const int64_t* __restrict__ base, T* __restrict__ out, int32_t* __restrict__ ofirst,
                                                    int32_t* __restrict__ olast, int32_t* __restrict__ ocount, int64_t* __restrict__ ooff,
                                                    int32_t* __restrict__ zcnt, const int64_t* __restrict__ nzoff, int32_t* __restrict__ zout,
                                                    int64_t bound, unsigned long long* __restrict__ stat) {
@@ -992,7 +1008,7 @@ __global__ __launch_bounds__(256) void k_pm_update(int n, PmRuns X, const int64_
     zdst = nzoff[j];
     if (nzoff[j + 1] == zdst) return;
   }
-  const PmCol cx = pm_col(X, j), c2 = pm_col(X2, j), c3 = pm_col(X3, j);
+  const PmCol<T> cx = pm_col<T>(X, j), c2 = pm_col<T>(X2, j), c3 = pm_col<T>(X3, j);
   const int64_t z0 = zoff ? zoff[j] : 0, z1 = zoff ? zoff[j + 1] : 0;
   const int zf = z1 > z0 ? zrow[z0] : INT_MAX, zl = z1 > z0 ? zrow[z1 - 1] : -1;
   const int exhx = max(cx.l, zl);
@@ -1014,46 +1030,46 @@ __global__ __launch_bounds__(256) void k_pm_update(int n, PmRuns X, const int64_
     return;
   }
   const int r0 = lo / al * al, r1 = (hi / al + 1) * al;
-  const bool fits = r1 - r0 <= PM_KC * WAVE;
-  double vx[PM_KC], v2[PM_KC], v3[PM_KC];
+  const bool fits = r1 - r0 <= KC * WAVE;
+  T vx[KC], v2[KC], v3[KC];
   unsigned pm = 0;   // bit c: the row of chunk c is present in X
   int ey = -1;
   if (fits) {
 #pragma unroll
-    for (int c = 0; c < PM_KC; ++c) {
+    for (int c = 0; c < KC; ++c) {
       const int r = r0 + c * WAVE + lane;
       const bool in = r < r1;
-      vx[c] = in ? cx.at(r) : 0.0;
-      v2[c] = in ? c2.at(r) : 0.0;
-      v3[c] = in ? c3.at(r) : 0.0;
+      vx[c] = in ? cx.at(r) : Sc<T>::zero();
+      v2[c] = in ? c2.at(r) : Sc<T>::zero();
+      v3[c] = in ? c3.at(r) : Sc<T>::zero();
     }
 #pragma unroll
-    for (int c = 0; c < PM_KC; ++c) {
+    for (int c = 0; c < KC; ++c) {
       const int r = r0 + c * WAVE + lane;
-      const bool px = r < r1 && (vx[c] != 0.0 || pm_listed(zrow, z0, z1, r));
+      const bool px = r < r1 && (!Sc<T>::is_zero(vx[c]) || pm_listed(zrow, z0, z1, r));
       pm |= px ? (1u << c) : 0u;
-      double y;
-      if (pm_merge(v2[c] != 0.0, px, __dmul_rn(a2, v2[c]), __dmul_rn(a1, vx[c]), r, c2.l, exhx, thr, &y)) ey = max(ey, r);
+      T y;
+      if (pm_merge<T>(!Sc<T>::is_zero(v2[c]), px, Sc<T>::scale(a2, v2[c]), Sc<T>::scale(a1, vx[c]), r, c2.l, exhx, thr, &y)) ey = max(ey, r);
     }
   } else {
     for (int r = r0 + lane; r < r1; r += WAVE) {
-      const double x = cx.at(r), x2 = c2.at(r);
-      const bool px = x != 0.0 || pm_listed(zrow, z0, z1, r);
-      double y;
-      if (pm_merge(x2 != 0.0, px, __dmul_rn(a2, x2), __dmul_rn(a1, x), r, c2.l, exhx, thr, &y)) ey = max(ey, r);
+      const T x = cx.at(r), x2 = c2.at(r);
+      const bool px = !Sc<T>::is_zero(x) || pm_listed(zrow, z0, z1, r);
+      T y;
+      if (pm_merge<T>(!Sc<T>::is_zero(x2), px, Sc<T>::scale(a2, x2), Sc<T>::scale(a1, x), r, c2.l, exhx, thr, &y)) ey = max(ey, r);
     }
   }
   ey = wave_max_i32(ey);
-  double* __restrict__ dst = MODE == 0 ? out + (slot - a0) : out;
+  T* __restrict__ dst = MODE == 0 ? out + (slot - a0) : out;
   int cnt = 0, kf = INT_MAX, kl = -1, nz = 0;
   // one chunk of 64 rows of loop 2 (every lane of the wave comes here: MODE 1 orders its rows with a ballot)
-  auto row2 = [&](int r, bool in, double x, bool px, double x2, double x3) {
-    double y, o;
-    const bool py = in && pm_merge(x2 != 0.0, px, __dmul_rn(a2, x2), __dmul_rn(a1, x), r, c2.l, exhx, thr, &y);
-    const bool keep = in && pm_merge(x3 != 0.0, py, __dmul_rn(a3, x3), py ? y : 0.0, r, c3.l, ey, thr, &o);
-    const bool kz = keep && o == 0.0, kv = keep && o != 0.0;
+  auto row2 = [&](int r, bool in, T x, bool px, T x2, T x3) {
+    T y, o;
+    const bool py = in && pm_merge<T>(!Sc<T>::is_zero(x2), px, Sc<T>::scale(a2, x2), Sc<T>::scale(a1, x), r, c2.l, exhx, thr, &y);
+    const bool keep = in && pm_merge<T>(!Sc<T>::is_zero(x3), py, Sc<T>::scale(a3, x3), py ? y : Sc<T>::zero(), r, c3.l, ey, thr, &o);
+    const bool kz = keep && Sc<T>::is_zero(o), kv = keep && !Sc<T>::is_zero(o);
     if (MODE == 0) {
-      if (in && r >= a0 && r < a1r) dst[r] = kv ? o : 0.0;
+      if (in && r >= a0 && r < a1r) dst[r] = kv ? o : Sc<T>::zero();
       cnt += kv ? 1 : 0;
       nz += kz ? 1 : 0;
       kf = min(kf, kv ? r : INT_MAX);
@@ -1066,7 +1082,7 @@ __global__ __launch_bounds__(256) void k_pm_update(int n, PmRuns X, const int64_
   };
   if (fits) {
 #pragma unroll
-    for (int c = 0; c < PM_KC; ++c) {
+    for (int c = 0; c < KC; ++c) {
       const int r = r0 + c * WAVE + lane;
       row2(r, r < r1, vx[c], (pm >> c) & 1u, v2[c], v3[c]);
     }
@@ -1074,8 +1090,8 @@ __global__ __launch_bounds__(256) void k_pm_update(int n, PmRuns X, const int64_
     for (int rb = r0; rb < r1; rb += WAVE) {
       const int r = rb + lane;
       const bool in = r < r1;
-      const double x = in ? cx.at(r) : 0.0;
-      row2(r, in, x, in && (x != 0.0 || pm_listed(zrow, z0, z1, r)), in ? c2.at(r) : 0.0, in ? c3.at(r) : 0.0);
+      const T x = in ? cx.at(r) : Sc<T>::zero();
+      row2(r, in, x, in && (!Sc<T>::is_zero(x) || pm_listed(zrow, z0, z1, r)), in ? c2.at(r) : Sc<T>::zero(), in ? c3.at(r) : Sc<T>::zero());
     }
   }
   if (MODE == 0) {
@@ -1089,18 +1105,22 @@ __global__ __launch_bounds__(256) void k_pm_update(int n, PmRuns X, const int64_
     }
   }
 }
-bool pm_operands(const DevMat& X, const DevMat& X2, const DevMat* X3) {
-  if (!trs4_operands(X, X2)) return false;
-  return !X3 || (trs4_operands(X, *X3) && X.rows == X3->rows);
+// zero-free slab forms of one kind, one alignment and one shape (complex: runs of (re, im) pairs in slots of 16 rows, no view)
+bool pm_operands(bool cplx, const DevMat& X, const DevMat& X2, const DevMat* X3) {
+  auto pair = [cplx](const DevMat& A, const DevMat& B) { return cplx ? trs4_operands_c(A, B) : trs4_operands(A, B); };
+  if (!pair(X, X2)) return false;
+  return !X3 || (pair(X, *X3) && X.rows == X3->rows);
 }
-// column j of Out = column j of A with the rows zrow[zoff[j] ..) inserted as stored zeros (both ascending and disjoint)
+// column j of Out = column j of A with the rows zrow[zoff[j] ..) inserted as stored zeros (both ascending and disjoint); T = double2:
+// stored (0, 0) entries
+template <typename T>
 __global__ __launch_bounds__(256) void k_insert_zeros(Csc A, const int64_t* __restrict__ zoff, const int32_t* __restrict__ zrow,
-                                                      int64_t* __restrict__ oouter, int32_t* __restrict__ oinner, double* __restrict__ oval) {
+                                                      int64_t* __restrict__ oouter, int32_t* __restrict__ oinner, T* __restrict__ oval) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= A.cols) return;
   const int lane = lane_id();
   const int64_t as = A.outer[j], ae = A.outer[j + 1], z0 = zoff[j], z1 = zoff[j + 1], dst = as + z0;
-  const double* __restrict__ av = static_cast<const double*>(A.val);
+  const T* __restrict__ av = static_cast<const T*>(A.val);
   for (int64_t p = as + lane; p < ae; p += WAVE) {
     const int r = A.inner[p];
     int k = 0;
@@ -1117,28 +1137,30 @@ __global__ __launch_bounds__(256) void k_insert_zeros(Csc A, const int64_t* __re
       else b = m;
     }
     oinner[dst + (q - z0) + (a - as)] = r;
-    oval[dst + (q - z0) + (a - as)] = 0.0;
+    oval[dst + (q - z0) + (a - as)] = Sc<T>::zero();
   }
   if (lane == 0) {
     oouter[j] = dst;
     if (j == A.cols - 1) oouter[j + 1] = ae + z1;
   }
 }
-}  // namespace
-
-bool slab_pm_sigma(const DevMat& X, const ZeroList& Z, const DevMat& X2, double thr, int32_t col_offset, double out2[2]) {
-  if (!pm_operands(X, X2, nullptr)) return false;
+// the two passes on operands of one kind
+template <typename T>
+bool pm_sigma_run(const DevMat& X, const ZeroList& Z, const DevMat& X2, double thr, int32_t col_offset, double out2[2]) {
+  if (!pm_operands(Sc<T>::cplx, X, X2, nullptr)) return false;
   const int n = X.cols;
   DevBuf<double> part((size_t)2 * n);
-  hipLaunchKernelGGL(k_pm_sigma, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, pm_runs(X), Z.count ? Z.off.p : nullptr, Z.row.p,
-                     pm_runs(X2), col_offset, std::max(1, X.slab->row_pad), thr, part.p);
+  hipLaunchKernelGGL(k_pm_sigma<T>, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, pm_runs(X), Z.count ? Z.off.p : nullptr,
+                     Z.row.p, pm_runs(X2), col_offset, std::max(1, X.slab->row_pad), thr, part.p);
   fetch_pair_sums(part, n, out2);
   return true;
 }
-
-bool slab_pm_update(const DevMat& X, const ZeroList& Z, const DevMat& X2, const DevMat& X3, double a1, double a2, double a3, double thr,
-                    DevMat& Out, ZeroList& Zout) {
-  if (!pm_operands(X, X2, &X3)) return false;
+// (the slots, `bound` and the output's buffer count entries of T)
+template <typename T, int KC>
+bool pm_update_run(const DevMat& X, const ZeroList& Z, const DevMat& X2, const DevMat& X3, double a1, double a2, double a3, double thr,
+                   DevMat& Out, ZeroList& Zout) {
+  constexpr bool cplx = Sc<T>::cplx;
+  if (!pm_operands(cplx, X, X2, &X3)) return false;
   const SlabForm &fx = *X.slab, &f2 = *X2.slab, &f3 = *X3.slab;
   const int n = X.cols, al = std::max(1, fx.row_pad);
   std::unique_ptr<SlabForm> fo(new SlabForm());
@@ -1152,14 +1174,14 @@ bool slab_pm_update(const DevMat& X, const ZeroList& Z, const DevMat& X2, const 
   scan_i32_async(span.p, base.p, (int64_t)n);
   // (a column's slot is at most its operands' three slots and two pads: what the kernel refuses beyond)
   const int64_t bound = fx.slots + f2.slots + f3.slots + 2LL * al * n;
-  fo->val.alloc((size_t)bound + kIndexSlack);
+  fo->val.alloc(((size_t)bound + kIndexSlack) * (cplx ? 2 : 1));
   DevBuf<unsigned long long> stat(1), tot(1);
   stat.zero();
   tot.zero();
   const int64_t* zoff = Z.count ? Z.off.p : nullptr;
   const dim3 grid(cdiv((int64_t)n * WAVE, 256));
-  hipLaunchKernelGGL((k_pm_update<0>), grid, dim3(256), 0, stream(), n, pm_runs(X), zoff, Z.row.p, pm_runs(X2), pm_runs(X3), a1, a2, a3, thr, al,
-                     base.p, fo->val.p, fo->first.p, fo->last.p, fo->count.p, fo->off.p, zcnt.p, (const int64_t*)nullptr, (int32_t*)nullptr,
+  hipLaunchKernelGGL((k_pm_update<T, 0, KC>), grid, dim3(256), 0, stream(), n, pm_runs(X), zoff, Z.row.p, pm_runs(X2), pm_runs(X3), a1, a2, a3, thr,
+                     al, base.p, reinterpret_cast<T*>(fo->val.p), fo->first.p, fo->last.p, fo->count.p, fo->off.p, zcnt.p, (const int64_t*)nullptr, (int32_t*)nullptr,
                      bound, stat.p);
   scan_i32_async(zcnt.p, zn.off.p, (int64_t)n);
   hipLaunchKernelGGL(k_sa_count_sum, dim3(std::max(1, std::min(256, cdiv(n, 1024)))), dim3(256), 0, stream(), fo->count.p, n, tot.p);
@@ -1176,29 +1198,48 @@ bool slab_pm_update(const DevMat& X, const ZeroList& Z, const DevMat& X2, const 
   if (hs != 0) return false;
   if (nzero > 0) {
     zn.row.alloc((size_t)nzero);
-    hipLaunchKernelGGL((k_pm_update<1>), grid, dim3(256), 0, stream(), n, pm_runs(X), zoff, Z.row.p, pm_runs(X2), pm_runs(X3), a1, a2, a3, thr,
-                       al, (const int64_t*)nullptr, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
+    hipLaunchKernelGGL((k_pm_update<T, 1, KC>), grid, dim3(256), 0, stream(), n, pm_runs(X), zoff, Z.row.p, pm_runs(X2), pm_runs(X3), a1, a2, a3,
+                       thr, al, (const int64_t*)nullptr, (T*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
                        (int64_t*)nullptr, (int32_t*)nullptr, zn.off.p, zn.row.p, bound, (unsigned long long*)nullptr);
   }
   zn.count = nzero;
   fo->row_pad = al;
   fo->slots = slots;
   DevMat R;
-  R.rows = X.rows; R.cols = n; R.cplx = false; R.nnz = nnz; R.zero_free = 1;
+  R.rows = X.rows; R.cols = n; R.cplx = cplx; R.nnz = nnz; R.zero_free = 1;
   R.slab = std::move(fo);
   Out = std::move(R);
   Zout = std::move(zn);
   return true;
 }
+}  // namespace
+
+bool slab_pm_sigma(const DevMat& X, const ZeroList& Z, const DevMat& X2, double thr, int32_t col_offset, double out2[2]) {
+  return pm_sigma_run<double>(X, Z, X2, thr, col_offset, out2);
+}
+bool slab_pm_sigma_c(const DevMat& X, const ZeroList& Z, const DevMat& X2, double thr, int32_t col_offset, double out2[2]) {
+  return pm_sigma_run<double2>(X, Z, X2, thr, col_offset, out2);
+}
+bool slab_pm_update(const DevMat& X, const ZeroList& Z, const DevMat& X2, const DevMat& X3, double a1, double a2, double a3, double thr,
+                    DevMat& Out, ZeroList& Zout) {
+  return pm_update_run<double, PM_KC>(X, Z, X2, X3, a1, a2, a3, thr, Out, Zout);
+}
+bool slab_pm_update_c(const DevMat& X, const ZeroList& Z, const DevMat& X2, const DevMat& X3, double a1, double a2, double a3, double thr,
+                      DevMat& Out, ZeroList& Zout) {
+  return pm_update_run<double2, PM_KC_C>(X, Z, X2, X3, a1, a2, a3, thr, Out, Zout);
+}
 
 void insert_stored_zeros(DevMat& M, const ZeroList& Z) {
   if (Z.count == 0) return;
-  if (M.cplx) NTP_FATAL("internal: insert_stored_zeros takes real matrices");
   pack(M);
   DevMat R;
-  R.alloc(M.rows, M.cols, false, M.nnz + Z.count);
-  hipLaunchKernelGGL(k_insert_zeros, dim3(cdiv((int64_t)M.cols * WAVE, 256)), dim3(256), 0, stream(), view(M), Z.off.p, Z.row.p, R.outer.p,
-                     R.inner.p, R.val.p);
+  R.alloc(M.rows, M.cols, M.cplx, M.nnz + Z.count);
+  const dim3 grid(cdiv((int64_t)M.cols * WAVE, 256));
+  dispatch_type(M.cplx, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_insert_zeros<T>, grid, dim3(256), 0, stream(), view(M), Z.off.p, Z.row.p, R.outer.p, R.inner.p,
+                       reinterpret_cast<T*>(R.val.p));
+  });
   M = std::move(R);
 }
 
@@ -1213,13 +1254,13 @@ void zero_list_from_pattern(const DevMat& M, ZeroList& Z) {
   Z.count = M.nnz;
 }
 
-DevMat zero_list_matrix(const ZeroList& Z, int32_t rows, int32_t cols) {
+DevMat zero_list_matrix(const ZeroList& Z, int32_t rows, int32_t cols, bool cplx) {
   DevMat R;
-  if (Z.count == 0) { R.reset_empty(rows, cols, false); return R; }
-  R.alloc(rows, cols, false, Z.count);
+  if (Z.count == 0) { R.reset_empty(rows, cols, cplx); return R; }
+  R.alloc(rows, cols, cplx, Z.count);
   HIP_CHECK(hipMemcpyAsync(R.outer.p, Z.off.p, sizeof(int64_t) * ((size_t)cols + 1), hipMemcpyDeviceToDevice, stream()));
   HIP_CHECK(hipMemcpyAsync(R.inner.p, Z.row.p, sizeof(int32_t) * (size_t)Z.count, hipMemcpyDeviceToDevice, stream()));
-  HIP_CHECK(hipMemsetAsync(R.val.p, 0, sizeof(double) * (size_t)Z.count, stream()));
+  HIP_CHECK(hipMemsetAsync(R.val.p, 0, sizeof(double) * (size_t)Z.count * R.wval(), stream()));
   return R;
 }
 
@@ -1434,10 +1475,7 @@ constexpr int HPCP_KC = 4;
 // VGPRs of load data the real kernel's four are -- 84 VGPRs, five waves per SIMD, no scratch; a hull of up to 128 aligned rows is
 // one trip
 constexpr int HPCP_KC_C = 2;
-// the term of DotMatrix(D1, WH) one row adds: o wh, and for complex operands the real part of conj(o) wh with each product and
-// the pair's sum rounded (the terms of k_sa_dot_trace_c)
-__device__ inline double hpcp_term(double o, double w) { return __dmul_rn(o, w); }
-__device__ inline double hpcp_term(double2 o, double2 w) { return __dadd_rn(__dmul_rn(o.x, w.x), __dmul_rn(o.y, w.y)); }
+// (the term of DotMatrix(D1, WH) one row adds is hpcp_term, above)
 __device__ inline double hpcp_negate(double u) { return -u; }   // ScaleMatrix(., -1): exact
 __device__ inline double2 hpcp_negate(double2 u) { return Sc<double2>::scale(-1.0, u); }
 // One wave per column, lanes on consecutive rows of the aligned hull [a0, a1) of the runs of A = D1, B = DDH, C = D2DH and the

@@ -496,25 +496,32 @@ void solver_pm(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K
   // in `zeros` beside a zero-free X (slab_extra.hip), the scalars of sigma and the update are one pass each.  Every decision to
   // leave that path is collective and rides on a reduction the iteration makes anyway; it is taken once per solve: the iterate
   // is materialised (compressed columns with the listed rows as stored zeros), the session closed, the loop body below as it was.
-  SlabSession slab(options().pm_session != 0 && !X.cplx && !WH.cplx);
+  // Option complex_pm, a complex Hamiltonian on one rank without process slices: a complex session, as solver_trs4 opens it -- the
+  // products on the complex tile kernel, the same calls on runs of (re, im) pairs with the rows of stored (0, 0) entries in `zeros`.
+  // Its books are complex_pm_counts(); a solve whose iterates take block form (a gate, not a refusal) leaves uncounted.
+  const bool real = !X.cplx && !WH.cplx;
+  const bool complex_session = X.cplx && WH.cplx && complex_slab_loop(X) && options().complex_pm != 0 && !world().active() &&
+                               !(X.grid && X.grid->num_slices > 1);
+  SlabSession slab((options().pm_session != 0 && real) || complex_session, false, complex_session);
   const bool in_session = slab.opened;
   bool fused = slab.opened;
   ZeroList zeros;
-  auto leave_fused = [&]() {
+  auto leave_fused = [&](bool counted = true) {
     ps_pm_materialise(X, zeros);
     slab.close();
     ps_slab_leave(X2);
     ps_slab_leave(X3);
     ps_slab_leave(f.WH);
     fused = false;
-    pm_session_counts()[3] += 1;
+    if (counted) (complex_session ? complex_pm_counts() : pm_session_counts())[3] += 1;
   };
   for (II = 1; II <= p.max_iterations; ++II) {                     // :145-200
     ps_multiply(X, X, X2, 1.0, 0.0, p.threshold);
     ps_multiply(X, X2, X3, 1.0, 0.0, p.threshold);
     double trace_value2 = 0.0;
     // (an iterate that is no zero-free slab -- the starting iterate stores a zero, a product declined -- is refused here, on every rank)
-    if (fused && !ps_pm_sigma(X, zeros, X2, p.threshold, &trace_value, &trace_value2)) leave_fused();
+    bool gated = false;
+    if (fused && !ps_pm_sigma(X, zeros, X2, p.threshold, &trace_value, &trace_value2, &gated)) leave_fused(!gated);
     if (!fused) {
       ps_copy(X, Temp);
       ps_increment(X2, Temp, -1.0, p.threshold);

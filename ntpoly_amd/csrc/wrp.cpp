@@ -198,6 +198,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "complex_poly_sessions") options().complex_poly_sessions = *value;
   else if (n == "stored_zero_views") options().stored_zero_views = *value;
   else if (n == "pm_session") options().pm_session = *value;
+  else if (n == "complex_pm") options().complex_pm = *value;
   else if (n == "isr_chain") options().isr_chain = *value;
   else if (n == "hpcp_step") options().hpcp_step = *value;
   else if (n == "scale_fold_step") options().scale_fold_step = *value;
@@ -242,6 +243,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "complex_poly_sessions") return options().complex_poly_sessions;
   if (n == "stored_zero_views") return options().stored_zero_views;
   if (n == "pm_session") return options().pm_session;
+  if (n == "complex_pm") return options().complex_pm;
   if (n == "isr_chain") return options().isr_chain;
   if (n == "hpcp_step") return options().hpcp_step;
   if (n == "scale_fold_step") return options().scale_fold_step;
@@ -411,8 +413,17 @@ void ntpoly_amd_pm_session_counts(long long out[4]) {
 }
 // the longest zero list an update of the fused PM loop has left on this rank since start (rows of one panel)
 void ntpoly_amd_pm_session_longest_list(long long* out) { *out = pm_session_counts()[4]; }
-// DIAGNOSTIC surface (one rank, real matrices): one sigma pass and one update of the PM loop's fused path on caller-held operands.
-// X: the iterate's non-zeros; Z: a matrix whose STORED PATTERN is the iterate's zero list (rows that compressed columns would hold
+// Complex PM in a complex slab session (option complex_pm; engine.hpp ps_pm_sigma / ps_pm_update on complex operands) since start:
+// out[0] = sigma passes fused, out[1] = updates fused, out[2] = stored (0, 0) entries carried beside the runs (summed over the
+// updates), out[3] = solves that left the fused path.  A solve that a gate keeps out -- the option off, several ranks, iterates in
+// block form -- counts nowhere.  Real operands count in ntpoly_amd_pm_session_counts only, complex ones here only
+void ntpoly_amd_complex_pm_counts(long long out[4]) {
+  for (int q = 0; q < 4; ++q) out[q] = complex_pm_counts()[q];
+}
+// DIAGNOSTIC surface (one rank; matrices all real, or -- option complex_pm, FMA arithmetic, complex_tile, complex_sessions -- X, X2
+// and X3 all complex: Out is then complex and Zout a pattern of stored (0, 0) entries; Z is read as a pattern, whatever its kind;
+// mixed kinds, or complex operands with the option at 0, return 0): one sigma pass and one update of the PM loop's fused path on
+// caller-held operands.  X: the iterate's non-zeros; Z: a matrix whose STORED PATTERN is the iterate's zero list (rows that compressed columns would hold
 // as stored zeros; disjoint from X's pattern); X2, X3: what the loop's two products would be.  sc[0], sc[1] = trace and dot(., X)
 // of X - X2 merged at thr; Out = the non-zeros of ScaleMatrix(X u Z, a1); IncrementMatrix(X2, ., a2, thr); IncrementMatrix(X3, ., a3,
 // thr) and Zout = its stored zeros (as a pattern with zero values), both in compressed columns.  Returns 1 when taken, 0 when
@@ -422,20 +433,26 @@ int ntpoly_amd_pm_fused_step(const int* ih_X, const int* ih_Z, const int* ih_X2,
   const PSMatrix &X = *get<PSMatrix>(ih_X), &Z = *get<PSMatrix>(ih_Z), &X2 = *get<PSMatrix>(ih_X2), &X3 = *get<PSMatrix>(ih_X3);
   PSMatrix &Out = *get<PSMatrix>(ih_Out), &Zout = *get<PSMatrix>(ih_Zout);
   CommScope cs(X.grid);
-  if (world().active() || X.cplx || Z.cplx || X2.cplx || X3.cplx || X.dim != Z.dim || X.dim != X2.dim || X.dim != X3.dim) return 0;
+  if (world().active() || X.cplx != X2.cplx || X.cplx != X3.cplx || X.dim != Z.dim || X.dim != X2.dim || X.dim != X3.dim) return 0;
+  const bool cplx = X.cplx;
+  if (cplx ? (options().complex_pm == 0 || !complex_slab_loop(X)) : Z.cplx) return 0;
   DevMat x = X.loc.clone(), x2 = X2.loc.clone(), x3 = X3.loc.clone();
-  if (!slab_enter(x) || !slab_enter(x2) || !slab_enter(x3)) return 0;
+  // (complex: zero-free runs of (re, im) pairs, no read-only view)
+  auto enter = [cplx](DevMat& m) { return cplx ? slab_enter_c(m, nullptr, false) : slab_enter(m); };
+  if (!enter(x) || !enter(x2) || !enter(x3)) return 0;
   ZeroList zl, zn;
   zero_list_from_pattern(Z.loc, zl);
   DevMat R;
   double t[2] = {0.0, 0.0};
-  if (!slab_pm_sigma(x, zl, x2, *thr, X.c0, t) || !slab_pm_update(x, zl, x2, x3, *a1, *a2, *a3, *thr, R, zn)) return 0;
+  if (cplx ? (!slab_pm_sigma_c(x, zl, x2, *thr, X.c0, t) || !slab_pm_update_c(x, zl, x2, x3, *a1, *a2, *a3, *thr, R, zn))
+           : (!slab_pm_sigma(x, zl, x2, *thr, X.c0, t) || !slab_pm_update(x, zl, x2, x3, *a1, *a2, *a3, *thr, R, zn)))
+    return 0;
   sc[0] = t[0];
   sc[1] = t[1];
   pack(R);
-  for (PSMatrix* m : {&Out, &Zout}) { m->grid = X.grid; m->dim = X.dim; m->cplx = false; m->c0 = X.c0; m->c1 = X.c1; }
+  for (PSMatrix* m : {&Out, &Zout}) { m->grid = X.grid; m->dim = X.dim; m->cplx = cplx; m->c0 = X.c0; m->c1 = X.c1; }
   Out.loc = std::move(R);
-  Zout.loc = zero_list_matrix(zn, X.loc.rows, X.loc.cols);
+  Zout.loc = zero_list_matrix(zn, X.loc.rows, X.loc.cols, cplx);
   return 1;
 }
 // fused recurrence steps taken since start, by the Chebyshev / Hermite loops and by ntpoly_amd_recurrence_step (each is also

@@ -1073,10 +1073,21 @@ def pm_session_longest_list():
     return int(out.value)
 
 
+def complex_pm_counts():
+    """complex PM in a complex slab session (option complex_pm; csrc/slab_extra.hip k_pm_sigma / k_pm_update on runs of (re, im)
+    pairs) since start: sigma passes fused, updates fused, stored (0, 0) entries carried beside the runs (summed over the updates),
+    solves that left the fused path; slab_algebra_counts() counts a fused pass as the real branch does.  A solve kept out by a gate
+    (the option off, several ranks, iterates in block form) counts nowhere; real operands count in pm_session_counts() only"""
+    out = (C.c_longlong * 4)()
+    lib.ntpoly_amd_complex_pm_counts(out)
+    return dict(sigma=int(out[0]), updates=int(out[1]), zeros=int(out[2]), left=int(out[3]))
+
+
 def pm_fused_step(X, Z, X2, X3, a1, a2, a3, thr, Out, Zout):
-    """DIAGNOSTIC: one sigma pass and one update of the PM loop's fused path on caller-held real matrices (one rank).  Z's stored
-    pattern is the iterate's zero list.  Returns (trace, dot) of X - X2 merged at thr when taken -- Out then holds the update's
-    non-zeros and Zout its stored zeros, in compressed columns -- or None when refused (nothing written)."""
+    """DIAGNOSTIC: one sigma pass and one update of the PM loop's fused path on caller-held matrices (one rank), all real or -- option
+    complex_pm, FMA arithmetic -- X, X2 and X3 all complex.  Z's stored pattern is the iterate's zero list.  Returns (trace, dot) of
+    X - X2 merged at thr (complex: the real parts) when taken -- Out then holds the update's non-zeros and Zout its stored zeros, in
+    compressed columns of the operands' kind -- or None when refused or gated (nothing written)."""
     sc = (C.c_double * 2)()
     lib.ntpoly_amd_pm_fused_step.restype = C.c_int
     ok = lib.ntpoly_amd_pm_fused_step(X.ih, Z.ih, X2.ih, X3.ih, d(a1), d(a2), d(a3), d(thr), Out.ih, Zout.ih, sc)
