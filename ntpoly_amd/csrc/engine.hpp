@@ -134,6 +134,13 @@ struct SlabSession {
   bool opened = false;
   bool set_complex = false;
 };
+// Unfused arithmetic, real operands, until the outermost open session closes: the session's products stay on the register-slab
+// kernel also when an operand has become sparse inside wide extents (3 I - a^2 U^T U near the end of a Polar solve), where
+// ps_multiply otherwise hands the product to the general kernels and books a refusal that packs both operands.  For the loop that
+// transposes its iterate every iteration: a packed iterate sends the next transpose through the sort on compressed columns and the
+// next product through the expansion of both operands again.  The kernel multiplies the zeros of the runs, which changes no bit.
+// No session open: nothing happens
+void slab_keep_sparse_runs(bool on);
 // Out = alpha A + beta B: CopyMatrix(B, Out); ScaleMatrix(Out, beta); IncrementMatrix(A, Out, alpha, threshold) -- in a
 // slab session one pass without the copy (and B, an identity say, is turned into slab form once instead of its copies)
 void ps_copy_axpby(const PSMatrix& B, const PSMatrix& A, PSMatrix& Out, double alpha, double beta, double threshold);
@@ -360,6 +367,17 @@ double ps_sigma(const PSMatrix& A);
 void ps_gershgorin(const PSMatrix& A, double* e_min, double* e_max);
 void ps_transpose(const PSMatrix& A, PSMatrix& AT);
 void ps_conjugate(PSMatrix& A);
+// Option slab_transpose (>= 1), one rank without process slices, inside a slab session that takes the operand's kind: ps_transpose
+// of a square zero-free slab form is the tiled transpose of its runs (kernels.hpp slab_transpose) and leaves a slab form, and
+// ps_conjugate of a complex one runs in place.  A view, a labelled form or block form is gated: the path on compressed columns, A
+// untouched, counted nowhere.  A transpose the pass refuses past the gates (extents far apart) runs on a packed copy of A, leaves
+// compressed columns and counts as a refusal of the session.  slab_transpose_counts() since start: [0] transposes done in slab
+// form, [1] conjugations done in slab form, [2] refusals past the gates, [3] Polar solves that ran in a session.
+long long* slab_transpose_counts();
+// DIAGNOSTIC (the C ABI's ntpoly_amd_slab_transpose): one rank; a session of its own (a complex one where A is complex and FMA
+// arithmetic, complex_tile and complex_sessions allow it), A entered into slab form, the pass run with or without conjugation, the
+// PACKED result installed in AT.  false: gated or refused, AT untouched.  A is back in compressed columns either way
+bool ps_slab_transpose_step(const PSMatrix& A, PSMatrix& AT, bool conj);
 bool ps_is_identity(const PSMatrix& A);
 double ps_measure_asymmetry(const PSMatrix& A);
 void ps_symmetrize(PSMatrix& A);

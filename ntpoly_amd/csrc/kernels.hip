@@ -2718,6 +2718,7 @@ EngineOptions& options() {
     if (const char* v = std::getenv("NTPOLY_AMD_PM_SESSION")) e->pm_session = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PM")) e->complex_pm = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_ISR_CHAIN")) e->isr_chain = std::atoi(v);
+    if (const char* v = std::getenv("NTPOLY_AMD_SLAB_TRANSPOSE")) e->slab_transpose = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_HPCP_STEP")) e->hpcp_step = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_SCALE_FOLD_STEP")) e->scale_fold_step = std::atoi(v);
     if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_TRS4")) e->complex_trs4 = std::atoi(v);

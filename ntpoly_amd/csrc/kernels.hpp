@@ -107,6 +107,7 @@ struct EngineOptions {
   int complex_hpcp = 0;        // complex HPCP on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- D1, DH and both products stay runs of (re, im) pairs between the products on the complex tile kernel --, the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH (slab_extra.hip k_hpcp_traces<double2>: the real parts), and the two merges into D1, the energy Re dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update<double2, .>: the real kernel's chain on each part of an entry, the values and patterns of the vocabulary calls at threshold 0); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of hpcp_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
   int complex_pm = 0;          // complex PM on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and X X X stay runs of (re, im) pairs between the products on the complex tile kernel, the rows that compressed columns would hold as stored (0, 0) entries travel in the ZeroList beside a zero-free X, as in the real session --, sigma's trace and dot are ONE pass over X and X X (slab_extra.hip k_pm_sigma<double2>), the scaling and both merges at the solver's threshold another (k_pm_update<double2, ., 2>: the real kernel's rules on each part of an entry, the threshold on the modulus as the merge on compressed columns takes it), and the energy Re dot(X, WH) is one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses leaves the fused path for the rest of the solve, as the real session does; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of pm_session, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
   int complex_scale_fold = 0;  // complex ScaleAndFold on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X and its square stay runs of (re, im) pairs around the one product on the complex tile kernel --, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy Re dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of the vocabulary calls at threshold 0, the trace with the bits of k_sa_dot_trace_c, which with the option on is also MatrixTrace of a complex slab-form matrix in a complex session), and the scale branch takes the energy and the trace from one pass over X and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of scale_fold_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
+  int slab_transpose = 1;      // one rank, no process slices: TransposeMatrix of a square, zero-free slab form inside a slab session is a tiled transpose of the runs (slab_extra.hip k_tr_extents / k_tr_values: extents and counts by integer atomics, values through a padded LDS tile) and ConjugateMatrix of a complex one runs in place -- the result is a slab form again, the packed result the bits and pattern of transpose() (+ conjugate()) on compressed columns; with it PolarDecomposition opens a slab session as SignFunction does (1: real operands, results bit for bit those of 0; 2: also the complex session, the complex tile kernel's tolerance mode).  A transpose the pass refuses (extents far apart) runs on compressed columns.  0: everything on compressed columns, as before.  Default 1: Polar of a real band of N = 262 144 takes 5.17 against 14.97 ms per iteration of the call (profiles/README.md 135)
   int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
   int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
   int plan_fused = 1;          // the maxima and prefix sums of a slab step's plan in ONE launch (k_slab_offsets: every workgroup sums what lies before its part itself) instead of four to seven; 0: separate launches
@@ -322,6 +323,18 @@ bool trs4_operands_c(const DevMat& X, const DevMat& X2);
 bool slab_trs4_traces_c(const DevMat& X, const DevMat& X2, int32_t col_offset, double* trace_fx, double* trace_gx);
 bool slab_trs4_operand_c(const DevMat& X, const DevMat& X2, double sigma, int32_t col_offset, DevMat& Out);
 bool slab_norm_axpby(const DevMat& A, const DevMat& B, double alpha, double beta, double* out);   // MatrixNorm(alpha A + beta B), nothing built
+// The transpose of a slab form (slab_extra.hip; option slab_transpose).  slab_transpose_operand: what the pass takes -- a square,
+// zero-free slab form on one rank that is neither labelled nor a view, packed runs (row_pad 1) or slots aligned to a multiple of
+// 16 rows.  slab_transpose<T> (T = double or double2, the operand's kind): AT = A^T, with conj its conjugate, as a fresh slab form
+// with A's row_pad whose extents are the first and last non-zero row and whose count is the number of non-zero entries -- packed,
+// the pattern and bits of transpose() (then conjugate()) on the packed operand.  false: not taken, or refused because the
+// transposed extents need more than 4 A.slots + 4 row_pad n slots; AT is then untouched.  slab_transpose_any picks T.
+// slab_conjugate_c: ConjugateMatrix of a zero-free complex slab form in place (false: not taken)
+bool slab_transpose_operand(const DevMat& A);
+template <typename T>
+bool slab_transpose(const DevMat& A, bool conj, DevMat& AT);
+bool slab_transpose_any(const DevMat& A, bool conj, DevMat& AT);
+bool slab_conjugate_c(DevMat& A);
 // The polynomial chain of the square-root step on slab-form X and X2 = X X (slab_extra.hip k_sa_isr_chain; real or complex, square
 // or column panels with col_offset = the panel's first column), the values and patterns of the vocabulary calls at threshold 0 bit
 // for bit.  Order 5: Temp2 = (X2 + a X) + (X + b I), Temp = (X2 + a X) + c I (Temp may be X2).  Order 3: Out = 0.375 X2 + (I - X / 2)

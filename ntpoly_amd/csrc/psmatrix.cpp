@@ -205,6 +205,7 @@ bool slab_on() { return g_slab_depth > 0 && !g_slab_failed; }
 DevMat& mut(const PSMatrix& m) { return const_cast<DevMat&>(m.loc); }
 int g_slab_refusals = 0;
 bool g_complex_session = false;   // the open session's loop takes complex operands in slab form (SlabSession complex_ok)
+bool g_keep_sparse_runs = false;  // the open session's products stay on the register-slab kernel in unfused arithmetic (slab_keep_sparse_runs)
 long long g_recurrence_steps = 0;   // fused recurrence steps taken (ps_recurrence_step returned true)
 long long g_slab_counts[4] = {0, 0, 0, 0};   // products, merges / copies, other operations in slab form; refusals
 // the slab algebra of one element kind, for the operations that exist for both (kernels.hpp: name, name_c)
@@ -350,9 +351,12 @@ void SlabSession::close() {
   if (set_complex) { g_complex_session = false; set_complex = false; }
   if (opened) {
     g_slab_depth -= 1;
-    if (g_slab_depth == 0) slab_allow_panels(false);
+    if (g_slab_depth == 0) { slab_allow_panels(false); g_keep_sparse_runs = false; }
   }
   opened = false;
+}
+void slab_keep_sparse_runs(bool on) {
+  if (g_slab_depth > 0) g_keep_sparse_runs = on;
 }
 void ps_slab_leave(PSMatrix& m) {
   if (m.loc.expanded() || m.loc.blocked()) pack(m.loc);
@@ -1034,8 +1038,10 @@ void ps_multiply(const PSMatrix& A, const PSMatrix& B, PSMatrix& C, double alpha
     // (unfused arithmetic, real: the register-slab kernel multiplies whole runs, zeros included -- operands that have become
     // sparse inside wide extents, 3 I - X^2 near the end of a sign iteration, are better served by the general kernels,
     // which the compressed-column path picks per product; the MFMA tile kernel of the FMA mode takes them as they are)
+    // (the Polar session keeps them all the same, slab_keep_sparse_runs: a product handed over packs the iterate, and the next
+    // transpose and product would start from compressed columns again)
     auto runs_dense = [](const DevMat& M) {
-      return options().spgemm_fma != 0 || !M.expanded() || (double)slab_span_sum(M) <= 1.5 * (double)M.nnz + 64.0 * (double)M.cols;
+      return options().spgemm_fma != 0 || g_keep_sparse_runs || !M.expanded() || (double)slab_span_sum(M) <= 1.5 * (double)M.nnz + 64.0 * (double)M.cols;
     };
     if (k.enter(mut(A)) && (&A == &B || k.enter(mut(B))) && (A.cplx || (runs_dense(A.loc) && runs_dense(B.loc))) &&
         k.multiply(A.loc, B.loc, AB, alpha, threshold, dense_branch(A.dim, A.loc.nnz, B.loc.nnz), nullptr)) {
@@ -2494,6 +2500,20 @@ void ps_gershgorin(const PSMatrix& A, double* e_min, double* e_max) {
   *e_max = mx;
 }
 
+long long* slab_transpose_counts() {
+  static long long counts[4] = {0, 0, 0, 0};
+  return counts;
+}
+namespace {
+// the gates of the slab transpose (option slab_transpose): one rank without process slices, an open session that takes the
+// operand's kind, and an operand the pass reads (slab_transpose_operand: no view, no labelled form).  What they keep out takes
+// the path on compressed columns and counts nowhere
+bool slab_transpose_on(const PSMatrix& A) {
+  return options().slab_transpose >= 1 && !world().active() && !(A.grid && A.grid->num_slices > 1) && slab_on() && A.loc.expanded() &&
+         session_takes(A.cplx) && slab_transpose_operand(A.loc);
+}
+}  // namespace
+
 void ps_transpose(const PSMatrix& A, PSMatrix& AT) {
   CommScope cs(A.grid);  // TransposeMatrix_ps
   unblock({&A});
@@ -2501,14 +2521,58 @@ void ps_transpose(const PSMatrix& A, PSMatrix& AT) {
   if (world().active()) {
     DevMat full = ps_gather_full(A);
     R = transpose_slice(full, A.c0, A.c1);
+  } else if (slab_transpose_on(A)) {
+    if (slab_transpose_any(A.loc, false, R)) {
+      g_slab_counts[2] += 1;
+      slab_transpose_counts()[0] += 1;
+    } else {
+      // (the transposed extents lie far apart: a refusal in the session's books, but A keeps its slab form -- this one transpose
+      // runs on a packed copy and its result stays in compressed columns)
+      g_slab_refusals += 1;
+      g_slab_counts[3] += 1;
+      slab_transpose_counts()[2] += 1;
+      if (g_slab_refusals > 4) g_slab_failed = true;
+      if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+        std::fprintf(stderr, "[slab session] a transpose was refused: this one on compressed columns (%d refusals so far)\n", g_slab_refusals);
+      DevMat tmp;
+      R = transpose(columns_of(A, tmp));
+    }
   } else {
-    R = transpose(A.loc);
+    DevMat tmp;
+    R = transpose(columns_of(A, tmp));
   }
   install(AT, A.grid, A.dim, A.cplx, A.c0, A.c1, std::move(R));
 }
 
 void ps_conjugate(PSMatrix& A) {
-  CommScope cs(A.grid); conjugate(A.loc); }
+  CommScope cs(A.grid);
+  if (options().slab_transpose >= 1 && A.cplx && slab_on() && session_takes(true) && A.loc.expanded() && !world().active() &&
+      slab_conjugate_c(A.loc)) {
+    g_slab_counts[2] += 1;
+    slab_transpose_counts()[1] += 1;
+    return;
+  }
+  conjugate(A.loc);
+}
+
+bool ps_slab_transpose_step(const PSMatrix& A, PSMatrix& AT, bool conj) {
+  CommScope cs(A.grid);
+  if (world().active() || (A.grid && A.grid->num_slices > 1)) return false;
+  const bool complex_ok = A.cplx && options().complex_sessions != 0 && options().spgemm_fma == 1 && options().complex_tile != 0;
+  if (A.cplx && !complex_ok) return false;
+  SlabSession ses(true, false, complex_ok);
+  if (!ses.opened || !session_takes(A.cplx)) return false;
+  unblock({&A});
+  DevMat R;
+  const bool entered = slab_kind(A.cplx).enter(mut(A)) && slab_transpose_operand(A.loc);
+  const bool done = entered && slab_transpose_any(A.loc, conj, R);
+  if (entered) slab_transpose_counts()[done ? 0 : 2] += 1;
+  pack(mut(A));   // (the session ends with this call: A goes back to compressed columns)
+  if (!done) return false;
+  pack(R);
+  install_like(AT, A, A.cplx, std::move(R));
+  return true;
+}
 
 bool ps_is_identity(const PSMatrix& A) {
   CommScope cs(A.grid);  // distributed_includes/IsIdentity.f90:7-38

@@ -1837,4 +1837,220 @@ long long slab_product_count(const DevMat& A, const DevMat& B) {
   return (long long)h;
 }
 
+// ------------------------------------------------------------------ the transpose of a slab form (option slab_transpose)
+// AT(j, i) = A(i, j) (conj: its conjugate) for a square, zero-free, unlabelled slab form A that is no view, as a fresh slab form
+// with A's row_pad: the Polar loop's U^H and a caller's Transpose of a product without leaving the tile kernel's operand form.
+// Three steps on the FreshSlabs scaffold, one host wait:
+//   1. k_tr_extents: column i of AT spans the first to the last j with A(i, j) != 0 (complex: either part) and holds `count` of
+//      them.  A workgroup walks TR_CB consecutive columns of A in tiles of 64 rows, lanes along rows (the runs are read
+//      coalesced), every wave two of each eight columns in ascending order; the four waves' (min, max, count) per row meet in
+//      LDS and ONE atomicMin / atomicMax / atomicAdd per row and column block goes out.  Integer atomics only: the same bits
+//      every run.
+//   2. k_tr_span: spans aligned to row_pad (an empty column: none), then the scan.
+//   3. k_tr_values: a workgroup owns TR_T consecutive columns of AT and walks their aligned hull in tiles of TR_T rows: the tile
+//      of A is read with lanes along A's rows into LDS (pitch TR_T + 1 elements: the transposed read then touches every bank
+//      once), and written with lanes along AT's rows.  Every slot of [a0, a1) of every column is written exactly once, zeros
+//      where A has no entry; a zero inside a run of A (padding, a hole) is no entry.  A slot total beyond `bound`: stat |= 2,
+//      nothing written.
+// No matrix instruction, no scratch.
+namespace {
+constexpr int TR_CB = 32;   // columns of A per workgroup of the extents pass
+constexpr int TR_T = 32;    // tile edge of the values pass
+__global__ void k_tr_init(int n, int32_t* __restrict__ ofirst, int32_t* __restrict__ olast, int32_t* __restrict__ ocount) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  ofirst[i] = INT_MAX;
+  olast[i] = -1;
+  ocount[i] = 0;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_tr_extents(int n, const int32_t* __restrict__ fa, const int32_t* __restrict__ la,
+                                                    const int64_t* __restrict__ offa, const T* __restrict__ va, int32_t* __restrict__ ofirst,
+                                                    int32_t* __restrict__ olast, int32_t* __restrict__ ocount) {
+  __shared__ int sf[TR_CB], sl[TR_CB];
+  __shared__ long long so[TR_CB];
+  __shared__ int rmn[4][WAVE], rmx[4][WAVE], rct[4][WAVE];
+  const int c0 = blockIdx.x * TR_CB, t = threadIdx.x, lane = t % WAVE, w = t / WAVE;
+  if (t < TR_CB) {
+    const int j = c0 + t;
+    const bool in = j < n;
+    sf[t] = in ? fa[j] : INT_MAX;
+    sl[t] = in ? la[j] : -1;
+    so[t] = in ? offa[j] : 0;
+  }
+  __syncthreads();
+  int lo = INT_MAX, hi = -1;
+  for (int c = 0; c < TR_CB; ++c)
+    if (sl[c] >= sf[c]) { lo = min(lo, sf[c]); hi = max(hi, sl[c]); }
+  if (hi < lo) return;   // (uniform: every column of the block is empty)
+  for (int r0 = lo / WAVE * WAVE; r0 <= hi; r0 += WAVE) {
+    const int r = r0 + lane;
+    int mn = INT_MAX, mx = -1, ct = 0;
+    for (int q = 0; q < TR_CB / 4; ++q) {
+      const int c = w * (TR_CB / 4) + q, f = sf[c], l = sl[c];
+      if (r >= f && r <= l) {
+        const T v = va[so[c] + (r - f)];
+        if (!Sc<T>::is_zero(v)) { mn = min(mn, c0 + c); mx = max(mx, c0 + c); ct += 1; }
+      }
+    }
+    rmn[w][lane] = mn; rmx[w][lane] = mx; rct[w][lane] = ct;
+    __syncthreads();
+    if (w == 0) {
+      const int cnt = rct[0][lane] + rct[1][lane] + rct[2][lane] + rct[3][lane];
+      if (cnt > 0 && r < n) {
+        atomicMin(&ofirst[r], min(min(rmn[0][lane], rmn[1][lane]), min(rmn[2][lane], rmn[3][lane])));
+        atomicMax(&olast[r], max(max(rmx[0][lane], rmx[1][lane]), max(rmx[2][lane], rmx[3][lane])));
+        atomicAdd(&ocount[r], cnt);
+      }
+    }
+    __syncthreads();
+  }
+}
+__global__ void k_tr_span(const int32_t* __restrict__ ofirst, const int32_t* __restrict__ olast, int n, int al, int32_t* __restrict__ span) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int f = ofirst[i], l = olast[i];
+  span[i] = l >= f ? (l / al + 1) * al - f / al * al : 0;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_tr_values(int n, const int32_t* __restrict__ fa, const int32_t* __restrict__ la,
+                                                   const int64_t* __restrict__ offa, const T* __restrict__ va, int conj, int al,
+                                                   const int64_t* __restrict__ base, const int32_t* __restrict__ ofirst,
+                                                   const int32_t* __restrict__ olast, int64_t* __restrict__ ooff, T* __restrict__ out,
+                                                   int64_t bound, unsigned long long* __restrict__ stat) {
+  __shared__ T tile[TR_T][TR_T + 1];
+  __shared__ int sa0[TR_T], sa1[TR_T];       // the aligned extent [a0, a1) of AT's columns i0 .. (empty: a1 = a0 = 0)
+  __shared__ long long sbase[TR_T];
+  __shared__ int sf[TR_T], sl[TR_T];         // the runs of A's columns of the current tile
+  __shared__ long long so[TR_T];
+  const int t = threadIdx.x, i0 = blockIdx.x * TR_T;
+  if (base[n] > bound) {   // (runs far apart: the transposed extents do not fit the output -- refused by the host)
+    if (blockIdx.x == 0 && t == 0) atomicOr(stat, 2ull);
+    return;
+  }
+  if (t < TR_T) {
+    const int i = i0 + t;
+    int a0 = 0, a1 = 0;
+    long long b = 0;
+    if (i < n) {
+      const int f = ofirst[i], l = olast[i];
+      b = base[i];
+      if (l >= f) { a0 = f / al * al; a1 = (l / al + 1) * al; }
+      ooff[i] = b + (l >= f ? f - a0 : 0);
+    }
+    sa0[t] = a0; sa1[t] = a1; sbase[t] = b;
+  }
+  __syncthreads();
+  int lo = INT_MAX, hi = -1;
+  for (int c = 0; c < TR_T; ++c)
+    if (sa1[c] > sa0[c]) { lo = min(lo, sa0[c]); hi = max(hi, sa1[c]); }
+  if (hi < lo) return;   // (uniform: every column of the block is empty)
+  const int lx = t % TR_T, ly = t / TR_T;   // (256 threads: 8 rows of the tile per sweep)
+  for (int j0 = lo / TR_T * TR_T; j0 < hi; j0 += TR_T) {
+    if (t < TR_T) {
+      const int j = j0 + t;
+      const bool in = j < n;
+      sf[t] = in ? fa[j] : INT_MAX;
+      sl[t] = in ? la[j] : -1;
+      so[t] = in ? offa[j] : 0;
+    }
+    __syncthreads();
+    // A(i0 + lx, j0 + c): lanes along the rows of A
+    for (int c = ly; c < TR_T; c += 256 / TR_T) {
+      const int r = i0 + lx, f = sf[c], l = sl[c];
+      T v = Sc<T>::zero();
+      if (r >= f && r <= l) v = va[so[c] + (r - f)];
+      tile[c][lx] = (conj && !Sc<T>::is_zero(v)) ? Sc<T>::conj(v) : v;   // (k_conj's negation; a slot without an entry stays (0, 0))
+    }
+    __syncthreads();
+    // AT(j0 + lx, i0 + c): lanes along the rows of AT
+    for (int c = ly; c < TR_T; c += 256 / TR_T) {
+      const int j = j0 + lx, a0 = sa0[c];
+      if (j >= a0 && j < sa1[c]) out[sbase[c] + (j - a0)] = tile[lx][c];
+    }
+    __syncthreads();
+  }
+}
+}  // namespace
+
+bool slab_transpose_operand(const DevMat& A) {
+  return A.expanded() && A.rows == A.cols && !A.slab->labelled() && !A.slab->origin && A.zero_free == 1 && !slab_panels_ok() &&
+         (A.cplx ? A.slab->row_pad % 16 == 0 : (A.slab->row_pad == 1 || A.slab->row_pad % 16 == 0));
+}
+
+template <typename T>
+bool slab_transpose(const DevMat& A, bool conj, DevMat& AT) {
+  if (!slab_transpose_operand(A) || A.cplx != Sc<T>::cplx) return false;
+  const SlabForm& fa = *A.slab;
+  const int n = A.cols, al = std::max(1, fa.row_pad);
+  const int64_t bound = 4 * fa.slots + 4LL * al * n;   // (slots of T)
+  FreshSlabs fs(n, 1, bound, Sc<T>::cplx, false);
+  const IsrOut o = fs.out(0);
+  const T* va = reinterpret_cast<const T*>(fa.val.p);
+  // (statistics, option time_kernels with NTPOLY_AMD_DEBUG_SPGEMM set: the pass between two events, for tools/bench_polar_session.py)
+  const bool timed = options().time_kernels != 0 && std::getenv("NTPOLY_AMD_DEBUG_SPGEMM") != nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (timed) {
+    HIP_CHECK(hipEventCreate(&ev[0]));
+    HIP_CHECK(hipEventCreate(&ev[1]));
+    HIP_CHECK(hipEventRecord(ev[0], stream()));
+  }
+  hipLaunchKernelGGL(k_tr_init, dim3(cdiv(n, 256)), dim3(256), 0, stream(), n, o.first, o.last, o.count);
+  hipLaunchKernelGGL((k_tr_extents<T>), dim3(cdiv(n, TR_CB)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p, va, o.first, o.last, o.count);
+  hipLaunchKernelGGL(k_tr_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), o.first, o.last, n, al, fs.span.p);
+  fs.scan();
+  hipLaunchKernelGGL((k_tr_values<T>), dim3(cdiv(n, TR_T)), dim3(256), 0, stream(), n, fa.first.p, fa.last.p, fa.off.p, va, conj ? 1 : 0, al,
+                     fs.base.p, o.first, o.last, o.off, static_cast<T*>(o.val), bound, fs.stat.p);
+  if (timed) HIP_CHECK(hipEventRecord(ev[1], stream()));
+  DevMat R;
+  const bool done = fs.finish("slab transpose", A.rows, al, &R);
+  if (timed) {   // (finish waited for the stream)
+    float ms = 0.f;
+    HIP_CHECK(hipEventSynchronize(ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    HIP_CHECK(hipEventDestroy(ev[0]));
+    HIP_CHECK(hipEventDestroy(ev[1]));
+    // bytes: the runs of A read by the extents pass and by the values pass, the runs of AT written, the extents of both
+    const double bytes = (double)sizeof(T) * (2.0 * (double)fa.slots + (done ? (double)R.slab->slots : 0.0)) + 40.0 * (double)n;
+    std::fprintf(stderr, "[slab transpose] timed: n %d slots_in %lld slots_out %lld bytes %.0f ms %.5f\n", n, (long long)fa.slots,
+                 done ? (long long)R.slab->slots : -1LL, bytes, (double)ms);
+  }
+  if (!done) return false;
+  AT = std::move(R);
+  return true;
+}
+template bool slab_transpose<double>(const DevMat& A, bool conj, DevMat& AT);
+template bool slab_transpose<double2>(const DevMat& A, bool conj, DevMat& AT);
+
+bool slab_transpose_any(const DevMat& A, bool conj, DevMat& AT) {
+  return A.cplx ? slab_transpose<double2>(A, conj, AT) : slab_transpose<double>(A, conj, AT);
+}
+
+// ConjugateMatrix of a complex slab form in place: one pass over the runs, k_conj's negation on every entry (pads and holes stay
+// (0, 0)); the moduli, and with them amax, stay what they were
+namespace {
+__global__ __launch_bounds__(256) void k_sa_conj(int n, const int32_t* __restrict__ first, const int32_t* __restrict__ last,
+                                                 const int64_t* __restrict__ off, double2* __restrict__ val) {
+  const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  if (j >= n) return;
+  const int f = first[j], l = last[j];
+  if (l < f) return;
+  double2* __restrict__ v = val + off[j];
+  for (int r = lane_id(); r <= l - f; r += WAVE) {
+    const double2 e = v[r];
+    if (!Sc<double2>::is_zero(e)) v[r].y = -e.y;
+  }
+}
+}  // namespace
+bool slab_conjugate_c(DevMat& A) {
+  if (!sa_operand_c(A) || A.zero_free != 1) return false;
+  SlabForm& f = *A.slab;
+  bump_matrix_value_epoch();
+  hipLaunchKernelGGL(k_sa_conj, dim3(cdiv((int64_t)A.cols * WAVE, 256)), dim3(256), 0, stream(), A.cols, f.first.p, f.last.p, f.off.p,
+                     reinterpret_cast<double2*>(f.val.p));
+  f.tiles.release();   // (multiplier tiles would hold the old values)
+  f.tile_off.release();
+  return true;
+}
+
 }  // namespace ntp

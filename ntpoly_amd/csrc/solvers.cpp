@@ -759,7 +759,15 @@ void sign_core(const PSMatrix& InMat, PSMatrix& OutMat, const SolverParameters& 
   int II;
   // (complex operands under FMA arithmetic: the loop's products, identity increment and norm take them in slab form as well)
   const bool complex_session = complex_slab_loop(Out);
-  SlabSession slab(!needs_transpose && (!Out.cplx || complex_session), false, complex_session);
+  // (PolarDecomposition: the loop transposes its iterate, which a session keeps in slab form only under option slab_transpose --
+  // one rank without process slices; 1: real operands, 2: complex ones as well.  Several ranks: compressed columns, as ever)
+  const bool polar_ok = options().slab_transpose >= 1 && !world().active() && !(Out.grid && Out.grid->num_slices > 1) &&
+                        (!Out.cplx || (options().slab_transpose >= 2 && complex_session));
+  SlabSession slab((!needs_transpose || polar_ok) && (!Out.cplx || complex_session), false, complex_session);
+  if (needs_transpose && slab.opened) {
+    slab_transpose_counts()[3] += 1;
+    slab_keep_sparse_runs(true);   // (unfused arithmetic: no product of this loop leaves slab form for the general kernels)
+  }
   for (II = 1; II <= p.max_iterations; ++II) {
     const double alpha_k = std::fmin(std::sqrt(3.0 / (1.0 + xk + xk * xk)), alpha);
     xk = 0.5 * alpha_k * xk * (3.0 - (alpha_k * alpha_k) * (xk * xk));

@@ -200,6 +200,7 @@ void ntpoly_amd_set_option(const char* name, const int* value) {
   else if (n == "pm_session") options().pm_session = *value;
   else if (n == "complex_pm") options().complex_pm = *value;
   else if (n == "isr_chain") options().isr_chain = *value;
+  else if (n == "slab_transpose") options().slab_transpose = *value;
   else if (n == "hpcp_step") options().hpcp_step = *value;
   else if (n == "scale_fold_step") options().scale_fold_step = *value;
   else if (n == "complex_trs4") options().complex_trs4 = *value;
@@ -245,6 +246,7 @@ int ntpoly_amd_get_option(const char* name) {
   if (n == "pm_session") return options().pm_session;
   if (n == "complex_pm") return options().complex_pm;
   if (n == "isr_chain") return options().isr_chain;
+  if (n == "slab_transpose") return options().slab_transpose;
   if (n == "hpcp_step") return options().hpcp_step;
   if (n == "scale_fold_step") return options().scale_fold_step;
   if (n == "complex_trs4") return options().complex_trs4;
@@ -321,6 +323,20 @@ void ntpoly_amd_isr_chain_counts(long long out[3]) {
 int ntpoly_amd_isr_chain_step(const int* ih_X, const int* ih_X2, const int* order, const double* a, const double* b, const double* c,
                               int* ih_Out1, int* ih_Out2) {
   return ps_isr_chain_step(*get_unpacked(ih_X), *get_unpacked(ih_X2), *order, *a, *b, *c, *get_unpacked(ih_Out1), *get_unpacked(ih_Out2)) ? 1 : 0;
+}
+// The transpose of a slab form (option slab_transpose; engine.hpp ps_transpose / ps_conjugate) since start: out[0] = transposes
+// done in slab form, out[1] = conjugations done in slab form, out[2] = transposes refused past the gates (extents far apart: that
+// one ran on compressed columns), out[3] = PolarDecomposition solves that ran in a slab session.  A gated operand -- no session,
+// several ranks, compressed columns, a view, a labelled form, block form -- counts nowhere
+void ntpoly_amd_slab_transpose_counts(long long out[4]) {
+  for (int q = 0; q < 4; ++q) out[q] = slab_transpose_counts()[q];
+}
+// DIAGNOSTIC surface, one rank: A is brought into slab form in a session of this call's own (a complex one where A is complex and
+// FMA arithmetic, complex_tile and complex_sessions allow it), the transpose pass runs on it -- *conjugate != 0: the conjugate
+// transpose -- and the PACKED result is installed in AT.  Returns 1, or 0 when gated or refused: AT is then as it was.  Does
+// not depend on option slab_transpose
+int ntpoly_amd_slab_transpose(const int* ih_A, int* ih_AT, const int* conjugate) {
+  return ps_slab_transpose_step(*get<PSMatrix>(ih_A), *get<PSMatrix>(ih_AT), *conjugate != 0) ? 1 : 0;
 }
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update)
 // since start: out[0] = trace passes fused, out[1] = updates fused, out[2] = updates refused (the vocabulary calls ran instead).  A
@@ -1079,10 +1095,18 @@ void GetMatrixTripletList_psc_wrp(const int* ih_this, int* ih_triplet_list) {
     ps_get_triplets(*m, *t);
   }
 }
+// (in a session of their own like the vocabulary calls above: a product of an earlier call that is still in slab form is transposed
+// or conjugated there and stays there, option slab_transpose; a matrix in compressed columns is not converted for it)
 void TransposeMatrix_ps_wrp(const int* ih_matA, int* ih_transmat) {
-  ps_transpose(*get<PSMatrix>(ih_matA), *get<PSMatrix>(ih_transmat));
+  if (options().slab_transpose == 0) { ps_transpose(*get<PSMatrix>(ih_matA), *get<PSMatrix>(ih_transmat)); return; }
+  ApiSession ses(ih_matA);
+  ps_transpose(*ses.mat(ih_matA), *ses.mat(ih_transmat));
 }
-void ConjugateMatrix_ps_wrp(int* ih_matA) { ps_conjugate(*get<PSMatrix>(ih_matA)); }
+void ConjugateMatrix_ps_wrp(int* ih_matA) {
+  if (options().slab_transpose == 0) { ps_conjugate(*get<PSMatrix>(ih_matA)); return; }
+  ApiSession ses(ih_matA);
+  ps_conjugate(*ses.mat(ih_matA));
+}
 void GetMatrixProcessGrid_ps_wrp(const int* ih_this, int* ih_grid) {
   put(ih_grid, const_cast<ProcessGrid*>(get<PSMatrix>(ih_this)->grid));
 }

@@ -1113,6 +1113,24 @@ def isr_chain_step(X, X2, order, a, b, c, Out1, Out2):
     return True if ok else None
 
 
+def slab_transpose_counts():
+    """the transpose of a slab form (option slab_transpose; csrc/slab_extra.hip k_tr_extents / k_tr_values) since start: transposes
+    done in slab form, conjugations done in slab form, transposes refused past the gates (extents far apart: that one ran on
+    compressed columns), PolarDecomposition solves that ran in a slab session.  A gated operand (no session, several ranks,
+    compressed columns, a view, a labelled form, block form) counts nowhere"""
+    out = (C.c_longlong * 4)()
+    lib.ntpoly_amd_slab_transpose_counts(out)
+    return dict(transposes=int(out[0]), conjugates=int(out[1]), refused=int(out[2]), polar_sessions=int(out[3]))
+
+
+def slab_transpose(A, AT, conjugate=False):
+    """DIAGNOSTIC, one rank -- A is brought into slab form in a session of the call's own, the transpose pass runs on it (conjugate:
+    the conjugate transpose) and the PACKED result is installed in AT.  True: taken; None: gated or refused, AT as it was."""
+    lib.ntpoly_amd_slab_transpose.restype = C.c_int
+    ok = lib.ntpoly_amd_slab_transpose(A.ih, AT.ih, C.byref(C.c_int(1 if conjugate else 0)))
+    return True if ok else None
+
+
 def hpcp_step_counts():
     """HPCP purification with its traces and its update in one pass each (option hpcp_step; csrc/slab_extra.hip k_hpcp_traces /
     k_hpcp_update) since start: trace passes fused, updates fused, updates refused (the vocabulary calls ran instead);
