@@ -5158,6 +5158,11 @@ void pairwise(const DevMat& A, const DevMat& B, DevMat& C, bool conj_a) {
   if (A.rows != B.rows || A.cols != B.cols || A.cplx != B.cplx) NTP_FATAL("pairwise: operand mismatch");
   const int n = A.cols;
   DevMat R;
+  if (n == 0) {   // (a panel of width 0: a grid of cdiv(0, 64) = 0 blocks is no valid launch)
+    R.reset_empty(A.rows, 0, A.cplx);
+    C = std::move(R);
+    return;
+  }
   R.rows = A.rows;
   R.cols = n;
   R.cplx = A.cplx;
