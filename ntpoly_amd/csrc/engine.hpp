@@ -167,7 +167,7 @@ bool ps_trs4_energy(const PSMatrix& X, const PSMatrix& WH, double* energy);
 // or refused, every matrix as it was
 bool ps_trs4_chain_step(const PSMatrix& X, const PSMatrix& X2, double sigma, PSMatrix& P, double* trace_fx, double* trace_gx);
 bool ps_trs4_energy_step(const PSMatrix& X, const PSMatrix& WH, double* energy);
-long long* complex_trs4_counts();   // since start: [0] trace passes fused, [1] operands fused, [2] energies fused, [3] passes refused (past the gates: a gated pass counts nowhere)
+long long* complex_trs4_counts();   // (slots: counters.inc)
 // PM purification with the iterate X kept in slab form (zero-free runs) and the rows compressed columns would hold as stored
 // zeros in Z (kernels.hpp ZeroList; option pm_session), inside a real slab session, one rank or column panels across ranks.
 // ps_pm_sigma: trace and dot(., X) of X - X2 merged at `threshold`, X - X2 not formed.  Collective: the two sums and "some rank
@@ -191,8 +191,8 @@ bool ps_pm_sigma(const PSMatrix& X, const ZeroList& Z, const PSMatrix& X2, doubl
 bool ps_pm_update(PSMatrix& X, ZeroList& Z, const PSMatrix& X2, const PSMatrix& X3, double a1, double a2, double a3, double threshold);
 double ps_pm_energy(const PSMatrix& X, const PSMatrix& WH, bool refused_here, bool* some_refused);
 void ps_pm_materialise(PSMatrix& X, ZeroList& Z);
-long long* complex_pm_counts();   // since start: [0] sigma passes fused, [1] updates fused, [2] stored zeros carried (summed over the updates), [3] solves that left the fused path (past the gates: a gated solve counts nowhere)
-long long* pm_session_counts();   // since start: [0] sigma passes fused, [1] updates fused, [2] stored zeros carried (summed over the updates), [3] solves that left the fused path; [4] the longest zero list an update left on this rank
+long long* complex_pm_counts();   // (slots: counters.inc)
+long long* pm_session_counts();   // (slots [0..3]: counters.inc; [4] the longest zero list an update left on this rank)
 // MatrixNorm of alpha A + beta B (ScaleMatrix(B, beta); IncrementMatrix(A, B, alpha, 0); MatrixNorm(B)) for the loops
 // that build the sum only for its norm; false: not done (outside a slab session, operands in compressed columns ...)
 bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double beta, double* norm);
@@ -218,7 +218,7 @@ bool ps_isr_chain3(PSMatrix& X, const PSMatrix& X2);
 // DIAGNOSTIC (the C ABI's ntpoly_amd_isr_chain_step): X and X2 are brought into slab form where they are, one chain of the given
 // order runs, the outputs are packed into Out1 (order 5: Temp2, order 3: the new X) and Out2 (order 5: Temp; order 3: untouched)
 bool ps_isr_chain_step(const PSMatrix& X, const PSMatrix& X2, int order, double a, double b, double c, PSMatrix& Out1, PSMatrix& Out2);
-long long* isr_chain_counts();   // since start: [0] order-5 chains fused, [1] order-3 chains fused, [2] chains refused (past the gates: a gated step counts nowhere)
+long long* isr_chain_counts();   // (slots: counters.inc)
 // HPCP purification (DensityMatrixSolversModule.F90:839-878) inside a real slab session, option hpcp_step (slab_extra.hip
 // k_hpcp_traces / k_hpcp_update).
 // ps_hpcp_traces: out = trace(DDH), trace(D2DH), each with the bits of ps_trace, from one pass and one read-back.  Collective: one
@@ -252,11 +252,11 @@ bool ps_hpcp_update_step(const PSMatrix& D1, const PSMatrix& DDH, const PSMatrix
 // nothing; past them a sigma that is zero or not finite, an operand the kernel's rules exclude once it is in slab form (stored
 // zeros in a merged operand) and a non-zero status (runs far apart, an underflow) count as refused in complex_hpcp_counts().
 // slab_algebra_counts() counts a fused pass as the real branch does; hpcp_step_counts() never counts a complex pass.
-long long* complex_hpcp_counts();   // since start: [0] trace passes fused, [1] updates fused, [2] passes refused
+long long* complex_hpcp_counts();   // (slots: counters.inc)
 // DIAGNOSTIC (the C ABI's ntpoly_amd_hpcp_traces_step): both matrices are brought into slab form where they are and the fused trace
 // pass runs, real (option hpcp_step) or complex (option complex_hpcp); false: gated or refused, out as it was
 bool ps_hpcp_traces_step(const PSMatrix& DDH, const PSMatrix& D2DH, double out[2]);
-long long* hpcp_step_counts();   // since start: [0] trace passes fused, [1] updates fused, [2] updates refused (past the gates: a gated step counts nowhere)
+long long* hpcp_step_counts();   // (slots: counters.inc)
 // ScaleAndFold (DensityMatrixSolversModule.F90:1049-1081) inside a real slab session, option scale_fold_step (slab_extra.hip
 // k_saf_update / k_saf_dot_trace).
 // ps_saf_update: what ps_axpby(X2, X, a, b, 0) -- ScaleMatrix(X, b); IncrementMatrix(X2, X, a) -- leaves in X, values and pattern bit
@@ -277,7 +277,7 @@ bool ps_saf_dot_trace(const PSMatrix& X, const PSMatrix& WH, double* dot, double
 // one pass runs, the new X is packed into Xout; false: refused or gated, everything as it was
 bool ps_saf_update_step(const PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, PSMatrix& Xout, double* dot, double* trace);
 bool ps_saf_dot_trace_step(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace);
-long long* scale_fold_step_counts();   // since start: [0] updates fused, [1] dot-and-trace passes fused, [2] refused (past the gates: a gated step counts nowhere)
+long long* scale_fold_step_counts();   // (slots: counters.inc)
 // Option complex_scale_fold (one rank, inside a session that takes complex operands): the four calls above take COMPLEX operands
 // (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of
 // the vocabulary calls at threshold 0 bit for bit; the scale branch's pass is slab_dot_trace_c over X and WH as it stands -- slab
@@ -290,17 +290,17 @@ long long* scale_fold_step_counts();   // since start: [0] updates fused, [1] do
 // kernel's rules exclude once it is in slab form (stored zeros in a merged operand) and a non-zero status (runs far apart, an
 // underflow) count as refused in complex_scale_fold_counts().  slab_algebra_counts() counts a fused pass as the real branch does;
 // scale_fold_step_counts() never counts a complex pass.
-long long* complex_scale_fold_counts();   // since start: [0] fold updates fused, [1] dot-and-trace passes fused, [2] passes refused
+long long* complex_scale_fold_counts();   // (slots: counters.inc)
 // solvers.cpp: this loop may take a complex operand like m in slab form (FMA arithmetic, complex tile kernel, complex_sessions)
 bool complex_slab_loop(const PSMatrix& m);
 void ps_slab_leave(PSMatrix& m);   // back to compressed columns (no-op for a matrix that is not in slab form)
-const long long* column_fused_counts();   // [2] since start: IncrementMatrix(Identity, .) done in place, norms of differences taken without forming them (column_fused.hip)
-const long long* block_algebra_counts();  // [2] since start: operations done in block form (spgemm_block.hpp block algebra); fallbacks
+const long long* column_fused_counts();   // (slots: counters.inc)
+const long long* block_algebra_counts();   // (slots: counters.inc)
 long long block_scope_products();   // panel products of block-order solves that took the block path (psmatrix.cpp)
 bool block_scope_active();   // band_scope.cpp: the solve in progress runs on operands redistributed in a block order (several ranks)
-const long long* panel_product_counts();  // [3] products of slab sessions across ranks: in slab form on every rank; declined; host synchronisations inside the former
+const long long* panel_product_counts();   // (slots: counters.inc)
 long long recurrence_step_count();         // fused recurrence steps taken since start (each also counted as two merges below)
-const long long* slab_algebra_counts();   // [4] since start: products, merges / copies, other operations done in slab form; refusals
+const long long* slab_algebra_counts();   // (slots: counters.inc)
 void ps_fill_identity(PSMatrix& m);
 void ps_fill_permutation(PSMatrix& m, const std::vector<int32_t>& lookup /*1-based*/, bool rows);
 void ps_fill_from_triplets(PSMatrix& m, const HostTriplets& t);
@@ -371,9 +371,8 @@ void ps_conjugate(PSMatrix& A);
 // of a square zero-free slab form is the tiled transpose of its runs (kernels.hpp slab_transpose) and leaves a slab form, and
 // ps_conjugate of a complex one runs in place.  A view, a labelled form or block form is gated: the path on compressed columns, A
 // untouched, counted nowhere.  A transpose the pass refuses past the gates (extents far apart) runs on a packed copy of A, leaves
-// compressed columns and counts as a refusal of the session.  slab_transpose_counts() since start: [0] transposes done in slab
-// form, [1] conjugations done in slab form, [2] refusals past the gates, [3] Polar solves that ran in a session.
-long long* slab_transpose_counts();
+// compressed columns and counts as a refusal of the session.
+long long* slab_transpose_counts();   // (slots: counters.inc)
 // DIAGNOSTIC (the C ABI's ntpoly_amd_slab_transpose): one rank; a session of its own (a complex one where A is complex and FMA
 // arithmetic, complex_tile and complex_sessions allow it), A entered into slab form, the pass run with or without conjugation, the
 // PACKED result installed in AT.  false: gated or refused, AT untouched.  A is back in compressed columns either way
@@ -480,7 +479,7 @@ double trs2_step(PSMatrix& X, PSMatrix& X2, const PSMatrix& WH, double trace_tar
 // solver itself on the relabelled operands; the outputs are carried back to the caller's labels
 bool band_scope_try(const std::vector<const PSMatrix*>& ins, const std::vector<PSMatrix*>& outs,
                     const std::function<void(const std::vector<const PSMatrix*>&, const std::vector<PSMatrix*>&)>& run);
-const long long* band_scope_counts();
+const long long* band_scope_counts();   // (slots [0..1]: counters.inc; [2] solves that ran in a block order across ranks)
 
 // ------------------------------------------------------------------ solvers
 void solver_trs2(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSMatrix& K, double* energy, double* mu,

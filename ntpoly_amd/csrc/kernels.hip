@@ -2697,36 +2697,19 @@ __global__ void k_row_range(Csc A, int* __restrict__ mm) {
 EngineOptions& options() {
   static EngineOptions* o = [] {
     auto* e = new EngineOptions();
-    if (const char* v = std::getenv("NTPOLY_AMD_HALO_OVERLAP")) e->halo_overlap = std::atoi(v);  // see kernels.hpp
-    if (const char* v = std::getenv("NTPOLY_AMD_SPGEMM_FMA")) e->spgemm_fma = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_ARITHMETIC")) {   // the documented selector
+    for (const OptionEntry& o : option_table) {   // NTPOLY_AMD_<NAME> for the entries that options.inc marks ENV
+      if (!o.has_env) continue;
+      std::string var = "NTPOLY_AMD_";
+      for (const char* c = o.name; *c; ++c) var += (*c >= 'a' && *c <= 'z') ? (char)(*c - 'a' + 'A') : *c;
+      if (const char* v = std::getenv(var.c_str())) e->*o.field = std::atoi(v);
+    }
+    // the documented selector, behind the table: it overrides NTPOLY_AMD_SPGEMM_FMA
+    if (const char* v = std::getenv("NTPOLY_AMD_ARITHMETIC")) {
       const std::string a(v);
       if (a == "fma") e->spgemm_fma = 1;
       else if (a == "unfused") e->spgemm_fma = 0;
       else NTP_FATAL("NTPOLY_AMD_ARITHMETIC must be fma or unfused, not " + a);
     }
-    if (const char* v = std::getenv("NTPOLY_AMD_TILE_ROWS")) e->tile_rows = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_TILE_WAVES")) e->tile_waves = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_PLAN_AHEAD")) e->plan_ahead = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_SLAB_ALGEBRA")) e->slab_algebra = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_PANEL_SESSIONS")) e->panel_sessions = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PANELS")) e->complex_panels = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_THIN_SLAB_COMPLEX")) e->thin_slab_complex = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_GHASH_MFMA_COMPLEX")) e->ghash_mfma_complex = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_POLY_SESSIONS")) e->complex_poly_sessions = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_STORED_ZERO_VIEWS")) e->stored_zero_views = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_PM_SESSION")) e->pm_session = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_PM")) e->complex_pm = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_ISR_CHAIN")) e->isr_chain = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_SLAB_TRANSPOSE")) e->slab_transpose = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_HPCP_STEP")) e->hpcp_step = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_SCALE_FOLD_STEP")) e->scale_fold_step = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_TRS4")) e->complex_trs4 = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_HPCP")) e->complex_hpcp = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_SCALE_FOLD")) e->complex_scale_fold = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_COMPLEX_DENSITY")) e->complex_density = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_SCOPE_COMPLEX")) e->block_scope_complex = std::atoi(v);
-    if (const char* v = std::getenv("NTPOLY_AMD_BLOCK_UNFUSED")) e->block_unfused = std::atoi(v);
     return e;
   }();
   return *o;

@@ -34,109 +34,28 @@ struct SpgemmStats {
   float ms_numeric = 0.f;
 };
 
+// the option table (options.inc, where every option is documented) as plain int fields ...
 struct EngineOptions {
-  int spgemm_force_bin = -1;   // tests: force every non-empty column through one path (1..5), 6 = HBM fallback
-  int increment_force_seq = 0; // tests: 1 force the sequential-merge fallback, 2 force the rank-merge kernel (columns of <= 2048 entries)
-  int time_kernels = 0;        // record HIP-event timings in SpgemmStats
-  int spgemm_fma = 1;          // arithmetic of the real products (NTPOLY_AMD_ARITHMETIC=fma|unfused in the environment).
-                               // 1 (default since round 4): every product entry is the chain fma(a, b, acc) over ascending k, one
-                               // rounding per product -- the reference built with FP contraction, bit for bit; run-like operands on
-                               // the FP64 matrix cores (spgemm_tile.hip), operands without runs as 16 x 16 blocks on the same
-                               // instruction (spgemm_block.hip).  0: separate multiply and add, bit-identical to the reference's
-                               // default x86-64 build (register-slab / LDS kernels).  3: the v_fma_f64 vector loop (tests)
-  int block_path = 1;          // FMA arithmetic, one rank, real square operands WITHOUT run structure (3-D Hamiltonians, relabelled bands outside
-                               // a TRS2 loop): products on 16 x 16 blocks of a clustered index order through v_mfma_f64_16x16x4_f64
-                               // (spgemm_block.hip) instead of the grouped LDS-hash kernel; 0: never; 2: every real square one-rank
-                               // product that no run-based kernel takes, whatever the fill (tests)
-  int slab_algebra = 1;        // solver loops (TRS4, sign, inverse, square roots; one rank, real, FMA arithmetic): iterates stay in slab form
-                               // between products, merges, dots and norms (psmatrix.cpp SlabSession); 0: compressed columns between the operations
-  int plan_ahead = 1;          // TRS2 steps on the slab form (tile kernel, one rank): the step plans its successor behind its own kernel and
-                               // reads the sizes back with its results -- one host round trip per step instead of two;
-                               // 0: every step makes its plan and reads it back before the launch
-  int operand_cache = 1;       // 1: the expanded WH (and WH in a recovered band order) of a purification solve stays on the
-                               // device for the next solve on the same operand (SCF loops): at most 8 (nnz + 32 n) + 12 nnz + 8 n
-                               // bytes, replaced when the operand changes; 0: freed at the end of every solve;
-                               // ntpoly_amd_release_cache() frees it at any time
-  int tile_rows = 2;           // MFMA tile kernel (spgemm_fma = 1): consecutive rows per lane of the A operand, 1 / 2 / 4 (spgemm_tile.hpp)
-  int tile_waves = 0;          // ... waves per workgroup, 4 / 8 (0: chosen from the LDS footprint)
-  int thin_left = 1;           // products whose left operand holds a handful of entries per row (identities, near-diagonal factors of the
-                               // square-root loops): the output-driven gather kernel of spgemm_thin.hip, both arithmetic modes, bit for bit
- int complex_sessions = 1;    // the complex SignFunction loop keeps its iterates in the complex tile kernel's operand form between products (no
-                               // expansion, no pack; FMA arithmetic with complex_tile); 0: compressed columns between the operations
-  int column_fused = 1;        // IncrementMatrix(Identity, B) in place and the norm of a difference without forming it, on compressed columns
-                               // (column_fused.hip: complex solver loops, real ones outside slab sessions); 0: the merge kernels
-  int complex_tile = 1;        // FMA arithmetic: run-like COMPLEX operands on the matrix cores (spgemm_tile_c.hip: two FMA chains per part of an
-                               // entry -- a tolerance mode, 1e-13 of the largest entry); 0: the register-slab kernel with the reference's
-                               // complex multiply-add, bit for bit (what unfused arithmetic always runs)
-  int block_complex = 1;       // FMA arithmetic with complex_tile: COMPLEX square operands without run structure on the block path too (complex
-                               // 16 x 16 tiles, two FMA chains per part of an entry -- the tolerance mode of complex_tile); the same rule as
-                               // real operands (block_path).  0: never (the grouped LDS-hash kernel)
-  int tile2 = 0;               // run-like real operands in FMA arithmetic: the two-block chunk-streaming geometry of the MFMA kernel (spgemm_tile2.hip) (1) where it fits -- slower than k_spgemm_tile as measured in round 5 (profiles/README.md 83): 0 by default
-  int tile_skip = 1;           // TRS2 steps on the tile kernel (one rank, tiles of 32 rows, 32-bit offsets): iterates carry the largest modulus of
-                               // every 32 slots (SlabForm::amax) and the kernel skips, before it loads anything for them, the tiles whose products
-                               // are bounded at or below the threshold by them -- exact: such a tile stores nothing (spgemm_tile.hip, DESIGN.md
-                               // section 4); 0: no test, amax neither read nor written
-  int tile_runs_only = 1;      // TRS2 steps on the tile kernel (one rank): the result is written as runs only and the next step builds its
-                               // multiplier tiles from them (1.5 GB -> 1.0 GB written per launch at the headline size, no tile read);
-                               // 0: runs + multiplier tiles as the unfused loop needs them
-  int load_balance = 1;        // 1: solvers permute with the caller's load-balancing permutation as the reference does;
-                               // 0: SetParametersLoadBalance is ignored -- the same results up to summation order (a
-                               // symmetric permutation only relabels entries), but banded operands stay on the run-based
-                               // kernels (a random permutation costs ~25x in SpGEMM time and turns the halo into a full gather)
-  int virtual_grid = 0;        // tests: a process grid of any rows x columns x slices may be constructed on the ranks there
-                               // are (the shape only selects the summation semantics of the multiply: slices > 1)
-  int fused_update = 1;        // TRS2 on one rank, real operands: the update X <- 2X - X*X (or X*X), its energy and its trace
-                               // come out of the epilogue of the register-slab kernel; 0: separate merge / reduction passes
-  int block_scope = 1;         // several ranks, FMA arithmetic: a solve whose first operand has neither runs nor a hidden band (a 3-D Hamiltonian) runs in the pattern's block order -- operands redistributed so that a rank owns a range of positions, panel products on the block path instead of the LDS hash (band_scope.cpp); 0: the operands as they are
-  int block_scope_complex = 1; // the same block-order scope for a COMPLEX first operand (a complex 3-D Hamiltonian on several ranks), where the complex block path multiplies on one rank (FMA arithmetic, complex_tile, block_complex, block_path): the order made from the moduli, complex panel products on k_bs_numeric_c (psmatrix.cpp multiply_panel); needs block_scope; 0: complex operands as they are
-  int block_match = 0;         // block path, an experiment (profiles/README.md 94): 1 = the matches of every candidate super-tile (the K with super-tiles on both sides) are found once, by a kernel of its own (k_bs_match), and read by the numeric kernel; 0: the numeric kernel searches itself.  Measured: no difference (37.4 against 37.2 iterations/s on the 64^3 lattice).  Results do not depend on it
-  int block_unfused = 0;       // the block path (spgemm_block.hip) in UNFUSED arithmetic too: products rounded, then added, on the vector units, in ascending POSITION of the block order -- the reference's default build on the matrix relabelled by that order (what its own load balancer does), 1e-13 of the sums over ascending labels.  0 (default): operands without runs keep the label-ordered kernels in unfused arithmetic, bit for bit the reference on the caller's labels
-  int panel_sessions = 1;      // slab sessions (TRS4, sign, inverse, square roots, polynomials ...) on more than one rank: the loops' matrices stay in slab form as column panels, a product exchanges the runs of the left operand's halo (psmatrix.cpp panel_slab_multiply); 0: compressed columns across ranks
-  int thin_slab_complex = 1;   // complex slab sessions (one rank and column panels across ranks): a product with a thin operand on the complex gather kernels of spgemm_thin.hip (the reference's own multiply-add, bit for bit) instead of the complex tile kernel; 0: every complex session product on the tile kernel; thin_left = 0 switches these off too
-  int complex_poly_sessions = 2;   // complex operands of the polynomial and function families (Horner, Paterson-Stockmeyer, the two Chebyshev evaluations, Hermite, the exponential's squarings, sine / cosine): 1: their loops open a complex slab session as the sign loop does (needs complex_sessions, FMA arithmetic, complex_tile; across ranks complex_panels); 2: and the two merges behind a product of the Chebyshev / Hermite recurrence are one kernel (slab_extra.hip slab_recurrence_step_c, the same values bit for bit); 0: compressed columns between the operations
-  int stored_zero_views = 1;   // an operand in compressed columns that STORES zero values (a Hamiltonian with a zero on its diagonal) enters a slab session as a read-only view (SlabForm::origin keeps the compressed columns, SlabForm::zlast the row of the last stored zero per column): complex operands as real ones already did, products / dots / norms read the runs, and a merge on a view is done in slab form wherever no stored zero of one operand lies beyond the other operand's last row (k_sa_axpby; otherwise that one merge runs on compressed columns and the view stays); copies and scalings keep the view.  0: complex operands with stored zeros are refused by slab_enter_c, real views refuse merges
-  int complex_panels = 1;      // complex loops (sign, inverse, square roots) on more than one rank: the iterates stay complex column panels in slab form, a product exchanges the complex runs of the left operand's halo (psmatrix.cpp panel_slab_multiply, complex tile kernel); needs panel_sessions and complex_sessions; 0: compressed columns across ranks
-  int complex_density = 1;     // complex TRS2 on one rank (FMA arithmetic, complex_tile, complex_sessions): the iterate stays out of compressed columns from step to step -- run-like iterates in complex slab form (X*X on the complex tile kernel, then the merge pass, then one energy / trace pass), iterates without runs in complex block form (block_complex, block_path: X*X on k_bs_numeric_c, the complex block merge, block_dot_trace) (psmatrix.cpp complex_trs2_step); 0: every complex density solve as before
-  int ghash_mfma = 1;          // grouped LDS-hash SpGEMM, real operands, FMA arithmetic: the products of a phase (four steps) as ONE v_mfma_f64_16x16x4_f64 per tile of 16 slots x 16 columns instead of 64 vector FMAs -- the same chain of fma() over ascending k, bit for bit; 0: vector units
-  int ghash_mfma_complex = 1;  // grouped LDS-hash SpGEMM, COMPLEX operands, FMA arithmetic with complex_tile (where complex products are a tolerance mode already): table class 0 (512 slots) on the matrix cores -- two v_mfma_f64_16x16x4_f64 per tile of 16 slots x 8 complex columns and phase, Re x against the interleaved multiplier row, Im x against the row with its parts swapped and the new real part negated; every part of an entry is the sum of two FMA chains over ascending k (1e-13 of the largest entry, as complex_tile and block_complex).  Classes 1 and 2 stay on the vector units (LDS).  0, unfused arithmetic or complex_tile = 0: the reference's complex multiply-add on the vector units, bit for bit
-  int pm_session = 1;          // PM purification, real operands, wherever a real slab session opens (one rank and column panels across ranks): the iterate stays in slab form, the scalars of sigma come from one pass over X and X2 without forming X - X2, the update a1 X + a2 X2 + a3 X3 is one pass over the three runs, and the stored zeros that compressed columns would carry (ScaleMatrix by a1 = 0 when sigma > 1/2, unfiltered tails) travel in a per-panel zero list next to the zero-free runs (slab_extra.hip k_pm_sigma / k_pm_update); 0: the loop on compressed columns, bit for bit as before
-  int isr_chain = 1;           // the Taylor square-root loop (InverseSquareRoot / SquareRoot, orders 5 and 3) inside a slab session, real operands and complex ones in a complex session, one rank and column panels: the vocabulary calls between the product X X and the next product (order 5: four merges that build Temp2 and Temp; order 3: two that build the new X) are ONE pass over the runs of X and X X (slab_extra.hip k_sa_isr_chain) -- the same values and patterns bit for bit, one host read-back instead of up to four; a step the kernel refuses runs the calls as before.  0: the calls, one by one
-  int hpcp_step = 1;           // HPCP purification, real operands, inside a real slab session (one rank and column panels across ranks): the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH with one read-back (slab_extra.hip k_hpcp_traces: the bits of two MatrixTrace calls), and the two merges into D1, the energy dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update: the values and patterns of the vocabulary calls at threshold 0 bit for bit; the energy is summed in another order and only feeds the convergence monitor) -- two read-backs per iteration instead of five; an update the kernel refuses runs the calls as before.  0: the eight calls, one by one
-  int scale_fold_step = 1;     // ScaleAndFold, real operands, inside a real slab session (one rank and column panels across ranks): behind the step's one product, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update: the values and pattern of the vocabulary calls at threshold 0 and the trace of slab_trace bit for bit; the energy is summed in another order and only feeds the convergence monitor); the scale branch, whose product's result is the new X, takes the energy and the trace from one pass over X and WH (k_saf_dot_trace) -- one read-back per step instead of two or three; a step the kernel refuses runs the calls as before.  0: the three calls, one by one
-  int complex_trs4 = 0;        // complex TRS4 on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and the second product's operand stay runs of (re, im) pairs between the products on the complex tile kernel --, the traces dot(X2, Fx) and dot(X2, Gx) come from ONE pass over X and X X without building Fx and Gx, the operand Fx + sigma Gx from a second one (slab_extra.hip k_sa_trs4<double2, .>: the real kernel's arithmetic on each part, the values and pattern of the four merges at threshold 0), and the energy Re dot(X, WH) from one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  0 (default; measured 4.51 against 10.62 ms per iteration on configs[4]'s operand, profiles/README.md 130, but the rule that decides defaults also wants option 0 and the parent commit equal within the block spread, which one run missed by a hair): the loop on compressed columns, bit for bit as before
-  int complex_hpcp = 0;        // complex HPCP on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- D1, DH and both products stay runs of (re, im) pairs between the products on the complex tile kernel --, the two traces behind sigma come from ONE pass over the diagonals of D1 DH and D1 D1 DH (slab_extra.hip k_hpcp_traces<double2>: the real parts), and the two merges into D1, the energy Re dot(D1, WH) and the next iteration's DH = I - D1 are ONE pass over the three runs and WH (k_hpcp_update<double2, .>: the real kernel's chain on each part of an entry, the values and patterns of the vocabulary calls at threshold 0); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of hpcp_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
-  int complex_pm = 0;          // complex PM on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X, X X and X X X stay runs of (re, im) pairs between the products on the complex tile kernel, the rows that compressed columns would hold as stored (0, 0) entries travel in the ZeroList beside a zero-free X, as in the real session --, sigma's trace and dot are ONE pass over X and X X (slab_extra.hip k_pm_sigma<double2>), the scaling and both merges at the solver's threshold another (k_pm_update<double2, ., 2>: the real kernel's rules on each part of an entry, the threshold on the modulus as the merge on compressed columns takes it), and the energy Re dot(X, WH) is one pass over X's runs and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses leaves the fused path for the rest of the solve, as the real session does; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of pm_session, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
-  int complex_scale_fold = 0;  // complex ScaleAndFold on one rank (FMA arithmetic, complex_tile, complex_sessions, no process slices): the loop opens a complex slab session -- X and its square stay runs of (re, im) pairs around the one product on the complex tile kernel --, the fold branch's update x <- (2 alpha) x + (-alpha^2) x2, the energy Re dot(X, WH) and the NEXT step's trace(X) are ONE pass over the runs of X, X X and WH (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of the vocabulary calls at threshold 0, the trace with the bits of k_sa_dot_trace_c, which with the option on is also MatrixTrace of a complex slab-form matrix in a complex session), and the scale branch takes the energy and the trace from one pass over X and WH as it stands (k_sa_dot_trace_c); a pass the kernel refuses runs the vocabulary calls as before; iterates without runs stay in complex block form (block_complex), which the passes leave to the block algebra.  Independent of scale_fold_step, which is for real operands.  0 (default): the loop on compressed columns, bit for bit as before
-  int slab_transpose = 1;      // one rank, no process slices: TransposeMatrix of a square, zero-free slab form inside a slab session is a tiled transpose of the runs (slab_extra.hip k_tr_extents / k_tr_values: extents and counts by integer atomics, values through a padded LDS tile) and ConjugateMatrix of a complex one runs in place -- the result is a slab form again, the packed result the bits and pattern of transpose() (+ conjugate()) on compressed columns; with it PolarDecomposition opens a slab session as SignFunction does (1: real operands, results bit for bit those of 0; 2: also the complex session, the complex tile kernel's tolerance mode).  A transpose the pass refuses (extents far apart) runs on compressed columns.  0: everything on compressed columns, as before.  Default 1: Polar of a real band of N = 262 144 takes 5.17 against 14.97 ms per iteration of the call (profiles/README.md 135)
-  int tile_off32 = 1;          // MFMA tile kernel: the runs of the left operand read through a buffer resource with 32-bit offsets where they lie in ONE allocation below 4 GB (no halo): lanes outside a run get an out-of-range offset and the bounds check returns 0.0 -- four vector instructions per run load instead of seven; 0: 64-bit addresses everywhere
-  int tile_bbuf = 2;           // MFMA tile kernel: the multiplier tile of a block read from the runs of its columns through a buffer resource (operand below 4 GB): a row outside a run reads as 0.0 by the bounds check -- no branch and no 64-bit address per element (1); 2 (default): as PAIRS of rows, a wave per group of columns, where the operand's slots are padded to even rows -- a third of the requests; 0: per-element address selection
-  int plan_fused = 1;          // the maxima and prefix sums of a slab step's plan in ONE launch (k_slab_offsets: every workgroup sums what lies before its part itself) instead of four to seven; 0: separate launches
-  int exchange_ahead = 1;      // panel steps across ranks: a step prepares the NEXT step's exchange (extents all-gathered, counts, plan) from its result and reads it back with its own totals -- one host round trip per panel step (psmatrix.cpp PanelExchange); 0: two
-  int band_scope = 1;          // solvers on SEVERAL ranks, FMA arithmetic: an operand without run structure is searched for a hidden band once per solve, the operands are redistributed in the recovered order, the results carried back (band_scope.cpp).  2: in unfused arithmetic too (the results are then the reference's under its load balancer with that permutation, not its bits on the caller's labels); 0: never
-  int label_order = 1;         // TRS2 on one rank: an operand without run structure is searched for a hidden band (relabel.hip)
-                               // and, if there is one, the loop runs in that order with label-ordered arithmetic; 0: never
-  int label_rowoff = 1;        // label-ordered steps: the loop takes a step's multiplier row from its run record (no copy of
-                               // the tiles in step order); 0: the tiles are copied in step order before every launch
-  int loose_iterates = 1;      // TRS2 on one rank, real operands: the iterate X stays in the slots the update / the slab
-                               // kernel wrote it to between the steps (no compaction pass per iteration); 0: packed
-  int halo_overlap = 1;        // distributed multiply: 0 exchange then multiply, 1 overlap the exchange with the interior
-                               // columns when the halo is a sizeable part of the panel, 2 always split, 3 split even
-                               // with an empty halo (tests; also NTPOLY_AMD_HALO_OVERLAP in the environment)
-  int spgemm_variant = -1;     // numeric kernel: -1 automatic (register-slab kernels for run-like operands, real and complex,
-                               // geometry by the widest row window; else the column-pair kernel for real operands, one
-                               // column per wave for complex ones; LDS hash beyond 4096-row windows); 0 one column per wave
-                               // for everything (first generation); 3<MAXCH><NW> column-pair kernel with that geometry;
-                               // 400 register-slab kernel whenever it fits (also when its run-density test says no);
-                               // timing experiments on the three-slab real kernel: 401..404 ablations (WRONG results:
-                               // no slab loads / no multiplier loads / no arithmetic / cache-hot multipliers; compiled only
-                               // with -DNTP_ABLATIONS, NTPOLY_AMD_EXTRA_FLAGS of ntpoly_amd/_build.py -- the product library
-                               // runs the ordinary loop for these values), 405 plain
-                               // loop + rotating prefetch, 406 lean periods, 407 both (= the default loop), 408 / 409
-                               // two / three workgroups per CU, 410 plain loop and three slabs also for narrow windows;
-                               // 500 grouped LDS-hash kernel for every multiply the slab kernels do not take (automatic: when
-                               // at least half of the columns have row windows beyond the direct-mapped LDS kernels),
-                               // 501 never the grouped kernel (one column per wave LDS hash, the previous path)
+#define NTP_OPTION(name, dflt, env) int name = dflt;
+#include "options.inc"
+#undef NTP_OPTION
 };
+// ... and as the one array that set, get and the environment walk go through (has_env: NTPOLY_AMD_<NAME> sets the field at start)
+struct OptionEntry {
+  const char* name;
+  int EngineOptions::*field;
+  bool has_env;
+};
+constexpr OptionEntry option_table[] = {   // (internal linkage: the library exports no symbol for it)
+#define NTP_OPTION_ENV true
+#define NTP_OPTION_NOENV false
+#define NTP_OPTION(name, dflt, env) {#name, &EngineOptions::name, NTP_OPTION_##env},
+#include "options.inc"
+#undef NTP_OPTION
+#undef NTP_OPTION_ENV
+#undef NTP_OPTION_NOENV
+};
+// read once, at the first call: the table's defaults, then the environment
 EngineOptions& options();
 SpgemmStats& last_spgemm_stats();
 // accumulated since reset: number of calls, products, algorithmic bytes, numeric-kernel ms
@@ -274,14 +193,8 @@ bool sa_readable_c(const DevMat& M);
 // (not_run_like: set when it refused because the columns are not run-like; allow_view false: an input with stored zeros is
 // refused as without option stored_zero_views, but keeps its chance to become a view later)
 bool slab_enter_c(DevMat& M, bool* not_run_like = nullptr, bool allow_view = true);
-// [4] since start: views built from compressed columns (real and complex); products with a view operand done in slab form;
-// merges / copies / scalings with a view operand done in slab form; merges on a view declined because the result would hold
-// a stored zero
-long long* slab_view_counts();
-// [4] since start: groups finished by the grouped LDS-hash kernel (spgemm_grouped.hip), by path: real operands on the matrix
-// cores (option ghash_mfma), real on the vector units, complex on the matrix cores (option ghash_mfma_complex, table class 0),
-// complex on the vector units
-long long* ghash_class_counts();
+long long* slab_view_counts();     // [4] views of operands with stored zeros (slots: counters.inc)
+long long* ghash_class_counts();   // [4] groups finished by the grouped LDS-hash kernel, by path (slots: counters.inc)
 // forgets everything the grouped path keeps between products (the kept column orders, the table class hints, the dimensions
 // whose next product goes to the grouped kernel first): which class a product starts in then no longer depends on the products
 // before it
@@ -437,14 +350,12 @@ bool find_band_order(const DevMat& A, DevBuf<int32_t>& newpos, int64_t* bandwidt
 int64_t column_span_sum(const DevMat& A);
 // order-independent fingerprint of a sparsity pattern (compressed columns)
 unsigned long long pattern_fingerprint_of(const DevMat& A);
-// since start: [0] steps computed with SlabFusion mode 1, [1] mode 2, [2] fused steps repeated on the unfused path
+// counters of the multiply paths (slots: counters.inc): fused TRS2 steps, complex TRS2 steps in slab or block form, the two-block
+// geometry, the tile-skip test (that one since the last reset_spgemm_accum)
 long long* fusion_counts();
-// since start: complex TRS2 steps done in complex slab or block form (product, merge and energy pass; not a fused tile epilogue) --
-// [0] X*X, [1] 2X - X*X, [2] steps that had to be repeated the old way
 long long* complex_fusion_counts();
-// [0] multiplies done in the two-block geometry (spgemm_tile2.hip), [1] launches of it that did not fit and were repeated on k_spgemm_tile
 long long* tile2_counts();
-long long* tile_skip_counts();   // [0] tiles the MFMA tile kernel tested against the operand's segment maxima, [1] tiles it skipped (option tile_skip), since the last reset_spgemm_accum
+long long* tile_skip_counts();
 long long& band_searches();   // searches for a bandwidth-reducing order since start (one per sparsity PATTERN: relabel_enter)
 
 // B <- alpha*A + B (AddSparseVectors semantics), same shape and scalar type.
@@ -580,9 +491,7 @@ void thin_rows_from_runs(bool cplx, const int32_t* first, const int32_t* last, c
 inline int slab_thin_rule(int64_t nnz_a, int64_t nnz_b, int64_t dim) {
   return (nnz_a <= 8 * dim && nnz_b >= nnz_a) ? 1 : (nnz_b <= 8 * dim) ? 2 : 0;
 }
-// since start: products of slab sessions on the gather kernels -- [0] real left, [1] real right, [2] complex left, [3] complex
-// right; of those, panel products: [4] real, [5] complex
-long long* thin_slab_counts();
+long long* thin_slab_counts();   // [6] products of slab sessions on the gather kernels (slots: counters.inc)
 // counts the operations that change the values of a matrix in place (scale, conjugate, ...): together with the serial
 // number of the value buffer's allocation it tells whether a cached derivative of a matrix is still that matrix
 unsigned long long matrix_value_epoch();

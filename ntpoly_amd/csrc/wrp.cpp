@@ -112,6 +112,12 @@ void local_print(const DevMat& m, const char* path) {
   else std::fflush(f);
 }
 std::unique_ptr<SlabSession> g_test_session;   // (ntpoly_amd_session_begin / _end: a diagnostic surface)
+// the field of options() that the option table (kernels.hpp option_table) lists under this name
+int& option_field(const char* name) {
+  for (const OptionEntry& o : option_table)
+    if (std::strcmp(o.name, name) == 0) return options().*o.field;
+  NTP_FATAL("unknown option " + std::string(name));
+}
 }  // namespace
 
 extern "C" {
@@ -154,108 +160,16 @@ void ntpoly_amd_panel_exchange_layout(const int* dim, const int* nranks, const i
   panel_exchange_layout(*dim, *nranks, *me, reinterpret_cast<const int64_t*>(req), reinterpret_cast<const int64_t*>(cnt), sa, sb,
                         reinterpret_cast<int64_t*>(soff), ra, rb, reinterpret_cast<int64_t*>(zoff));
 }
-void ntpoly_amd_set_option(const char* name, const int* value) {
-  const std::string n(name);
-  if (n == "spgemm_force_bin") options().spgemm_force_bin = *value;
-  else if (n == "increment_force_seq") options().increment_force_seq = *value;
-  else if (n == "spgemm_fma") options().spgemm_fma = *value;
-  else if (n == "plan_ahead") options().plan_ahead = *value;
-  else if (n == "slab_algebra") options().slab_algebra = *value;
-  else if (n == "operand_cache") options().operand_cache = *value;
-  else if (n == "tile_rows") options().tile_rows = *value;
-  else if (n == "tile_waves") options().tile_waves = *value;
-  else if (n == "time_kernels") options().time_kernels = *value;
-  else if (n == "spgemm_variant") options().spgemm_variant = *value;
-  else if (n == "halo_overlap") options().halo_overlap = *value;
-  else if (n == "load_balance") options().load_balance = *value;
-  else if (n == "virtual_grid") options().virtual_grid = *value;
-  else if (n == "loose_iterates") options().loose_iterates = *value;
-  else if (n == "fused_update") options().fused_update = *value;
-  else if (n == "label_order") options().label_order = *value;
-  else if (n == "band_scope") options().band_scope = *value;
-  else if (n == "exchange_ahead") options().exchange_ahead = *value;
-  else if (n == "plan_fused") options().plan_fused = *value;
-  else if (n == "tile_off32") options().tile_off32 = *value;
-  else if (n == "tile_bbuf") options().tile_bbuf = *value;
-  else if (n == "ghash_mfma") options().ghash_mfma = *value;
-  else if (n == "ghash_mfma_complex") options().ghash_mfma_complex = *value;
-  else if (n == "block_unfused") options().block_unfused = *value;
-  else if (n == "block_match") options().block_match = *value;
-  else if (n == "block_scope") options().block_scope = *value;
-  else if (n == "block_scope_complex") options().block_scope_complex = *value;
-  else if (n == "panel_sessions") options().panel_sessions = *value;
-  else if (n == "complex_panels") options().complex_panels = *value;
-  else if (n == "complex_density") options().complex_density = *value;
-  else if (n == "label_rowoff") options().label_rowoff = *value;
-  else if (n == "block_path") options().block_path = *value;
-  else if (n == "tile_runs_only") options().tile_runs_only = *value;
-  else if (n == "tile2") options().tile2 = *value;
-  else if (n == "tile_skip") options().tile_skip = *value;
-  else if (n == "complex_tile") options().complex_tile = *value;
-  else if (n == "block_complex") options().block_complex = *value;
-  else if (n == "thin_left") options().thin_left = *value;
-  else if (n == "thin_slab_complex") options().thin_slab_complex = *value;
-  else if (n == "complex_poly_sessions") options().complex_poly_sessions = *value;
-  else if (n == "stored_zero_views") options().stored_zero_views = *value;
-  else if (n == "pm_session") options().pm_session = *value;
-  else if (n == "complex_pm") options().complex_pm = *value;
-  else if (n == "isr_chain") options().isr_chain = *value;
-  else if (n == "slab_transpose") options().slab_transpose = *value;
-  else if (n == "hpcp_step") options().hpcp_step = *value;
-  else if (n == "scale_fold_step") options().scale_fold_step = *value;
-  else if (n == "complex_trs4") options().complex_trs4 = *value;
-  else if (n == "complex_hpcp") options().complex_hpcp = *value;
-  else if (n == "complex_scale_fold") options().complex_scale_fold = *value;
-  else if (n == "column_fused") options().column_fused = *value;
-  else if (n == "complex_sessions") options().complex_sessions = *value;
-  else NTP_FATAL("unknown option " + n);
-}
-// the current value of the options a caller may want to report (bench.py prints the arithmetic a drop-in caller gets)
-int ntpoly_amd_get_option(const char* name) {
-  const std::string n(name);
-  if (n == "spgemm_fma") return options().spgemm_fma;
-  if (n == "slab_algebra") return options().slab_algebra;
-  if (n == "plan_ahead") return options().plan_ahead;
-  if (n == "tile_rows") return options().tile_rows;
-  if (n == "tile2") return options().tile2;
-  if (n == "tile_skip") return options().tile_skip;
-  if (n == "block_path") return options().block_path;
-  if (n == "label_order") return options().label_order;
-  if (n == "band_scope") return options().band_scope;
-  if (n == "exchange_ahead") return options().exchange_ahead;
-  if (n == "plan_fused") return options().plan_fused;
-  if (n == "tile_off32") return options().tile_off32;
-  if (n == "tile_bbuf") return options().tile_bbuf;
-  if (n == "ghash_mfma") return options().ghash_mfma;
-  if (n == "ghash_mfma_complex") return options().ghash_mfma_complex;
-  if (n == "block_unfused") return options().block_unfused;
-  if (n == "block_match") return options().block_match;
-  if (n == "block_scope") return options().block_scope;
-  if (n == "block_scope_complex") return options().block_scope_complex;
-  if (n == "panel_sessions") return options().panel_sessions;
-  if (n == "complex_panels") return options().complex_panels;
-  if (n == "complex_density") return options().complex_density;
-  if (n == "fused_update") return options().fused_update;
-  if (n == "loose_iterates") return options().loose_iterates;
-  if (n == "complex_tile") return options().complex_tile;
-  if (n == "block_complex") return options().block_complex;
-  if (n == "thin_left") return options().thin_left;
-  if (n == "thin_slab_complex") return options().thin_slab_complex;
-  if (n == "complex_poly_sessions") return options().complex_poly_sessions;
-  if (n == "stored_zero_views") return options().stored_zero_views;
-  if (n == "pm_session") return options().pm_session;
-  if (n == "complex_pm") return options().complex_pm;
-  if (n == "isr_chain") return options().isr_chain;
-  if (n == "slab_transpose") return options().slab_transpose;
-  if (n == "hpcp_step") return options().hpcp_step;
-  if (n == "scale_fold_step") return options().scale_fold_step;
-  if (n == "complex_trs4") return options().complex_trs4;
-  if (n == "complex_hpcp") return options().complex_hpcp;
-  if (n == "complex_scale_fold") return options().complex_scale_fold;
-  if (n == "column_fused") return options().column_fused;
-  if (n == "complex_sessions") return options().complex_sessions;
-  NTP_FATAL("unknown option " + n);
-}
+// every option of csrc/options.inc by its name; an unknown name is fatal
+void ntpoly_amd_set_option(const char* name, const int* value) { option_field(name) = *value; }
+// the current value of an option (bench.py prints the arithmetic a drop-in caller gets)
+int ntpoly_amd_get_option(const char* name) { return option_field(name); }
+// ntpoly_amd_<name>_counts(out) for every entry of csrc/counters.inc, where the slots are documented
+#define NTP_COUNTER(name, N, accessor) \
+  void ntpoly_amd_##name##_counts(long long out[N]) { std::copy_n(accessor(), N, out); }
+#include "counters.inc"
+#undef NTP_COUNTER
+// (not in counters.inc: fields of a struct and two timings, not a counter array)
 // statistics of the last SpGEMM: out[0..12]: nnzA, nnzB, nnzC, products, tmp_entries, bins[6], overflow, slab kernel used
 void ntpoly_amd_last_spgemm_stats(long long* out, float* ms_numeric, float* ms_total) {
   flush_spgemm_timers();
@@ -267,6 +181,7 @@ void ntpoly_amd_last_spgemm_stats(long long* out, float* ms_numeric, float* ms_t
   *ms_numeric = s.ms_numeric;
   *ms_total = s.ms_total;
 }
+// (not in counters.inc: fields of the same struct and a ratio)
 // grouped LDS-hash path of the last SpGEMM: out[0..5] = used, columns handed back to the per-column kernels, groups,
 // table class, min-hash clustering used, steps (sum of the groups' row unions of B); ratio = steps / (nnz(B) / columns per group)
 void ntpoly_amd_last_grouped_stats(long long* out, double* ratio) {
@@ -275,23 +190,11 @@ void ntpoly_amd_last_grouped_stats(long long* out, double* ratio) {
   out[5] = s.gh_tile_rows;
   *ratio = s.gh_union_ratio;
 }
-// groups finished by the grouped LDS-hash kernel since start, by path: out[0] real operands on the matrix cores (option
-// ghash_mfma), [1] real on the vector units, [2] complex on the matrix cores (option ghash_mfma_complex: table class 0 in FMA
-// arithmetic with complex_tile), [3] complex on the vector units
-void ntpoly_amd_ghash_class_counts(long long out[4]) {
-  for (int q = 0; q < 4; ++q) out[q] = ghash_class_counts()[q];
-}
 // forgets what the grouped path keeps between products (kept column orders, table class hints, "grouped kernel first"
 // dimensions): the class a product starts in then does not depend on earlier products of the process
 void ntpoly_amd_drop_grouped_caches() { drop_grouped_caches(); }
 // 1: the last SpGEMM ran on the thin-left kernel (spgemm_thin.hip)
 int ntpoly_amd_last_spgemm_thin() { return last_spgemm_stats().thin; }
-// products of slab sessions computed by the thin-operand gather kernels (spgemm_thin.hip) since start: out[0] real, thin left
-// operand; [1] real, thin right; [2] complex left; [3] complex right; of those, panel products (slab sessions on several
-// ranks): [4] real, [5] complex
-void ntpoly_amd_thin_slab_counts(long long* out) {
-  for (int q = 0; q < 6; ++q) out[q] = thin_slab_counts()[q];
-}
 // DIAGNOSTIC surface (like ntpoly_amd_trs2_step): a session of the kind the solver loops open (engine.hpp SlabSession), held
 // open across the vocabulary calls that follow -- MatrixMultiply, IncrementMatrix, ScaleMatrix, CopyMatrix keep their
 // matrices in slab form between the calls; *complex_ok != 0: complex operands too, which the one-call sessions of the C ABI
@@ -308,13 +211,6 @@ void ntpoly_amd_session_end() { g_test_session.reset(); }
 int ntpoly_amd_recurrence_step(const int* ih_P, const int* ih_Tkm2, int* ih_Tk, int* ih_R, const double* a, const double* c) {
   return ps_recurrence_step(*get_unpacked(ih_P), *get_unpacked(ih_Tkm2), *get_unpacked(ih_Tk), *get_unpacked(ih_R), *a, *c) ? 1 : 0;
 }
-// The polynomial chain of the Taylor square-root step in one pass (option isr_chain; engine.hpp ps_isr_chain5 / ps_isr_chain3) since
-// start: out[0] = order-5 chains fused, out[1] = order-3 chains fused, out[2] = chains refused (the vocabulary calls ran instead).
-// A step that never reaches the kernel's decision -- the option off, no session for the operands' kind, X and X X both in compressed
-// columns (unfused arithmetic near convergence), a labelled slab form -- is neither fused nor counted as refused
-void ntpoly_amd_isr_chain_counts(long long out[3]) {
-  for (int q = 0; q < 3; ++q) out[q] = isr_chain_counts()[q];
-}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: one fused chain on caller-held matrices X and X2 (what
 // the loop's product X X would be), real or -- in a session with complex_ok -- complex.  The two operands are brought into slab
 // form, the chain of *order (5 or 3) runs, the outputs are packed into the result handles: order 5: Out1 = (X2 + a X) + (X + b I)
@@ -324,26 +220,12 @@ int ntpoly_amd_isr_chain_step(const int* ih_X, const int* ih_X2, const int* orde
                               int* ih_Out1, int* ih_Out2) {
   return ps_isr_chain_step(*get_unpacked(ih_X), *get_unpacked(ih_X2), *order, *a, *b, *c, *get_unpacked(ih_Out1), *get_unpacked(ih_Out2)) ? 1 : 0;
 }
-// The transpose of a slab form (option slab_transpose; engine.hpp ps_transpose / ps_conjugate) since start: out[0] = transposes
-// done in slab form, out[1] = conjugations done in slab form, out[2] = transposes refused past the gates (extents far apart: that
-// one ran on compressed columns), out[3] = PolarDecomposition solves that ran in a slab session.  A gated operand -- no session,
-// several ranks, compressed columns, a view, a labelled form, block form -- counts nowhere
-void ntpoly_amd_slab_transpose_counts(long long out[4]) {
-  for (int q = 0; q < 4; ++q) out[q] = slab_transpose_counts()[q];
-}
 // DIAGNOSTIC surface, one rank: A is brought into slab form in a session of this call's own (a complex one where A is complex and
 // FMA arithmetic, complex_tile and complex_sessions allow it), the transpose pass runs on it -- *conjugate != 0: the conjugate
 // transpose -- and the PACKED result is installed in AT.  Returns 1, or 0 when gated or refused: AT is then as it was.  Does
 // not depend on option slab_transpose
 int ntpoly_amd_slab_transpose(const int* ih_A, int* ih_AT, const int* conjugate) {
   return ps_slab_transpose_step(*get<PSMatrix>(ih_A), *get<PSMatrix>(ih_AT), *conjugate != 0) ? 1 : 0;
-}
-// HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update)
-// since start: out[0] = trace passes fused, out[1] = updates fused, out[2] = updates refused (the vocabulary calls ran instead).  A
-// step that never reaches the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled
-// slab form, alignments that differ, a WH the dot cannot read as runs -- is neither fused nor counted as refused
-void ntpoly_amd_hpcp_step_counts(long long out[3]) {
-  for (int q = 0; q < 3; ++q) out[q] = hpcp_step_counts()[q];
 }
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: one fused HPCP update on caller-held real matrices D1, DDH
 // (what the loop's product D1 (I - D1) would be), D2DH (D1 DDH) and WH.  The operands are brought into slab form, the update runs,
@@ -355,29 +237,12 @@ int ntpoly_amd_hpcp_update_step(const int* ih_D1, const int* ih_DDH, const int* 
   return ps_hpcp_update_step(*get_unpacked(ih_D1), *get_unpacked(ih_DDH), *get_unpacked(ih_D2DH), *sigma, *get_unpacked(ih_WH),
                              *get_unpacked(ih_D1out), *get_unpacked(ih_DHout), energy) ? 1 : 0;
 }
-// Complex HPCP in a complex slab session (option complex_hpcp; engine.hpp ps_hpcp_traces / ps_hpcp_update on complex operands)
-// since start: out[0] = trace passes fused, out[1] = updates fused, out[2] = passes refused (the vocabulary calls ran instead).  A
-// pass that never reaches the kernel's decision -- the option off, no open complex session, several ranks, block form, a labelled
-// slab form, alignments that differ, a WH the dot cannot read as runs -- is neither fused nor counted as refused.  Real operands
-// count in ntpoly_amd_hpcp_step_counts only, complex ones here only.  With the option on, ntpoly_amd_hpcp_update_step takes four
-// complex matrices in a session with complex_ok: the chain on each part of an entry, *energy = the real part of DotMatrix
-void ntpoly_amd_complex_hpcp_counts(long long out[3]) {
-  for (int q = 0; q < 3; ++q) out[q] = complex_hpcp_counts()[q];
-}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: the fused trace pass of the HPCP loop on caller-held
 // matrices, real (option hpcp_step) or complex (option complex_hpcp).  Both are brought into slab form where they are; out[0] =
 // MatrixTrace(DDH), out[1] = MatrixTrace(D2DH) from one pass and one read-back.  Returns 1 when taken, 0 when refused or gated: out
 // is then as it was.
 int ntpoly_amd_hpcp_traces_step(const int* ih_DDH, const int* ih_D2DH, double out[2]) {
   return ps_hpcp_traces_step(*get_unpacked(ih_DDH), *get_unpacked(ih_D2DH), out) ? 1 : 0;
-}
-// ScaleAndFold with the update, the energy and the next step's trace in one pass (option scale_fold_step; engine.hpp ps_saf_update /
-// ps_saf_dot_trace) since start: out[0] = fold updates fused, out[1] = dot-and-trace passes fused (the scale branch), out[2] = passes
-// refused (the vocabulary calls ran instead).  A step that never reaches the kernel's decision -- the option off, no open real
-// session, a complex operand, block form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs -- is
-// neither fused nor counted as refused
-void ntpoly_amd_scale_fold_step_counts(long long out[3]) {
-  for (int q = 0; q < 3; ++q) out[q] = scale_fold_step_counts()[q];
 }
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: one fused fold update on caller-held real matrices X, X2
 // (what the loop's product X X would be) and WH.  The operands are brought into slab form, the pass runs, the new X is packed into
@@ -392,22 +257,6 @@ int ntpoly_amd_scale_fold_update_step(const int* ih_X, const int* ih_X2, const d
 int ntpoly_amd_scale_fold_dot_trace(const int* ih_X, const int* ih_WH, double* dot, double* trace) {
   return ps_saf_dot_trace_step(*get_unpacked(ih_X), *get_unpacked(ih_WH), dot, trace) ? 1 : 0;
 }
-// Complex ScaleAndFold in a complex slab session (option complex_scale_fold; engine.hpp ps_saf_update / ps_saf_dot_trace on complex
-// operands) since start: out[0] = fold updates fused, out[1] = dot-and-trace passes fused (the scale branch), out[2] = passes refused
-// (the vocabulary calls ran instead).  A pass that never reaches the kernel's decision -- the option off, no open complex session,
-// several ranks, block form, a labelled slab form, alignments that differ, a WH the dot cannot read -- is neither fused nor counted
-// as refused.  Real operands count in ntpoly_amd_scale_fold_step_counts only, complex ones here only.  With the option on, the two
-// diagnostics above take complex matrices in a session with complex_ok: *dot = the real part of DotMatrix, *trace = MatrixTrace
-void ntpoly_amd_complex_scale_fold_counts(long long out[3]) {
-  for (int q = 0; q < 3; ++q) out[q] = complex_scale_fold_counts()[q];
-}
-// Complex TRS4 in a complex slab session (option complex_trs4; engine.hpp ps_trs4_traces / ps_trs4_operand / ps_trs4_energy on
-// complex operands) since start: out[0] = trace passes fused, out[1] = operands Fx + sigma Gx fused, out[2] = energies fused, out[3] =
-// passes refused (the vocabulary calls ran instead).  A pass that never reaches the kernel's decision -- the option off, no open
-// complex session, several ranks, block form, a labelled slab form -- is neither fused nor counted as refused
-void ntpoly_amd_complex_trs4_counts(long long out[4]) {
-  for (int q = 0; q < 4; ++q) out[q] = complex_trs4_counts()[q];
-}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: TRS4's chain on caller-held matrices X and X2 (what the
 // loop's product X X would be), real or -- in a session with complex_ok and option complex_trs4 -- complex.  The two operands are
 // brought into slab form, *trace_fx = dot(X2, 4 X - 3 X2) and *trace_gx = dot(X2, I - 2 X + X2) (their real parts) come from the
@@ -421,21 +270,9 @@ int ntpoly_amd_trs4_chain_step(const int* ih_X, const int* ih_X2, const double* 
 int ntpoly_amd_trs4_energy(const int* ih_X, const int* ih_WH, double* energy) {
   return ps_trs4_energy_step(*get_unpacked(ih_X), *get_unpacked(ih_WH), energy) ? 1 : 0;
 }
-// PM purification on a slab-form iterate (option pm_session; engine.hpp ps_pm_sigma / ps_pm_update) since start: out[0] = sigma passes
-// fused, out[1] = updates fused, out[2] = stored zeros carried beside the runs (summed over the updates), out[3] = solves that left
-// the fused path
-void ntpoly_amd_pm_session_counts(long long out[4]) {
-  for (int q = 0; q < 4; ++q) out[q] = pm_session_counts()[q];
-}
-// the longest zero list an update of the fused PM loop has left on this rank since start (rows of one panel)
+// the longest zero list an update of the fused PM loop has left on this rank since start (rows of one panel).  Not in
+// counters.inc: it is the fifth slot of pm_session_counts(), a maximum, behind the four that ntpoly_amd_pm_session_counts gives
 void ntpoly_amd_pm_session_longest_list(long long* out) { *out = pm_session_counts()[4]; }
-// Complex PM in a complex slab session (option complex_pm; engine.hpp ps_pm_sigma / ps_pm_update on complex operands) since start:
-// out[0] = sigma passes fused, out[1] = updates fused, out[2] = stored (0, 0) entries carried beside the runs (summed over the
-// updates), out[3] = solves that left the fused path.  A solve that a gate keeps out -- the option off, several ranks, iterates in
-// block form -- counts nowhere.  Real operands count in ntpoly_amd_pm_session_counts only, complex ones here only
-void ntpoly_amd_complex_pm_counts(long long out[4]) {
-  for (int q = 0; q < 4; ++q) out[q] = complex_pm_counts()[q];
-}
 // DIAGNOSTIC surface (one rank; matrices all real, or -- option complex_pm, FMA arithmetic, complex_tile, complex_sessions -- X, X2
 // and X3 all complex: Out is then complex and Zout a pattern of stored (0, 0) entries; Z is read as a pattern, whatever its kind;
 // mixed kinds, or complex operands with the option at 0, return 0): one sigma pass and one update of the PM loop's fused path on
@@ -472,8 +309,10 @@ int ntpoly_amd_pm_fused_step(const int* ih_X, const int* ih_Z, const int* ih_X2,
   return 1;
 }
 // fused recurrence steps taken since start, by the Chebyshev / Hermite loops and by ntpoly_amd_recurrence_step (each is also
-// counted as the two merges it replaces in ntpoly_amd_slab_algebra_counts; a declined step counts nothing here)
+// counted as the two merges it replaces in ntpoly_amd_slab_algebra_counts; a declined step counts nothing here).  Not in
+// counters.inc: one number by value, not an array
 void ntpoly_amd_recurrence_step_count(long long* out) { *out = recurrence_step_count(); }
+// (not in counters.inc: fields of the same struct and a fill ratio)
 // block path of the last SpGEMM (spgemm_block.hip): out[0..2] = used, 16 x 16 x 16 tile products issued, candidate output
 // super-tiles; fill = entries / (256 tiles) of the left operand
 void ntpoly_amd_last_block_stats(long long* out, double* fill) {
@@ -503,6 +342,7 @@ int ntpoly_amd_block_order_of_pattern(const int* ih, int* position, int* ns) {
   *ns = s;
   return 1;
 }
+// (not in counters.inc: composed from a struct and the stream's own count)
 // out[0] = halo exchanges of distributed multiplies so far, out[1] = host synchronisations inside them (counted where the
 // host waits: sync_stream), out[2] = ALL host synchronisations of the process so far: a caller brackets a call with two
 // reads to learn what the whole call cost (exchange, plan, totals)
@@ -523,25 +363,7 @@ int ntpoly_amd_band_order(const int* ih, int* newpos, long long* bandwidth) {
   *bandwidth = bw;
   return 1;
 }
-// out[0..2]: purification steps computed inside the SpGEMM kernel's epilogue (X*X; 2X - X*X) and fused steps that had
-// to be repeated on the unfused path, since start
-void ntpoly_amd_fusion_counts(long long* out) {
-  for (int q = 0; q < 3; ++q) out[q] = fusion_counts()[q];
-}
-// out[0..2]: complex TRS2 steps done in complex slab or block form (X*X; 2X - X*X) and such steps repeated the old way, since start
-void ntpoly_amd_complex_fusion_counts(long long* out) {
-  for (int q = 0; q < 3; ++q) out[q] = complex_fusion_counts()[q];
-}
-// out[0] = multiplies computed in the two-block geometry of the MFMA kernel (spgemm_tile2.hip) since start, out[1] = launches
-// of it whose geometry did not fit after all and were repeated on k_spgemm_tile
-void ntpoly_amd_tile2_counts(long long* out) {
-  for (int q = 0; q < 2; ++q) out[q] = tile2_counts()[q];
-}
-// out[0] = tiles the MFMA tile kernel tested against the operand's segment maxima (option tile_skip), out[1] = tiles it skipped,
-// since the last ntpoly_amd_reset_spgemm_accum
-void ntpoly_amd_tile_skip_counts(long long* out) {
-  for (int q = 0; q < 2; ++q) out[q] = tile_skip_counts()[q];
-}
+// (not in counters.inc: a record of the last launch behind a count, read from a struct)
 // what the last launch of the MFMA tile kernel chose (spgemm_tile.hpp TileLaunchInfo): out[0] = launches since the last
 // ntpoly_amd_reset_spgemm_accum; of the last one out[1..8] = epi, waves per workgroup, rows per lane, label-aware, 32-bit
 // offsets, source of the multiplier tile (0 prepared tiles, 1 runs through 64-bit pointers, 2 runs through the buffer per
@@ -592,23 +414,11 @@ void ntpoly_amd_grid_comm_info(const int* ih_grid, int* out) {
   out[1] = g->total;
   out[2] = g->comm != nullptr ? 1 : 0;
 }
-// out[0] = solves that ran in a recovered band order across ranks (band_scope.cpp), out[1] = operands searched for one
-void ntpoly_amd_band_scope_counts(long long* out) {
-  for (int q = 0; q < 2; ++q) out[q] = band_scope_counts()[q];
-}
 // solves that ran in a BLOCK order across ranks (operands without runs or band: 3-D Hamiltonians), panel products of such
-// solves that took the block path
+// solves that took the block path.  Not in counters.inc: composed from two sources
 void ntpoly_amd_block_scope_counts(long long* out) {
   out[0] = band_scope_counts()[2];
   out[1] = block_scope_products();
-}
-// out[0..3]: operations the solver loops did on matrices in slab form since start (products, merges / copies, scalings
-// / dots / norms) and operations that had to go back to compressed columns
-// out[0] = vocabulary operations (copy, scale, merge, dot, trace, norm) done on matrices in block form, out[1] = fallbacks
-// [2] since start: identity increments done in place, norms of differences taken from the operands (column_fused.hip)
-void ntpoly_amd_column_fused_counts(long long* out) {
-  out[0] = column_fused_counts()[0];
-  out[1] = column_fused_counts()[1];
 }
 // tests: the two vocabulary operations of the solver loops that have no entry point of their own in the reference's C ABI --
 // IncrementMatrix(Identity, B, alpha) as the loops call it, and the norm of alpha A + beta B (returns 0 when the engine would
@@ -621,28 +431,8 @@ void ntpoly_amd_increment_identity(const int* ih_identity, int* ih_matB, const d
 int ntpoly_amd_norm_axpby(const int* ih_matA, const int* ih_matB, const double* alpha, const double* beta, double* norm) {
   return ps_norm_axpby(*get<PSMatrix>(ih_matA), *get<PSMatrix>(ih_matB), *alpha, *beta, norm) ? 1 : 0;
 }
-void ntpoly_amd_block_algebra_counts(long long* out) {
-  out[0] = block_algebra_counts()[0];
-  out[1] = block_algebra_counts()[1];
-}
-void ntpoly_amd_slab_algebra_counts(long long* out) {
-  for (int q = 0; q < 4; ++q) out[q] = slab_algebra_counts()[q];
-}
-// read-only slab views of operands with stored zeros (option stored_zero_views) since start: out[0] = views built from compressed
-// columns, out[1] = products with a view operand done in slab form, out[2] = merges / copies / scalings with a view operand done in
-// slab form, out[3] = merges on a view declined because the result would hold a stored zero (done on compressed columns instead)
-void ntpoly_amd_slab_view_counts(long long out[4]) {
-  for (int q = 0; q < 4; ++q) out[q] = slab_view_counts()[q];
-}
-// products of slab sessions on more than one rank since start: done in slab form on every rank, declined (compressed columns),
-// host synchronisations inside the former (measured)
-void ntpoly_amd_panel_product_counts(long long* out) {
-  out[0] = panel_product_counts()[0];
-  out[1] = panel_product_counts()[1];
-  out[2] = panel_product_counts()[2];
-}
 // searches for a bandwidth-reducing order since start: one per sparsity pattern, not per operand (the next cycle of an
-// SCF loop -- same pattern, other values -- reuses the order)
+// SCF loop -- same pattern, other values -- reuses the order).  Not in counters.inc: one number by value, not an array
 void ntpoly_amd_band_searches(long long* out) { *out = band_searches(); }
 void ntpoly_amd_reset_spgemm_accum() {
   flush_spgemm_timers();

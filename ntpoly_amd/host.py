@@ -922,33 +922,103 @@ def band_order(M):
     return (pos, int(bw.value)) if ok else None
 
 
-def fusion_counts():
-    """(steps X*X, steps 2X - X*X) computed inside the SpGEMM kernel's epilogue and fused steps repeated unfused"""
-    out = (C.c_longlong * 3)()
-    lib.ntpoly_amd_fusion_counts(out)
-    return dict(square=out[0], update=out[1], repeated=out[2])
+# The counter arrays of csrc/counters.inc: name -> (keys of the slots in the table's order, docstring[, tuple]).  Every entry
+# becomes <name>_counts(), which reads ntpoly_amd_<name>_counts and returns a dict under these keys (with `tuple`: the bare values).
+_COUNTERS = {
+    "fusion": (("square", "update", "repeated"),
+               """(steps X*X, steps 2X - X*X) computed inside the SpGEMM kernel's epilogue and fused steps repeated unfused"""),
+    "complex_fusion": (("square", "update", "repeated"),
+                       """complex TRS2 steps X*X and 2X - X*X done in complex slab or block form (product, merge and energy pass -- not a fused
+    tile epilogue), and such steps repeated the old way"""),
+    "tile2": (("done", "repeated"),
+              """(multiplies computed in the two-block geometry of the MFMA kernel, launches of it repeated on k_spgemm_tile)"""),
+    "tile_skip": (("tested", "skipped"),
+                  """(tiles the MFMA tile kernel tested against the operand's segment maxima, tiles it skipped) since reset_spgemm_accum""",
+                  tuple),
+    "band_scope": (("solves", "searched"),
+                   """(solves run in a recovered band order across ranks, operands searched for a hidden band)"""),
+    "slab_algebra": (("products", "merges", "others", "refusals"),
+                     """operations of the solver loops done on matrices in slab form since start, and those that went back to compressed columns"""),
+    "slab_view": (("built", "products", "taken", "declined"),
+                  """read-only slab views of operands that store zeros (option stored_zero_views) since start: views built from compressed
+    columns, products / merges-copies-scalings with a view operand done in slab form, merges on a view declined because the
+    result would hold a stored zero"""),
+    "ghash_class": (("real_mfma", "real_vector", "complex_mfma", "complex_vector"),
+                    """groups finished by the grouped LDS-hash kernel (csrc/spgemm_grouped.hip) since start, by path: real operands on the matrix
+    cores (option ghash_mfma) / on the vector units, complex operands on the matrix cores (option ghash_mfma_complex: table class 0
+    in FMA arithmetic with complex_tile, two FMA chains per part of an entry) / on the vector units"""),
+    "panel_product": (("slab", "declined", "host_syncs"),
+                      """products of slab sessions on more than one rank since start: done in slab form on every rank, declined"""),
+    "thin_slab": (("real_left", "real_right", "complex_left", "complex_right", "panel_real", "panel_complex"),
+                  """products of slab sessions on the thin-operand gather kernels (csrc/spgemm_thin.hip) since start: real / complex, thin left /
+    right operand; of those, the panel products (slab sessions on several ranks), real and complex"""),
+    "pm_session": (("sigma", "updates", "zeros", "left"),
+                   """PM purification on a slab-form iterate (option pm_session; csrc/slab_extra.hip) since start: sigma passes fused, updates fused,
+    stored zeros carried beside the runs (summed over the updates), solves that left the fused path"""),
+    "complex_pm": (("sigma", "updates", "zeros", "left"),
+                   """complex PM in a complex slab session (option complex_pm; csrc/slab_extra.hip k_pm_sigma / k_pm_update on runs of (re, im)
+    pairs) since start: sigma passes fused, updates fused, stored (0, 0) entries carried beside the runs (summed over the updates),
+    solves that left the fused path; slab_algebra_counts() counts a fused pass as the real branch does.  A solve kept out by a gate
+    (the option off, several ranks, iterates in block form) counts nowhere; real operands count in pm_session_counts() only"""),
+    "isr_chain": (("order5", "order3", "refused"),
+                  """the polynomial chain of the Taylor square-root step in one pass (option isr_chain; csrc/slab_extra.hip k_sa_isr_chain) since
+    start: order-5 chains fused, order-3 chains fused, chains refused (the vocabulary calls ran instead); slab_algebra_counts()
+    counts a fused chain as the four / two merges it replaces.  A step kept out by a gate (the option off, no session for the
+    operands' kind, X and X X both in compressed columns, a labelled slab form) is neither fused nor counted as refused"""),
+    "slab_transpose": (("transposes", "conjugates", "refused", "polar_sessions"),
+                       """the transpose of a slab form (option slab_transpose; csrc/slab_extra.hip k_tr_extents / k_tr_values) since start: transposes
+    done in slab form, conjugations done in slab form, transposes refused past the gates (extents far apart: that one ran on
+    compressed columns), PolarDecomposition solves that ran in a slab session.  A gated operand (no session, several ranks,
+    compressed columns, a view, a labelled form, block form) counts nowhere"""),
+    "hpcp_step": (("traces", "updates", "refused"),
+                  """HPCP purification with its traces and its update in one pass each (option hpcp_step; csrc/slab_extra.hip k_hpcp_traces /
+    k_hpcp_update) since start: trace passes fused, updates fused, updates refused (the vocabulary calls ran instead);
+    slab_algebra_counts() counts a fused update as the four merges / copies and the two other operations it replaces.  A step kept
+    out by a gate (the option off, no open real session, a complex operand, block form, a labelled slab form, alignments that
+    differ, a WH the dot cannot read as runs) is neither fused nor counted as refused"""),
+    "complex_hpcp": (("traces", "updates", "refused"),
+                     """complex HPCP in a complex slab session (option complex_hpcp; csrc/slab_extra.hip k_hpcp_traces / k_hpcp_update on runs of
+    (re, im) pairs) since start: trace passes fused, updates fused, passes refused (the vocabulary calls ran instead);
+    slab_algebra_counts() counts a fused pass as the real branch does.  A pass kept out by a gate (the option off, no open complex
+    session, several ranks, block form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs) is neither
+    fused nor counted as refused; real operands count in hpcp_step_counts() only"""),
+    "scale_fold_step": (("updates", "dot_traces", "refused"),
+                        """ScaleAndFold with the update, the energy and the next step's trace in one pass (option scale_fold_step; csrc/slab_extra.hip
+    k_saf_update / k_saf_dot_trace) since start: fold updates fused, dot-and-trace passes fused (the scale branch), passes refused
+    (the vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the calls it replaces (the merge of an
+    update, the dot, the next trace).  A step kept out by a gate (the option off, no open real session, a complex operand, block
+    form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs) is neither fused nor counted as refused"""),
+    "complex_scale_fold": (("updates", "dot_traces", "refused"),
+                           """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
+    pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
+    vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the real branch does.  A pass kept out by a gate (the
+    option off, no open complex session, several ranks, block form, a labelled slab form, alignments that differ, a WH the dot
+    cannot read) is neither fused nor counted as refused; real operands count in scale_fold_step_counts() only"""),
+    "complex_trs4": (("traces", "operands", "energies", "refused"),
+                     """complex TRS4 in a complex slab session (option complex_trs4; csrc/slab_extra.hip k_sa_trs4<double2, .>) since start: trace passes
+    fused, operands Fx + sigma Gx fused, energies fused, passes refused (the vocabulary calls ran instead); slab_algebra_counts()
+    counts a fused pass as the real branch does.  A pass kept out by a gate (the option off, no open complex session, several
+    ranks, block form, a labelled slab form) is neither fused nor counted as refused"""),
+    "column_fused": (("identity_in_place", "norms_of_differences"),
+                     """operations on compressed columns done without the merge pass (csrc/column_fused.hip) since start"""),
+    "block_algebra": (("operations", "fallbacks"),
+                      """(operations of solver loops / C-ABI loops done on matrices in block form, fallbacks to compressed columns)"""),
+}
 
 
-def complex_fusion_counts():
-    """complex TRS2 steps X*X and 2X - X*X done in complex slab or block form (product, merge and energy pass -- not a fused
-    tile epilogue), and such steps repeated the old way"""
-    out = (C.c_longlong * 3)()
-    lib.ntpoly_amd_complex_fusion_counts(out)
-    return dict(square=out[0], update=out[1], repeated=out[2])
+def _define_counter(name, keys, doc, kind=dict):
+    def read():
+        out = (C.c_longlong * len(keys))()
+        getattr(lib, "ntpoly_amd_%s_counts" % name)(out)
+        values = [int(v) for v in out]
+        return tuple(values) if kind is tuple else dict(zip(keys, values))
+    read.__name__ = read.__qualname__ = name + "_counts"
+    read.__doc__ = doc
+    globals()[read.__name__] = read
 
 
-def tile2_counts():
-    """(multiplies computed in the two-block geometry of the MFMA kernel, launches of it repeated on k_spgemm_tile)"""
-    out = (C.c_longlong * 2)()
-    lib.ntpoly_amd_tile2_counts(out)
-    return dict(done=out[0], repeated=out[1])
-
-
-def tile_skip_counts():
-    """(tiles the MFMA tile kernel tested against the operand's segment maxima, tiles it skipped) since reset_spgemm_accum"""
-    out = (C.c_longlong * 2)()
-    lib.ntpoly_amd_tile_skip_counts(out)
-    return (int(out[0]), int(out[1]))
+for _name, _entry in _COUNTERS.items():
+    _define_counter(_name, *_entry)
 
 
 def last_tile_launch():
@@ -961,13 +1031,6 @@ def last_tile_launch():
     lib.ntpoly_amd_last_tile_launch(out)
     names = ("launches", "epi", "nw", "rows", "labelled", "off32", "bsrc", "max_kn", "skip")
     return {k: int(out[q]) for q, k in enumerate(names)}
-
-
-def band_scope_counts():
-    """(solves run in a recovered band order across ranks, operands searched for a hidden band)"""
-    out = (C.c_longlong * 2)()
-    lib.ntpoly_amd_band_scope_counts(out)
-    return dict(solves=out[0], searched=out[1])
 
 
 def block_scope_counts():
@@ -984,50 +1047,10 @@ def band_searches():
     return int(out.value)
 
 
-def slab_algebra_counts():
-    """operations of the solver loops done on matrices in slab form since start, and those that went back to compressed columns"""
-    out = (C.c_longlong * 4)()
-    lib.ntpoly_amd_slab_algebra_counts(out)
-    return dict(products=out[0], merges=out[1], others=out[2], refusals=out[3])
-
-
-def slab_view_counts():
-    """read-only slab views of operands that store zeros (option stored_zero_views) since start: views built from compressed
-    columns, products / merges-copies-scalings with a view operand done in slab form, merges on a view declined because the
-    result would hold a stored zero"""
-    out = (C.c_longlong * 4)()
-    lib.ntpoly_amd_slab_view_counts(out)
-    return dict(built=out[0], products=out[1], taken=out[2], declined=out[3])
-
-
-def ghash_class_counts():
-    """groups finished by the grouped LDS-hash kernel (csrc/spgemm_grouped.hip) since start, by path: real operands on the matrix
-    cores (option ghash_mfma) / on the vector units, complex operands on the matrix cores (option ghash_mfma_complex: table class 0
-    in FMA arithmetic with complex_tile, two FMA chains per part of an entry) / on the vector units"""
-    out = (C.c_longlong * 4)()
-    lib.ntpoly_amd_ghash_class_counts(out)
-    return dict(real_mfma=out[0], real_vector=out[1], complex_mfma=out[2], complex_vector=out[3])
-
-
 def drop_grouped_caches():
     """forget what the grouped LDS-hash path keeps between products (the kept column orders, the table class hints, the dimensions
     whose next product goes to the grouped kernel first): the class a product starts in then does not depend on earlier products"""
     lib.ntpoly_amd_drop_grouped_caches()
-
-
-def panel_product_counts():
-    """products of slab sessions on more than one rank since start: done in slab form on every rank, declined"""
-    out = (C.c_longlong * 3)()
-    lib.ntpoly_amd_panel_product_counts(out)
-    return dict(slab=out[0], declined=out[1], host_syncs=out[2])
-
-
-def thin_slab_counts():
-    """products of slab sessions on the thin-operand gather kernels (csrc/spgemm_thin.hip) since start: real / complex, thin left /
-    right operand; of those, the panel products (slab sessions on several ranks), real and complex"""
-    out = (C.c_longlong * 6)()
-    lib.ntpoly_amd_thin_slab_counts(out)
-    return dict(real_left=out[0], real_right=out[1], complex_left=out[2], complex_right=out[3], panel_real=out[4], panel_complex=out[5])
 
 
 @contextlib.contextmanager
@@ -1058,29 +1081,11 @@ def recurrence_step_count():
     return int(out.value)
 
 
-def pm_session_counts():
-    """PM purification on a slab-form iterate (option pm_session; csrc/slab_extra.hip) since start: sigma passes fused, updates fused,
-    stored zeros carried beside the runs (summed over the updates), solves that left the fused path"""
-    out = (C.c_longlong * 4)()
-    lib.ntpoly_amd_pm_session_counts(out)
-    return dict(sigma=int(out[0]), updates=int(out[1]), zeros=int(out[2]), left=int(out[3]))
-
-
 def pm_session_longest_list():
     """the longest zero list an update of the fused PM loop has left on this rank since start"""
     out = C.c_longlong()
     lib.ntpoly_amd_pm_session_longest_list(C.byref(out))
     return int(out.value)
-
-
-def complex_pm_counts():
-    """complex PM in a complex slab session (option complex_pm; csrc/slab_extra.hip k_pm_sigma / k_pm_update on runs of (re, im)
-    pairs) since start: sigma passes fused, updates fused, stored (0, 0) entries carried beside the runs (summed over the updates),
-    solves that left the fused path; slab_algebra_counts() counts a fused pass as the real branch does.  A solve kept out by a gate
-    (the option off, several ranks, iterates in block form) counts nowhere; real operands count in pm_session_counts() only"""
-    out = (C.c_longlong * 4)()
-    lib.ntpoly_amd_complex_pm_counts(out)
-    return dict(sigma=int(out[0]), updates=int(out[1]), zeros=int(out[2]), left=int(out[3]))
 
 
 def pm_fused_step(X, Z, X2, X3, a1, a2, a3, thr, Out, Zout):
@@ -1094,16 +1099,6 @@ def pm_fused_step(X, Z, X2, X3, a1, a2, a3, thr, Out, Zout):
     return (sc[0], sc[1]) if ok else None
 
 
-def isr_chain_counts():
-    """the polynomial chain of the Taylor square-root step in one pass (option isr_chain; csrc/slab_extra.hip k_sa_isr_chain) since
-    start: order-5 chains fused, order-3 chains fused, chains refused (the vocabulary calls ran instead); slab_algebra_counts()
-    counts a fused chain as the four / two merges it replaces.  A step kept out by a gate (the option off, no session for the
-    operands' kind, X and X X both in compressed columns, a labelled slab form) is neither fused nor counted as refused"""
-    out = (C.c_longlong * 3)()
-    lib.ntpoly_amd_isr_chain_counts(out)
-    return dict(order5=int(out[0]), order3=int(out[1]), refused=int(out[2]))
-
-
 def isr_chain_step(X, X2, order, a, b, c, Out1, Out2):
     """DIAGNOSTIC, inside `with solver_session():` -- one fused chain of the square-root step on caller-held matrices (X2: what the
     product X X would be).  Order 5: Out1 = (X2 + a X) + (X + b I), Out2 = (X2 + a X) + c I; order 3: Out1 = 0.375 X2 + (I - X / 2),
@@ -1113,33 +1108,12 @@ def isr_chain_step(X, X2, order, a, b, c, Out1, Out2):
     return True if ok else None
 
 
-def slab_transpose_counts():
-    """the transpose of a slab form (option slab_transpose; csrc/slab_extra.hip k_tr_extents / k_tr_values) since start: transposes
-    done in slab form, conjugations done in slab form, transposes refused past the gates (extents far apart: that one ran on
-    compressed columns), PolarDecomposition solves that ran in a slab session.  A gated operand (no session, several ranks,
-    compressed columns, a view, a labelled form, block form) counts nowhere"""
-    out = (C.c_longlong * 4)()
-    lib.ntpoly_amd_slab_transpose_counts(out)
-    return dict(transposes=int(out[0]), conjugates=int(out[1]), refused=int(out[2]), polar_sessions=int(out[3]))
-
-
 def slab_transpose(A, AT, conjugate=False):
     """DIAGNOSTIC, one rank -- A is brought into slab form in a session of the call's own, the transpose pass runs on it (conjugate:
     the conjugate transpose) and the PACKED result is installed in AT.  True: taken; None: gated or refused, AT as it was."""
     lib.ntpoly_amd_slab_transpose.restype = C.c_int
     ok = lib.ntpoly_amd_slab_transpose(A.ih, AT.ih, C.byref(C.c_int(1 if conjugate else 0)))
     return True if ok else None
-
-
-def hpcp_step_counts():
-    """HPCP purification with its traces and its update in one pass each (option hpcp_step; csrc/slab_extra.hip k_hpcp_traces /
-    k_hpcp_update) since start: trace passes fused, updates fused, updates refused (the vocabulary calls ran instead);
-    slab_algebra_counts() counts a fused update as the four merges / copies and the two other operations it replaces.  A step kept
-    out by a gate (the option off, no open real session, a complex operand, block form, a labelled slab form, alignments that
-    differ, a WH the dot cannot read as runs) is neither fused nor counted as refused"""
-    out = (C.c_longlong * 3)()
-    lib.ntpoly_amd_hpcp_step_counts(out)
-    return dict(traces=int(out[0]), updates=int(out[1]), refused=int(out[2]))
 
 
 def hpcp_update_step(D1, DDH, D2DH, sigma, WH, D1out, DHout):
@@ -1153,17 +1127,6 @@ def hpcp_update_step(D1, DDH, D2DH, sigma, WH, D1out, DHout):
     return float(e.value) if ok else None
 
 
-def complex_hpcp_counts():
-    """complex HPCP in a complex slab session (option complex_hpcp; csrc/slab_extra.hip k_hpcp_traces / k_hpcp_update on runs of
-    (re, im) pairs) since start: trace passes fused, updates fused, passes refused (the vocabulary calls ran instead);
-    slab_algebra_counts() counts a fused pass as the real branch does.  A pass kept out by a gate (the option off, no open complex
-    session, several ranks, block form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs) is neither
-    fused nor counted as refused; real operands count in hpcp_step_counts() only"""
-    out = (C.c_longlong * 3)()
-    lib.ntpoly_amd_complex_hpcp_counts(out)
-    return dict(traces=int(out[0]), updates=int(out[1]), refused=int(out[2]))
-
-
 def hpcp_traces_step(DDH, D2DH):
     """DIAGNOSTIC, inside `with solver_session():` -- the fused trace pass of the HPCP loop on caller-held matrices, real (option
     hpcp_step) or complex (option complex_hpcp): returns (trace(DDH), trace(D2DH)) from one pass; None: refused or gated."""
@@ -1171,17 +1134,6 @@ def hpcp_traces_step(DDH, D2DH):
     lib.ntpoly_amd_hpcp_traces_step.restype = C.c_int
     ok = lib.ntpoly_amd_hpcp_traces_step(DDH.ih, D2DH.ih, out)
     return (float(out[0]), float(out[1])) if ok else None
-
-
-def scale_fold_step_counts():
-    """ScaleAndFold with the update, the energy and the next step's trace in one pass (option scale_fold_step; csrc/slab_extra.hip
-    k_saf_update / k_saf_dot_trace) since start: fold updates fused, dot-and-trace passes fused (the scale branch), passes refused
-    (the vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the calls it replaces (the merge of an
-    update, the dot, the next trace).  A step kept out by a gate (the option off, no open real session, a complex operand, block
-    form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs) is neither fused nor counted as refused"""
-    out = (C.c_longlong * 3)()
-    lib.ntpoly_amd_scale_fold_step_counts(out)
-    return dict(updates=int(out[0]), dot_traces=int(out[1]), refused=int(out[2]))
 
 
 def scale_fold_update_step(X, X2, a, b, WH, Xout):
@@ -1204,27 +1156,6 @@ def scale_fold_dot_trace(X, WH):
     lib.ntpoly_amd_scale_fold_dot_trace.restype = C.c_int
     ok = lib.ntpoly_amd_scale_fold_dot_trace(X.ih, WH.ih, C.byref(dot), C.byref(tr))
     return (float(dot.value), float(tr.value)) if ok else None
-
-
-def complex_scale_fold_counts():
-    """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
-    pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
-    vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the real branch does.  A pass kept out by a gate (the
-    option off, no open complex session, several ranks, block form, a labelled slab form, alignments that differ, a WH the dot
-    cannot read) is neither fused nor counted as refused; real operands count in scale_fold_step_counts() only"""
-    out = (C.c_longlong * 3)()
-    lib.ntpoly_amd_complex_scale_fold_counts(out)
-    return dict(updates=int(out[0]), dot_traces=int(out[1]), refused=int(out[2]))
-
-
-def complex_trs4_counts():
-    """complex TRS4 in a complex slab session (option complex_trs4; csrc/slab_extra.hip k_sa_trs4<double2, .>) since start: trace passes
-    fused, operands Fx + sigma Gx fused, energies fused, passes refused (the vocabulary calls ran instead); slab_algebra_counts()
-    counts a fused pass as the real branch does.  A pass kept out by a gate (the option off, no open complex session, several
-    ranks, block form, a labelled slab form) is neither fused nor counted as refused"""
-    out = (C.c_longlong * 4)()
-    lib.ntpoly_amd_complex_trs4_counts(out)
-    return dict(traces=int(out[0]), operands=int(out[1]), energies=int(out[2]), refused=int(out[3]))
 
 
 def trs4_chain_step(X, X2, sigma, P):
@@ -1300,20 +1231,6 @@ def norm_axpby(A, B, alpha, beta):
     lib.ntpoly_amd_norm_axpby.restype = C.c_int
     ok = lib.ntpoly_amd_norm_axpby(A.ih, B.ih, d(alpha), d(beta), C.byref(r))
     return r.value if ok else None
-
-
-def column_fused_counts():
-    """operations on compressed columns done without the merge pass (csrc/column_fused.hip) since start"""
-    out = (C.c_longlong * 2)()
-    lib.ntpoly_amd_column_fused_counts(out)
-    return dict(identity_in_place=int(out[0]), norms_of_differences=int(out[1]))
-
-
-def block_algebra_counts():
-    """(operations of solver loops / C-ABI loops done on matrices in block form, fallbacks to compressed columns)"""
-    out = (C.c_longlong * 2)()
-    lib.ntpoly_amd_block_algebra_counts(out)
-    return dict(operations=int(out[0]), fallbacks=int(out[1]))
 
 
 def drop_block_caches():

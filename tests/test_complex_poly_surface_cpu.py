@@ -7,14 +7,13 @@ import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import surface_checks as S
+
+ROOT = S.ROOT
 ENTRY_POINTS = ("ntpoly_amd_recurrence_step", "ntpoly_amd_recurrence_step_count")
 OPTION = "complex_poly_sessions"
 ENV = "NTPOLY_AMD_COMPLEX_POLY_SESSIONS"
-
-
-def src(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
+src = S.src
 
 
 def test_header_declares_the_entry_point():
@@ -27,10 +26,8 @@ def test_header_declares_the_entry_point():
 
 
 def test_option_in_every_layer():
-    wrp = src("ntpoly_amd", "csrc", "wrp.cpp")
-    assert wrp.count('"%s"' % OPTION) == 2   # (set_option and get_option)
-    assert re.search(r"^\s*int %s = 2;" % OPTION, src("ntpoly_amd", "csrc", "kernels.hpp"), re.M)
-    assert ('getenv("%s")' % ENV) in src("ntpoly_amd", "csrc", "kernels.hip")
+    S.check_registered_once(OPTION)
+    assert (OPTION, 2, "ENV") in S.OPTIONS   # (the table's entry: the field, its default, its environment variable)
     host = src("ntpoly_amd", "host.py")
     for name in ENTRY_POINTS:
         assert "lib.%s(" % name in host, name

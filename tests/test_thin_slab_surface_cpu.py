@@ -6,13 +6,15 @@ import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import surface_checks as S
+
+ROOT = S.ROOT
 ENTRY_POINTS = ("ntpoly_amd_thin_slab_counts", "ntpoly_amd_session_begin", "ntpoly_amd_session_end")
 
 
 def test_header_declares_the_entry_points():
-    h = open(os.path.join(ROOT, "include", "ntpoly_amd.h")).read()
-    assert re.search(r"^void ntpoly_amd_thin_slab_counts\(long long\* out\);", h, re.M)
+    h = S.src("include", "ntpoly_amd.h")
+    assert re.search(r"^void ntpoly_amd_thin_slab_counts\(long long out\[6\]\);", h, re.M)
     assert re.search(r"^void ntpoly_amd_session_begin\(const int\* complex_ok\);", h, re.M)
     assert re.search(r"^void ntpoly_amd_session_end\(\);", h, re.M)
     from ntpoly_amd import capi
@@ -20,13 +22,15 @@ def test_header_declares_the_entry_points():
 
 
 def test_ctypes_layer_and_option_name():
-    src = open(os.path.join(ROOT, "ntpoly_amd", "host.py")).read()
-    for name in ENTRY_POINTS:
+    import ntpoly_amd as nt
+    src = S.src("ntpoly_amd", "host.py")
+    for name in ENTRY_POINTS[1:]:
         assert "lib.%s(" % name in src, name
-    assert re.search(r"^def thin_slab_counts\(\):", src, re.M) and re.search(r"^def solver_session\(complex_ok=True\):", src, re.M)
+    # (thin_slab_counts is defined from host.py's counter table, which calls the entry point of that name)
+    assert "thin_slab" in nt.host._COUNTERS and callable(nt.thin_slab_counts) and len(nt.thin_slab_counts()) == 6
+    assert re.search(r"^def solver_session\(complex_ok=True\):", src, re.M)
     assert "finally:\n        lib.ntpoly_amd_session_end()" in src
-    wrp = open(os.path.join(ROOT, "ntpoly_amd", "csrc", "wrp.cpp")).read()
-    assert wrp.count('"thin_slab_complex"') == 2   # (set_option and get_option)
+    S.check_registered_once("thin_slab_complex")
 
 
 def test_library_exports_and_default():

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generate include/*.h from the engine's own C ABI definitions (ntpoly_amd/csrc/wrp.cpp).
+"""Generate include/*.h from the engine's own C ABI definitions (ntpoly_amd/csrc/wrp.cpp and the counter table
+ntpoly_amd/csrc/counters.inc that it expands).
 
 For every exported *_wrp symbol the header records which reference declaration it replaces
 (Source/C/<header>:line) and which Fortran wrapper implements it there (Source/Wrapper/<file>:line).
@@ -14,6 +15,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/Source"
 SRC = open(os.path.join(ROOT, "ntpoly_amd/csrc/wrp.cpp")).read()
+COUNTERS = open(os.path.join(ROOT, "ntpoly_amd/csrc/counters.inc")).read()
 
 
 def ref_index():
@@ -32,7 +34,8 @@ def ref_index():
 
 
 def expand_macros(src):
-    """expand the two function-generating macros of wrp.cpp into plain prototypes"""
+    """expand the function-generating macros of wrp.cpp into plain prototypes: the density solvers, the local-matrix API and
+    the counter entry points of csrc/counters.inc"""
     out = src
     dens = re.findall(r"^DENSITY_SOLVER\((\w+), \w+\)", src, re.M)
     protos = []
@@ -44,6 +47,8 @@ def expand_macros(src):
     body = m.group(1).replace("\\\n", "\n")
     for suf in ("lsr", "lsc"):
         protos.append(body.replace("##SUF##", suf).replace("_##SUF", "_" + suf))
+    for name, n in re.findall(r"^NTP_COUNTER\((\w+), (\d+), \w+\)", COUNTERS, re.M):
+        protos.append("void ntpoly_amd_%s_counts(long long out[%s]) {" % (name, n))
     return out + "\n" + "\n".join(protos)
 
 
