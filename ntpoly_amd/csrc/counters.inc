@@ -22,6 +22,11 @@ NTP_COUNTER(isr_chain, 3, isr_chain_counts)
 // columns), [3] PolarDecomposition solves that ran in a slab session.  A gated operand -- no session, several ranks, compressed
 // columns, a view, a labelled form, block form -- counts nowhere
 NTP_COUNTER(slab_transpose, 4, slab_transpose_counts)
+// PowerBounds on one vector (option power_vector; engine.hpp ps_power_vector_open / ps_power_vector_step): [0] PowerBounds solves
+// that ran on one vector, [1] power steps computed by k_pv_step, [2] solves that passed the gates but were refused (the gather form
+// could not be built: the N-column loop ran).  A solve kept out by a gate -- the option off, process slices > 1 -- counts nowhere;
+// the diagnostic entry point ntpoly_amd_power_vector_step counts nothing
+NTP_COUNTER(power_vector, 3, power_vector_counts)
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update):
 // [0] trace passes fused, [1] updates fused, [2] updates refused (the vocabulary calls ran instead).  A step that never reaches
 // the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled slab form, alignments

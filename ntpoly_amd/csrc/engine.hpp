@@ -377,6 +377,27 @@ long long* slab_transpose_counts();   // (slots: counters.inc)
 // arithmetic, complex_tile and complex_sessions allow it), A entered into slab form, the pass run with or without conjugation, the
 // PACKED result installed in AT.  false: gated or refused, AT untouched.  A is back in compressed columns either way
 bool ps_slab_transpose_step(const PSMatrix& A, PSMatrix& AT, bool conj);
+// PowerBounds on one vector (option power_vector; power_vector.hip).  The N columns of the reference's iterate are one vector and
+// stay one vector, so the loop carries that column as a dense array on the device: x (the iterate), y = A x pruned as the product
+// prunes, and the three sums of a step -- d1 = sum conj(x) x, d2 = Re sum conj(x) y, n1 = sum |y| -- in one read-back.
+// ps_power_vector_open: the gate (no process slices; the option is the caller's) and the gather form of A, built from its
+// compressed columns as ps_transpose takes them, A untouched.  Collective: false on EVERY rank when a gate holds or some rank
+// could not build its form (32-bit indices, device memory).  Across ranks a rank's form holds the k of its own panel, a step sums
+// the ranks' partial vectors through the transport and every rank prunes, reduces and scales the full vector identically.
+// ps_power_vector_step: one step on pv.x; scale: x <- y / n1 behind it (ScaleMatrix's one multiplication); sums = (d1, d2, n1).
+struct PowerVector {
+  PowerGather G;
+  DevBuf<double> x, y, part, out;
+  int32_t n = 0;
+  bool cplx = false, multi = false;
+};
+bool ps_power_vector_open(const PSMatrix& A, PowerVector& pv);
+void ps_power_vector_set(PowerVector& pv, const double* host_x);   // n doubles, 2 n interleaved for a complex A
+void ps_power_vector_step(PowerVector& pv, double threshold, bool scale, double sums[3]);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_power_vector_step): one unscaled step on a caller's x; y = the pruned product.  false:
+// refused, nothing written.  Does not depend on the option and counts nothing
+bool ps_power_vector_diag(const PSMatrix& A, const double* x, double* y, double threshold, double sums[3]);
+long long* power_vector_counts();   // (slots: counters.inc)
 bool ps_is_identity(const PSMatrix& A);
 double ps_measure_asymmetry(const PSMatrix& A);
 void ps_symmetrize(PSMatrix& A);

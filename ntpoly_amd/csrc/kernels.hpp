@@ -248,6 +248,32 @@ template <typename T>
 bool slab_transpose(const DevMat& A, bool conj, DevMat& AT);
 bool slab_transpose_any(const DevMat& A, bool conj, DevMat& AT);
 bool slab_conjugate_c(DevMat& A);
+// PowerBounds on one vector (power_vector.hip; option power_vector).  PowerGather: the rows of A (for every row i the pairs
+// (k, A(i, k)) in ascending k) in slices of 64 rows, column-major within a slice: entry t of row r lies at soff[r / 64] + 64 t +
+// r % 64 of idx / val; a slice is padded to its longest row with (0, 0), which the kernels mask by len[r].
+// power_gather_build: from the compressed columns of A (a rank's panel: all rows, its own columns; koff = its first column, added
+// to every k), by a stable 32-bit sort of the entries' positions by row -- ascending k within a row, as transpose() orders them;
+// false: 32-bit indices do not suffice or the device cannot hold the form -- G is then unusable.
+// power_vector_chains: y_i = the chain over ascending k of A(i, k) x(k) in the product kernels' arithmetic (fma: option
+// spgemm_fma != 0; complex: the reference's multiply-add); tail: and the product's pruning (|y_i| > threshold, else 0) with the
+// workgroups' partial sums in part (3 per block of power_vector_blocks(n)).  power_vector_tail: pruning and partial sums for a y
+// that holds unpruned sums (several ranks).  power_vector_finish: out = (sum conj(x) x, Re sum conj(x) y, sum |y|, 1 / that),
+// summed in a fixed order.  power_vector_scale: x = y * out[3], pruned slots 0.  Everything on the engine stream, no host wait.
+struct PowerGather {
+  int32_t n = 0, nslices = 0;
+  bool cplx = false;
+  int64_t entries = 0;      // padded entries
+  DevBuf<int32_t> len;      // 64 nslices: entries of row r (0 beyond n)
+  DevBuf<int64_t> soff;     // nslices + 1
+  DevBuf<int32_t> idx;
+  DevBuf<double> val;
+};
+bool power_gather_build(const DevMat& A, int32_t koff, PowerGather& G);
+int power_vector_blocks(int32_t n);
+void power_vector_chains(const PowerGather& G, const double* x, double* y, double threshold, bool fma, bool tail, double* part);
+void power_vector_tail(int32_t n, bool cplx, const double* x, double* y, double threshold, double* part);
+void power_vector_finish(int32_t n, const double* part, double* out);
+void power_vector_scale(int32_t n, bool cplx, const double* y, const double* out, double* x);
 // The polynomial chain of the square-root step on slab-form X and X2 = X X (slab_extra.hip k_sa_isr_chain; real or complex, square
 // or column panels with col_offset = the panel's first column), the values and patterns of the vocabulary calls at threshold 0 bit
 // for bit.  Order 5: Temp2 = (X2 + a X) + (X + b I), Temp = (X2 + a X) + c I (Temp may be X2).  Order 3: Out = 0.375 X2 + (I - X / 2)

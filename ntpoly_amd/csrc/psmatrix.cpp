@@ -2574,6 +2574,73 @@ bool ps_slab_transpose_step(const PSMatrix& A, PSMatrix& AT, bool conj) {
   return true;
 }
 
+// ------------------------------------------------------------------ PowerBounds on one vector (option power_vector)
+long long* power_vector_counts() {
+  static long long counts[3] = {0, 0, 0};
+  return counts;
+}
+
+bool ps_power_vector_open(const PSMatrix& A, PowerVector& pv) {
+  CommScope cs(A.grid);
+  if (A.grid && A.grid->num_slices > 1) return false;   // (a gate: counted nowhere)
+  pv.n = A.dim;
+  pv.cplx = A.cplx;
+  pv.multi = world().active();
+  // (the rows of A from its compressed columns, whatever form it is kept in: A itself stays as it is)
+  bool ok;
+  {
+    DevMat tmp;
+    const DevMat& Ac = columns_of(A, tmp);
+    ok = Ac.rows == A.dim && Ac.cols == A.c1 - A.c0 && power_gather_build(Ac, A.c0, pv.G);
+  }
+  if (pv.multi) {   // (every rank or none)
+    int64_t bad = ok ? 0 : 1;
+    comm_allreduce_sum_i64(&bad, 1);
+    ok = bad == 0;
+  }
+  if (!ok) {
+    pv.G = PowerGather();
+    return false;
+  }
+  const size_t w = A.cplx ? 2 : 1;
+  pv.x.alloc((size_t)pv.n * w);
+  pv.y.alloc((size_t)pv.n * w);
+  pv.part.alloc((size_t)power_vector_blocks(pv.n) * 3);
+  pv.out.alloc(4);
+  return true;
+}
+
+void ps_power_vector_set(PowerVector& pv, const double* host_x) {
+  pv.x.upload(host_x, pv.x.n);
+  sync_stream();   // (the caller's array is free again)
+}
+
+void ps_power_vector_step(PowerVector& pv, double threshold, bool scale, double sums[3]) {
+  const bool fma = options().spgemm_fma != 0;
+  if (pv.multi) {
+    // (a rank's chains run over the k of its own panel; the ranks' partial vectors are summed, then every rank prunes, reduces
+    // and scales the full vector identically)
+    power_vector_chains(pv.G, pv.x.p, pv.y.p, threshold, fma, false, pv.part.p);
+    world().tr->allreduce(pv.y.p, pv.y.n, true, 0);
+    power_vector_tail(pv.n, pv.cplx, pv.x.p, pv.y.p, threshold, pv.part.p);
+  } else {
+    power_vector_chains(pv.G, pv.x.p, pv.y.p, threshold, fma, true, pv.part.p);
+  }
+  power_vector_finish(pv.n, pv.part.p, pv.out.p);
+  if (scale) power_vector_scale(pv.n, pv.cplx, pv.y.p, pv.out.p, pv.x.p);
+  pv.out.download(sums, 3);   // (the step's one read-back)
+}
+
+bool ps_power_vector_diag(const PSMatrix& A, const double* x, double* y, double threshold, double sums[3]) {
+  CommScope cs(A.grid);
+  PowerVector pv;
+  if (!ps_power_vector_open(A, pv)) return false;
+  ps_power_vector_set(pv, x);
+  ps_power_vector_step(pv, threshold, false, sums);
+  pv.y.download(y, pv.y.n);
+  return true;
+}
+
 bool ps_is_identity(const PSMatrix& A) {
   CommScope cs(A.grid);  // distributed_includes/IsIdentity.f90:7-38
   int64_t d = identity_check(A.loc, A.c0);

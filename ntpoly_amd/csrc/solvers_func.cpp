@@ -26,9 +26,22 @@ void power_bounds(const PSMatrix& A, double* max_value_out, const SolverParamete
   }
   // the reference's "vector" is a matrix whose first row is 1/N in every column (:98-113): every column carries the
   // same power iteration started from e_1
+  // Option power_vector: those N columns are one vector and stay one vector, so the loop carries one column as a dense array and
+  // a step is one sparse matrix-vector product in the product kernels' arithmetic (power_vector.hip).  Decided once, here: the
+  // option, one process slice, and a gather form of A that could be built; a solve the gates keep out counts nowhere
+  PowerVector pv;
+  bool one_vector = false;
+  if (options().power_vector != 0 && !(A.grid && A.grid->num_slices > 1)) {
+    one_vector = ps_power_vector_open(A, pv);
+    power_vector_counts()[one_vector ? 0 : 2] += 1;
+  }
   PSMatrix vec, vec2;
-  ps_construct_like(vec, A);
-  {
+  if (one_vector) {
+    std::vector<double> x((size_t)A.dim * (A.cplx ? 2 : 1), 0.0);
+    x[0] = 1.0 / (double)A.dim;
+    ps_power_vector_set(pv, x.data());
+  } else {
+    ps_construct_like(vec, A);
     HostTriplets t;
     t.cplx = false;
     for (int32_t c = vec.c0; c < vec.c1; ++c) {
@@ -49,14 +62,23 @@ void power_bounds(const PSMatrix& A, double* max_value_out, const SolverParamete
   }
   int II;
   for (II = 1; II <= p.max_iterations; ++II) {                     // :121-165
-    ps_multiply(A, vec, vec2, 1.0, 0.0, p.threshold);
-    double d1[2], d2[2];
-    ps_dot(vec, vec, d1);
-    ps_dot(vec, vec2, d2);
-    max_value = d2[0] / d1[0];
-    const double scale_value = 1.0 / ps_norm(vec2);
-    ps_scale(vec2, scale_value);
-    std::swap(vec.loc, vec2.loc);
+    if (one_vector) {
+      // (the sums over N identical columns are N d1 and N d2: the same quotient; the matrix's 1-norm is the one column's n1, and
+      // the scaling by 1 / n1 runs behind the step on the device)
+      double sums[3];
+      ps_power_vector_step(pv, p.threshold, true, sums);
+      power_vector_counts()[1] += 1;
+      max_value = sums[1] / sums[0];
+    } else {
+      ps_multiply(A, vec, vec2, 1.0, 0.0, p.threshold);
+      double d1[2], d2[2];
+      ps_dot(vec, vec, d1);
+      ps_dot(vec, vec2, d2);
+      max_value = d2[0] / d1[0];
+      const double scale_value = 1.0 / ps_norm(vec2);
+      ps_scale(vec2, scale_value);
+      std::swap(vec.loc, vec2.loc);
+    }
     ritz[0] = ritz[1]; ritz[1] = ritz[2]; ritz[2] = max_value;
     aitken[0] = aitken[1]; aitken[1] = aitken[2];
     if (II >= 3) {

@@ -227,6 +227,14 @@ int ntpoly_amd_isr_chain_step(const int* ih_X, const int* ih_X2, const int* orde
 int ntpoly_amd_slab_transpose(const int* ih_A, int* ih_AT, const int* conjugate) {
   return ps_slab_transpose_step(*get<PSMatrix>(ih_A), *get<PSMatrix>(ih_AT), *conjugate != 0) ? 1 : 0;
 }
+// DIAGNOSTIC surface: one step of PowerBounds on one vector (option power_vector's kernels, whatever the option says) on the
+// caller's x -- host arrays of N doubles, 2 N interleaved (re, im) for a complex A.  y = A x with every entry the chain over
+// ascending k in the product's arithmetic, pruned as the product prunes (|y_i| > *threshold, else 0), NOT scaled; out = (sum conj(x)
+// x, Re sum conj(x) y, sum |y|).  Returns 1 when the kernel ran, 0 when it was refused (process slices, a gather form that could
+// not be built): y and out are then as they were.  Counts nothing
+int ntpoly_amd_power_vector_step(const int* ih_A, const double* x, double* y, const double* threshold, double out[3]) {
+  return ps_power_vector_diag(*get<PSMatrix>(ih_A), x, y, *threshold, out) ? 1 : 0;
+}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: one fused HPCP update on caller-held real matrices D1, DDH
 // (what the loop's product D1 (I - D1) would be), D2DH (D1 DDH) and WH.  The operands are brought into slab form, the update runs,
 // the outputs are packed into the result handles: D1out = (D1 + 2 D2DH) + (-2 sigma) DDH, DHout = I - D1out as CopyMatrix,

@@ -970,6 +970,10 @@ _COUNTERS = {
     done in slab form, conjugations done in slab form, transposes refused past the gates (extents far apart: that one ran on
     compressed columns), PolarDecomposition solves that ran in a slab session.  A gated operand (no session, several ranks,
     compressed columns, a view, a labelled form, block form) counts nowhere"""),
+    "power_vector": (("solves", "steps", "refused"),
+                     """PowerBounds on one vector (option power_vector; csrc/power_vector.hip) since start: solves that ran on one vector, power
+    steps computed by k_pv_step, solves that passed the gates but were refused (the gather form could not be built: the N-column
+    loop ran).  A solve kept out by a gate (the option off, process slices > 1) counts nowhere; power_vector_step() counts nothing"""),
     "hpcp_step": (("traces", "updates", "refused"),
                   """HPCP purification with its traces and its update in one pass each (option hpcp_step; csrc/slab_extra.hip k_hpcp_traces /
     k_hpcp_update) since start: trace passes fused, updates fused, updates refused (the vocabulary calls ran instead);
@@ -1114,6 +1118,22 @@ def slab_transpose(A, AT, conjugate=False):
     lib.ntpoly_amd_slab_transpose.restype = C.c_int
     ok = lib.ntpoly_amd_slab_transpose(A.ih, AT.ih, C.byref(C.c_int(1 if conjugate else 0)))
     return True if ok else None
+
+
+def power_vector_step(A, x, threshold):
+    """DIAGNOSTIC -- one step of PowerBounds on one vector (csrc/power_vector.hip) on a caller's x: N values, complex ones for a
+    complex A.  Returns (y, d1, d2, n1): y = A x, every entry the chain over ascending k in the product's arithmetic, pruned as
+    the product prunes (|y_i| > threshold, else 0) and NOT scaled; d1 = sum conj(x) x, d2 = Re sum conj(x) y, n1 = sum |y|.  None:
+    refused (process slices, a gather form that could not be built).  Does not depend on option power_vector; counts nothing."""
+    n = A.GetActualDimension()
+    kind = np.complex128 if A.IsComplex() else np.float64
+    xs = np.ascontiguousarray(np.asarray(x, dtype=kind).reshape(n))
+    ys = np.zeros(n, dtype=kind)
+    out = (C.c_double * 3)()
+    lib.ntpoly_amd_power_vector_step.restype = C.c_int
+    ok = lib.ntpoly_amd_power_vector_step(A.ih, xs.ctypes.data_as(C.POINTER(C.c_double)), ys.ctypes.data_as(C.POINTER(C.c_double)),
+                                          d(threshold), out)
+    return (ys, float(out[0]), float(out[1]), float(out[2])) if ok else None
 
 
 def hpcp_update_step(D1, DDH, D2DH, sigma, WH, D1out, DHout):
