@@ -27,6 +27,12 @@ NTP_COUNTER(slab_transpose, 4, slab_transpose_counts)
 // could not be built: the N-column loop ran).  A solve kept out by a gate -- the option off, process slices > 1 -- counts nowhere;
 // the diagnostic entry point ntpoly_amd_power_vector_step counts nothing
 NTP_COUNTER(power_vector, 3, power_vector_counts)
+// CGSolver with its traces from column dot passes (option cg_dots; engine.hpp ps_cg_dots): [0] solves that ran with the passes, [1]
+// dot passes done by k_cg_dots, [2] passes refused past the gates (the same chains ran on the rank's compressed columns), [3]
+// products and transposes not formed.  A solve kept out by a gate -- the option off, no session for the operands' kind, block
+// form, process slices > 1, complex operands with the option below 2 or on several ranks -- counts nowhere; the diagnostic entry
+// point ntpoly_amd_cg_dots counts nothing
+NTP_COUNTER(cg_dots, 4, cg_dots_counts)
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update):
 // [0] trace passes fused, [1] updates fused, [2] updates refused (the vocabulary calls ran instead).  A step that never reaches
 // the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled slab form, alignments

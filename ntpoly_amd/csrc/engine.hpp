@@ -398,6 +398,23 @@ void ps_power_vector_step(PowerVector& pv, double threshold, bool scale, double 
 // refused, nothing written.  Does not depend on the option and counts nothing
 bool ps_power_vector_diag(const PSMatrix& A, const double* x, double* y, double threshold, double sums[3]);
 long long* power_vector_counts();   // (slots: counters.inc)
+// The traces of CGSolver from column dot passes (option cg_dots; cg_dots.hip k_cg_dots / k_cg_trace), inside a slab session.
+// ps_cg_dots: out[0] = trace(prune(U1^H V1)), and with a second pair out[1] = trace(prune(U2^H V2)), pruned at `threshold` as
+// MatrixMultiply prunes: what conj_transpose + ps_multiply(., ., ., 1, 0, threshold) + ps_trace give outside a session, bit for bit,
+// without the transpose and without the product -- entry (j, j) of U^H V is the dot of column j of U with column j of V.  Operands
+// still in compressed columns are brought into slab form where they are.  Collective as ps_hpcp_traces: past gates that are the
+// same on every rank -- the option off, no open session for the operands' kind, block form, process slices > 1, complex operands
+// with the option below 2 or on several ranks -- every rank enters ONE reduction of both sums; a rank whose panels the kernel does
+// not take (an empty panel, operands that are not run-like, a labelled form) adds the same chains computed on its compressed columns
+// (counted as refused).  false: gated, nothing done -- the caller runs transpose + product + trace.  Counted in
+// slab_algebra_counts() as the operations it replaces: per pair a product, and a transpose and a trace as other operations.
+bool ps_cg_dots(const PSMatrix& U1, const PSMatrix& V1, const PSMatrix* U2, const PSMatrix* V2, double threshold, double out[2]);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_cg_dots): a session of its own for the operands' kind, both operands into slab form, one pass
+// with one pair -- k_cg_dots, or for operands without a slab form (not run-like, an empty panel) the chains on compressed columns,
+// as in the loop; diag = the d_j of the local columns (U.c1 - U.c0 doubles), *trace = their sum over all ranks.  false: gated,
+// nothing written.  Under the option's gates (real operands: 1, complex ones: 2, one rank); counts nothing
+bool ps_cg_dots_diag(const PSMatrix& U, const PSMatrix& V, double threshold, double* diag, double* trace);
+long long* cg_dots_counts();   // (slots: counters.inc)
 bool ps_is_identity(const PSMatrix& A);
 double ps_measure_asymmetry(const PSMatrix& A);
 void ps_symmetrize(PSMatrix& A);

@@ -248,6 +248,19 @@ template <typename T>
 bool slab_transpose(const DevMat& A, bool conj, DevMat& AT);
 bool slab_transpose_any(const DevMat& A, bool conj, DevMat& AT);
 bool slab_conjugate_c(DevMat& A);
+// Column dot passes for the traces of CGSolver (cg_dots.hip; option cg_dots).  For every local column j and pair (U, V): d_j = the
+// chain over ascending row k of conj(U(k, j)) V(k, j) in the product kernels' arithmetic (fma: option spgemm_fma != 0; complex: the
+// reference's multiply-add), kept iff |d_j| > threshold (strict, the modulus for complex), else 0 -- entry (j, j) of
+// MatrixMultiply(U^H, V, threshold).  out[p] = the sum of the real parts of pair p's d_j in the order of trace() on compressed
+// columns: MatrixTrace of that product on this rank, bit for bit.  Rows are global in both operands, so no column offset enters.
+// slab_cg_dots: operands in slab form (one pair with U2 == V2 == nullptr); gates: every operand expanded and not labelled, one kind
+// and shape (the slots' alignment does not matter: a run is addressed by first / last / off alone); a read-only view is readable
+// (its stored zeros are zeros of the run).  false: not taken, out untouched.
+// diag != nullptr: the d_j of the FIRST pair copied to that host array (cols doubles).
+// cg_dots_columns: the same chains and sums for one pair in packed compressed columns (a merge of the two columns' row lists);
+// diag as above.
+bool slab_cg_dots(const DevMat& U1, const DevMat& V1, const DevMat* U2, const DevMat* V2, double threshold, double out[2], double* diag = nullptr);
+double cg_dots_columns(const DevMat& U, const DevMat& V, double threshold, double* diag = nullptr);
 // PowerBounds on one vector (power_vector.hip; option power_vector).  PowerGather: the rows of A (for every row i the pairs
 // (k, A(i, k)) in ascending k) in slices of 64 rows, column-major within a slice: entry t of row r lies at soff[r / 64] + 64 t +
 // r % 64 of idx / val; a slice is padded to its longest row with (0, 0), which the kernels mask by len[r].

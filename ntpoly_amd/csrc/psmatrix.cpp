@@ -2641,6 +2641,80 @@ bool ps_power_vector_diag(const PSMatrix& A, const double* x, double* y, double 
   return true;
 }
 
+// ------------------------------------------------------------------ the traces of CGSolver from column dot passes (option cg_dots)
+long long* cg_dots_counts() {
+  static long long counts[4] = {0, 0, 0, 0};
+  return counts;
+}
+namespace {
+// the gates, the same on every rank: a call they keep out is neither done nor refused
+bool cg_dots_gates(std::initializer_list<const PSMatrix*> ms) {
+  const PSMatrix& U = **ms.begin();
+  const int opt = options().cg_dots;
+  if (opt == 0 || g_slab_depth == 0 || !session_takes(U.cplx) || (U.grid && U.grid->num_slices > 1)) return false;
+  if (U.cplx && (opt < 2 || world().active())) return false;
+  for (const PSMatrix* m : ms)
+    if (m->cplx != U.cplx || m->dim != U.dim || m->loc.blocked()) return false;
+  return world().active() || slab_on();
+}
+// this rank's sums: the kernel on the operands' slab forms (true), or the same chains on its compressed columns (false)
+bool cg_dots_local(const PSMatrix& U1, const PSMatrix& V1, const PSMatrix* U2, const PSMatrix* V2, double threshold, double t[2], double* diag) {
+  const bool cplx = U1.cplx;
+  auto enter = [cplx](const PSMatrix& M) { return !labelled(M) && (cplx ? slab_enter_c(mut(M)) : slab_enter(mut(M))); };
+  if (slab_on() && enter(U1) && enter(V1) && (!U2 || (enter(*U2) && enter(*V2))) &&
+      slab_cg_dots(U1.loc, V1.loc, U2 ? &U2->loc : nullptr, V2 ? &V2->loc : nullptr, threshold, t, diag))
+    return true;
+  {
+    DevMat a, b;
+    t[0] = cg_dots_columns(columns_of(U1, a), columns_of(V1, b), threshold, diag);
+  }
+  if (U2) {
+    DevMat a, b;
+    t[1] = cg_dots_columns(columns_of(*U2, a), columns_of(*V2, b), threshold);
+  }
+  return false;
+}
+}  // namespace
+
+bool ps_cg_dots(const PSMatrix& U1, const PSMatrix& V1, const PSMatrix* U2, const PSMatrix* V2, double threshold, double out[2]) {
+  CommScope cs(U1.grid);
+  if ((U2 == nullptr) != (V2 == nullptr)) return false;
+  if (U2 ? !cg_dots_gates({&U1, &V1, U2, V2}) : !cg_dots_gates({&U1, &V1})) return false;
+  const int pairs = U2 ? 2 : 1;
+  double t[2] = {0.0, 0.0};
+  if (cg_dots_local(U1, V1, U2, V2, threshold, t, nullptr)) {
+    g_slab_counts[0] += pairs;       // the products
+    g_slab_counts[2] += 2 * pairs;   // their transposes and traces
+    cg_dots_counts()[1] += 1;
+    cg_dots_counts()[3] += 2 * pairs;
+  } else {
+    cg_dots_counts()[2] += 1;
+  }
+  comm_allreduce_sum(t, 2);   // (MatrixTrace's reduction, both sums in one)
+  out[0] = t[0];
+  if (U2) out[1] = t[1];
+  return true;
+}
+
+bool ps_cg_dots_diag(const PSMatrix& U, const PSMatrix& V, double threshold, double* diag, double* trace) {
+  CommScope cs(U.grid);
+  const bool complex_ok = U.cplx && complex_slab_loop(U);
+  if (U.cplx && !complex_ok) return false;
+  SlabSession ses(true, false, complex_ok);
+  if (!ses.opened || !cg_dots_gates({&U, &V})) return false;
+  std::vector<double> d((size_t)std::max(0, U.c1 - U.c0), 0.0);
+  double t[2] = {0.0, 0.0};
+  // (an operand without a slab form -- not run-like, an empty panel --: the chains on its compressed columns, as in the loop)
+  cg_dots_local(U, V, nullptr, nullptr, threshold, t, d.data());
+  comm_allreduce_sum(t, 2);
+  // (the session ends with this call: the operands go back to compressed columns)
+  if (U.loc.expanded()) pack(mut(U));
+  if (V.loc.expanded()) pack(mut(V));
+  std::copy(d.begin(), d.end(), diag);
+  *trace = t[0];
+  return true;
+}
+
 bool ps_is_identity(const PSMatrix& A) {
   CommScope cs(A.grid);  // distributed_includes/IsIdentity.f90:7-38
   int64_t d = identity_check(A.loc, A.c0);

@@ -54,6 +54,14 @@ void solver_cg(const PSMatrix& AMat, PSMatrix& XMat, const PSMatrix& BMat, const
   balance_permute(Identity, p);
   balance_copy(AMat, ABalanced, p);
   balance_copy(BMat, BBalanced, p);
+  // Option cg_dots: of the iteration's four products three exist only to be traced, and entry (j, j) of U^H V is the dot of column
+  // j of U with column j of V -- so the loop runs in a slab session (R, P, Q and X stay in slab form around the one product
+  // Q = A P) and takes top, bottom and the new top from column dot passes over the runs (ps_cg_dots: the bits of transpose +
+  // product + trace).  1: real operands; 2: also complex ones on one rank in a complex session.  A call the gates keep out runs
+  // the three calls as before
+  const bool dots = options().cg_dots != 0 && !(AMat.grid && AMat.grid->num_slices > 1);
+  const bool complex_session = dots && options().cg_dots >= 2 && AMat.cplx && BMat.cplx && complex_slab_loop(AMat) && !world().active();
+  SlabSession slab(dots && ((!AMat.cplx && !BMat.cplx) || complex_session), false, complex_session);
   ps_copy(Identity, X);                                                        // initial guess X = I (:89)
   ps_multiply(ABalanced, X, TempMat, 1.0, 0.0, p.threshold);
   ps_copy(BBalanced, RMat);
@@ -63,28 +71,52 @@ void solver_cg(const PSMatrix& AMat, PSMatrix& XMat, const PSMatrix& BMat, const
     log_header("Iterations");
     log_enter();
   }
+  // trace(prune(U^H V)) the old way
+  auto traced_product = [&](const PSMatrix& U, PSMatrix& UT, const PSMatrix& V) {
+    conj_transpose(U, UT);
+    ps_multiply(UT, V, TempMat, 1.0, 0.0, p.threshold);
+    return ps_trace(TempMat);
+  };
+  double top = 0.0, both[2];
+  bool have_top = false, counted = false;   // (have_top: the new top of the last iteration is this one's top -- same matrix, same bits)
+  auto count_solve = [&]() {
+    if (!counted) cg_dots_counts()[0] += 1;
+    counted = true;
+  };
   int II;
   for (II = 1; II <= p.max_iterations; ++II) {                                 // :101-139
     ps_multiply(ABalanced, PMat, QMat, 1.0, 0.0, p.threshold);
-    conj_transpose(RMat, RMatT);
-    ps_multiply(RMatT, RMat, TempMat, 1.0, 0.0, p.threshold);
-    const double top = ps_trace(TempMat);
-    conj_transpose(PMat, PMatT);
-    ps_multiply(PMatT, QMat, TempMat, 1.0, 0.0, p.threshold);
-    const double bottom = ps_trace(TempMat);
+    double bottom;
+    if (dots && (have_top ? ps_cg_dots(PMat, QMat, nullptr, nullptr, p.threshold, both) : ps_cg_dots(PMat, QMat, &RMat, &RMat, p.threshold, both))) {
+      count_solve();
+      bottom = both[0];
+      if (have_top) cg_dots_counts()[3] += 2;   // (the carried top: a product and a transpose more)
+      else top = both[1];
+    } else {
+      if (!have_top) top = traced_product(RMat, RMatT, RMat);
+      bottom = traced_product(PMat, PMatT, QMat);
+    }
     double step_size = top / bottom;
     ps_increment(PMat, X, step_size, 0.0);
     const double norm_value = std::fabs(step_size * ps_norm(PMat));
     ps_increment(QMat, RMat, -1.0 * step_size, 0.0);
-    conj_transpose(RMat, RMatT);
-    ps_multiply(RMatT, RMat, TempMat, 1.0, 0.0, p.threshold);
-    const double new_top = ps_trace(TempMat);
+    double new_top;
+    if (dots && ps_cg_dots(RMat, RMat, nullptr, nullptr, p.threshold, both)) {
+      count_solve();
+      new_top = both[0];
+    } else {
+      new_top = traced_product(RMat, RMatT, RMat);
+    }
     step_size = new_top / top;
     ps_scale(PMat, step_size);
     ps_increment(RMat, PMat, 1.0, 0.0);
+    top = new_top;
+    have_top = dots;
     monitor_append(mon, norm_value);
     if (monitor_converged(mon, p.be_verbose)) break;
   }
+  slab.close();
+  ps_slab_leave(X);
   if (p.be_verbose) {
     log_exit();
     log_element("Total Iterations", II - 1);

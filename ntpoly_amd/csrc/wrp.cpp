@@ -235,6 +235,16 @@ int ntpoly_amd_slab_transpose(const int* ih_A, int* ih_AT, const int* conjugate)
 int ntpoly_amd_power_vector_step(const int* ih_A, const double* x, double* y, const double* threshold, double out[3]) {
   return ps_power_vector_diag(*get<PSMatrix>(ih_A), x, y, *threshold, out) ? 1 : 0;
 }
+// DIAGNOSTIC surface: one column dot pass of CGSolver's traces (option cg_dots: 1 for real operands, 2 for complex ones on one rank
+// in FMA arithmetic) on caller-held U and V.  A session of its own for the operands' kind is opened, both operands are brought
+// into slab form, k_cg_dots runs with one pair: diag_out[j] = the real part of entry (j, j) of MatrixMultiply(U^H, V, threshold) --
+// the chain over ascending k of conj(U(k, j)) V(k, j) in the product's arithmetic, 0 where the product prunes it or has no entry --
+// for the local columns, *trace_out = their sum in MatrixTrace's order over all ranks.  Operands that get no slab form (not
+// run-like, an empty panel) go through the same chains on compressed columns, as in the loop.  Returns 1, or 0 when gated: both
+// outputs are then as they were.  Counts nothing
+int ntpoly_amd_cg_dots(const int* ih_U, const int* ih_V, double threshold, double* diag_out, double* trace_out) {
+  return ps_cg_dots_diag(*get<PSMatrix>(ih_U), *get<PSMatrix>(ih_V), threshold, diag_out, trace_out) ? 1 : 0;
+}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: one fused HPCP update on caller-held real matrices D1, DDH
 // (what the loop's product D1 (I - D1) would be), D2DH (D1 DDH) and WH.  The operands are brought into slab form, the update runs,
 // the outputs are packed into the result handles: D1out = (D1 + 2 D2DH) + (-2 sigma) DDH, DHout = I - D1out as CopyMatrix,

@@ -974,6 +974,12 @@ _COUNTERS = {
                      """PowerBounds on one vector (option power_vector; csrc/power_vector.hip) since start: solves that ran on one vector, power
     steps computed by k_pv_step, solves that passed the gates but were refused (the gather form could not be built: the N-column
     loop ran).  A solve kept out by a gate (the option off, process slices > 1) counts nowhere; power_vector_step() counts nothing"""),
+    "cg_dots": (("solves", "passes", "refused", "not_formed"),
+                """CGSolver with its traces from column dot passes (option cg_dots; csrc/cg_dots.hip k_cg_dots / k_cg_trace) since start: solves
+    that ran with the passes, dot passes done by the kernel, passes refused past the gates (the same chains ran on the rank's
+    compressed columns), products and transposes not formed.  A solve kept out by a gate (the option off, no session for the
+    operands' kind, block form, process slices > 1, complex operands with the option below 2 or on several ranks) counts nowhere;
+    cg_dots() counts nothing"""),
     "hpcp_step": (("traces", "updates", "refused"),
                   """HPCP purification with its traces and its update in one pass each (option hpcp_step; csrc/slab_extra.hip k_hpcp_traces /
     k_hpcp_update) since start: trace passes fused, updates fused, updates refused (the vocabulary calls ran instead);
@@ -1134,6 +1140,21 @@ def power_vector_step(A, x, threshold):
     ok = lib.ntpoly_amd_power_vector_step(A.ih, xs.ctypes.data_as(C.POINTER(C.c_double)), ys.ctypes.data_as(C.POINTER(C.c_double)),
                                           d(threshold), out)
     return (ys, float(out[0]), float(out[1]), float(out[2])) if ok else None
+
+
+def cg_dots(U, V, threshold):
+    """DIAGNOSTIC -- one column dot pass of CGSolver's traces (csrc/cg_dots.hip; option cg_dots: 1 for real operands, 2 for complex
+    ones on one rank in FMA arithmetic) on caller-held U and V.  Returns (diag, trace): diag[j] = the real part of entry (j, j) of
+    MatrixMultiply(U^H, V, threshold) for this rank's columns -- the chain over ascending k of conj(U(k, j)) V(k, j) in the product's
+    arithmetic, 0.0 where the product prunes the entry or has none -- and trace = their sum in MatrixTrace's order over all ranks.
+    Operands that get no slab form (not run-like) go through the same chains on compressed columns, as in the loop.  None: gated.
+    Counts nothing."""
+    lo, hi = U.local_columns()
+    diag = np.zeros(max(0, hi - lo), dtype=np.float64)
+    tr = C.c_double(0.0)
+    lib.ntpoly_amd_cg_dots.restype = C.c_int
+    ok = lib.ntpoly_amd_cg_dots(U.ih, V.ih, C.c_double(float(threshold)), diag.ctypes.data_as(C.POINTER(C.c_double)), C.byref(tr))
+    return (diag, float(tr.value)) if ok else None
 
 
 def hpcp_update_step(D1, DDH, D2DH, sigma, WH, D1out, DHout):
