@@ -33,6 +33,11 @@ NTP_COUNTER(power_vector, 3, power_vector_counts)
 // form, process slices > 1, complex operands with the option below 2 or on several ranks -- counts nowhere; the diagnostic entry
 // point ntpoly_amd_cg_dots counts nothing
 NTP_COUNTER(cg_dots, 4, cg_dots_counts)
+// WOM_GC / WOM_C in a slab session (option wom_session; engine.hpp ps_wom_heun / ps_wom_c_dots): [0] solves that ran in a slab
+// session, [1] Heun tails fused (k_wom_heun), [2] pairs of dots of the canonical step fused (k_wom_c_dots), [3] passes refused past
+// the gates (the vocabulary calls ran instead).  A pass kept out by a gate -- the option below 2, no open real session, a complex
+// operand, block form, a labelled slab form, dimensions that differ, one matrix given twice -- counts nowhere
+NTP_COUNTER(wom_session, 4, wom_session_counts)
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update):
 // [0] trace passes fused, [1] updates fused, [2] updates refused (the vocabulary calls ran instead).  A step that never reaches
 // the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled slab form, alignments

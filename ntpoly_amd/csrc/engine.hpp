@@ -278,6 +278,26 @@ bool ps_saf_dot_trace(const PSMatrix& X, const PSMatrix& WH, double* dot, double
 bool ps_saf_update_step(const PSMatrix& X, const PSMatrix& X2, double a, double b, const PSMatrix& WH, PSMatrix& Xout, double* dot, double* trace);
 bool ps_saf_dot_trace_step(const PSMatrix& X, const PSMatrix& WH, double* dot, double* trace);
 long long* scale_fold_step_counts();   // (slots: counters.inc)
+// The WOM solvers (FermiOperatorModule.F90:349-520) inside a real slab session, option wom_session = 2 (wom_heun.hip).
+// ps_wom_heun: what CopyMatrix(W, RK2); IncrementMatrix(K0, RK2, step * 0.5, threshold); IncrementMatrix(K1, RK2, step * 0.5, threshold)
+// leave in RK2, values and pattern bit for bit, *err = MatrixNorm of RK1 - RK2 and *err2 = MatrixNorm of RK2 - W (each difference
+// merged at threshold) with the bits ps_norm gives on them in the session, from one pass and one read-back.  ps_wom_c_dots: out =
+// {dot(X, W), dot(W, XA)} with the bits of two ps_dot calls in the session.  Counted in slab_algebra_counts() as the calls replaced
+// (seven merges / copies and two norms; two dots).
+// Collective: past gates that are the same on every rank (the option below 2, no open real session, a complex operand, block form,
+// a labelled slab form, dimensions that differ, one matrix given twice) each rank enters ONE max-reduction of {err, err2} (ONE
+// sum-reduction of the two dots); across ranks a rank whose panel is not taken builds its RK2 with the local merges, takes its two
+// maxima from the local column sums, joins the reduction, and the call still returns true.  false: nothing done (an operand still
+// in compressed columns may have been turned into slab form) -- the caller makes the calls.  On one rank that is also the answer
+// where the pass is refused (counted so: step or threshold not finite, an operand the slab form cannot hold, alignments that
+// differ, runs far apart, a kept value that is exactly zero).
+bool ps_wom_heun(const PSMatrix& W, const PSMatrix& K0, const PSMatrix& K1, const PSMatrix& RK1, double step, double threshold, PSMatrix& RK2,
+                 double* err, double* err2);
+bool ps_wom_c_dots(const PSMatrix& X, const PSMatrix& W, const PSMatrix& XA, double out[2]);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_wom_heun_step): the same pass with RK2 packed into RK2out; false: refused or gated, everything as it was
+bool ps_wom_heun_step(const PSMatrix& W, const PSMatrix& K0, const PSMatrix& K1, const PSMatrix& RK1, double step, double threshold,
+                      PSMatrix& RK2out, double* err, double* err2);
+long long* wom_session_counts();   // (slots: counters.inc)
 // Option complex_scale_fold (one rank, inside a session that takes complex operands): the four calls above take COMPLEX operands
 // (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of
 // the vocabulary calls at threshold 0 bit for bit; the scale branch's pass is slab_dot_trace_c over X and WH as it stands -- slab

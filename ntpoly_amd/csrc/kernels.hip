@@ -2800,6 +2800,8 @@ __global__ __launch_bounds__(256) void k_fused_totals(const int32_t* __restrict_
 }
 
 void scan_i32_async(const int32_t* d_in, int64_t* d_out, int64_t n) { scan_async<int32_t>(d_in, d_out, n); }
+void reduce_sum_pairs_async(const double* part, int n, double* out2) { reduce_sum2_async(part, n, out2); }
+void reduce_max_async(const double* v, int64_t n, double* out2) { launch_reduce_minmax(nullptr, v, n, out2); }
 void scan_i64_async(const int64_t* d_in, int64_t* d_out, int64_t n) { scan_async<int64_t>(d_in, d_out, n); }
 
 namespace {

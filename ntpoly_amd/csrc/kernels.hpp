@@ -329,6 +329,19 @@ bool slab_saf_dot_trace(const DevMat& X, const DevMat& WH, int32_t col_offset, d
 // a read-only view; slots and the bound count pairs.  The scale branch's pass on complex operands is slab_dot_trace_c itself
 bool slab_saf_update_c(const DevMat& X, const DevMat& X2, double a, double b, const DevMat& WH, int32_t col_offset, DevMat& Out, double* dot,
                        double* trace);
+// The tail of a Heun trial of the WOM solvers on slab-form matrices (wom_heun.hip; real, square or column panels).  slab_wom_heun:
+// Out = RK2 = (W + c K0) + c K1 with c = h * 0.5, every merge at `thr` by AddSparseVectors' rules with each link's "other operand's
+// last row" the last KEPT row of the link before -- the values and pattern of CopyMatrix(W, RK2); IncrementMatrix(K0, RK2, c, thr);
+// IncrementMatrix(K1, RK2, c, thr) bit for bit; *err = the LOCAL MatrixNorm of RK1 - RK2 and *err2 of RK2 - W, both merged at thr,
+// with the bits slab_norm gives on those differences in slab form.  One pass over the four runs, one host read-back.  false:
+// refused (an operand not in zero-free slab form, labelled, a view, alignments that are no multiples of one another, h or thr not finite, runs far apart, a
+// kept value that is exactly zero), nothing changed.  slab_wom_heun_register_rows(): the hull of a column's four runs up to which
+// the kernel holds the column in registers; longer columns read their runs once per sweep
+bool slab_wom_heun(const DevMat& W, const DevMat& K0, const DevMat& K1, const DevMat& RK1, double h, double thr, DevMat& Out, double* err,
+                   double* err2);
+int slab_wom_heun_register_rows();
+// out[0] = the LOCAL dot(X, W), out[1] = the LOCAL dot(W, XA), each with the bits of slab_dot, from one kernel and one read-back
+bool slab_wom_c_dots(const DevMat& X, const DevMat& W, const DevMat& XA, double out[2]);
 // PM purification on a slab-form iterate (slab_extra.hip).  The rows of each column that compressed columns would hold as STORED
 // ZEROS (a1 = 0 when sigma > 1/2, unfiltered tails that underflow) travel next to the zero-free runs: rows row[off[j] .. off[j + 1])
 // of column j, ascending, disjoint from the run's non-zeros.  off.p == nullptr: no such row.
@@ -552,5 +565,9 @@ int64_t exclusive_scan_i64(const int64_t* d_in, int64_t* d_out, int64_t n);
 // the same without the read-back: out[0..n] = exclusive prefix sums, out[n] = total; asynchronous on the engine stream
 void scan_i32_async(const int32_t* d_in, int64_t* d_out, int64_t n);
 void scan_i64_async(const int64_t* d_in, int64_t* d_out, int64_t n);
+// the reductions behind slab_dot and slab_norm for passes in other translation units, asynchronous on the engine stream: out2[0]
+// = the deterministic two-level sum of the first members of n (x, y) pairs, out2[1] = of the second; out2[1] = the maximum of v[0..n)
+void reduce_sum_pairs_async(const double* part, int n, double* out2);
+void reduce_max_async(const double* v, int64_t n, double* out2);
 
 }  // namespace ntp

@@ -2443,20 +2443,15 @@ bool ps_saf_dot_trace_step(const PSMatrix& X, const PSMatrix& WH, double* dot, d
   return true;
 }
 
-double ps_norm(const PSMatrix& A) {
-  CommScope cs(A.grid);  // MatrixNorm: max column abs-sum; columns are local
-  if (blk_any({&A})) {
-    double v = 0.0;
-    if (block_norm(A.loc, &v)) { g_block_counts[0] += 1; return v; }
-    g_block_counts[1] += 1;
-  }
+namespace {
+// MatrixNorm of the local panel of a matrix that is not in block form: ps_norm without its maximum over the ranks
+double norm_local(const PSMatrix& A) {
   unblock({&A});
   if (slab_on() && A.loc.expanded()) {
     // (a complex operand outside a session that takes them is refused: the real slab_norm declines it untouched)
     double v = 0.0;
     if (session_takes(A.cplx) && slab_kind(A.cplx).norm(A.loc, &v)) {
       g_slab_counts[2] += 1;
-      comm_allreduce_max(&v, 1);   // (columns are local: a rank that declines computes its part below, every rank reduces once)
       return v;
     }
     slab_refused({&A});
@@ -2465,9 +2460,112 @@ double ps_norm(const PSMatrix& A) {
   }
   DevBuf<double> sums;
   column_abs_sums(A.loc, sums);
-  double n = max_of(sums, (size_t)A.loc.cols);
-  comm_allreduce_max(&n, 1);
+  return max_of(sums, (size_t)A.loc.cols);
+}
+}  // namespace
+double ps_norm(const PSMatrix& A) {
+  CommScope cs(A.grid);  // MatrixNorm: max column abs-sum; columns are local
+  if (blk_any({&A})) {
+    double v = 0.0;
+    if (block_norm(A.loc, &v)) { g_block_counts[0] += 1; return v; }
+    g_block_counts[1] += 1;
+  }
+  double n = norm_local(A);
+  comm_allreduce_max(&n, 1);   // (columns are local: a rank whose slab form declines computed its part from compressed columns, every rank reduces once)
   return n;
+}
+
+long long* wom_session_counts() {
+  static long long counts[4] = {0, 0, 0, 0};
+  return counts;
+}
+namespace {
+// the gates of a fused WOM pass that are the same on every rank: a call they keep out is neither fused nor refused, and past them
+// every rank enters ONE reduction
+bool wom_gates(std::initializer_list<const PSMatrix*> ms, const PSMatrix* out = nullptr) {
+  if (options().wom_session < 2 || g_slab_depth == 0 || !all_distinct(ms) || !same_dim(ms) || blk_any(ms)) return false;
+  for (const PSMatrix* m : ms)
+    if (m->cplx || labelled(*m) || m == out) return false;
+  return world().active() || slab_on();
+}
+// the Heun tail on this rank's panel into `out`, maxima = {err, err2} of the panel; false: refused (counted)
+bool wom_heun_local(const PSMatrix& W, const PSMatrix& K0, const PSMatrix& K1, const PSMatrix& RK1, double step, double threshold, DevMat& out,
+                    double maxima[2]) {
+  const bool taken = std::isfinite(step) && std::isfinite(threshold) && slab_on() && slab_enter(mut(W)) && slab_enter(mut(K0)) &&
+                     slab_enter(mut(K1)) && slab_enter(mut(RK1)) &&
+                     slab_wom_heun(W.loc, K0.loc, K1.loc, RK1.loc, step, threshold, out, &maxima[0], &maxima[1]);
+  if (taken) {
+    g_slab_counts[1] += 7;   // the two copies and the merges into RK2 and the two differences
+    g_slab_counts[2] += 2;   // the two norms
+    wom_session_counts()[1] += 1;
+  } else {
+    wom_session_counts()[3] += 1;
+  }
+  return taken;
+}
+}  // namespace
+bool ps_wom_heun(const PSMatrix& W, const PSMatrix& K0, const PSMatrix& K1, const PSMatrix& RK1, double step, double threshold, PSMatrix& RK2,
+                 double* err, double* err2) {
+  CommScope cs(W.grid);
+  if (!wom_gates({&W, &K0, &K1, &RK1}, &RK2)) return false;
+  DevMat o;
+  double m[2] = {0.0, 0.0};
+  if (wom_heun_local(W, K0, K1, RK1, step, threshold, o, m)) {
+    install_like(RK2, W, false, std::move(o));
+  } else {
+    if (!world().active()) return false;
+    // (across ranks: this rank runs the calls on its panel and brings the maxima of its own columns to the one reduction)
+    PSMatrix Temp;
+    ps_copy(W, RK2);
+    ps_increment(K0, RK2, step * 0.5, threshold);
+    ps_increment(K1, RK2, step * 0.5, threshold);
+    ps_copy(RK1, Temp);
+    ps_increment(RK2, Temp, -1.0, threshold);
+    m[0] = norm_local(Temp);
+    ps_copy(RK2, Temp);
+    ps_increment(W, Temp, -1.0, threshold);
+    m[1] = norm_local(Temp);
+  }
+  comm_allreduce_max(m, 2);
+  *err = m[0];
+  *err2 = m[1];
+  return true;
+}
+bool ps_wom_heun_step(const PSMatrix& W, const PSMatrix& K0, const PSMatrix& K1, const PSMatrix& RK1, double step, double threshold,
+                      PSMatrix& RK2out, double* err, double* err2) {
+  CommScope cs(W.grid);
+  if (!wom_gates({&W, &K0, &K1, &RK1}, &RK2out)) return false;
+  DevMat o;
+  double m[2] = {0.0, 0.0};
+  if (!wom_heun_local(W, K0, K1, RK1, step, threshold, o, m)) return false;
+  pack(o);
+  install_like(RK2out, W, false, std::move(o));
+  comm_allreduce_max(m, 2);
+  *err = m[0];
+  *err2 = m[1];
+  return true;
+}
+bool ps_wom_c_dots(const PSMatrix& X, const PSMatrix& W, const PSMatrix& XA, double out[2]) {
+  CommScope cs(X.grid);
+  if (!wom_gates({&X, &W, &XA})) return false;
+  double s[2] = {0.0, 0.0};
+  const bool taken = slab_on() && slab_enter(mut(X)) && slab_enter(mut(W)) && slab_enter(mut(XA)) && slab_wom_c_dots(X.loc, W.loc, XA.loc, s);
+  if (taken) {
+    g_slab_counts[2] += 2;   // the two dots
+    wom_session_counts()[2] += 1;
+  } else {
+    wom_session_counts()[3] += 1;
+    if (!world().active()) return false;
+    double d[2];
+    dot_local(X, W, d);
+    s[0] = d[0];
+    dot_local(W, XA, d);
+    s[1] = d[0];
+  }
+  comm_allreduce_sum(s, 2);
+  out[0] = s[0];
+  out[1] = s[1];
+  return true;
 }
 
 double ps_sigma(const PSMatrix& A) {

@@ -517,29 +517,42 @@ void compute_dense_foe(const PSMatrix& H, const PSMatrix& ISQ, double trace, PSM
 
 namespace {
 // ComputeX (:449-473): X = W (I - W^2), optionally hands W^2 back
-void wom_compute_x(const PSMatrix& W, const PSMatrix& I, double threshold, PSMatrix& Out, PSMatrix* W2_out) {
+// (session: option wom_session -- a copy, a scaling and a merge are one ps_copy_axpby where that has their bits)
+void wom_compute_x(const PSMatrix& W, const PSMatrix& I, double threshold, PSMatrix& Out, PSMatrix* W2_out, bool session) {
   PSMatrix W2, Temp;
   ps_multiply(W, W, W2, 1.0, 0.0, threshold);
-  ps_copy(W2, Temp);
-  ps_scale(Temp, -1.0);
-  ps_increment(I, Temp, 1.0, threshold);
+  if (session) {
+    ps_copy_axpby(W2, I, Temp, 1.0, -1.0, threshold);   // CopyMatrix(W2, Temp); ScaleMatrix(Temp, -1); IncrementMatrix(I, Temp, 1, threshold)
+  } else {
+    ps_copy(W2, Temp);
+    ps_scale(Temp, -1.0);
+    ps_increment(I, Temp, 1.0, threshold);
+  }
   ps_multiply(W, Temp, Out, 1.0, 0.0, threshold);
   if (W2_out) *W2_out = std::move(W2);
 }
 void wom_gc_step(const PSMatrix& X, const PSMatrix& A, double threshold, PSMatrix& Out) {  // :474-483
   ps_multiply(X, A, Out, -0.5, 0.0, threshold);
 }
-void wom_c_step(const PSMatrix& X, const PSMatrix& A, const PSMatrix& W, double threshold, PSMatrix& Out) {  // :484-507
+void wom_c_step(const PSMatrix& X, const PSMatrix& A, const PSMatrix& W, double threshold, PSMatrix& Out, bool session) {  // :484-507
   PSMatrix XA;
   ps_multiply(X, A, XA, 1.0, 0.0, threshold);
   double d[2];
-  ps_dot(X, W, d);
-  const double denom = d[0];
-  ps_dot(W, XA, d);
-  const double num = d[0];
-  ps_copy(X, Out);
-  ps_scale(Out, -1.0 * num / denom);
-  ps_increment(XA, Out, 1.0, 0.0);
+  if (!session || !ps_wom_c_dots(X, W, XA, d)) {   // (option wom_session = 2: both dots from one kernel and one read-back)
+    double e[2];
+    ps_dot(X, W, e);
+    d[0] = e[0];
+    ps_dot(W, XA, e);
+    d[1] = e[0];
+  }
+  const double denom = d[0], num = d[1];
+  if (session) {
+    ps_copy_axpby(X, XA, Out, 1.0, -1.0 * num / denom, 0.0);   // CopyMatrix(X, Out); ScaleMatrix(Out, -num / denom); IncrementMatrix(XA, Out)
+  } else {
+    ps_copy(X, Out);
+    ps_scale(Out, -1.0 * num / denom);
+    ps_increment(XA, Out, 1.0, 0.0);
+  }
   ps_scale(Out, -0.5);
 }
 }  // namespace
@@ -548,6 +561,8 @@ void wom_c_step(const PSMatrix& X, const PSMatrix& A, const PSMatrix& W, double 
 void solver_wom(const PSMatrix& H, const PSMatrix& ISQ, PSMatrix& K, double inv_temp, const double* trace_in,
                 const double* mu_in, double* energy_out, const SolverParameters& p) {
   CommScope cs(H.grid);
+  last_trace() = SolverTrace();
+  drop_pending_exchange();
   const bool GC = mu_in != nullptr;
   if (p.be_verbose) {
     log_header("Density Matrix Solver");
@@ -565,6 +580,13 @@ void solver_wom(const PSMatrix& H, const PSMatrix& ISQ, PSMatrix& K, double inv_
   ps_similarity(H, ISQ, ISQT, WH, p.threshold);
   balance_permute(WH, p);
   balance_permute(IMat, p);
+  // Option wom_session: the loop runs in a slab session as CGSolver's does (W, A, X, W W, K0, K1, RK1 and RK2 stay in slab form
+  // between the six products of a step; real operands, no process slices), 2: the tail of a trial -- RK2, err and err2 -- is one
+  // pass over the runs (ps_wom_heun) and the canonical step's two dots are one kernel (ps_wom_c_dots).  A call the gates keep out
+  // runs the calls as before
+  const bool session = options().wom_session != 0 && !H.cplx && !ISQ.cplx && !(H.grid && H.grid->num_slices > 1);
+  SlabSession slab(session);
+  if (slab.opened) wom_session_counts()[0] += 1;
   ps_copy(WH, A);
   if (GC) ps_increment(IMat, A, -1.0 * (*mu_in), 0.0);
   ps_copy(IMat, W);
@@ -576,43 +598,60 @@ void solver_wom(const PSMatrix& H, const PSMatrix& ISQ, PSMatrix& K, double inv_
   }
   auto gradient = [&](const PSMatrix& Xm, const PSMatrix& Wm, PSMatrix& Kout) {
     if (GC) wom_gc_step(Xm, A, p.threshold, Kout);
-    else wom_c_step(Xm, A, Wm, p.threshold, Kout);
+    else wom_c_step(Xm, A, Wm, p.threshold, Kout, session);
   };
   int II = 0;
   double B_I = 0.0, step = 1.0, energy = 0.0;
   while (B_I < inv_temp) {
     step = std::fmin(step, inv_temp - B_I);
-    wom_compute_x(W, IMat, p.threshold, X, &KOrth);
+    wom_compute_x(W, IMat, p.threshold, X, &KOrth, session);
     double d[2];
     ps_dot(WH, KOrth, d);
     energy = d[0];
     gradient(X, W, K0);
     ++II;
-    double err = 0.0;
+    double err = 0.0, err2 = 0.0;
+    bool have_err2 = false;   // (the fused tail computes the accepted step's err2 with every trial's err)
     auto trial = [&]() {                                                       // :358-377 / :380-398
-      ps_copy(K0, RK1);
-      ps_scale(RK1, step);
-      ps_increment(W, RK1, 1.0, p.threshold);
-      wom_compute_x(RK1, IMat, p.threshold, X, nullptr);
+      if (session) {
+        ps_copy_axpby(K0, W, RK1, 1.0, step, p.threshold);   // CopyMatrix(K0, RK1); ScaleMatrix(RK1, step); IncrementMatrix(W, RK1, 1, threshold)
+      } else {
+        ps_copy(K0, RK1);
+        ps_scale(RK1, step);
+        ps_increment(W, RK1, 1.0, p.threshold);
+      }
+      wom_compute_x(RK1, IMat, p.threshold, X, nullptr, session);
       gradient(X, RK1, K1);
       ++II;
-      ps_copy(W, RK2);
-      ps_increment(K0, RK2, step * 0.5, p.threshold);
-      ps_increment(K1, RK2, step * 0.5, p.threshold);
-      ps_copy(RK1, Temp);
-      ps_increment(RK2, Temp, -1.0, p.threshold);
-      err = ps_norm(Temp);
+      have_err2 = session && ps_wom_heun(W, K0, K1, RK1, step, p.threshold, RK2, &err, &err2);
+      if (!have_err2) {
+        ps_copy(W, RK2);
+        ps_increment(K0, RK2, step * 0.5, p.threshold);
+        ps_increment(K1, RK2, step * 0.5, p.threshold);
+        ps_copy(RK1, Temp);
+        ps_increment(RK2, Temp, -1.0, p.threshold);
+        err = ps_norm(Temp);
+      }
+      SolverTrace& t = last_trace();   // (one record per trial, rejected ones included)
+      t.value.push_back(err);
+      t.sigma.push_back(step);
+      t.energy.push_back(energy);
+      t.nnz.push_back(RK2.loc.nnz);
+      t.iterations += 1;
     };
     trial();
     while (err > 1.1 * p.step_thresh) {
       step = step * std::pow(p.step_thresh / err, 0.5);
       trial();
     }
-    ps_copy(RK2, Temp);
-    ps_increment(W, Temp, -1.0, p.threshold);
-    const double err2 = ps_norm(Temp);
+    if (!have_err2) {
+      ps_copy(RK2, Temp);
+      ps_increment(W, Temp, -1.0, p.threshold);
+      err2 = ps_norm(Temp);
+    }
     if (err2 < p.converge_diff) break;                                         // "Early Exit Triggered"
-    ps_copy(RK2, W);
+    if (session) W = std::move(RK2);   // (CopyMatrix(RK2, W): the next trial rebuilds RK2 before it is read)
+    else ps_copy(RK2, W);
     const double B_I_old = B_I;
     B_I = B_I + step;
     step = step * std::pow(p.step_thresh / err, 0.5);
@@ -638,6 +677,9 @@ void solver_wom(const PSMatrix& H, const PSMatrix& ISQ, PSMatrix& K, double inv_
     ps_dot(WH, KOrth, d);
     *energy_out = d[0];
   }
+  slab.close();
+  ps_slab_leave(KOrth);
+  ps_slab_leave(WH);
   balance_undo(KOrth, p);
   ps_similarity(KOrth, ISQT, ISQ, Out, p.threshold);
   if (p.be_verbose) log_exit();

@@ -275,6 +275,28 @@ int ntpoly_amd_scale_fold_update_step(const int* ih_X, const int* ih_X2, const d
 int ntpoly_amd_scale_fold_dot_trace(const int* ih_X, const int* ih_WH, double* dot, double* trace) {
   return ps_saf_dot_trace_step(*get_unpacked(ih_X), *get_unpacked(ih_WH), dot, trace) ? 1 : 0;
 }
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end, option wom_session = 2: the tail of one Heun trial of the WOM
+// solvers on caller-held real matrices W, K0, K1 and RK1.  The operands are brought into slab form, the pass runs, RK2 is packed into
+// the result handle: RK2out = (W + c K0) + c K1 with c = *step * 0.5 as CopyMatrix and two IncrementMatrix calls at *threshold build
+// it, *err = MatrixNorm of RK1 - RK2 and *err2 = MatrixNorm of RK2 - W, each difference merged at *threshold.  Returns 1 when taken, 0
+// when refused or gated: every handle, *err and *err2 are then as they were.
+int ntpoly_amd_wom_heun_step(const int* ih_W, const int* ih_K0, const int* ih_K1, const int* ih_RK1, const double* step, const double* threshold,
+                             int* ih_RK2out, double* err, double* err2) {
+  return ps_wom_heun_step(*get_unpacked(ih_W), *get_unpacked(ih_K0), *get_unpacked(ih_K1), *get_unpacked(ih_RK1), *step, *threshold,
+                          *get_unpacked(ih_RK2out), err, err2) ? 1 : 0;
+}
+// ... and the two dots of the canonical step: out[0] = DotMatrix(X, W), out[1] = DotMatrix(W, XA) from one kernel and one read-back,
+// nothing written.  Returns 1 when taken, 0 when refused or gated: out is then as it was.
+int ntpoly_amd_wom_c_dots(const int* ih_X, const int* ih_W, const int* ih_XA, double out[2]) {
+  double d[2];
+  if (!ps_wom_c_dots(*get_unpacked(ih_X), *get_unpacked(ih_W), *get_unpacked(ih_XA), d)) return 0;
+  out[0] = d[0];
+  out[1] = d[1];
+  return 1;
+}
+// the hull of a column's four runs, in rows, up to which the Heun pass holds the column in registers (longer columns read their
+// runs once per sweep): tests build operands on both sides of it
+int ntpoly_amd_wom_heun_register_rows() { return slab_wom_heun_register_rows(); }
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: TRS4's chain on caller-held matrices X and X2 (what the
 // loop's product X X would be), real or -- in a session with complex_ok and option complex_trs4 -- complex.  The two operands are
 // brought into slab form, *trace_fx = dot(X2, 4 X - 3 X2) and *trace_gx = dot(X2, I - 2 X + X2) (their real parts) come from the

@@ -998,6 +998,12 @@ _COUNTERS = {
     (the vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the calls it replaces (the merge of an
     update, the dot, the next trace).  A step kept out by a gate (the option off, no open real session, a complex operand, block
     form, a labelled slab form, alignments that differ, a WH the dot cannot read as runs) is neither fused nor counted as refused"""),
+    "wom_session": (("solves", "heun_passes", "c_dot_passes", "refused"),
+                    """WOM_GC / WOM_C in a slab session (option wom_session; csrc/wom_heun.hip k_wom_heun / k_wom_c_dots) since start: solves that
+    ran in a slab session, Heun tails fused, pairs of dots of the canonical step fused, passes refused past the gates (the vocabulary
+    calls ran instead); slab_algebra_counts() counts a fused pass as the calls it replaces (seven merges / copies and two norms; two
+    dots).  A pass kept out by a gate (the option below 2, no open real session, a complex operand, block form, a labelled slab
+    form, dimensions that differ, one matrix given twice) counts nowhere"""),
     "complex_scale_fold": (("updates", "dot_traces", "refused"),
                            """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
     pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
@@ -1197,6 +1203,32 @@ def scale_fold_dot_trace(X, WH):
     lib.ntpoly_amd_scale_fold_dot_trace.restype = C.c_int
     ok = lib.ntpoly_amd_scale_fold_dot_trace(X.ih, WH.ih, C.byref(dot), C.byref(tr))
     return (float(dot.value), float(tr.value)) if ok else None
+
+
+def wom_heun_step(W, K0, K1, RK1, step, threshold, RK2out):
+    """DIAGNOSTIC, inside `with solver_session():`, option wom_session = 2 -- the tail of one Heun trial of the WOM solvers on
+    caller-held real matrices (csrc/wom_heun.hip): RK2out = (W + c K0) + c K1 with c = step * 0.5, as CopyMatrix and two
+    IncrementMatrix calls at `threshold` build it.  Returns (err, err2) = (MatrixNorm(RK1 - RK2), MatrixNorm(RK2 - W)), each
+    difference merged at `threshold`, when taken; None: refused or gated, every matrix as it was."""
+    err, err2 = C.c_double(0.0), C.c_double(0.0)
+    lib.ntpoly_amd_wom_heun_step.restype = C.c_int
+    ok = lib.ntpoly_amd_wom_heun_step(W.ih, K0.ih, K1.ih, RK1.ih, d(step), d(threshold), RK2out.ih, C.byref(err), C.byref(err2))
+    return (float(err.value), float(err2.value)) if ok else None
+
+
+def wom_c_dots(X, W, XA):
+    """DIAGNOSTIC, inside `with solver_session():`, option wom_session = 2 -- the two dots of WOM_C's step on caller-held real
+    matrices from one kernel and one read-back: (denom, num) = (dot(X, W), dot(W, XA)); None: refused or gated."""
+    out = (C.c_double * 2)()
+    lib.ntpoly_amd_wom_c_dots.restype = C.c_int
+    ok = lib.ntpoly_amd_wom_c_dots(X.ih, W.ih, XA.ih, out)
+    return (float(out[0]), float(out[1])) if ok else None
+
+
+def wom_heun_register_rows():
+    """the hull of a column's four runs, in rows, up to which the Heun pass (csrc/wom_heun.hip) holds the column in registers"""
+    lib.ntpoly_amd_wom_heun_register_rows.restype = C.c_int
+    return int(lib.ntpoly_amd_wom_heun_register_rows())
 
 
 def trs4_chain_step(X, X2, sigma, P):
