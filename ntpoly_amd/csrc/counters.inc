@@ -38,6 +38,12 @@ NTP_COUNTER(cg_dots, 4, cg_dots_counts)
 // the gates (the vocabulary calls ran instead).  A pass kept out by a gate -- the option below 2, no open real session, a complex
 // operand, block form, a labelled slab form, dimensions that differ, one matrix given twice -- counts nowhere
 NTP_COUNTER(wom_session, 4, wom_session_counts)
+// PurificationExtrapolate in a slab session (option purify_session; engine.hpp ps_purify_tail): [0] solves that ran in a slab
+// session, [1] tails fused in the fold branch (k_purify_tail writes N' = 2 D - D S D), [2] tails fused in the plain branch (nothing
+// written), [3] passes refused past the gates (the vocabulary calls ran instead).  A pass kept out by a gate -- the option below 2,
+// no open real session, a complex operand, block form, a labelled slab form, dimensions that differ, one matrix given twice --
+// counts nowhere
+NTP_COUNTER(purify_session, 4, purify_session_counts)
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update):
 // [0] trace passes fused, [1] updates fused, [2] updates refused (the vocabulary calls ran instead).  A step that never reaches
 // the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled slab form, alignments

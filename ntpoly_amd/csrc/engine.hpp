@@ -298,6 +298,25 @@ bool ps_wom_c_dots(const PSMatrix& X, const PSMatrix& W, const PSMatrix& XA, dou
 bool ps_wom_heun_step(const PSMatrix& W, const PSMatrix& K0, const PSMatrix& K1, const PSMatrix& RK1, double step, double threshold,
                       PSMatrix& RK2out, double* err, double* err2);
 long long* wom_session_counts();   // (slots: counters.inc)
+// PurificationExtrapolate (GeometryOptimizationModule.F90:24-136) inside a real slab session, option purify_session = 2
+// (purify_tail.hip).  ps_purify_tail: everything behind the iteration's two products in one pass and one read-back.  D = the
+// working density, N = the product D S D, S = the working overlap.  fold: N becomes N' = 2 D - N, what ScaleMatrix(N, -1);
+// IncrementMatrix(D, N, 2) leave, values and pattern bit for bit; otherwise N' = N stays the product's output.  *norm = MatrixNorm of
+// D - N' (merged at threshold 0) and *next_trace = DotMatrix(N', S), each with the bits ps_norm / ps_dot give in the session.  D
+// and S are only read.  Counted in slab_algebra_counts() as the calls replaced (fold: two merges, the copy, the scaling, the norm
+// and the dot; plain: one merge, the copy, the norm and the dot).
+// Collective: past gates that are the same on every rank (the option below 2, no open real session, a complex operand, block form,
+// a labelled slab form, dimensions that differ, one matrix given twice) each rank enters ONE sum-reduction of the dot and ONE
+// max-reduction of the norm; across ranks a rank whose panel is not taken builds its N' with the local calls, takes its parts
+// from the local dot and column sums, joins the reductions, and the call still returns true.  false: nothing done (an operand
+// still in compressed columns may have been turned into slab form) -- the caller makes the calls.  On one rank that is also the
+// answer where the pass is refused (counted so: an operand the slab form cannot hold, a D or N that is a view, alignments that
+// differ, runs far apart, an input that is not finite, a kept value that is exactly zero).
+bool ps_purify_tail(const PSMatrix& D, PSMatrix& N, const PSMatrix& S, bool fold, double* norm, double* next_trace);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_purify_tail_step): the same pass with N' packed into Nout (plain: a copy of N); D, N and S keep
+// their values.  One rank only (across ranks it is gated: no reduction is entered).  false: refused or gated, everything as it was
+bool ps_purify_tail_step(const PSMatrix& D, const PSMatrix& N, const PSMatrix& S, bool fold, PSMatrix& Nout, double* norm, double* next_trace);
+long long* purify_session_counts();   // (slots: counters.inc)
 // Option complex_scale_fold (one rank, inside a session that takes complex operands): the four calls above take COMPLEX operands
 // (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of
 // the vocabulary calls at threshold 0 bit for bit; the scale branch's pass is slab_dot_trace_c over X and WH as it stands -- slab

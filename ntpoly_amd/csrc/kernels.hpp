@@ -342,6 +342,14 @@ bool slab_wom_heun(const DevMat& W, const DevMat& K0, const DevMat& K1, const De
 int slab_wom_heun_register_rows();
 // out[0] = the LOCAL dot(X, W), out[1] = the LOCAL dot(W, XA), each with the bits of slab_dot, from one kernel and one read-back
 bool slab_wom_c_dots(const DevMat& X, const DevMat& W, const DevMat& XA, double out[2]);
+// The tail of an iteration of PurificationExtrapolate on slab-form matrices (purify_tail.hip; real, square or column panels), D the
+// working density, N = D S D the product's output, S the overlap.  fold: Out = N' = 2 D - N as a fresh slab-form matrix, the values
+// and pattern of ScaleMatrix(N, -1); IncrementMatrix(D, N, 2) bit for bit; otherwise N' = N and nothing is written.  *norm = the
+// LOCAL MatrixNorm of D - N' merged at threshold 0 with the bits slab_norm gives on that difference in slab form; dot = the LOCAL
+// DotMatrix(N', S) with the bits of slab_dot(N', S).  One pass over the three runs, one host read-back.  false: refused (D or N not
+// in zero-free slab form, labelled, a view, alignments that differ, an S that is neither a zero-free slab form nor a read-only
+// view, runs far apart, an input that is not finite, a kept value that is exactly zero), nothing changed
+bool slab_purify_tail(const DevMat& D, const DevMat& N, const DevMat& S, bool fold, DevMat& Out, double* norm, double dot[2]);
 // PM purification on a slab-form iterate (slab_extra.hip).  The rows of each column that compressed columns would hold as STORED
 // ZEROS (a1 = 0 when sigma > 1/2, unfiltered tails that underflow) travel next to the zero-free runs: rows row[off[j] .. off[j + 1])
 // of column j, ascending, disjoint from the run's non-zeros.  off.p == nullptr: no such row.

@@ -2568,6 +2568,74 @@ bool ps_wom_c_dots(const PSMatrix& X, const PSMatrix& W, const PSMatrix& XA, dou
   return true;
 }
 
+long long* purify_session_counts() {
+  static long long counts[4] = {0, 0, 0, 0};
+  return counts;
+}
+namespace {
+// the gates of a fused extrapolator tail that are the same on every rank: a call they keep out is neither fused nor refused, and
+// past them every rank enters the same two reductions
+bool purify_gates(std::initializer_list<const PSMatrix*> ms, const PSMatrix* out = nullptr) {
+  if (options().purify_session < 2 || g_slab_depth == 0 || !all_distinct(ms) || !same_dim(ms) || blk_any(ms)) return false;
+  for (const PSMatrix* m : ms)
+    if (m->cplx || m->loc.blocked() || labelled(*m) || m == out) return false;
+  return world().active() || slab_on();
+}
+// the tail on this rank's panel: `out` = N' in the fold branch, parts = {dot, 0, norm} of the panel; false: refused (counted)
+bool purify_tail_local(const PSMatrix& D, const PSMatrix& N, const PSMatrix& S, bool fold, DevMat& out, double parts[3]) {
+  const bool taken = slab_on() && slab_enter(mut(S)) && slab_enter(mut(D)) && slab_enter(mut(N)) &&
+                     slab_purify_tail(D.loc, N.loc, S.loc, fold, out, &parts[2], parts);
+  if (taken) {
+    g_slab_counts[1] += fold ? 3 : 2;   // the merges and the copy
+    g_slab_counts[2] += fold ? 3 : 2;   // (the scaling,) the norm and the dot
+    purify_session_counts()[fold ? 1 : 2] += 1;
+  } else {
+    purify_session_counts()[3] += 1;
+  }
+  return taken;
+}
+}  // namespace
+bool ps_purify_tail(const PSMatrix& D, PSMatrix& N, const PSMatrix& S, bool fold, double* norm, double* next_trace) {
+  CommScope cs(D.grid);
+  if (!purify_gates({&D, &N, &S})) return false;
+  DevMat o;
+  double s[3] = {0.0, 0.0, 0.0};
+  if (purify_tail_local(D, N, S, fold, o, s)) {
+    if (fold) install_like(N, D, false, std::move(o));
+  } else {
+    if (!world().active()) return false;
+    // (across ranks: this rank runs the calls on its panel and brings its parts to the two reductions)
+    if (fold) {
+      ps_scale(N, -1.0);
+      ps_increment(D, N, 2.0, 0.0);
+    }
+    PSMatrix Temp;
+    ps_copy(D, Temp);
+    ps_increment(N, Temp, -1.0, 0.0);
+    s[2] = norm_local(Temp);
+    dot_local(N, S, s);
+  }
+  comm_allreduce_sum(s, 2);
+  comm_allreduce_max(&s[2], 1);
+  *next_trace = s[0];
+  *norm = s[2];
+  return true;
+}
+bool ps_purify_tail_step(const PSMatrix& D, const PSMatrix& N, const PSMatrix& S, bool fold, PSMatrix& Nout, double* norm, double* next_trace) {
+  CommScope cs(D.grid);
+  // (one rank only: a refusal is this rank's own answer, so across ranks the call is gated before any rank could wait in a reduction)
+  if (world().active() || !purify_gates({&D, &N, &S}, &Nout)) return false;
+  DevMat o;
+  double s[3] = {0.0, 0.0, 0.0};
+  if (!purify_tail_local(D, N, S, fold, o, s)) return false;
+  if (fold) pack(o);
+  else o = packed_copy(N.loc);
+  install_like(Nout, D, false, std::move(o));
+  *next_trace = s[0];
+  *norm = s[2];
+  return true;
+}
+
 double ps_sigma(const PSMatrix& A) {
   CommScope cs(A.grid);  // MatrixSigma (distributed_algebra_includes/MatrixSigma.f90)
   const double n = ps_norm(A);

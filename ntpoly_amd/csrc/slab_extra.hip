@@ -14,6 +14,7 @@
 #include <memory>
 
 #include "device_util.hpp"
+#include "fresh_slabs.hpp"
 #include "kernels.hpp"
 
 namespace ntp {
@@ -222,49 +223,6 @@ __global__ void k_sa_trs4_span(const int32_t* __restrict__ fa, const int32_t* __
   if (lb[j] >= fb[j]) { f = min(f, fb[j]); l = max(l, lb[j]); }
   span[j] = (l / al + 1) * al - f / al * al;
 }
-__global__ __launch_bounds__(256) void k_sa_count_sum(const int32_t* __restrict__ v, int n, unsigned long long* __restrict__ out) {
-  __shared__ long long red[4];
-  long long s = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) s += v[i];
-  s = wave_sum_i64(s);
-  if (lane_id() == 0) red[threadIdx.x / WAVE] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const long long t = red[0] + red[1] + red[2] + red[3];
-    if (t) atomicAdd(out, (unsigned long long)t);
-  }
-}
-// deterministic sum of n (a, b) pairs: fixed assignment of elements to threads, fixed tree -- the same bits every run
-__global__ __launch_bounds__(256) void k_sa_sum_pairs(const double* __restrict__ in, int n, int chunk, double* __restrict__ out) {
-  __shared__ double ra[256], rb[256];
-  const int lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
-  double a = 0.0, b = 0.0;
-  for (int i = lo + threadIdx.x; i < hi; i += 256) {
-    a = __dadd_rn(a, in[2 * (size_t)i]);
-    b = __dadd_rn(b, in[2 * (size_t)i + 1]);
-  }
-  ra[threadIdx.x] = a;
-  rb[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      ra[threadIdx.x] = __dadd_rn(ra[threadIdx.x], ra[threadIdx.x + o]);
-      rb[threadIdx.x] = __dadd_rn(rb[threadIdx.x], rb[threadIdx.x + o]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { out[2 * blockIdx.x] = ra[0]; out[2 * blockIdx.x + 1] = rb[0]; }
-}
-void sum_pairs_async(const double* part, int n, double* out2) {
-  const int chunk = 2048, g = cdiv(n, chunk);
-  if (g <= 1) {
-    hipLaunchKernelGGL(k_sa_sum_pairs, dim3(1), dim3(256), 0, stream(), part, n, std::max(n, 1), out2);
-    return;
-  }
-  DevBuf<double> lvl((size_t)2 * g);
-  hipLaunchKernelGGL(k_sa_sum_pairs, dim3(g), dim3(256), 0, stream(), part, n, chunk, lvl.p);
-  hipLaunchKernelGGL(k_sa_sum_pairs, dim3(1), dim3(256), 0, stream(), lvl.p, g, g, out2);
-}
 // the tail of a traces-style pass: the n pairs of `part` summed member by member, both sums fetched in the pass's one host wait
 void fetch_pair_sums(const DevBuf<double>& part, int n, double out2[2]) {
   DevBuf<double> res(2);
@@ -273,70 +231,6 @@ void fetch_pair_sums(const DevBuf<double>& part, int n, double out2[2]) {
   ft.add(res.p, 2, out2);
   ft.run();
 }
-struct IsrOut {   // one output: values into the slot at base[j], the kept extent and count per column
-  void* val;
-  int32_t* first;
-  int32_t* last;
-  int32_t* count;
-  int64_t* off;
-};
-// The scaffold of a pass that writes one or two fresh slab-form matrices of n columns, `bound` entries (+ kIndexSlack) each.
-// The pass launches its span kernel into `span`, calls scan(), launches its chain kernel on out(q), base, stat (and part, with
-// sums), then finish(): the kept counts summed per output, the pairs of `part` summed, and the pass's one host wait.
-struct FreshSlabs {
-  const int n, outs;
-  const bool cplx;
-  std::unique_ptr<SlabForm> fo[2];
-  DevBuf<int32_t> span;
-  DevBuf<int64_t> base;
-  DevBuf<unsigned long long> stat, tot;
-  DevBuf<double> part, res;   // (with sums only)
-  FreshSlabs(int n_, int outs_, int64_t bound, bool cplx_, bool sums)
-      : n(n_), outs(outs_), cplx(cplx_), span((size_t)n_), base((size_t)n_ + 1), stat(1), tot((size_t)outs_) {
-    for (int q = 0; q < outs; ++q) {
-      fo[q].reset(new SlabForm());
-      fo[q]->first.alloc((size_t)n); fo[q]->last.alloc((size_t)n); fo[q]->count.alloc((size_t)n); fo[q]->off.alloc((size_t)n + 1);
-      fo[q]->val.alloc(((size_t)bound + kIndexSlack) * (cplx ? 2 : 1));
-    }
-    if (sums) { part.alloc((size_t)2 * n); res.alloc(2); }
-    stat.zero();
-    tot.zero();
-  }
-  IsrOut out(int q) const {
-    if (q >= outs) return IsrOut{nullptr, nullptr, nullptr, nullptr, nullptr};
-    return IsrOut{fo[q]->val.p, fo[q]->first.p, fo[q]->last.p, fo[q]->count.p, fo[q]->off.p};
-  }
-  void scan() { scan_i32_async(span.p, base.p, (int64_t)n); }
-  // R[q]: the finished outputs of `rows` rows in slots aligned to `al`; sums: the first nsums sums of part's pairs.
-  // false: the chain kernel set stat (1: a scaled entry underflows to zero, 2: a union extent beyond `bound`) -- nothing returned
-  bool finish(const char* tag, int32_t rows, int al, DevMat* R, double* sums = nullptr, int nsums = 0) {
-    const dim3 sum_grid(std::max(1, std::min(256, cdiv(n, 1024))));
-    for (int q = 0; q < outs; ++q) hipLaunchKernelGGL(k_sa_count_sum, sum_grid, dim3(256), 0, stream(), fo[q]->count.p, n, tot.p + q);
-    if (nsums) sum_pairs_async(part.p, n, res.p);
-    int64_t nnz[2] = {0, 0}, slots = 0;
-    unsigned long long hs = 0;
-    {
-      ScalarFetch ft;
-      ft.add(tot.p, outs, nnz);
-      ft.add(base.p + n, 1, &slots);
-      ft.add(stat.p, 1, &hs);
-      if (nsums) ft.add(res.p, nsums, sums);
-      ft.run();
-    }
-    if (hs != 0) {   // (the caller takes the vocabulary calls)
-      if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
-        std::fprintf(stderr, "[%s] refused:%s%s\n", tag, (hs & 1ull) ? " a scaled entry underflows to zero" : "", (hs & 2ull) ? " runs far apart" : "");
-      return false;
-    }
-    for (int q = 0; q < outs; ++q) {
-      fo[q]->row_pad = al;
-      fo[q]->slots = slots;
-      R[q].rows = rows; R[q].cols = n; R[q].cplx = cplx; R[q].nnz = nnz[q]; R[q].zero_free = 1;
-      R[q].slab = std::move(fo[q]);
-    }
-    return true;
-  }
-};
 bool trs4_operands(const DevMat& X, const DevMat& X2) {
   auto ok = [](const DevMat& M) {
     return M.expanded() && !M.cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1;

@@ -189,6 +189,8 @@ void compute_exponential_pade(const PSMatrix& In, PSMatrix& OutMat, const Solver
 void purification_extrapolate(const PSMatrix& PreviousDensity, const PSMatrix& Overlap, double trace, PSMatrix& NewDensityOut,
                               const SolverParameters& p_in) {
   CommScope cs(PreviousDensity.grid);                  // :24-136
+  last_trace() = SolverTrace();
+  drop_pending_exchange();
   Monitor mon;
   const SolverParameters p = with_monitor(p_in, mon);
   solver_header("Density Matrix Extrapolator", "niklasson2010trace", p, "Purification");
@@ -198,24 +200,56 @@ void purification_extrapolate(const PSMatrix& PreviousDensity, const PSMatrix& O
   ps_copy(Overlap, WorkingOverlap);
   balance_permute(WorkingDensity, p);
   balance_permute(WorkingOverlap, p);
+  // Option purify_session: the loop runs in a slab session as WOM's does (the density, the overlap and both products stay in slab
+  // form; real operands, no process slices; CopyMatrix(NewDensity, WorkingDensity) is a move), 2: everything behind the two
+  // products -- the fold, the norm of the change and the NEXT iteration's trace -- is one pass over the runs (ps_purify_tail); a
+  // trace the pass did not leave (the first iteration, a refused pass) comes from ps_dot.  A call the gates keep out runs the
+  // calls as before
+  const bool session = options().purify_session != 0 && !PreviousDensity.cplx && !Overlap.cplx &&
+                       !(PreviousDensity.grid && PreviousDensity.grid->num_slices > 1);
+  SlabSession slab(session);
+  if (slab.opened) purify_session_counts()[0] += 1;
   if (p.be_verbose) {
     log_header("Iterations");
     log_enter();
   }
+  double carried_trace = 0.0;
+  bool have_trace = false, moved = false;   // (moved: the result sits in WorkingDensity)
   int II;
   for (II = 1; II <= p.max_iterations; ++II) {
     ps_multiply(WorkingDensity, WorkingOverlap, TempMat, 1.0, 0.0, p.threshold);
     ps_multiply(TempMat, WorkingDensity, NewDensity, 1.0, 0.0, p.threshold);
-    double d[2];
-    ps_dot(WorkingDensity, WorkingOverlap, d);
-    const double trace_value = d[0];
-    if (trace > trace_value) {
-      ps_scale(NewDensity, -1.0);
-      ps_increment(WorkingDensity, NewDensity, 2.0, 0.0);
+    double trace_value = carried_trace;
+    if (!have_trace) {
+      double d[2];
+      ps_dot(WorkingDensity, WorkingOverlap, d);
+      trace_value = d[0];
     }
-    ps_increment(NewDensity, WorkingDensity, -1.0, 0.0);
-    const double norm_value = ps_norm(WorkingDensity);
-    ps_copy(NewDensity, WorkingDensity);
+    const bool fold = trace > trace_value;
+    double norm_value = 0.0;
+    have_trace = session && ps_purify_tail(WorkingDensity, NewDensity, WorkingOverlap, fold, &norm_value, &carried_trace);
+    if (!have_trace) {
+      if (fold) {
+        ps_scale(NewDensity, -1.0);
+        ps_increment(WorkingDensity, NewDensity, 2.0, 0.0);
+      }
+      ps_increment(NewDensity, WorkingDensity, -1.0, 0.0);
+      norm_value = ps_norm(WorkingDensity);
+    }
+    {
+      SolverTrace& t = last_trace();
+      t.value.push_back(norm_value);
+      t.sigma.push_back(fold ? 1.0 : -1.0);
+      t.energy.push_back(trace_value);
+      t.nnz.push_back(NewDensity.loc.nnz);
+      t.iterations += 1;
+    }
+    if (slab.opened) {   // (the next iteration rebuilds NewDensity before it is read)
+      WorkingDensity = std::move(NewDensity);
+      moved = true;
+    } else {
+      ps_copy(NewDensity, WorkingDensity);
+    }
     monitor_append(mon, norm_value);
     if (monitor_converged(mon, p.be_verbose)) break;
     if (p.be_verbose) {
@@ -223,6 +257,11 @@ void purification_extrapolate(const PSMatrix& PreviousDensity, const PSMatrix& O
       log_element("Trace", trace_value);
       log_exit();
     }
+  }
+  if (moved) NewDensity = std::move(WorkingDensity);   // (the result is in hand wherever the loop ended)
+  if (slab.opened) {
+    slab.close();
+    ps_slab_leave(NewDensity);
   }
   if (p.be_verbose) {
     log_exit();

@@ -297,6 +297,17 @@ int ntpoly_amd_wom_c_dots(const int* ih_X, const int* ih_W, const int* ih_XA, do
 // the hull of a column's four runs, in rows, up to which the Heun pass holds the column in registers (longer columns read their
 // runs once per sweep): tests build operands on both sides of it
 int ntpoly_amd_wom_heun_register_rows() { return slab_wom_heun_register_rows(); }
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end, option purify_session = 2: the tail of one iteration of
+// PurificationExtrapolate on caller-held real matrices D (the working density), N (what the product D S D would be) and S (the
+// overlap).  The operands are brought into slab form, the pass runs, N' is packed into the result handle: with *fold != 0 Nout = 2 D - N
+// as ScaleMatrix(N, -1) and IncrementMatrix(D, N, 2) at threshold 0 build it, otherwise a copy of N; *norm = MatrixNorm of D - N'
+// merged at threshold 0, *next_trace = DotMatrix(N', S).  One rank only.  Returns 1 when taken, 0 when refused or gated (several
+// ranks are a gate): every handle, *norm and *next_trace are then as they were.
+int ntpoly_amd_purify_tail_step(const int* ih_D, const int* ih_N, const int* ih_S, const int* fold, int* ih_Nout, double* norm,
+                                double* next_trace) {
+  return ps_purify_tail_step(*get_unpacked(ih_D), *get_unpacked(ih_N), *get_unpacked(ih_S), *fold != 0, *get_unpacked(ih_Nout), norm,
+                             next_trace) ? 1 : 0;
+}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: TRS4's chain on caller-held matrices X and X2 (what the
 // loop's product X X would be), real or -- in a session with complex_ok and option complex_trs4 -- complex.  The two operands are
 // brought into slab form, *trace_fx = dot(X2, 4 X - 3 X2) and *trace_gx = dot(X2, I - 2 X + X2) (their real parts) come from the

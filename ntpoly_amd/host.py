@@ -1004,6 +1004,13 @@ _COUNTERS = {
     calls ran instead); slab_algebra_counts() counts a fused pass as the calls it replaces (seven merges / copies and two norms; two
     dots).  A pass kept out by a gate (the option below 2, no open real session, a complex operand, block form, a labelled slab
     form, dimensions that differ, one matrix given twice) counts nowhere"""),
+    "purify_session": (("solves", "fold_passes", "plain_passes", "refused"),
+                       """PurificationExtrapolate in a slab session (option purify_session; csrc/purify_tail.hip k_purify_tail) since start: solves
+    that ran in a slab session, tails fused in the fold branch (N' = 2 D - D S D written), tails fused in the plain branch (nothing
+    written), passes refused past the gates (the vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the
+    calls it replaces (fold: two merges, the copy, the scaling, the norm and the dot; plain: one merge, the copy, the norm and the
+    dot).  A pass kept out by a gate (the option below 2, no open real session, a complex operand, block form, a labelled slab
+    form, dimensions that differ, one matrix given twice) counts nowhere"""),
     "complex_scale_fold": (("updates", "dot_traces", "refused"),
                            """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
     pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
@@ -1229,6 +1236,17 @@ def wom_heun_register_rows():
     """the hull of a column's four runs, in rows, up to which the Heun pass (csrc/wom_heun.hip) holds the column in registers"""
     lib.ntpoly_amd_wom_heun_register_rows.restype = C.c_int
     return int(lib.ntpoly_amd_wom_heun_register_rows())
+
+
+def purify_tail_step(D, N, S, fold, Nout):
+    """DIAGNOSTIC, inside `with solver_session():`, option purify_session = 2, one rank -- the tail of one iteration of PurificationExtrapolate
+    on caller-held real matrices (csrc/purify_tail.hip): D the working density, N what the product D S D would be, S the overlap.
+    With `fold` Nout = 2 D - N as ScaleMatrix(N, -1) and IncrementMatrix(D, N, 2) at threshold 0 build it, otherwise a copy of N.
+    Returns (norm, next_trace) = (MatrixNorm(D - N'), DotMatrix(N', S)) when taken; None: refused or gated, every matrix as it was."""
+    norm, nxt = C.c_double(0.0), C.c_double(0.0)
+    lib.ntpoly_amd_purify_tail_step.restype = C.c_int
+    ok = lib.ntpoly_amd_purify_tail_step(D.ih, N.ih, S.ih, C.byref(C.c_int(1 if fold else 0)), Nout.ih, C.byref(norm), C.byref(nxt))
+    return (float(norm.value), float(nxt.value)) if ok else None
 
 
 def trs4_chain_step(X, X2, sigma, P):
