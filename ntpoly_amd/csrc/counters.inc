@@ -44,6 +44,12 @@ NTP_COUNTER(wom_session, 4, wom_session_counts)
 // no open real session, a complex operand, block form, a labelled slab form, dimensions that differ, one matrix given twice --
 // counts nowhere
 NTP_COUNTER(purify_session, 4, purify_session_counts)
+// ComputeExponentialPade in a slab session (option pade_session; engine.hpp ps_pade_chain): [0] calls that ran in a slab session,
+// [1] sum passes fused (k_pade_chain<3> writes P1 and TempMat), [2] pair passes fused (k_pade_chain<1> writes LeftMat and RightMat),
+// [3] passes refused past the gates (the vocabulary calls ran instead).  A pass kept out by a gate -- the option below 2, no open
+// real session, a complex operand, block form, a labelled slab form, dimensions that differ, one matrix given twice, a number of
+// addends other than 1 or 3 -- counts nowhere
+NTP_COUNTER(pade_session, 4, pade_session_counts)
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update):
 // [0] trace passes fused, [1] updates fused, [2] updates refused (the vocabulary calls ran instead).  A step that never reaches
 // the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled slab form, alignments

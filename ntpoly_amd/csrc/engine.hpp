@@ -317,6 +317,27 @@ bool ps_purify_tail(const PSMatrix& D, PSMatrix& N, const PSMatrix& S, bool fold
 // their values.  One rank only (across ranks it is gated: no reduction is entered).  false: refused or gated, everything as it was
 bool ps_purify_tail_step(const PSMatrix& D, const PSMatrix& N, const PSMatrix& S, bool fold, PSMatrix& Nout, double* norm, double* next_trace);
 long long* purify_session_counts();   // (slots: counters.inc)
+// ComputeExponentialPade (ExponentialSolversModule.F90:152-271) inside a real slab session, option pade_session = 2
+// (pade_chain.hip).  ps_pade_chain: one of the call's two groups of merges in one pass and one read-back.  For q = 1, 2
+//   Out_q = CopyMatrix(Base); ScaleMatrix(Out_q, scales[q - 1]); IncrementMatrix(*addends[k], Out_q, coeffs[(q - 1) n_addends + k], 0)
+// for k = 0 .. n_addends - 1, n_addends 1 or 3, values and patterns bit for bit.  The inputs are only read (one still in compressed
+// columns is turned into slab form where it is).  Counted in slab_algebra_counts() as the calls replaced.  Local: no reduction
+// is entered, and the calls it replaces are local too, so across ranks each panel decides for itself.  false: nothing done --
+// kept out by a gate (the option below 2, no open real session, a complex operand, block form, a labelled slab form, dimensions
+// that differ, one matrix given twice, another n_addends: counted nowhere) or refused (counted so: an operand the slab form
+// cannot hold or a view, alignments that differ, runs far apart, an input that is not finite, a scaled value that is exactly zero
+// where an entry is held) -- the caller makes the calls.
+bool ps_pade_chain(const PSMatrix& Base, const PSMatrix* const* addends, int n_addends, const double scales[2], const double* coeffs,
+                   PSMatrix& Out1, PSMatrix& Out2);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_pade_chain_step): the same pass with both outputs packed.  One rank only (several ranks are a gate)
+bool ps_pade_chain_step(const PSMatrix& Base, const PSMatrix* const* addends, int n_addends, const double scales[2], const double* coeffs,
+                        PSMatrix& Out1, PSMatrix& Out2);
+long long* pade_session_counts();   // (slots: counters.inc)
+// solver_cg will run its loop in a slab session of its own on these operands (option cg_dots; the gate of its SlabSession).
+// *dots: the loop takes its traces from column dot passes; *complex_session: that session takes complex operands.  solver_cg
+// permutes its operands (a load balancer's permutation) BEFORE that session opens: a caller with such a permutation hands it
+// compressed columns
+bool solver_cg_opens_session(const PSMatrix& AMat, const PSMatrix& BMat, bool* dots = nullptr, bool* complex_session = nullptr);
 // Option complex_scale_fold (one rank, inside a session that takes complex operands): the four calls above take COMPLEX operands
 // (slab_extra.hip k_saf_update<double2, .>: the real kernel's scaling and merge on each part of an entry, the values and pattern of
 // the vocabulary calls at threshold 0 bit for bit; the scale branch's pass is slab_dot_trace_c over X and WH as it stands -- slab

@@ -350,6 +350,15 @@ bool slab_wom_c_dots(const DevMat& X, const DevMat& W, const DevMat& XA, double 
 // in zero-free slab form, labelled, a view, alignments that differ, an S that is neither a zero-free slab form nor a read-only
 // view, runs far apart, an input that is not finite, a kept value that is exactly zero), nothing changed
 bool slab_purify_tail(const DevMat& D, const DevMat& N, const DevMat& S, bool fold, DevMat& Out, double* norm, double dot[2]);
+// The two groups of merges of ComputeExponentialPade on slab-form matrices (pade_chain.hip; real, square or column panels): for
+// q = 1, 2  Out_q = CopyMatrix(Base); ScaleMatrix(Out_q, scales[q - 1]); IncrementMatrix(addends[k], Out_q, coeffs[(q - 1) n_addends
+// + k], threshold 0) for k = 0 .. n_addends - 1 (n_addends 1 or 3), values and patterns of the calls bit for bit, both outputs as
+// fresh slab-form matrices from ONE pass over the inputs' runs and one host read-back.  false: refused (an operand that is not a
+// zero-free, unlabelled slab form or is a view, operands named twice, alignments that differ, another n_addends, a scalar that is
+// zero or not finite, runs far apart, an input that is not finite, a scaled value that is exactly zero where an entry is held),
+// nothing changed
+bool slab_pade_chain(const DevMat& Base, const DevMat* const* addends, int n_addends, const double scales[2], const double* coeffs, DevMat& Out1,
+                     DevMat& Out2);
 // PM purification on a slab-form iterate (slab_extra.hip).  The rows of each column that compressed columns would hold as STORED
 // ZEROS (a1 = 0 when sigma > 1/2, unfiltered tails that underflow) travel next to the zero-free runs: rows row[off[j] .. off[j + 1])
 // of column j, ascending, disjoint from the run's non-zeros.  off.p == nullptr: no such row.

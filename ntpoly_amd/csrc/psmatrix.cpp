@@ -2636,6 +2636,60 @@ bool ps_purify_tail_step(const PSMatrix& D, const PSMatrix& N, const PSMatrix& S
   return true;
 }
 
+long long* pade_session_counts() {
+  static long long counts[4] = {0, 0, 0, 0};
+  return counts;
+}
+namespace {
+// the chain on this rank's panels into o1 / o2; false: kept out by a gate (counted nowhere) or refused (counted).  No reduction is
+// entered and the calls it replaces are local, so across ranks a refusal is the rank's own
+bool pade_chain_local(const PSMatrix& Base, const PSMatrix* const* A, int n_addends, const double scales[2], const double* coeffs,
+                      const PSMatrix* out1, const PSMatrix* out2, DevMat& o1, DevMat& o2) {
+  if (options().pade_session < 2 || g_slab_depth == 0 || (n_addends != 1 && n_addends != 3) || out1 == out2) return false;
+  const PSMatrix* ms[4] = {&Base, nullptr, nullptr, nullptr};
+  for (int k = 0; k < n_addends; ++k) ms[k + 1] = A[k];
+  for (int k = 0; k <= n_addends; ++k) {
+    const PSMatrix* m = ms[k];
+    if (!m || m->cplx || m->dim != Base.dim || m->loc.blocked() || labelled(*m) || m == out1 || m == out2) return false;
+    for (int i = 0; i < k; ++i)
+      if (ms[i] == m) return false;
+  }
+  bool taken = slab_on();
+  const DevMat* locs[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; taken && k <= n_addends; ++k) taken = slab_enter(mut(*ms[k]));
+  for (int k = 0; k < n_addends; ++k) locs[k] = &A[k]->loc;
+  taken = taken && slab_pade_chain(Base.loc, locs, n_addends, scales, coeffs, o1, o2);
+  if (taken) {
+    g_slab_counts[1] += 2 * (n_addends + 1);                                      // the copies and the merges
+    g_slab_counts[2] += (scales[0] != 1.0 ? 1 : 0) + (scales[1] != 1.0 ? 1 : 0);   // the scalings
+    pade_session_counts()[n_addends == 3 ? 1 : 2] += 1;
+  } else {
+    pade_session_counts()[3] += 1;
+  }
+  return taken;
+}
+}  // namespace
+bool ps_pade_chain(const PSMatrix& Base, const PSMatrix* const* addends, int n_addends, const double scales[2], const double* coeffs,
+                   PSMatrix& Out1, PSMatrix& Out2) {
+  CommScope cs(Base.grid);
+  DevMat o1, o2;
+  if (!pade_chain_local(Base, addends, n_addends, scales, coeffs, &Out1, &Out2, o1, o2)) return false;
+  install_like(Out1, Base, false, std::move(o1));
+  install_like(Out2, Base, false, std::move(o2));
+  return true;
+}
+bool ps_pade_chain_step(const PSMatrix& Base, const PSMatrix* const* addends, int n_addends, const double scales[2], const double* coeffs,
+                        PSMatrix& Out1, PSMatrix& Out2) {
+  CommScope cs(Base.grid);
+  DevMat o1, o2;
+  if (world().active() || !pade_chain_local(Base, addends, n_addends, scales, coeffs, &Out1, &Out2, o1, o2)) return false;
+  pack(o1);
+  pack(o2);
+  install_like(Out1, Base, false, std::move(o1));
+  install_like(Out2, Base, false, std::move(o2));
+  return true;
+}
+
 double ps_sigma(const PSMatrix& A) {
   CommScope cs(A.grid);  // MatrixSigma (distributed_algebra_includes/MatrixSigma.f90)
   const double n = ps_norm(A);

@@ -38,6 +38,14 @@ void ps_gather_triplets(const PSMatrix& m, HostTriplets& t) {
 }
 
 // ------------------------------------------------------------------ CG (LinearSolversModule.F90:31-171)
+// the gate of solver_cg's own slab session (option cg_dots): a caller that holds an outer session open across the solve asks it too
+bool solver_cg_opens_session(const PSMatrix& AMat, const PSMatrix& BMat, bool* dots_out, bool* complex_session_out) {
+  const bool dots = options().cg_dots != 0 && !(AMat.grid && AMat.grid->num_slices > 1);
+  const bool complex_session = dots && options().cg_dots >= 2 && AMat.cplx && BMat.cplx && complex_slab_loop(AMat) && !world().active();
+  if (dots_out) *dots_out = dots;
+  if (complex_session_out) *complex_session_out = complex_session;
+  return dots && ((!AMat.cplx && !BMat.cplx) || complex_session);
+}
 void solver_cg(const PSMatrix& AMat, PSMatrix& XMat, const PSMatrix& BMat, const SolverParameters& p_in) {
   CommScope cs(AMat.grid);
   Monitor mon;
@@ -59,9 +67,9 @@ void solver_cg(const PSMatrix& AMat, PSMatrix& XMat, const PSMatrix& BMat, const
   // Q = A P) and takes top, bottom and the new top from column dot passes over the runs (ps_cg_dots: the bits of transpose +
   // product + trace).  1: real operands; 2: also complex ones on one rank in a complex session.  A call the gates keep out runs
   // the three calls as before
-  const bool dots = options().cg_dots != 0 && !(AMat.grid && AMat.grid->num_slices > 1);
-  const bool complex_session = dots && options().cg_dots >= 2 && AMat.cplx && BMat.cplx && complex_slab_loop(AMat) && !world().active();
-  SlabSession slab(dots && ((!AMat.cplx && !BMat.cplx) || complex_session), false, complex_session);
+  bool dots = false, complex_session = false;
+  const bool eligible = solver_cg_opens_session(AMat, BMat, &dots, &complex_session);
+  SlabSession slab(eligible, false, complex_session);
   ps_copy(Identity, X);                                                        // initial guess X = I (:89)
   ps_multiply(ABalanced, X, TempMat, 1.0, 0.0, p.threshold);
   ps_copy(BBalanced, RMat);
@@ -155,28 +163,70 @@ void compute_exponential_pade(const PSMatrix& In, PSMatrix& OutMat, const Solver
   }
   SolverParameters sub = p;
   sub.threshold = sub.threshold / sigma_val;
+  // Option pade_session: everything around the CG solve runs in a slab session as purification_extrapolate's loop does (the powers,
+  // both Pade sums, P2, LeftMat and RightMat stay in slab form; real operands, no process slices; the norm above was taken before
+  // it opens), 2: each of the two groups of merges is one pass over the runs (ps_pade_chain); a pass that is refused runs the
+  // calls.  Where solver_cg opens a session of its own (solver_cg_opens_session) the outer one stays open across it and LeftMat
+  // and RightMat enter CG in slab form; otherwise they are packed, the session is closed before the solve -- the CG loop on
+  // compressed columns, as cg_dots = 0 promises -- and a second one is opened for the squarings behind it.  The same with a load
+  // balancer's permutation: solver_cg permutes its operands BEFORE its session opens, and ps_permute reads compressed columns.
+  // solver_cg packs X when its own session closes, so X re-enters once at the first squaring.  A call the gates keep out runs
+  // the calls as before
+  const bool session = options().pade_session != 0 && !In.cplx && !(In.grid && In.grid->num_slices > 1);
+  SlabSession slab(session);
+  const bool in_session = slab.opened;
+  if (in_session) pade_session_counts()[0] += 1;
   ps_multiply(ScaledMat, ScaledMat, B1, 1.0, 0.0, sub.threshold);
   ps_multiply(B1, B1, B2, 1.0, 0.0, sub.threshold);
   ps_multiply(B2, B2, B3, 1.0, 0.0, sub.threshold);
-  ps_copy(IdentityMat, P1);                                                    // :222-226
-  ps_scale(P1, 17297280.0);
-  ps_increment(B1, P1, 1995840.0, 0.0);
-  ps_increment(B2, P1, 25200.0, 0.0);
-  ps_increment(B3, P1, 56.0, 0.0);
-  ps_copy(IdentityMat, TempMat);                                               // :228-234
-  ps_scale(TempMat, 8648640.0);
-  ps_increment(B1, TempMat, 277200.0, 0.0);
-  ps_increment(B2, TempMat, 1512.0, 0.0);
-  ps_increment(B3, TempMat, 1.0, 0.0);
+  // CopyMatrix(Base, Out); ScaleMatrix(Out, s); IncrementMatrix(A, Out, c): in the session one ps_copy_axpby, which has their bits
+  auto copy_scale_add = [&](const PSMatrix& Base, double s, const PSMatrix& A, double c, PSMatrix& Res) {
+    if (in_session) {
+      ps_copy_axpby(Base, A, Res, c, s, 0.0);
+      return;
+    }
+    ps_copy(Base, Res);
+    if (s != 1.0) ps_scale(Res, s);
+    ps_increment(A, Res, c, 0.0);
+  };
+  {
+    const PSMatrix* powers[3] = {&B1, &B2, &B3};
+    const double s[2] = {17297280.0, 8648640.0}, c[6] = {1995840.0, 25200.0, 56.0, 277200.0, 1512.0, 1.0};
+    if (!(in_session && ps_pade_chain(IdentityMat, powers, 3, s, c, P1, TempMat))) {
+      copy_scale_add(IdentityMat, s[0], B1, c[0], P1);                         // :222-226
+      ps_increment(B2, P1, c[1], 0.0);
+      ps_increment(B3, P1, c[2], 0.0);
+      copy_scale_add(IdentityMat, s[1], B1, c[3], TempMat);                    // :228-234
+      ps_increment(B2, TempMat, c[4], 0.0);
+      ps_increment(B3, TempMat, c[5], 0.0);
+    }
+  }
   ps_multiply(ScaledMat, TempMat, P2, 1.0, 0.0, sub.threshold);
-  ps_copy(P1, LeftMat);
-  ps_increment(P2, LeftMat, -1.0, 0.0);
-  ps_copy(P1, RightMat);
-  ps_increment(P2, RightMat, 1.0, 0.0);
+  {
+    const PSMatrix* addend[1] = {&P2};
+    const double s[2] = {1.0, 1.0}, c[2] = {-1.0, 1.0};
+    if (!(in_session && ps_pade_chain(P1, addend, 1, s, c, LeftMat, RightMat))) {
+      copy_scale_add(P1, 1.0, P2, -1.0, LeftMat);
+      copy_scale_add(P1, 1.0, P2, 1.0, RightMat);
+    }
+  }
+  if (in_session && (sub.do_load_balancing || !solver_cg_opens_session(LeftMat, RightMat))) {
+    ps_slab_leave(LeftMat);
+    ps_slab_leave(RightMat);
+    slab.close();
+  }
   solver_cg(LeftMat, Out, RightMat, sub);
+  SlabSession behind(in_session && !slab.opened);
+  const bool squaring_in_session = slab.opened || behind.opened;
   for (int II = 1; II <= sigma_counter - 1; ++II) {                            // undo the scaling by squaring
     ps_multiply(Out, Out, TempMat, 1.0, 0.0, p.threshold);
-    ps_copy(TempMat, Out);
+    if (squaring_in_session) Out = std::move(TempMat);   // (the next squaring rebuilds TempMat before it is read)
+    else ps_copy(TempMat, Out);
+  }
+  if (in_session) {
+    behind.close();
+    slab.close();
+    ps_slab_leave(Out);
   }
   if (p.be_verbose) {
     print_matrix_information(Out);

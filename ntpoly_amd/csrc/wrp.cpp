@@ -308,6 +308,22 @@ int ntpoly_amd_purify_tail_step(const int* ih_D, const int* ih_N, const int* ih_
   return ps_purify_tail_step(*get_unpacked(ih_D), *get_unpacked(ih_N), *get_unpacked(ih_S), *fold != 0, *get_unpacked(ih_Nout), norm,
                              next_trace) ? 1 : 0;
 }
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end, option pade_session = 2: one of the two groups of merges of
+// ComputeExponentialPade on caller-held real matrices.  For q = 1, 2  Out_q = CopyMatrix(Base); ScaleMatrix(Out_q, scales[q - 1]);
+// IncrementMatrix(A_k, Out_q, coeffs[(q - 1) n_addends + k - 1], threshold 0) for k = 1 .. *n_addends; *n_addends is 1 (A2 and A3
+// are not looked at) or 3.  The inputs are brought into slab form, the pass runs, both outputs are packed into the result handles.
+// One rank only.  Returns 1 when taken, 0 when refused or gated (several ranks and any other *n_addends are gates): every handle is
+// then as it was.
+int ntpoly_amd_pade_chain_step(const int* ih_Base, const int* ih_A1, const int* ih_A2, const int* ih_A3, const int* n_addends, const double* scales,
+                               const double* coeffs, int* ih_Out1, int* ih_Out2) {
+  if (*n_addends != 1 && *n_addends != 3) return 0;
+  const PSMatrix* addends[3] = {get_unpacked(ih_A1), nullptr, nullptr};
+  if (*n_addends == 3) {
+    addends[1] = get_unpacked(ih_A2);
+    addends[2] = get_unpacked(ih_A3);
+  }
+  return ps_pade_chain_step(*get_unpacked(ih_Base), addends, *n_addends, scales, coeffs, *get_unpacked(ih_Out1), *get_unpacked(ih_Out2)) ? 1 : 0;
+}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end: TRS4's chain on caller-held matrices X and X2 (what the
 // loop's product X X would be), real or -- in a session with complex_ok and option complex_trs4 -- complex.  The two operands are
 // brought into slab form, *trace_fx = dot(X2, 4 X - 3 X2) and *trace_gx = dot(X2, I - 2 X + X2) (their real parts) come from the

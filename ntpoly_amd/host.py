@@ -1011,6 +1011,13 @@ _COUNTERS = {
     calls it replaces (fold: two merges, the copy, the scaling, the norm and the dot; plain: one merge, the copy, the norm and the
     dot).  A pass kept out by a gate (the option below 2, no open real session, a complex operand, block form, a labelled slab
     form, dimensions that differ, one matrix given twice) counts nowhere"""),
+    "pade_session": (("solves", "sum_passes", "pair_passes", "refused"),
+                     """ComputeExponentialPade in a slab session (option pade_session; csrc/pade_chain.hip k_pade_chain) since start: calls that ran in
+    a slab session, sum passes fused (P1 and TempMat from I, B1, B2, B3 in one pass), pair passes fused (LeftMat and RightMat from P1
+    and P2 in one pass), passes refused past the gates (the vocabulary calls ran instead); slab_algebra_counts() counts a fused pass
+    as the calls it replaces (two copies, the merges, the scalings).  A pass kept out by a gate (the option below 2, no open real
+    session, a complex operand, block form, a labelled slab form, dimensions that differ, one matrix given twice, a number of
+    addends other than 1 or 3) counts nowhere"""),
     "complex_scale_fold": (("updates", "dot_traces", "refused"),
                            """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
     pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
@@ -1247,6 +1254,25 @@ def purify_tail_step(D, N, S, fold, Nout):
     lib.ntpoly_amd_purify_tail_step.restype = C.c_int
     ok = lib.ntpoly_amd_purify_tail_step(D.ih, N.ih, S.ih, C.byref(C.c_int(1 if fold else 0)), Nout.ih, C.byref(norm), C.byref(nxt))
     return (float(norm.value), float(nxt.value)) if ok else None
+
+
+def pade_chain_step(Base, addends, scales, coeffs, Out1, Out2):
+    """DIAGNOSTIC, inside `with solver_session():`, option pade_session = 2, one rank -- one of the two groups of merges of
+    ComputeExponentialPade on caller-held real matrices (csrc/pade_chain.hip): for q = 1, 2
+    Out_q = CopyMatrix(Base); ScaleMatrix(Out_q, scales[q - 1]); IncrementMatrix(addends[k], Out_q, coeffs[q - 1][k], threshold 0)
+    for every k.  `addends`: 1 or 3 matrices; `coeffs`: two rows of len(addends) numbers.  Returns True when taken (both outputs
+    packed); None: refused or gated, every matrix as it was."""
+    addends = list(addends)
+    m = len(addends)
+    c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float64).reshape(-1))
+    s = np.ascontiguousarray(np.asarray(scales, dtype=np.float64).reshape(-1))
+    if m == 0 or c.size != 2 * m or s.size != 2:
+        raise ValueError("pade_chain_step: two scales and two rows of len(addends) coefficients")
+    ih = [a.ih for a in addends[:3]] + [addends[0].ih] * max(0, 3 - m)
+    lib.ntpoly_amd_pade_chain_step.restype = C.c_int
+    ok = lib.ntpoly_amd_pade_chain_step(Base.ih, ih[0], ih[1], ih[2], C.byref(C.c_int(m)), s.ctypes.data_as(C.POINTER(C.c_double)),
+                                        c.ctypes.data_as(C.POINTER(C.c_double)), Out1.ih, Out2.ih)
+    return True if ok else None
 
 
 def trs4_chain_step(X, X2, sigma, P):
