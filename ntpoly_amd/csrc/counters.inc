@@ -50,6 +50,12 @@ NTP_COUNTER(purify_session, 4, purify_session_counts)
 // real session, a complex operand, block form, a labelled slab form, dimensions that differ, one matrix given twice, a number of
 // addends other than 1 or 3 -- counts nowhere
 NTP_COUNTER(pade_session, 4, pade_session_counts)
+// The real Chebyshev / Hermite step in one pass and ComputeExponential's squarings in a slab session (option poly_step; engine.hpp
+// ps_poly_step): [0] ComputeExponential calls whose real squarings ran in a slab session, [1] steps fused (k_poly_step writes Tk
+// and the new sum), [2] passes refused past the gates (the two merges ran instead).  A step kept out by a gate -- the option
+// below 2, no open real session, a complex operand, block form, a labelled slab form, dimensions that differ, one matrix in two
+// roles, a zero coefficient, a grid with process slices -- counts nowhere
+NTP_COUNTER(poly_step, 3, poly_step_counts)
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update):
 // [0] trace passes fused, [1] updates fused, [2] updates refused (the vocabulary calls ran instead).  A step that never reaches
 // the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled slab form, alignments

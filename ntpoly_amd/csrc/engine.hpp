@@ -201,6 +201,22 @@ bool ps_norm_axpby(const PSMatrix& A, const PSMatrix& B, double alpha, double be
 // IncrementMatrix(Tk, R, c, 0), in one pass (slab_extra.hip slab_recurrence_step_c: the same values bit for bit); false:
 // not done and nothing changed -- the caller makes the two ps_increment calls
 bool ps_recurrence_step(const PSMatrix& P, const PSMatrix& Tkm2, PSMatrix& Tk, PSMatrix& R, double a, double c);
+// The same step on REAL operands inside a real slab session, option poly_step = 2 (poly_step.hip k_poly_step): what
+// IncrementMatrix(Tkm2, P, a, 0) leaves in P goes to Tk (which may be P), what IncrementMatrix(Tk, R, c, 0) then leaves in R
+// replaces R -- one pass over the runs of P, Tkm2 and R with two fresh outputs and one read-back, values and patterns of the two
+// calls bit for bit.  An operand still in compressed columns (the identity as T0, the input as T1, the sum before the first
+// product) is turned into slab form where it is.  Counted in slab_algebra_counts() as the two merges replaced.  Local: no
+// reduction is entered, and the calls it replaces are local too, so across ranks each panel decides for itself.  false: nothing
+// done -- kept out by a gate (the option below 2, no open real session or one that has given up, a complex operand, block form, a
+// labelled slab form, dimensions that differ, one matrix in two roles, a == 0 or c == 0, a grid with process slices: counted
+// nowhere) or refused (counted in poly_step_counts(): an operand the slab form cannot hold or a view, alignments without a common
+// multiple among them, runs far apart, an input that is not finite, a scaled value that is exactly zero where an entry is held)
+// -- the caller makes the two ps_increment calls.  ps_recurrence_step is the complex loops' and stays as it is.
+bool ps_poly_step(const PSMatrix& P, const PSMatrix& Tkm2, PSMatrix& Tk, PSMatrix& R, double a, double c);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_poly_step): the same pass on caller-held matrices with both outputs packed into TkOut and
+// ROut, which are none of the inputs and not one another; the inputs keep their values.  One rank only (several ranks are a gate)
+bool ps_poly_step_diag(const PSMatrix& P, const PSMatrix& Tkm2, const PSMatrix& R, double a, double c, PSMatrix& TkOut, PSMatrix& ROut);
+long long* poly_step_counts();   // (slots: counters.inc)
 // The polynomial chain of the Taylor square-root step (SquareRootSolversModule.F90:425-479) in one pass over the runs of X and
 // X2 = X X (option isr_chain; slab_extra.hip k_sa_isr_chain), inside an open slab session that takes the operands' kind, both in
 // slab form.  ps_isr_chain5: what ps_increment(X, T, a, 0); ps_copy_axpby(I, X, Temp2, 1, b, 0); ps_increment(T, Temp2, 1, 0);
@@ -552,7 +568,10 @@ SolverTrace& last_trace();
 // matrix polynomials (solvers_poly.cpp): coefficient i of the vector multiplies x^i / T_i(x) / H_i(x)
 void polynomial_horner(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p);
 void polynomial_paterson_stockmeyer(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p);
-void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p);
+// (keep_slab_form, internal: Out stays in the slab form the evaluation's session left it in -- for compute_exponential, whose own
+// session is open around the call and squares Out next; never with a load balancer's permutation, which is undone on compressed
+// columns.  The C ABI packs as ever)
+void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p, bool keep_slab_form = false);
 void chebyshev_factorized(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p);
 void hermite_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p);
 // matrix functions (solvers_func.cpp)

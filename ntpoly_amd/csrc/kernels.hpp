@@ -359,6 +359,14 @@ bool slab_purify_tail(const DevMat& D, const DevMat& N, const DevMat& S, bool fo
 // nothing changed
 bool slab_pade_chain(const DevMat& Base, const DevMat* const* addends, int n_addends, const double scales[2], const double* coeffs, DevMat& Out1,
                      DevMat& Out2);
+// The tail of a step of the Chebyshev / Hermite recurrences on slab-form matrices (poly_step.hip; real, square or column panels):
+// Tk = what IncrementMatrix(Q, P, a, threshold 0) leaves in P, Rout = what IncrementMatrix(Tk, R, c, threshold 0) then leaves in R,
+// values and patterns of the two calls bit for bit, both as fresh slab-form matrices from ONE pass over the runs of P, Q and R
+// (Tk passes from the first merge to the second in a register) and one host read-back.  The outputs' slots are aligned to the
+// largest row_pad of the three.  false: refused (an operand that is not a zero-free, unlabelled slab form or is a view, operands
+// named twice, a largest alignment that is no multiple of the others, a scalar that is zero or not finite, runs far apart, an
+// input that is not finite, a scaled value that is exactly zero where an entry is held), nothing changed
+bool slab_poly_step(const DevMat& P, const DevMat& Q, const DevMat& R, double a, double c, DevMat& Tk, DevMat& Rout);
 // PM purification on a slab-form iterate (slab_extra.hip).  The rows of each column that compressed columns would hold as STORED
 // ZEROS (a1 = 0 when sigma > 1/2, unfiltered tails that underflow) travel next to the zero-free runs: rows row[off[j] .. off[j + 1])
 // of column j, ascending, disjoint from the run's non-zeros.  off.p == nullptr: no such row.

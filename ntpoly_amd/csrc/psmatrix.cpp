@@ -2690,6 +2690,51 @@ bool ps_pade_chain_step(const PSMatrix& Base, const PSMatrix* const* addends, in
   return true;
 }
 
+long long* poly_step_counts() {
+  static long long counts[3] = {0, 0, 0};
+  return counts;
+}
+namespace {
+// the step's tail on this rank's panels into t / r; out1 / out2: the handles the results go to where they are not the step's own
+// (the diagnostic).  false: kept out by a gate (counted nowhere) or refused (counted).  No reduction is entered and the calls it
+// replaces are local, so across ranks a refusal is the rank's own
+bool poly_step_local(const PSMatrix& P, const PSMatrix& Tkm2, const PSMatrix& R, double a, double c, const PSMatrix* out1, const PSMatrix* out2,
+                     DevMat& t, DevMat& r) {
+  if (options().poly_step < 2 || !slab_on() || (P.grid && P.grid->num_slices > 1)) return false;
+  const PSMatrix* ms[3] = {&P, &Tkm2, &R};
+  for (const PSMatrix* m : ms)
+    if (m->cplx || m->dim != P.dim || m->loc.blocked() || labelled(*m) || m == out1 || m == out2) return false;
+  if (&P == &Tkm2 || &P == &R || &Tkm2 == &R || a == 0.0 || c == 0.0) return false;
+  const bool taken = slab_enter(mut(P)) && slab_enter(mut(Tkm2)) && slab_enter(mut(R)) && slab_poly_step(P.loc, Tkm2.loc, R.loc, a, c, t, r);
+  if (taken) {
+    g_slab_counts[1] += 2;   // the two merges
+    poly_step_counts()[1] += 1;
+  } else {
+    poly_step_counts()[2] += 1;
+  }
+  return taken;
+}
+}  // namespace
+bool ps_poly_step(const PSMatrix& P, const PSMatrix& Tkm2, PSMatrix& Tk, PSMatrix& R, double a, double c) {
+  CommScope cs(P.grid);
+  if (&Tk == &R || &Tk == &Tkm2) return false;
+  DevMat t, r;
+  if (!poly_step_local(P, Tkm2, R, a, c, nullptr, nullptr, t, r)) return false;
+  install_like(Tk, P, false, std::move(t));
+  install_like(R, P, false, std::move(r));
+  return true;
+}
+bool ps_poly_step_diag(const PSMatrix& P, const PSMatrix& Tkm2, const PSMatrix& R, double a, double c, PSMatrix& TkOut, PSMatrix& ROut) {
+  CommScope cs(P.grid);
+  DevMat t, r;
+  if (world().active() || &TkOut == &ROut || !poly_step_local(P, Tkm2, R, a, c, &TkOut, &ROut, t, r)) return false;
+  pack(t);
+  pack(r);
+  install_like(TkOut, P, false, std::move(t));
+  install_like(ROut, P, false, std::move(r));
+  return true;
+}
+
 double ps_sigma(const PSMatrix& A) {
   CommScope cs(A.grid);  // MatrixSigma (distributed_algebra_includes/MatrixSigma.f90)
   const double n = ps_norm(A);

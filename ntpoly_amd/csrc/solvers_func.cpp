@@ -137,18 +137,27 @@ void compute_exponential(const PSMatrix& In, PSMatrix& Out, const SolverParamete
                                5.474240442092110e-03, 5.429263119148932e-04, 4.497732295351912e-05, 3.198436462630565e-06,
                                1.992124801999838e-07, 1.103677287249654e-08, 5.505891628277851e-10, 2.498021534339559e-11,
                                1.038827668772902e-12, 4.032447357431817e-14, 2.127980007794583e-15, -1.629151584468762e-16};
-  chebyshev_compute(Scaled, R, std::vector<double>(c, c + 16), sub);
+  // (option poly_step >= 1, real operands: the squarings run in a slab session too, and where no load balancer's permutation is
+  // set an outer session, opened here behind power_bounds and the scaling, keeps the evaluation's result in slab form across the
+  // hand-over -- chebyshev_compute skips its pack and the first squaring its expansion.  With a permutation the result is packed,
+  // un-permuted, permuted and re-enters once.  Nothing of this with 0)
+  const bool real_session = !In.cplx && options().poly_step >= 1 && !(In.grid && In.grid->num_slices > 1);
+  const bool hand_over = real_session && !p.do_load_balancing;
+  SlabSession outer(hand_over);
+  chebyshev_compute(Scaled, R, std::vector<double>(c, c + 16), sub, hand_over && outer.opened);
   balance_permute(R, p);
   {
     // (complex operands: the squarings on an iterate kept in slab form, as the sign loop keeps its own -- option
-    // complex_poly_sessions; real operands: no session, as ever)
+    // complex_poly_sessions; real operands: a session with option poly_step, none without)
     const bool complex_session = complex_slab_loop(R) && options().complex_poly_sessions != 0;
-    SlabSession slab(complex_session, false, complex_session);
+    SlabSession slab(real_session || complex_session, false, complex_session);
+    if (real_session && slab.opened) poly_step_counts()[0] += 1;
     for (int k = 1; k <= sigma_counter - 1; ++k) {
       ps_multiply(R, R, Temp, 1.0, 0.0, p.threshold);
       std::swap(R.loc, Temp.loc);
     }
     slab.close();
+    outer.close();
     ps_slab_leave(R);
   }
   if (p.be_verbose) print_matrix_information(R);

@@ -128,7 +128,7 @@ void polynomial_paterson_stockmeyer(const PSMatrix& In, PSMatrix& Out, const std
 }
 
 // ------------------------------------------------------------------ Chebyshev, three-term recurrence
-void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p) {
+void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double>& c, const SolverParameters& p, bool keep_slab_form) {
   CommScope cs(In.grid);
   const int degree = (int)c.size();
   if (degree < 1) NTP_FATAL("polynomial without coefficients");
@@ -149,7 +149,8 @@ void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<doub
     ps_increment(Tkminus1, R, c[1], 0.0);
     if (degree > 2) {
       ps_multiply(b.Input, Tkminus1, Tk, 2.0, 0.0, p.threshold);
-      if (!ps_recurrence_step(Tk, Tkminus2, Tk, R, -1.0, c[2])) {   // (complex session: the two merges in one pass)
+      // (the two merges in one pass: real operands with option poly_step = 2, complex ones in a complex session)
+      if (!ps_poly_step(Tk, Tkminus2, Tk, R, -1.0, c[2]) && !ps_recurrence_step(Tk, Tkminus2, Tk, R, -1.0, c[2])) {
         ps_increment(Tkminus2, Tk, -1.0, 0.0);
         ps_increment(Tk, R, c[2], 0.0);
       }
@@ -157,7 +158,7 @@ void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<doub
         std::swap(Tkminus2.loc, Tkminus1.loc);  // Tkminus2 <- Tkminus1
         std::swap(Tkminus1.loc, Tk.loc);        // Tkminus1 <- Tk (Tk now holds scratch)
         ps_multiply(b.Input, Tkminus1, Tk, 2.0, 0.0, p.threshold);
-        if (!ps_recurrence_step(Tk, Tkminus2, Tk, R, -1.0, c[(size_t)II - 1])) {
+        if (!ps_poly_step(Tk, Tkminus2, Tk, R, -1.0, c[(size_t)II - 1]) && !ps_recurrence_step(Tk, Tkminus2, Tk, R, -1.0, c[(size_t)II - 1])) {
           ps_increment(Tkminus2, Tk, -1.0, 0.0);
           ps_increment(Tk, R, c[(size_t)II - 1], 0.0);
         }
@@ -165,7 +166,9 @@ void chebyshev_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<doub
     }
   }
   slab.close();
-  ps_slab_leave(R);
+  // (keep_slab_form: compute_exponential's outer session is open and squares the result next; it sets this only where no load
+  // balancer's permutation has to be undone on compressed columns)
+  if (!keep_slab_form) ps_slab_leave(R);
   if (p.be_verbose) print_matrix_information(R);
   balance_undo(R, p);
   Out = std::move(R);
@@ -259,7 +262,8 @@ void hermite_compute(const PSMatrix& In, PSMatrix& Out, const std::vector<double
         // matrices, IncrementMatrix(Hk = Hkplus1, OutputMat, c).  Hkprime already carries the coefficient 2 (k - 1), so the
         // recurrence's -2 (k - 1) H_{k-1} is a = -1 here; nothing between the two merges reads or writes Hkplus1 or the
         // output, so the second merge done right behind the first leaves the same values)
-        const bool stepped = ps_recurrence_step(Hkplus1, Hkprime, Hkplus1, R, -1.0, c[(size_t)II - 1]);
+        const bool stepped = ps_poly_step(Hkplus1, Hkprime, Hkplus1, R, -1.0, c[(size_t)II - 1]) ||
+                             ps_recurrence_step(Hkplus1, Hkprime, Hkplus1, R, -1.0, c[(size_t)II - 1]);
         if (!stepped) ps_increment(Hkprime, Hkplus1, -1.0, 0.0);
         ps_copy(Hk, Hkprime);
         ps_scale(Hkprime, (double)(2 * (II - 1)));

@@ -308,6 +308,14 @@ int ntpoly_amd_purify_tail_step(const int* ih_D, const int* ih_N, const int* ih_
   return ps_purify_tail_step(*get_unpacked(ih_D), *get_unpacked(ih_N), *get_unpacked(ih_S), *fold != 0, *get_unpacked(ih_Nout), norm,
                              next_trace) ? 1 : 0;
 }
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end, option poly_step = 2: the tail of a step of the real Chebyshev
+// / Hermite recurrences on caller-held real matrices (engine.hpp ps_poly_step_diag).  TkOut = what IncrementMatrix(Tkm2, P, *a, 0)
+// leaves in P, ROut = what IncrementMatrix(TkOut, R, *c, 0) then leaves in R.  The inputs are brought into slab form and keep their
+// values, the pass runs, both outputs are packed into the result handles, which are none of the inputs and not one another.  One
+// rank only.  Returns 1 when taken, 0 when refused or gated: every handle is then as it was.
+int ntpoly_amd_poly_step(const int* ih_P, const int* ih_Tkm2, const int* ih_R, const double* a, const double* c, int* ih_TkOut, int* ih_ROut) {
+  return ps_poly_step_diag(*get_unpacked(ih_P), *get_unpacked(ih_Tkm2), *get_unpacked(ih_R), *a, *c, *get_unpacked(ih_TkOut), *get_unpacked(ih_ROut)) ? 1 : 0;
+}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end, option pade_session = 2: one of the two groups of merges of
 // ComputeExponentialPade on caller-held real matrices.  For q = 1, 2  Out_q = CopyMatrix(Base); ScaleMatrix(Out_q, scales[q - 1]);
 // IncrementMatrix(A_k, Out_q, coeffs[(q - 1) n_addends + k - 1], threshold 0) for k = 1 .. *n_addends; *n_addends is 1 (A2 and A3

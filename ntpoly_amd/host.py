@@ -1018,6 +1018,13 @@ _COUNTERS = {
     as the calls it replaces (two copies, the merges, the scalings).  A pass kept out by a gate (the option below 2, no open real
     session, a complex operand, block form, a labelled slab form, dimensions that differ, one matrix given twice, a number of
     addends other than 1 or 3) counts nowhere"""),
+    "poly_step": (("exp_sessions", "steps", "refused"),
+                  """the real Chebyshev / Hermite step in one pass and ComputeExponential's squarings in a slab session (option poly_step;
+    csrc/poly_step.hip k_poly_step) since start: ComputeExponential calls whose real squarings ran in a slab session, steps fused
+    (Tk = P + a T(k-2) and R += c Tk in one pass), passes refused past the gates (the two merges ran instead); slab_algebra_counts()
+    counts a fused step as the two merges it replaces.  A step kept out by a gate (the option below 2, no open real session, a
+    complex operand, block form, a labelled slab form, dimensions that differ, one matrix in two roles, a zero coefficient, a grid
+    with process slices) counts nowhere"""),
     "complex_scale_fold": (("updates", "dot_traces", "refused"),
                            """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
     pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
@@ -1273,6 +1280,17 @@ def pade_chain_step(Base, addends, scales, coeffs, Out1, Out2):
     ok = lib.ntpoly_amd_pade_chain_step(Base.ih, ih[0], ih[1], ih[2], C.byref(C.c_int(m)), s.ctypes.data_as(C.POINTER(C.c_double)),
                                         c.ctypes.data_as(C.POINTER(C.c_double)), Out1.ih, Out2.ih)
     return True if ok else None
+
+
+def poly_step(P, Tkm2, R, a, c, TkOut, ROut):
+    """DIAGNOSTIC, inside `with solver_session():`, option poly_step = 2, one rank -- the tail of a step of the real Chebyshev /
+    Hermite recurrences on caller-held real matrices (csrc/poly_step.hip): TkOut = what IncrementMatrix(Tkm2, P, a, threshold 0)
+    leaves in P, ROut = what IncrementMatrix(TkOut, R, c, threshold 0) then leaves in R, both from one pass and packed.  TkOut and
+    ROut are none of the inputs and not one another; the inputs keep their values.  Returns True when taken; False: refused or
+    gated, every matrix as it was."""
+    lib.ntpoly_amd_poly_step.restype = C.c_int
+    ok = lib.ntpoly_amd_poly_step(P.ih, Tkm2.ih, R.ih, C.byref(C.c_double(float(a))), C.byref(C.c_double(float(c))), TkOut.ih, ROut.ih)
+    return bool(ok)
 
 
 def trs4_chain_step(X, X2, sigma, P):
