@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libntpoly_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["kernels.hip", "spgemm_tile.hip", "spgemm_tile_c.hip", "spgemm_thin.hip", "column_fused.hip", "spgemm_grouped.hip", "spgemm_block.hip", "relabel.hip", "slab_extra.hip", "power_vector.hip", "cg_dots.hip", "wom_heun.hip", "purify_tail.hip", "pade_chain.hip", "poly_step.hip", "dense.hip", "common.cpp", "comm.cpp", "psmatrix.cpp", "band_scope.cpp", "solvers.cpp", "solvers_poly.cpp", "solvers_func.cpp", "solvers_extra.cpp", "io.cpp", "wrp.cpp"]
+SOURCES = ["kernels.hip", "spgemm_tile.hip", "spgemm_tile_c.hip", "spgemm_thin.hip", "column_fused.hip", "spgemm_grouped.hip", "spgemm_block.hip", "relabel.hip", "slab_extra.hip", "power_vector.hip", "cg_dots.hip", "wom_heun.hip", "purify_tail.hip", "pade_chain.hip", "poly_step.hip", "sum_chain.hip", "dense.hip", "common.cpp", "comm.cpp", "psmatrix.cpp", "band_scope.cpp", "solvers.cpp", "solvers_poly.cpp", "solvers_func.cpp", "solvers_extra.cpp", "io.cpp", "wrp.cpp"]
 # experiments kept out of the product build (csrc/experiments/): NTPOLY_AMD_WITH_TILE2=1 adds the two-block geometry of the
 # MFMA kernel (measured slower than k_spgemm_tile in round 5, profiles/README.md 83; option tile2 is a no-op without it)
 WITH_TILE2 = os.environ.get("NTPOLY_AMD_WITH_TILE2", "0") == "1"

@@ -56,6 +56,12 @@ NTP_COUNTER(pade_session, 4, pade_session_counts)
 // below 2, no open real session, a complex operand, block form, a labelled slab form, dimensions that differ, one matrix in two
 // roles, a zero coefficient, a grid with process slices -- counts nowhere
 NTP_COUNTER(poly_step, 3, poly_step_counts)
+// The scaled sum chain of the real solver loops in one pass (option sum_chain; engine.hpp ps_sum_chain): [0] passes fused
+// (k_sum_chain<M> writes the sum), [1] passes refused past the gates (the vocabulary calls ran instead).  A pass kept out by a
+// gate -- the option at 0, no open real session or one that has given up, a complex operand, block form, a labelled slab form,
+// dimensions that differ, one matrix in two input roles, the output among the addends, a number of addends outside 1 .. 5, a
+// grid with process slices, a scalar that is zero or not finite -- counts nowhere
+NTP_COUNTER(sum_chain, 2, sum_chain_counts)
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update):
 // [0] trace passes fused, [1] updates fused, [2] updates refused (the vocabulary calls ran instead).  A step that never reaches
 // the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled slab form, alignments

@@ -217,6 +217,23 @@ bool ps_poly_step(const PSMatrix& P, const PSMatrix& Tkm2, PSMatrix& Tk, PSMatri
 // ROut, which are none of the inputs and not one another; the inputs keep their values.  One rank only (several ranks are a gate)
 bool ps_poly_step_diag(const PSMatrix& P, const PSMatrix& Tkm2, const PSMatrix& R, double a, double c, PSMatrix& TkOut, PSMatrix& ROut);
 long long* poly_step_counts();   // (slots: counters.inc)
+// The scaled sum chain of the real solver loops inside a real slab session, option sum_chain = 1 (sum_chain.hip k_sum_chain):
+//   CopyMatrix(Base, Out); ScaleMatrix(Out, s); IncrementMatrix(*addends[k], Out, coeffs[k], 0) for k = 0 .. n_addends - 1;
+//   ScaleMatrix(Out, post)
+// in one pass over the runs of Base and the addends and one read-back, values and pattern of the calls bit for bit; s == 1 and
+// post == 1 stand for no scaling call.  n_addends is 1 .. 5.  Out may be Base (the in-place sequences: the fresh result is
+// installed over it) or none of the inputs, never an addend.  The inputs are only read (one still in compressed columns is turned
+// into slab form where it is).  Counted in slab_algebra_counts() as the calls replaced.  Local: no reduction is entered, and the
+// calls it replaces are local too, so across ranks each panel decides for itself.  false: nothing done -- kept out by a gate (the
+// option at 0, no open real session or one that has given up, a complex operand, block form, a labelled slab form, dimensions
+// that differ, one matrix in two input roles, Out an addend, n_addends outside 1 .. 5, a grid with process slices, s, post or a
+// coefficient that is zero or not finite: counted nowhere) or refused (counted in sum_chain_counts(): an operand the slab form
+// cannot hold or a view, alignments that differ, runs far apart, an input that is not finite, a scaled value that is exactly zero
+// where an entry is held) -- the caller makes the calls.
+bool ps_sum_chain(const PSMatrix& Base, double s, const PSMatrix* const* addends, const double* coeffs, int n_addends, double post, PSMatrix& Out);
+// DIAGNOSTIC (the C ABI's ntpoly_amd_sum_chain): the same pass with the result packed.  One rank only (several ranks are a gate)
+bool ps_sum_chain_step(const PSMatrix& Base, double s, const PSMatrix* const* addends, const double* coeffs, int n_addends, double post, PSMatrix& Out);
+long long* sum_chain_counts();   // (slots: counters.inc)
 // The polynomial chain of the Taylor square-root step (SquareRootSolversModule.F90:425-479) in one pass over the runs of X and
 // X2 = X X (option isr_chain; slab_extra.hip k_sa_isr_chain), inside an open slab session that takes the operands' kind, both in
 // slab form.  ps_isr_chain5: what ps_increment(X, T, a, 0); ps_copy_axpby(I, X, Temp2, 1, b, 0); ps_increment(T, Temp2, 1, 0);

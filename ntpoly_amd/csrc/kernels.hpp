@@ -367,6 +367,14 @@ bool slab_pade_chain(const DevMat& Base, const DevMat* const* addends, int n_add
 // named twice, a largest alignment that is no multiple of the others, a scalar that is zero or not finite, runs far apart, an
 // input that is not finite, a scaled value that is exactly zero where an entry is held), nothing changed
 bool slab_poly_step(const DevMat& P, const DevMat& Q, const DevMat& R, double a, double c, DevMat& Tk, DevMat& Rout);
+// The scaled sum chain of the real solver loops on slab-form matrices (sum_chain.hip; real, square or column panels):
+// Out = CopyMatrix(Base); ScaleMatrix(Out, s); IncrementMatrix(addends[k], Out, coeffs[k], threshold 0) for k = 0 .. n_addends - 1
+// (n_addends 1 .. 5); ScaleMatrix(Out, post) -- values and pattern of the calls bit for bit (s == 1 and post == 1 stand for no
+// scaling call), as ONE fresh slab-form matrix from ONE pass over the inputs' runs and one host read-back.  Out is written only
+// on success and may be Base's own DevMat.  false: refused (an operand that is not a zero-free, unlabelled slab form or is a view,
+// operands named twice, alignments that differ, another n_addends, a scalar that is zero or not finite, runs far apart, an input
+// that is not finite, a scaled value that is exactly zero where an entry is held), nothing changed
+bool slab_sum_chain(const DevMat& Base, double s, const DevMat* const* addends, const double* coeffs, int n_addends, double post, DevMat& Out);
 // PM purification on a slab-form iterate (slab_extra.hip).  The rows of each column that compressed columns would hold as STORED
 // ZEROS (a1 = 0 when sigma > 1/2, unfiltered tails that underflow) travel next to the zero-free runs: rows row[off[j] .. off[j + 1])
 // of column j, ascending, disjoint from the run's non-zeros.  off.p == nullptr: no such row.

@@ -2735,6 +2735,73 @@ bool ps_poly_step_diag(const PSMatrix& P, const PSMatrix& Tkm2, const PSMatrix& 
   return true;
 }
 
+long long* sum_chain_counts() {
+  static long long counts[2] = {0, 0};
+  return counts;
+}
+namespace {
+// the chain on this rank's panels into o; out: the handle the result goes to (Base, or none of the inputs).  false: kept out by a
+// gate (counted nowhere) or refused (counted).  No reduction is entered and the calls it replaces are local, so across ranks a
+// refusal is the rank's own
+bool sum_chain_local(const PSMatrix& Base, double s, const PSMatrix* const* A, const double* coeffs, int n_addends, double post, const PSMatrix* out,
+                     DevMat& o) {
+  if (options().sum_chain == 0 || !slab_on() || n_addends < 1 || n_addends > 5 || (Base.grid && Base.grid->num_slices > 1)) return false;
+  const PSMatrix* ms[6] = {&Base, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < n_addends; ++k) ms[k + 1] = A[k];
+  for (int k = 0; k <= n_addends; ++k) {
+    const PSMatrix* m = ms[k];
+    if (!m || m->cplx || m->dim != Base.dim || m->loc.blocked() || labelled(*m) || (k > 0 && m == out)) return false;
+    for (int i = 0; i < k; ++i)
+      if (ms[i] == m) return false;
+  }
+  // (ScaleMatrix by zero and a zero coefficient leave stored zeros)
+  if (!std::isfinite(s) || s == 0.0 || !std::isfinite(post) || post == 0.0) return false;
+  for (int k = 0; k < n_addends; ++k)
+    if (!std::isfinite(coeffs[k]) || coeffs[k] == 0.0) return false;
+  bool taken = true;
+  const DevMat* locs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool entered[6] = {false, false, false, false, false, false};
+  for (int k = 0; taken && k <= n_addends; ++k) {
+    entered[k] = !ms[k]->loc.expanded();
+    taken = slab_enter(mut(*ms[k]));
+    if (!taken) {
+      if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
+        std::fprintf(stderr, "[sum chain] operand %d of %d does not enter slab form (loose %d, hint %d, %lld entries)\n", k, n_addends,
+                     (int)ms[k]->loc.loose(), (int)ms[k]->loc.slab_hint, (long long)ms[k]->loc.nnz);
+      // (an operand the slab form cannot hold: the calls the caller now makes must find the others as the option at 0 would --
+      // the ones this attempt turned into slab form go back to compressed columns)
+      for (int i = 0; i < k; ++i)
+        if (entered[i]) pack(mut(*ms[i]));
+    }
+  }
+  for (int k = 0; k < n_addends; ++k) locs[k] = &A[k]->loc;
+  taken = taken && slab_sum_chain(Base.loc, s, locs, coeffs, n_addends, post, o);
+  if (taken) {
+    g_slab_counts[1] += (out != &Base ? 1 : 0) + n_addends;           // the copy and the merges
+    g_slab_counts[2] += (s != 1.0 ? 1 : 0) + (post != 1.0 ? 1 : 0);   // the scalings
+    sum_chain_counts()[0] += 1;
+  } else {
+    sum_chain_counts()[1] += 1;
+  }
+  return taken;
+}
+}  // namespace
+bool ps_sum_chain(const PSMatrix& Base, double s, const PSMatrix* const* addends, const double* coeffs, int n_addends, double post, PSMatrix& Out) {
+  CommScope cs(Base.grid);
+  DevMat o;
+  if (!sum_chain_local(Base, s, addends, coeffs, n_addends, post, &Out, o)) return false;
+  install_like(Out, Base, false, std::move(o));
+  return true;
+}
+bool ps_sum_chain_step(const PSMatrix& Base, double s, const PSMatrix* const* addends, const double* coeffs, int n_addends, double post, PSMatrix& Out) {
+  CommScope cs(Base.grid);
+  DevMat o;
+  if (world().active() || !sum_chain_local(Base, s, addends, coeffs, n_addends, post, &Out, o)) return false;
+  pack(o);
+  install_like(Out, Base, false, std::move(o));
+  return true;
+}
+
 double ps_sigma(const PSMatrix& A) {
   CommScope cs(A.grid);  // MatrixSigma (distributed_algebra_includes/MatrixSigma.f90)
   const double n = ps_norm(A);

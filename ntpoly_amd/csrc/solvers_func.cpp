@@ -208,26 +208,39 @@ void scale_square_trig(const PSMatrix& In, PSMatrix& Out, const SolverParameters
   ps_multiply(T6, T2, T8, 2.0, 0.0, p.threshold);
   ps_increment(T4, T8, -1.0, 0.0);
 
-  ps_copy(T8, R);
-  ps_scale(R, 0.5 * c[17]);
-  ps_increment(T6, R, 0.5 * c[15], 0.0);
-  ps_increment(T4, R, 0.5 * c[13], 0.0);
-  ps_increment(T2, R, 0.5 * c[11], 0.0);
+  // (option sum_chain, real operands: each of the two sums and every doubling's 2 R - I in one pass, engine.hpp ps_sum_chain)
+  const PSMatrix* const upper[3] = {&T6, &T4, &T2};
+  const double upper_c[3] = {0.5 * c[15], 0.5 * c[13], 0.5 * c[11]};
+  if (!ps_sum_chain(T8, 0.5 * c[17], upper, upper_c, 3, 1.0, R)) {
+    ps_copy(T8, R);
+    ps_scale(R, 0.5 * c[17]);
+    ps_increment(T6, R, 0.5 * c[15], 0.0);
+    ps_increment(T4, R, 0.5 * c[13], 0.0);
+    ps_increment(T2, R, 0.5 * c[11], 0.0);
+  }
   ps_multiply(T8, R, Temp, 1.0, 0.0, p.threshold);
 
-  ps_copy(T8, R);
-  ps_scale(R, c[9]);
-  ps_increment(T6, R, c[7] + 0.5 * c[11], 0.0);
-  ps_increment(T4, R, c[5] + 0.5 * c[13], 0.0);
-  ps_increment(T2, R, c[3] + 0.5 * c[15], 0.0);
-  ps_increment(Ident, R, c[1] + 0.5 * c[17], 0.0);
-  ps_increment(Temp, R, 1.0, 0.0);
+  const PSMatrix* const lower[5] = {&T6, &T4, &T2, &Ident, &Temp};
+  const double lower_c[5] = {c[7] + 0.5 * c[11], c[5] + 0.5 * c[13], c[3] + 0.5 * c[15], c[1] + 0.5 * c[17], 1.0};
+  if (!ps_sum_chain(T8, c[9], lower, lower_c, 5, 1.0, R)) {
+    ps_copy(T8, R);
+    ps_scale(R, c[9]);
+    ps_increment(T6, R, c[7] + 0.5 * c[11], 0.0);
+    ps_increment(T4, R, c[5] + 0.5 * c[13], 0.0);
+    ps_increment(T2, R, c[3] + 0.5 * c[15], 0.0);
+    ps_increment(Ident, R, c[1] + 0.5 * c[17], 0.0);
+    ps_increment(Temp, R, 1.0, 0.0);
+  }
 
+  const PSMatrix* const ident[1] = {&Ident};
+  const double minus_one[1] = {-1.0};
   for (int II = 1; II <= sigma_counter - 1; ++II) {   // cos(2x) = 2 cos^2(x) - 1
     ps_multiply(R, R, Temp, 1.0, 0.0, p.threshold);
     std::swap(R.loc, Temp.loc);
-    ps_scale(R, 2.0);
-    ps_increment(Ident, R, -1.0, 0.0);
+    if (!ps_sum_chain(R, 2.0, ident, minus_one, 1, 1.0, R)) {
+      ps_scale(R, 2.0);
+      ps_increment(Ident, R, -1.0, 0.0);
+    }
   }
   slab.close();
   ps_slab_leave(R);
@@ -286,10 +299,15 @@ void inverse_root_impl(const PSMatrix& In, PSMatrix& Out, int root, const Solver
   SlabSession slab(!R.cplx && !Mk.cplx);   // (engine.hpp: the loop's matrices stay in slab form between its operations)
   for (II = 1; II <= p.max_iterations; ++II) {
     if (p.be_verbose && II > 1) log_list_element("Convergence", norm_value);
-    ps_copy(Ident, Inter);
-    ps_scale(Inter, (double)(target_root + 1));
-    ps_increment(Mk, Inter, -1.0, 0.0);
-    ps_scale(Inter, 1.0 / target_root);
+    // (option sum_chain: ((t + 1) I - Mk) / t in one pass, engine.hpp ps_sum_chain)
+    const PSMatrix* const mk[1] = {&Mk};
+    const double minus_one[1] = {-1.0};
+    if (!ps_sum_chain(Ident, (double)(target_root + 1), mk, minus_one, 1, 1.0 / target_root, Inter)) {
+      ps_copy(Ident, Inter);
+      ps_scale(Inter, (double)(target_root + 1));
+      ps_increment(Mk, Inter, -1.0, 0.0);
+      ps_scale(Inter, 1.0 / target_root);
+    }
     ps_multiply(R, Inter, Temp, 1.0, 0.0, p.threshold);
     std::swap(R.loc, Temp.loc);
     ps_copy(Inter, InterP);

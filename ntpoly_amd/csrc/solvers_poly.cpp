@@ -91,30 +91,47 @@ void polynomial_paterson_stockmeyer(const PSMatrix& In, PSMatrix& Out, const std
   PSMatrix Xs, Bk, R, Temp;
   ps_copy(x_powers[(size_t)s_value], Xs);
   auto coef = [&](int one_based) { return c[(size_t)one_based - 1]; };
+  // (option sum_chain, real operands: Bk = coef I + sum of `count` scaled powers in one pass, engine.hpp ps_sum_chain; a group
+  // without an addend, with more than five or with a zero coefficient is kept out by its gates and takes the calls)
+  auto bk_chain = [&](int k, int count) {
+    std::vector<const PSMatrix*> powers;
+    std::vector<double> weights;
+    for (int II = 1; II <= count; ++II) {
+      powers.push_back(&x_powers[(size_t)II]);
+      weights.push_back(coef(s_value * k + II + 1));
+    }
+    return ps_sum_chain(Identity, coef(s_value * k + 1), powers.data(), weights.data(), count, 1.0, Bk);
+  };
 
-  ps_copy(Identity, Bk);
-  ps_scale(Bk, coef(s_value * r_value + 1));
-  for (int II = 1; II <= m_value - s_value * r_value; ++II) {
-    const int c_index = s_value * r_value + II;
-    ps_increment(x_powers[(size_t)II], Bk, coef(c_index + 1), 0.0);
+  if (!bk_chain(r_value, m_value - s_value * r_value)) {
+    ps_copy(Identity, Bk);
+    ps_scale(Bk, coef(s_value * r_value + 1));
+    for (int II = 1; II <= m_value - s_value * r_value; ++II) {
+      const int c_index = s_value * r_value + II;
+      ps_increment(x_powers[(size_t)II], Bk, coef(c_index + 1), 0.0);
+    }
   }
   ps_multiply(Bk, Xs, R, 1.0, 0.0, 0.0);
 
   int k_value = r_value - 1;
-  ps_copy(Identity, Bk);
-  ps_scale(Bk, coef(s_value * k_value + 1));
-  for (int II = 1; II <= s_value - 1; ++II) {
-    const int c_index = s_value * k_value + II;
-    ps_increment(x_powers[(size_t)II], Bk, coef(c_index + 1), 0.0);
-  }
-  ps_increment(Bk, R, 1.0, 0.0);
-
-  for (k_value = r_value - 2; k_value >= 0; --k_value) {
+  if (!bk_chain(k_value, s_value - 1)) {
     ps_copy(Identity, Bk);
     ps_scale(Bk, coef(s_value * k_value + 1));
     for (int II = 1; II <= s_value - 1; ++II) {
       const int c_index = s_value * k_value + II;
       ps_increment(x_powers[(size_t)II], Bk, coef(c_index + 1), 0.0);
+    }
+  }
+  ps_increment(Bk, R, 1.0, 0.0);
+
+  for (k_value = r_value - 2; k_value >= 0; --k_value) {
+    if (!bk_chain(k_value, s_value - 1)) {
+      ps_copy(Identity, Bk);
+      ps_scale(Bk, coef(s_value * k_value + 1));
+      for (int II = 1; II <= s_value - 1; ++II) {
+        const int c_index = s_value * k_value + II;
+        ps_increment(x_powers[(size_t)II], Bk, coef(c_index + 1), 0.0);
+      }
     }
     ps_multiply(Xs, R, Temp, 1.0, 0.0, 0.0);
     std::swap(R.loc, Temp.loc);
@@ -184,9 +201,13 @@ void cheby_recursive(const std::vector<PSMatrix>& T, const std::vector<double>& 
     ps_copy(T[0], Out);
     ps_scale(Out, c[0]);
   } else if (n == 2) {
-    ps_copy(T[0], Out);
-    ps_scale(Out, c[0]);
-    ps_increment(T[1], Out, c[1], 0.0);
+    // (option sum_chain, real operands: c0 T0 + c1 T1 in one pass, engine.hpp ps_sum_chain)
+    const PSMatrix* const t1[1] = {&T[1]};
+    if (!ps_sum_chain(T[0], c[0], t1, &c[1], 1, 1.0, Out)) {
+      ps_copy(T[0], Out);
+      ps_scale(Out, c[0]);
+      ps_increment(T[1], Out, c[1], 0.0);
+    }
   } else {
     const int mid = n / 2;
     std::vector<double> left(c.begin(), c.begin() + mid), right(c.begin() + mid, c.end());
@@ -196,8 +217,13 @@ void cheby_recursive(const std::vector<PSMatrix>& T, const std::vector<double>& 
     const int full_midpoint = (int)T.size() - depth + 1;  // 1-based index into T_Powers
     cheby_recursive(T, right, RightMat, depth + 1, p);
     ps_multiply(T[(size_t)full_midpoint - 1], RightMat, R, 2.0, 0.0, p.threshold);
-    ps_increment(LeftMat, R, 1.0, 0.0);
-    ps_increment(T[(size_t)full_midpoint - 1], R, -1.0 * right[0], 0.0);
+    // (both merges behind the product in one pass)
+    const PSMatrix* const tail[2] = {&LeftMat, &T[(size_t)full_midpoint - 1]};
+    const double tail_c[2] = {1.0, -1.0 * right[0]};
+    if (!ps_sum_chain(R, 1.0, tail, tail_c, 2, 1.0, R)) {
+      ps_increment(LeftMat, R, 1.0, 0.0);
+      ps_increment(T[(size_t)full_midpoint - 1], R, -1.0 * right[0], 0.0);
+    }
     Out = std::move(R);
   }
 }

@@ -316,6 +316,19 @@ int ntpoly_amd_purify_tail_step(const int* ih_D, const int* ih_N, const int* ih_
 int ntpoly_amd_poly_step(const int* ih_P, const int* ih_Tkm2, const int* ih_R, const double* a, const double* c, int* ih_TkOut, int* ih_ROut) {
   return ps_poly_step_diag(*get_unpacked(ih_P), *get_unpacked(ih_Tkm2), *get_unpacked(ih_R), *a, *c, *get_unpacked(ih_TkOut), *get_unpacked(ih_ROut)) ? 1 : 0;
 }
+// DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end, option sum_chain = 1: the scaled sum chain of the real solver
+// loops on caller-held real matrices (engine.hpp ps_sum_chain_step).  Out = CopyMatrix(Base); ScaleMatrix(Out, *s);
+// IncrementMatrix(A_k, Out, coeffs[k], threshold 0) for the *n_addends (1 .. 5) matrices whose handles ih_addends[k] point to;
+// ScaleMatrix(Out, *post) -- *s == 1 and *post == 1 stand for no scaling call.  The inputs are brought into slab form and keep their
+// values, the pass runs, the result is packed into Out, which is Base or none of the inputs.  One rank only.  Returns 1 when taken,
+// 0 when refused or gated: every handle is then as it was.
+int ntpoly_amd_sum_chain(const int* ih_Base, const double* s, const int* n_addends, const int* const* ih_addends, const double* coeffs,
+                         const double* post, int* ih_Out) {
+  if (*n_addends < 1 || *n_addends > 5) return 0;
+  const PSMatrix* addends[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < *n_addends; ++k) addends[k] = get_unpacked(ih_addends[k]);
+  return ps_sum_chain_step(*get_unpacked(ih_Base), *s, addends, coeffs, *n_addends, *post, *get_unpacked(ih_Out)) ? 1 : 0;
+}
 // DIAGNOSTIC surface, for use between ntpoly_amd_session_begin and _end, option pade_session = 2: one of the two groups of merges of
 // ComputeExponentialPade on caller-held real matrices.  For q = 1, 2  Out_q = CopyMatrix(Base); ScaleMatrix(Out_q, scales[q - 1]);
 // IncrementMatrix(A_k, Out_q, coeffs[(q - 1) n_addends + k - 1], threshold 0) for k = 1 .. *n_addends; *n_addends is 1 (A2 and A3

@@ -1025,6 +1025,13 @@ _COUNTERS = {
     counts a fused step as the two merges it replaces.  A step kept out by a gate (the option below 2, no open real session, a
     complex operand, block form, a labelled slab form, dimensions that differ, one matrix in two roles, a zero coefficient, a grid
     with process slices) counts nowhere"""),
+    "sum_chain": (("passes", "refused"),
+                  """the scaled sum chain of the real solver loops in one pass (option sum_chain; csrc/sum_chain.hip k_sum_chain) since start:
+    passes fused (CopyMatrix, ScaleMatrix, up to five IncrementMatrix calls at threshold 0 and a trailing ScaleMatrix in one pass),
+    passes refused past the gates (the vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the calls it
+    replaces.  A pass kept out by a gate (the option at 0, no open real session, a complex operand, block form, a labelled slab
+    form, dimensions that differ, one matrix in two input roles, the output among the addends, a number of addends outside 1 .. 5,
+    a grid with process slices, a scalar that is zero or not finite) counts nowhere"""),
     "complex_scale_fold": (("updates", "dot_traces", "refused"),
                            """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
     pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
@@ -1290,6 +1297,24 @@ def poly_step(P, Tkm2, R, a, c, TkOut, ROut):
     gated, every matrix as it was."""
     lib.ntpoly_amd_poly_step.restype = C.c_int
     ok = lib.ntpoly_amd_poly_step(P.ih, Tkm2.ih, R.ih, C.byref(C.c_double(float(a))), C.byref(C.c_double(float(c))), TkOut.ih, ROut.ih)
+    return bool(ok)
+
+
+def sum_chain(Base, s, addends, coeffs, post, Out):
+    """DIAGNOSTIC, inside `with solver_session():`, option sum_chain = 1, one rank -- the scaled sum chain of the real solver loops
+    on caller-held real matrices (csrc/sum_chain.hip): Out = CopyMatrix(Base); ScaleMatrix(Out, s); IncrementMatrix(addends[k], Out,
+    coeffs[k], threshold 0) for every k; ScaleMatrix(Out, post), from one pass and packed (s = 1 and post = 1 stand for no scaling
+    call).  `addends`: 1 to 5 matrices; `coeffs`: as many numbers.  Out is Base or none of the inputs; the inputs keep their values.
+    Returns True when taken; False: refused or gated, every matrix as it was."""
+    addends = list(addends)
+    m = len(addends)
+    c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float64).reshape(-1))
+    if c.size != m:
+        raise ValueError("sum_chain: one coefficient per addend")
+    ih = (C.POINTER(C.c_int) * max(m, 1))(*[C.cast(a.ih, C.POINTER(C.c_int)) for a in addends])
+    lib.ntpoly_amd_sum_chain.restype = C.c_int
+    ok = lib.ntpoly_amd_sum_chain(Base.ih, C.byref(C.c_double(float(s))), C.byref(C.c_int(m)), ih, c.ctypes.data_as(C.POINTER(C.c_double)),
+                                  C.byref(C.c_double(float(post))), Out.ih)
     return bool(ok)
 
 
