@@ -62,6 +62,14 @@ NTP_COUNTER(poly_step, 3, poly_step_counts)
 // dimensions that differ, one matrix in two input roles, the output among the addends, a number of addends outside 1 .. 5, a
 // grid with process slices, a scalar that is zero or not finite -- counts nowhere
 NTP_COUNTER(sum_chain, 2, sum_chain_counts)
+// The complex side of the sum chain (option complex_sum_chain; engine.hpp ps_sum_chain on complex operands): [0] inverse-root
+// loops that opened a complex slab session (level 1; a loop that runs inside an outer session which already takes complex
+// operands stays in slab form too, but opens nothing and is not counted), [1] passes fused (k_sum_chain<double2, M> writes the sum; level 2), [2] passes
+// refused past the gates (the vocabulary calls ran instead).  A pass kept out by a gate -- the option below 2, no open session that
+// takes complex operands or one that has given up, block form, a labelled slab form, dimensions that differ, one matrix in two
+// input roles, the output among the addends, a number of addends outside 1 .. 5, a grid with process slices, real and complex
+// operands mixed, a scalar that is zero or not finite -- counts nowhere.  Real operands count in sum_chain only, complex ones here only
+NTP_COUNTER(complex_sum_chain, 3, complex_sum_chain_counts)
 // HPCP purification with its traces and its update in one pass each (option hpcp_step; engine.hpp ps_hpcp_traces / ps_hpcp_update):
 // [0] trace passes fused, [1] updates fused, [2] updates refused (the vocabulary calls ran instead).  A step that never reaches
 // the kernel's decision -- the option off, no open real session, a complex operand, block form, a labelled slab form, alignments

@@ -234,6 +234,16 @@ bool ps_sum_chain(const PSMatrix& Base, double s, const PSMatrix* const* addends
 // DIAGNOSTIC (the C ABI's ntpoly_amd_sum_chain): the same pass with the result packed.  One rank only (several ranks are a gate)
 bool ps_sum_chain_step(const PSMatrix& Base, double s, const PSMatrix* const* addends, const double* coeffs, int n_addends, double post, PSMatrix& Out);
 long long* sum_chain_counts();   // (slots: counters.inc)
+// The complex side, option complex_sum_chain (independent of sum_chain, as complex_hpcp is of hpcp_step).  1: the inverse-root
+// iteration opens a complex slab session as the Taylor square-root loop does ([0] of complex_sum_chain_counts() counts those loops).
+// 2: and ps_sum_chain / ps_sum_chain_step also take a chain whose operands are ALL complex, inside an open session that takes complex
+// operands (FMA arithmetic, complex_tile, complex_sessions; one rank, or complex column panels): k_sum_chain<double2, M> on runs of
+// (re, im) pairs -- every scalar real and applied to each part by itself, the merge part by part, an entry held iff it is not (0, 0),
+// the values and the pattern of the vocabulary calls at threshold 0.  Operands enter without views (a stored (0, 0) refuses).  The
+// gates are the real branch's, with "the option below 2", "no open session that takes complex operands" and "real and complex
+// operands mixed" among them; taken passes count in slab_algebra_counts() as the real branch's, passes and refusals in
+// complex_sum_chain_counts() [1] and [2] only -- sum_chain_counts() never moves for complex operands.
+long long* complex_sum_chain_counts();   // (slots: counters.inc)
 // The polynomial chain of the Taylor square-root step (SquareRootSolversModule.F90:425-479) in one pass over the runs of X and
 // X2 = X X (option isr_chain; slab_extra.hip k_sa_isr_chain), inside an open slab session that takes the operands' kind, both in
 // slab form.  ps_isr_chain5: what ps_increment(X, T, a, 0); ps_copy_axpby(I, X, Temp2, 1, b, 0); ps_increment(T, Temp2, 1, 0);

@@ -367,7 +367,8 @@ bool slab_pade_chain(const DevMat& Base, const DevMat* const* addends, int n_add
 // named twice, a largest alignment that is no multiple of the others, a scalar that is zero or not finite, runs far apart, an
 // input that is not finite, a scaled value that is exactly zero where an entry is held), nothing changed
 bool slab_poly_step(const DevMat& P, const DevMat& Q, const DevMat& R, double a, double c, DevMat& Tk, DevMat& Rout);
-// The scaled sum chain of the real solver loops on slab-form matrices (sum_chain.hip; real, square or column panels):
+// The scaled sum chain of the solver loops on slab-form matrices (sum_chain.hip; all operands real or all complex -- runs of (re, im)
+// pairs, every scalar real and applied to each part by itself, an entry held iff it is not (0, 0) --, square or column panels):
 // Out = CopyMatrix(Base); ScaleMatrix(Out, s); IncrementMatrix(addends[k], Out, coeffs[k], threshold 0) for k = 0 .. n_addends - 1
 // (n_addends 1 .. 5); ScaleMatrix(Out, post) -- values and pattern of the calls bit for bit (s == 1 and post == 1 stand for no
 // scaling call), as ONE fresh slab-form matrix from ONE pass over the inputs' runs and one host read-back.  Out is written only

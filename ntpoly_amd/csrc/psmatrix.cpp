@@ -2739,18 +2739,27 @@ long long* sum_chain_counts() {
   static long long counts[2] = {0, 0};
   return counts;
 }
+long long* complex_sum_chain_counts() {
+  static long long counts[3] = {0, 0, 0};
+  return counts;
+}
 namespace {
 // the chain on this rank's panels into o; out: the handle the result goes to (Base, or none of the inputs).  false: kept out by a
 // gate (counted nowhere) or refused (counted).  No reduction is entered and the calls it replaces are local, so across ranks a
-// refusal is the rank's own
+// refusal is the rank's own.  Real operands: option sum_chain, counted in sum_chain_counts(); ALL operands complex: option
+// complex_sum_chain = 2 inside a session that takes complex operands, counted in complex_sum_chain_counts() only (no view enters:
+// a stored (0, 0) refuses); real and complex operands mixed are a gate
 bool sum_chain_local(const PSMatrix& Base, double s, const PSMatrix* const* A, const double* coeffs, int n_addends, double post, const PSMatrix* out,
                      DevMat& o) {
-  if (options().sum_chain == 0 || !slab_on() || n_addends < 1 || n_addends > 5 || (Base.grid && Base.grid->num_slices > 1)) return false;
+  const bool cplx = Base.cplx;
+  if (cplx ? (options().complex_sum_chain < 2 || !session_takes(true)) : options().sum_chain == 0) return false;
+  if (!slab_on() || n_addends < 1 || n_addends > 5 || (Base.grid && Base.grid->num_slices > 1)) return false;
+  long long* counts = cplx ? complex_sum_chain_counts() + 1 : sum_chain_counts();   // ([0] fused, [1] refused)
   const PSMatrix* ms[6] = {&Base, nullptr, nullptr, nullptr, nullptr, nullptr};
   for (int k = 0; k < n_addends; ++k) ms[k + 1] = A[k];
   for (int k = 0; k <= n_addends; ++k) {
     const PSMatrix* m = ms[k];
-    if (!m || m->cplx || m->dim != Base.dim || m->loc.blocked() || labelled(*m) || (k > 0 && m == out)) return false;
+    if (!m || m->cplx != cplx || m->dim != Base.dim || m->loc.blocked() || labelled(*m) || (k > 0 && m == out)) return false;
     for (int i = 0; i < k; ++i)
       if (ms[i] == m) return false;
   }
@@ -2763,7 +2772,7 @@ bool sum_chain_local(const PSMatrix& Base, double s, const PSMatrix* const* A, c
   bool entered[6] = {false, false, false, false, false, false};
   for (int k = 0; taken && k <= n_addends; ++k) {
     entered[k] = !ms[k]->loc.expanded();
-    taken = slab_enter(mut(*ms[k]));
+    taken = cplx ? slab_enter_c(mut(*ms[k]), nullptr, false) : slab_enter(mut(*ms[k]));
     if (!taken) {
       if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
         std::fprintf(stderr, "[sum chain] operand %d of %d does not enter slab form (loose %d, hint %d, %lld entries)\n", k, n_addends,
@@ -2779,9 +2788,9 @@ bool sum_chain_local(const PSMatrix& Base, double s, const PSMatrix* const* A, c
   if (taken) {
     g_slab_counts[1] += (out != &Base ? 1 : 0) + n_addends;           // the copy and the merges
     g_slab_counts[2] += (s != 1.0 ? 1 : 0) + (post != 1.0 ? 1 : 0);   // the scalings
-    sum_chain_counts()[0] += 1;
+    counts[0] += 1;
   } else {
-    sum_chain_counts()[1] += 1;
+    counts[1] += 1;
   }
   return taken;
 }
@@ -2790,7 +2799,7 @@ bool ps_sum_chain(const PSMatrix& Base, double s, const PSMatrix* const* addends
   CommScope cs(Base.grid);
   DevMat o;
   if (!sum_chain_local(Base, s, addends, coeffs, n_addends, post, &Out, o)) return false;
-  install_like(Out, Base, false, std::move(o));
+  install_like(Out, Base, Base.cplx, std::move(o));
   return true;
 }
 bool ps_sum_chain_step(const PSMatrix& Base, double s, const PSMatrix* const* addends, const double* coeffs, int n_addends, double post, PSMatrix& Out) {
@@ -2798,7 +2807,7 @@ bool ps_sum_chain_step(const PSMatrix& Base, double s, const PSMatrix* const* ad
   DevMat o;
   if (world().active() || !sum_chain_local(Base, s, addends, coeffs, n_addends, post, &Out, o)) return false;
   pack(o);
-  install_like(Out, Base, false, std::move(o));
+  install_like(Out, Base, Base.cplx, std::move(o));
   return true;
 }
 

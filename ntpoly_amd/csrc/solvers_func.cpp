@@ -296,10 +296,15 @@ void inverse_root_impl(const PSMatrix& In, PSMatrix& Out, int root, const Solver
   }
   double norm_value = p.converge_diff + 1.0;
   int II;
-  SlabSession slab(!R.cplx && !Mk.cplx);   // (engine.hpp: the loop's matrices stay in slab form between its operations)
+  // (engine.hpp: the loop's matrices stay in slab form between its operations; complex operands: option complex_sum_chain, a complex
+  // session as the Taylor square-root loop opens it -- one rank or complex column panels, a grid with process slices keeps the
+  // loop on compressed columns)
+  const bool complex_session = options().complex_sum_chain != 0 && complex_slab_loop(R) && Mk.cplx && !(R.grid && R.grid->num_slices > 1);
+  SlabSession slab((!R.cplx && !Mk.cplx) || complex_session, false, complex_session);
+  if (complex_session && slab.opened && slab.set_complex) complex_sum_chain_counts()[0] += 1;
   for (II = 1; II <= p.max_iterations; ++II) {
     if (p.be_verbose && II > 1) log_list_element("Convergence", norm_value);
-    // (option sum_chain: ((t + 1) I - Mk) / t in one pass, engine.hpp ps_sum_chain)
+    // (option sum_chain, complex operands complex_sum_chain = 2: ((t + 1) I - Mk) / t in one pass, engine.hpp ps_sum_chain)
     const PSMatrix* const mk[1] = {&Mk};
     const double minus_one[1] = {-1.0};
     if (!ps_sum_chain(Ident, (double)(target_root + 1), mk, minus_one, 1, 1.0 / target_root, Inter)) {

@@ -16,6 +16,9 @@
 // stat |= 1: a scaled value is exactly zero where an entry is held (compressed columns would store it, no run can); |= 2: runs far
 // apart (the hull is not bounded by the inputs' own slots and pads), a slot beyond the output buffer, or an input that is not
 // finite -- the pass is refused.
+//
+// The complex loops' chain (option complex_sum_chain = 2, inside a complex slab session) is the same kernel on double2 elements:
+// k_sum_chain<double2, M>, the rules of step_merge (slab_extra.hip) at threshold 0 with real scalars.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -44,16 +47,22 @@ struct ScIn {   // in[0] = Base, in[1..M] = the addends; s scales Base, c[k] the
   double c[M];
 };
 
+template <typename T>
 struct ScCol {   // one column of an operand: p[r] is row r for f <= r <= l (an empty column: f = INT_MAX, l = -1)
-  const double* p;
+  const T* p;
   int f, l;
 };
-__device__ inline ScCol sc_col(const ScRuns& R, int j) {
+template <typename T>
+__device__ inline ScCol<T> sc_col(const ScRuns& R, int j) {
   const int f = R.first[j], l = R.last[j];
-  if (l < f) return ScCol{R.val, INT_MAX, -1};
-  return ScCol{R.val + (R.off[j] - f), f, l};
+  const T* v = reinterpret_cast<const T*>(R.val);
+  if (l < f) return ScCol<T>{v, INT_MAX, -1};
+  return ScCol<T>{v + (R.off[j] - f), f, l};
 }
-__device__ inline double sc_at(const ScCol& c, int r) { return (r >= c.f && r <= c.l) ? c.p[r] : 0.0; }
+template <typename T>
+__device__ inline T sc_at(const ScCol<T>& c, int r) { return (r >= c.f && r <= c.l) ? c.p[r] : Sc<T>::zero(); }
+__device__ inline bool sc_finite(double v) { return isfinite(v); }
+__device__ inline bool sc_finite(double2 v) { return isfinite(v.x) && isfinite(v.y); }
 
 // the aligned hull of the runs of all inputs, per column (nothing where all are empty): the slot of the output
 template <int M>
@@ -69,18 +78,22 @@ __global__ void k_sum_span(ScIn<M> P, int n, int al, int32_t* __restrict__ span)
 
 // One wave per column, lanes on consecutive rows of the aligned hull [a0, a1) of the runs of Base and the addends, chunks of 64
 // rows whose loads (M + 1 operands) are all requested before the first of them is used.  The output goes into the slot at base[j]
-// (every row of the hull written: pads and dropped rows zero) with its extent and count.
-template <int M>
+// (every row of the hull written: pads and dropped rows zero) with its extent and count.  T = double: the real loops' chain.
+// T = double2 (option complex_sum_chain): the same sweep on runs of (re, im) pairs -- slots, spans and `bound` count elements, a
+// lane's load and store are 16 bytes --, every scalar real and applied to each part by itself (Sc<double2>::scale), the merge part by
+// part (Sc<double2>::add); an entry is held iff it is not (0, 0), so a row that cancels in ONE part stays and only a row that
+// cancels in both is absent for the next addend, and only a scaled value that is (0, 0) where an entry is held sets stat bit 1
+template <typename T, int M>
 __global__ __launch_bounds__(256) void k_sum_chain(int n, ScIn<M> P, int al, const int64_t* __restrict__ base, IsrOut o, int64_t bound,
                                                    unsigned long long* __restrict__ stat) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= n) return;
   const int lane = lane_id();
-  ScCol col[M + 1];
+  ScCol<T> col[M + 1];
   int f = INT_MAX, l = -1, own = 0;   // the hull of the runs, and the rows their own aligned slots hold
 #pragma unroll
   for (int k = 0; k <= M; ++k) {
-    col[k] = sc_col(P.in[k], j);
+    col[k] = sc_col<T>(P.in[k], j);
     if (col[k].l >= 0) { f = min(f, col[k].f); l = max(l, col[k].l); own += (col[k].l / al + 1) * al - col[k].f / al * al; }
   }
   const int64_t slot = base[j];
@@ -94,35 +107,35 @@ __global__ __launch_bounds__(256) void k_sum_chain(int n, ScIn<M> P, int al, con
     }
     return;
   }
-  double* __restrict__ d = static_cast<double*>(o.val) + (slot - a0);
+  T* __restrict__ d = static_cast<T*>(o.val) + (slot - a0);
   int zk = 0, bad = 0, cnt = 0, kf = INT_MAX, kl = -1;
   for (int r = a0 + lane; r < a1; r += WAVE) {
-    double x[M + 1];
+    T x[M + 1];
 #pragma unroll
     for (int k = 0; k <= M; ++k) x[k] = sc_at(col[k], r);
     // CopyMatrix(Base, Out); ScaleMatrix(Out, s)
-    bool has = x[0] != 0.0;
-    double v = has ? __dmul_rn(P.s, x[0]) : 0.0;
-    zk |= (has && v == 0.0) ? 1 : 0;
+    bool has = !Sc<T>::is_zero(x[0]);
+    T v = has ? Sc<T>::scale(P.s, x[0]) : Sc<T>::zero();
+    zk |= (has && Sc<T>::is_zero(v)) ? 1 : 0;
 #pragma unroll
     for (int k = 0; k < M; ++k) {
       // IncrementMatrix(A_k, Out, c_k): A = the addend, B = the running value
-      const double a = x[k + 1];
-      const bool ha = a != 0.0;
-      const double wa = __dmul_rn(P.c[k], a);
-      zk |= (ha && wa == 0.0) ? 1 : 0;
-      if (ha && has) { v = __dadd_rn(wa, v); has = v != 0.0; }
+      const T a = x[k + 1];
+      const bool ha = !Sc<T>::is_zero(a);
+      const T wa = Sc<T>::scale(P.c[k], a);
+      zk |= (ha && Sc<T>::is_zero(wa)) ? 1 : 0;
+      if (ha && has) { v = Sc<T>::add(wa, v); has = !Sc<T>::is_zero(v); }
       else if (ha) { v = wa; has = true; }
     }
     // ScaleMatrix(Out, post)
-    v = has ? __dmul_rn(P.post, v) : 0.0;
-    zk |= (has && v == 0.0) ? 1 : 0;
+    v = has ? Sc<T>::scale(P.post, v) : Sc<T>::zero();
+    zk |= (has && Sc<T>::is_zero(v)) ? 1 : 0;
     d[r] = v;
     cnt += has ? 1 : 0;
     kf = min(kf, has ? r : INT_MAX);
     kl = max(kl, has ? r : -1);
 #pragma unroll
-    for (int k = 0; k <= M; ++k) bad |= isfinite(x[k]) ? 0 : 1;
+    for (int k = 0; k <= M; ++k) bad |= sc_finite(x[k]) ? 0 : 1;
   }
   cnt = (int)wave_sum_i64(cnt);
   kf = wave_min_i32(kf);
@@ -136,12 +149,13 @@ __global__ __launch_bounds__(256) void k_sum_chain(int n, ScIn<M> P, int al, con
   }
 }
 
-// what the pass merges: a real, unlabelled, zero-free slab form that is no view (square, or a column panel in a panel session)
-bool sc_operand(const DevMat& M) {
-  return M.expanded() && !M.cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1;
+// what the pass merges: an unlabelled, zero-free slab form of the chain's kind (all real, or all complex) that is no view (square,
+// or a column panel in a panel session)
+bool sc_operand(const DevMat& M, bool cplx) {
+  return M.expanded() && M.cplx == cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1;
 }
 
-template <int M>
+template <typename T, int M>
 bool sc_run(const DevMat* const* in, double s, const double* coeffs, double post, DevMat& Out) {
   const int n = in[0]->cols, al = std::max(1, in[0]->slab->row_pad);
   ScIn<M> P;
@@ -155,14 +169,14 @@ bool sc_run(const DevMat* const* in, double s, const double* coeffs, double post
   for (int k = 0; k < M; ++k) P.c[k] = coeffs[k];
   // (the operands' slots and per column the pads of a hull: what the kernel's per-column rule admits)
   const int64_t bound = slots + 2LL * (M + 1) * al * n;
-  FreshSlabs fs(n, 1, bound, false, false);
-  fs.why[0] = " a scaled value is exactly zero where an entry is held";
+  FreshSlabs fs(n, 1, bound, Sc<T>::cplx, false);
+  fs.why[0] = " a scaled value is exactly zero where an entry is held";   // (complex: both parts)
   fs.why[1] = " runs far apart or an input that is not finite";
   hipLaunchKernelGGL(k_sum_span<M>, dim3(cdiv(n, 256)), dim3(256), 0, stream(), P, n, al, fs.span.p);
   fs.scan();
-  hipLaunchKernelGGL(k_sum_chain<M>, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, P, al, fs.base.p, fs.out(0), bound, fs.stat.p);
+  hipLaunchKernelGGL((k_sum_chain<T, M>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, P, al, fs.base.p, fs.out(0), bound, fs.stat.p);
   DevMat R[1];
-  if (!fs.finish("sum chain", in[0]->rows, al, R)) return false;
+  if (!fs.finish(Sc<T>::cplx ? "complex sum chain" : "sum chain", in[0]->rows, al, R)) return false;
   Out = std::move(R[0]);
   return true;
 }
@@ -173,7 +187,7 @@ bool slab_sum_chain(const DevMat& Base, double s, const DevMat* const* addends, 
   const DevMat* in[6] = {&Base, nullptr, nullptr, nullptr, nullptr, nullptr};
   for (int k = 0; k < n_addends; ++k) in[k + 1] = addends[k];
   for (int k = 0; k <= n_addends; ++k) {
-    if (!in[k] || !sc_operand(*in[k]) || in[k]->cols != Base.cols || in[k]->rows != Base.rows || in[k]->slab->row_pad != Base.slab->row_pad) return false;
+    if (!in[k] || !sc_operand(*in[k], Base.cplx) || in[k]->cols != Base.cols || in[k]->rows != Base.rows || in[k]->slab->row_pad != Base.slab->row_pad) return false;
     for (int m = 0; m < k; ++m)
       if (in[m] == in[k]) return false;
   }
@@ -182,13 +196,18 @@ bool slab_sum_chain(const DevMat& Base, double s, const DevMat* const* addends, 
   if (!std::isfinite(s) || s == 0.0 || !std::isfinite(post) || post == 0.0) return false;
   for (int k = 0; k < n_addends; ++k)
     if (!std::isfinite(coeffs[k]) || coeffs[k] == 0.0) return false;
-  switch (n_addends) {
-    case 1: return sc_run<1>(in, s, coeffs, post, Out);
-    case 2: return sc_run<2>(in, s, coeffs, post, Out);
-    case 3: return sc_run<3>(in, s, coeffs, post, Out);
-    case 4: return sc_run<4>(in, s, coeffs, post, Out);
-    default: return sc_run<5>(in, s, coeffs, post, Out);
-  }
+  bool done = false;
+  dispatch_type(Base.cplx, [&](auto tag) {
+    using T = decltype(tag);
+    switch (n_addends) {
+      case 1: done = sc_run<T, 1>(in, s, coeffs, post, Out); break;
+      case 2: done = sc_run<T, 2>(in, s, coeffs, post, Out); break;
+      case 3: done = sc_run<T, 3>(in, s, coeffs, post, Out); break;
+      case 4: done = sc_run<T, 4>(in, s, coeffs, post, Out); break;
+      default: done = sc_run<T, 5>(in, s, coeffs, post, Out); break;
+    }
+  });
+  return done;
 }
 
 }  // namespace ntp

@@ -321,7 +321,9 @@ int ntpoly_amd_poly_step(const int* ih_P, const int* ih_Tkm2, const int* ih_R, c
 // IncrementMatrix(A_k, Out, coeffs[k], threshold 0) for the *n_addends (1 .. 5) matrices whose handles ih_addends[k] point to;
 // ScaleMatrix(Out, *post) -- *s == 1 and *post == 1 stand for no scaling call.  The inputs are brought into slab form and keep their
 // values, the pass runs, the result is packed into Out, which is Base or none of the inputs.  One rank only.  Returns 1 when taken,
-// 0 when refused or gated: every handle is then as it was.
+// 0 when refused or gated: every handle is then as it was.  Operands that are ALL complex: the same chain on (re, im) pairs with
+// option complex_sum_chain = 2 in a session begun with complex_ok (FMA arithmetic, complex_tile, complex_sessions), counted in
+// ntpoly_amd_complex_sum_chain_counts only; real and complex operands mixed are a gate.
 int ntpoly_amd_sum_chain(const int* ih_Base, const double* s, const int* n_addends, const int* const* ih_addends, const double* coeffs,
                          const double* post, int* ih_Out) {
   if (*n_addends < 1 || *n_addends > 5) return 0;

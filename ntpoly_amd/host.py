@@ -1032,6 +1032,14 @@ _COUNTERS = {
     replaces.  A pass kept out by a gate (the option at 0, no open real session, a complex operand, block form, a labelled slab
     form, dimensions that differ, one matrix in two input roles, the output among the addends, a number of addends outside 1 .. 5,
     a grid with process slices, a scalar that is zero or not finite) counts nowhere"""),
+    "complex_sum_chain": (("sessions", "passes", "refused"),
+                          """the complex side of the sum chain (option complex_sum_chain; csrc/sum_chain.hip k_sum_chain<double2, M>) since start:
+    inverse-root loops that opened a complex slab session (level 1), passes fused (level 2: the chain on runs of (re, im) pairs in one
+    pass), passes refused past the gates (the vocabulary calls ran instead); slab_algebra_counts() counts a fused pass as the real
+    branch does.  A pass kept out by a gate (the option below 2, no open session that takes complex operands, block form, a labelled
+    slab form, dimensions that differ, one matrix in two input roles, the output among the addends, a number of addends outside
+    1 .. 5, a grid with process slices, real and complex operands mixed, a scalar that is zero or not finite) counts nowhere; real
+    operands count in sum_chain_counts() only"""),
     "complex_scale_fold": (("updates", "dot_traces", "refused"),
                            """complex ScaleAndFold in a complex slab session (option complex_scale_fold; csrc/slab_extra.hip k_saf_update on runs of (re, im)
     pairs, k_sa_dot_trace_c for the scale branch) since start: fold updates fused, dot-and-trace passes fused, passes refused (the
@@ -1305,7 +1313,9 @@ def sum_chain(Base, s, addends, coeffs, post, Out):
     on caller-held real matrices (csrc/sum_chain.hip): Out = CopyMatrix(Base); ScaleMatrix(Out, s); IncrementMatrix(addends[k], Out,
     coeffs[k], threshold 0) for every k; ScaleMatrix(Out, post), from one pass and packed (s = 1 and post = 1 stand for no scaling
     call).  `addends`: 1 to 5 matrices; `coeffs`: as many numbers.  Out is Base or none of the inputs; the inputs keep their values.
-    Returns True when taken; False: refused or gated, every matrix as it was."""
+    Returns True when taken; False: refused or gated, every matrix as it was.  Operands that are ALL complex take the same chain on
+    (re, im) pairs with option complex_sum_chain = 2 inside `with solver_session(True):` (counted in complex_sum_chain_counts()
+    only); real and complex operands mixed are a gate."""
     addends = list(addends)
     m = len(addends)
     c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float64).reshape(-1))
