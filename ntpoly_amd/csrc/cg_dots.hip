@@ -27,8 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "device_util.hpp"
-#include "kernels.hpp"
+#include "slab_columns.hpp"
 
 namespace ntp {
 namespace {
@@ -41,15 +40,8 @@ struct CgWin<double> { static constexpr int W = 16; };
 template <>
 struct CgWin<double2> { static constexpr int W = 8; };
 
-struct CgRuns {   // one operand in slab form (HpcpRuns of slab_extra.hip)
-  const int32_t* first;
-  const int32_t* last;
-  const int64_t* off;
-  const double* val;
-};
-CgRuns cg_runs(const DevMat& M) { return CgRuns{M.slab->first.p, M.slab->last.p, M.slab->off.p, M.slab->val.p}; }
 struct CgPairs {
-  CgRuns u[2], v[2];
+  SlabRuns u[2], v[2];
 };
 
 template <typename T, bool FMA, int PAIRS>
@@ -191,10 +183,10 @@ bool slab_cg_dots(const DevMat& U1, const DevMat& V1, const DevMat* U2, const De
   const int n = U1.cols, pairs = U2 ? 2 : 1;
   if (n == 0) return false;
   CgPairs ops;
-  ops.u[0] = cg_runs(U1);
-  ops.v[0] = cg_runs(V1);
-  ops.u[1] = cg_runs(U2 ? *U2 : U1);
-  ops.v[1] = cg_runs(V2 ? *V2 : V1);
+  ops.u[0] = slab_runs(U1);
+  ops.v[0] = slab_runs(V1);
+  ops.u[1] = slab_runs(U2 ? *U2 : U1);
+  ops.v[1] = slab_runs(V2 ? *V2 : V1);
   DevBuf<double> diag((size_t)n * pairs);
   // (statistics, option time_kernels with NTPOLY_AMD_DEBUG_SPGEMM set: the pass between two events, for tools/bench_cg_dots.py)
   const bool timed = options().time_kernels != 0 && std::getenv("NTPOLY_AMD_DEBUG_SPGEMM") != nullptr;

@@ -1,5 +1,5 @@
 // The output scaffold of the fused slab passes (slab_extra.hip: TRS4, the square-root chain, HPCP, ScaleAndFold, the transpose;
-// purify_tail.hip): a pass that writes one or two fresh slab-form matrices launches its span kernel, scans the spans into slots,
+// and, with the input side of slab_columns.hpp, the chain passes, purify_tail.hip and wom_heun.hip): a pass that writes one or two fresh slab-form matrices launches its span kernel, scans the spans into slots,
 // launches its chain kernel and ends in ONE host wait that brings back the kept counts, the slots used, the kernel's flags and the
 // pass's sums.  Everything sits in an anonymous namespace: each translation unit gets its own copy, as with device_util.hpp.
 #pragma once

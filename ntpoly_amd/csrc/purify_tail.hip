@@ -7,9 +7,7 @@
 // and S once, writes N' in the fold branch (nothing in the plain one) and leaves per column the sum of |D - N'| and the terms of
 // dot(N', S): one read-back.
 //
-// Every merge is AddSparseVectors at threshold 0 as k_sa_axpby (kernels.hip) restates it on runs: the scaled addend is rounded,
-// then added; a row both operands hold is kept iff the sum is not zero; a row one operand holds keeps its (non-zero) value.  At
-// threshold 0 no rule looks at the other operand's last row, so ONE sweep decides a column.
+// The rules of a merge (merge0) and the pieces of the sweep are in slab_columns.hpp.
 //
 // The norm ends the loop and the dot decides the next branch, so both carry the bits the session's calls give on slab-form
 // matrices.  slab_norm (k_sa_colstat) gives lane t the rows first_kept + t + 64 m of the difference in ascending order, then runs
@@ -22,47 +20,10 @@
 // N is not bounded by their slots), a slot beyond the output buffer, or an input that is not finite -- the pass is refused.
 #include <hip/hip_runtime.h>
 
-#include <climits>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
-#include "device_util.hpp"
-#include "fresh_slabs.hpp"
-#include "kernels.hpp"
+#include "slab_columns.hpp"
 
 namespace ntp {
 namespace {
-struct PtRuns {   // one operand in slab form
-  const int32_t* first;
-  const int32_t* last;
-  const int64_t* off;
-  const double* val;
-};
-PtRuns pt_runs(const DevMat& M) { return PtRuns{M.slab->first.p, M.slab->last.p, M.slab->off.p, M.slab->val.p}; }
-
-struct PtCol {   // one column of an operand: p[r] is row r for f <= r <= l (an empty column: f = INT_MAX, l = -1)
-  const double* p;
-  int f, l;
-};
-__device__ inline PtCol pt_col(const PtRuns& R, int j) {
-  const int f = R.first[j], l = R.last[j];
-  if (l < f) return PtCol{R.val, INT_MAX, -1};
-  return PtCol{R.val + (R.off[j] - f), f, l};
-}
-__device__ inline double pt_at(const PtCol& c, int r) { return (r >= c.f && r <= c.l) ? c.p[r] : 0.0; }
-
-// the aligned hull of the runs of D and N, per column (nothing where both are empty): the slot of N' in the fold branch
-__global__ void k_purify_span(PtRuns D, PtRuns N, int n, int al, int32_t* __restrict__ span) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  int f = INT_MAX, l = -1;
-  if (D.last[j] >= D.first[j]) { f = min(f, D.first[j]); l = max(l, D.last[j]); }
-  if (N.last[j] >= N.first[j]) { f = min(f, N.first[j]); l = max(l, N.last[j]); }
-  span[j] = l >= 0 ? (l / al + 1) * al - f / al * al : 0;
-}
-
 // chunks of 64 rows whose loads (three operands each) are all requested before the first of them is used, as k_saf_update: 12
 // loads per lane, a hull of up to 256 aligned rows is one trip
 constexpr int PT_KC = 4;
@@ -72,38 +33,38 @@ constexpr int PT_KC = 4;
 // nothing is written.  colsum[j] = the column sum of |D - N'| in k_sa_colstat's order; part[2 j] = the column's share of dot(N', S)
 // in k_sa_dot's order, part[2 j + 1] = 0.
 template <bool FOLD>
-__global__ __launch_bounds__(256) void k_purify_tail(int n, PtRuns D, PtRuns N, PtRuns S, int al, const int64_t* __restrict__ base, IsrOut o1,
+__global__ __launch_bounds__(256) void k_purify_tail(int n, SlabRuns D, SlabRuns N, SlabRuns S, int al, const int64_t* __restrict__ base, IsrOut o1,
                                                      int64_t bound, double* __restrict__ colsum, double* __restrict__ part,
                                                      unsigned long long* __restrict__ stat) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= n) return;
   const int lane = lane_id();
-  const PtCol cd = pt_col(D, j), cn = pt_col(N, j), cs = pt_col(S, j);
+  const SlabCol<double> dn[2] = {slab_col<double>(D, j), slab_col<double>(N, j)}, cs = slab_col<double>(S, j);
+  const SlabCol<double>&cd = dn[0], &cn = dn[1];
   const int64_t slot = FOLD ? base[j] : 0;
-  int f = INT_MAX, l = -1, own = 0;   // the hull of the two runs, and the rows their own aligned slots hold
-  if (cd.l >= 0) { f = min(f, cd.f); l = max(l, cd.l); own += (cd.l / al + 1) * al - cd.f / al * al; }
-  if (cn.l >= 0) { f = min(f, cn.f); l = max(l, cn.l); own += (cn.l / al + 1) * al - cn.f / al * al; }
-  const int a0 = l >= 0 ? f / al * al : 0, a1 = l >= 0 ? (l / al + 1) * al : 0;
+  const SlabHull h(dn, al);   // (of D and N: S is read, it adds no row)
+  const int a0 = h.a0, a1 = h.a1;
   // (runs far apart: their hull is not bounded by the two slots and the pads between them -- refused per column; a column empty
   // in both operands is an empty column of the result, a zero of the norm and of the dot)
-  if (l < 0 || a1 - a0 > own + 2 * al || (FOLD && slot + (int64_t)(a1 - a0) > bound)) {
+  if (h.l < 0 || h.apart(2, al) || (FOLD && slot + (int64_t)(a1 - a0) > bound)) {
     if (lane == 0) {
-      if (FOLD) { o1.first[j] = INT_MAX; o1.last[j] = -1; o1.count[j] = 0; o1.off[j] = slot; }
+      if (FOLD) slab_empty_column(o1, j, slot);
       colsum[j] = 0.0;
       part[2 * (size_t)j] = 0.0; part[2 * (size_t)j + 1] = 0.0;
-      if (l >= 0) atomicOr(stat, 2ull);
+      if (h.l >= 0) atomicOr(stat, 2ull);
     }
     return;
   }
   double* __restrict__ dst = FOLD ? static_cast<double*>(o1.val) + (slot - a0) : nullptr;
-  int zk = 0, bad = 0, cnt = 0, kf = INT_MAX, kl = -1, df = INT_MAX;
+  int zk = 0, bad = 0, df = INT_MAX;
+  KeptExtent kept;
   double pn = 0.0, pd = 0.0;   // this lane's residue of the norm's and the dot's sums, rows ascending
   for (int rb = a0; rb < a1; rb += PT_KC * WAVE) {
     double vd[PT_KC], vn[PT_KC], vs[PT_KC];
 #pragma unroll
     for (int k = 0; k < PT_KC; ++k) {
       const int r = rb + k * WAVE + lane;
-      vd[k] = pt_at(cd, r); vn[k] = pt_at(cn, r); vs[k] = pt_at(cs, r);
+      vd[k] = slab_at(cd, r); vn[k] = slab_at(cn, r); vs[k] = slab_at(cs, r);
     }
 #pragma unroll
     for (int k = 0; k < PT_KC; ++k) {
@@ -115,19 +76,13 @@ __global__ __launch_bounds__(256) void k_purify_tail(int n, PtRuns D, PtRuns N, 
       double np = nn;   // N' on this row, 0.0 where it holds no entry
       if (FOLD) {
         // ScaleMatrix(N, -1) is exact; IncrementMatrix(D, N, 2): A = D, B = -N
-        const bool hn = nn != 0.0;
-        const double wa = __dmul_rn(2.0, d);
-        double o = 0.0;
-        bool keep = false;
-        if (hd && hn) { o = __dadd_rn(wa, -nn); keep = o != 0.0; }
-        else if (hd) { o = wa; keep = true; }
-        else if (hn) { o = -nn; keep = true; }
+        double o = -nn;
+        bool keep = nn != 0.0;
+        merge0(__dmul_rn(2.0, d), hd, o, keep);
         zk |= (keep && o == 0.0) ? 1 : 0;
         np = keep ? o : 0.0;
         dst[r] = np;
-        cnt += keep ? 1 : 0;
-        kf = min(kf, keep ? r : INT_MAX);
-        kl = max(kl, keep ? r : -1);
+        kept.note(keep, r);
       }
       // IncrementMatrix(N', D, -1): A = N', B = D
       const bool hp = np != 0.0;
@@ -142,12 +97,10 @@ __global__ __launch_bounds__(256) void k_purify_tail(int n, PtRuns D, PtRuns N, 
     }
   }
   if (FOLD) {
-    cnt = (int)wave_sum_i64(cnt);
-    kf = wave_min_i32(kf);
-    kl = wave_max_i32(kl);
+    kept.reduce();
   } else {   // (N' is N: its extent is the run's own)
-    kf = cn.f;
-    kl = cn.l;
+    kept.kf = cn.f;
+    kept.kl = cn.l;
   }
   df = wave_min_i32(df);
   // (lane t of k_sa_colstat holds the rows first_kept + t + 64 m: the partial sum of lane (first_kept - a0 + t) & 63 here.  The
@@ -157,32 +110,25 @@ __global__ __launch_bounds__(256) void k_purify_tail(int n, PtRuns D, PtRuns N, 
   pn = wave_sum_f64(__shfl(pn, (lane + rotn) & (WAVE - 1), WAVE));
   // (lane t of k_sa_dot holds the rows f + t + 64 m from the later first row of N' and S up to the earlier last row; the rows
   // outside add exact zeros here; runs that do not overlap: every term is zero)
-  const int fdot = max(kf, cs.f), ldot = min(kl, cs.l);
+  const int fdot = max(kept.kf, cs.f), ldot = min(kept.kl, cs.l);
   const int rotd = ldot >= fdot ? ((fdot - a0) & (WAVE - 1)) : 0;
   pd = wave_sum_f64(__shfl(pd, (lane + rotd) & (WAVE - 1), WAVE));
   const bool anyz = __ballot(zk != 0) != 0, anyb = __ballot(bad != 0) != 0;
   if (lane == 0) {
     if (anyz) atomicOr(stat, 1ull);
     if (anyb) atomicOr(stat, 2ull);
-    if (FOLD) {
-      o1.first[j] = kf; o1.last[j] = kl; o1.count[j] = cnt;
-      o1.off[j] = slot + (cnt ? kf - a0 : 0);
-    }
+    if (FOLD) kept.store(o1, j, slot, a0);
     colsum[j] = pn;
     part[2 * (size_t)j] = pd; part[2 * (size_t)j + 1] = 0.0;
   }
 }
 
-// what the pass merges: a real, unlabelled, zero-free slab form that is no view (square, or a column panel in a panel session)
-bool pt_operand(const DevMat& M) {
-  return M.expanded() && !M.cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1;
-}
 // S of the dot: a zero-free slab form or a read-only view (a view's stored zeros add nothing to the dot)
 bool pt_readable(const DevMat& S) {
   return S.expanded() && !S.cplx && !S.slab->labelled() && (S.rows == S.cols || slab_panels_ok()) && (S.zero_free == 1 || S.slab->origin);
 }
 // what the kernel's stat bits 1 and 2 mean (the debug line of either branch)
-const char* const PT_WHY[2] = {" a kept value is exactly zero", " runs far apart or an input that is not finite"};
+const char* const PT_WHY[2] = {" a kept value is exactly zero", SLAB_WHY_APART};
 void pt_report(unsigned long long hs) {
   if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
     std::fprintf(stderr, "[purify tail] refused:%s%s\n", (hs & 1ull) ? PT_WHY[0] : "", (hs & 2ull) ? PT_WHY[1] : "");
@@ -190,13 +136,13 @@ void pt_report(unsigned long long hs) {
 }  // namespace
 
 bool slab_purify_tail(const DevMat& D, const DevMat& N, const DevMat& S, bool fold, DevMat& Out, double* norm, double dot[2]) {
-  if (!pt_operand(D) || !pt_operand(N) || !pt_readable(S) || &D == &N || &D == &S || &N == &S) return false;
-  if (D.cols != N.cols || D.cols != S.cols || D.rows != N.rows || D.rows != S.rows || D.cols == 0) return false;
+  const DevMat* in[3] = {&D, &N, &S};
+  if (!slab_merge_operand(D, false) || !slab_merge_operand(N, false) || !pt_readable(S) || !same_frame(in, 3, false) || D.cols == 0) return false;
   const SlabForm &fd = *D.slab, &fn = *N.slab;
   if (fd.row_pad != fn.row_pad) return false;
   const int n = D.cols, al = std::max(1, fd.row_pad);
   const dim3 grid(cdiv((int64_t)n * WAVE, 256));
-  const PtRuns rd = pt_runs(D), rn = pt_runs(N), rs = pt_runs(S);
+  const SlabRuns rd = slab_runs(D), rn = slab_runs(N), rs = slab_runs(S);
   DevBuf<double> colsum((size_t)n), part((size_t)2 * n), res(4);
   double hr[4] = {0.0, 0.0, 0.0, 0.0};
   auto reduce = [&]() {
@@ -209,8 +155,7 @@ bool slab_purify_tail(const DevMat& D, const DevMat& N, const DevMat& S, bool fo
     FreshSlabs fs(n, 1, bound, false, false);
     fs.why[0] = PT_WHY[0];
     fs.why[1] = PT_WHY[1];
-    hipLaunchKernelGGL(k_purify_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), rd, rn, n, al, fs.span.p);
-    fs.scan();
+    hull_slots(SlabIn<2>{{rd, rn}}, n, al, fs);
     hipLaunchKernelGGL(k_purify_tail<true>, grid, dim3(256), 0, stream(), n, rd, rn, rs, al, fs.base.p, fs.out(0), bound, colsum.p, part.p,
                        fs.stat.p);
     reduce();

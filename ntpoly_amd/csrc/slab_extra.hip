@@ -15,6 +15,7 @@
 
 #include "device_util.hpp"
 #include "fresh_slabs.hpp"
+#include "slab_columns.hpp"
 #include "kernels.hpp"
 
 namespace ntp {
@@ -1333,17 +1334,10 @@ bool slab_isr_chain3(const DevMat& X, const DevMat& X2, int32_t col_offset, DevM
 // k_hpcp_update reads the three runs and WH once and writes the new D1 and DH; every merge is isr_merge (AddSparseVectors on two
 // operands at threshold 0, see the square-root chain above), the scaling by -1 is exact.
 namespace {
-struct HpcpRuns {   // one operand in slab form
-  const int32_t* first;
-  const int32_t* last;
-  const int64_t* off;
-  const double* val;
-};
-HpcpRuns hpcp_runs(const DevMat& M) { return HpcpRuns{M.slab->first.p, M.slab->last.p, M.slab->off.p, M.slab->val.p}; }
 // one thread per column: part[2 j] = A's diagonal entry, part[2 j + 1] = B's, each read as k_sa_diag reads it; T = double2 (runs of
 // (re, im) pairs): the real part, as k_sa_dot_trace_c reads it -- MatrixTrace of a complex matrix sums the real parts
 template <typename T>
-__global__ __launch_bounds__(256) void k_hpcp_traces(int n, HpcpRuns A, HpcpRuns B, int col_offset, double* __restrict__ part) {
+__global__ __launch_bounds__(256) void k_hpcp_traces(int n, SlabRuns A, SlabRuns B, int col_offset, double* __restrict__ part) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const T* __restrict__ va = reinterpret_cast<const T*>(A.val);
@@ -1353,7 +1347,7 @@ __global__ __launch_bounds__(256) void k_hpcp_traces(int n, HpcpRuns A, HpcpRuns
   part[2 * (size_t)j + 1] = (lB >= fB && d >= fB && d <= lB) ? Sc<T>::re(vb[B.off[j] + (d - fB)]) : 0.0;
 }
 // the aligned hull of the three runs and the diagonal row, per column
-__global__ void k_hpcp_span(HpcpRuns A, HpcpRuns B, HpcpRuns C, int n, int col_offset, int al, int32_t* __restrict__ span) {
+__global__ void k_hpcp_span(SlabRuns A, SlabRuns B, SlabRuns C, int n, int col_offset, int al, int32_t* __restrict__ span) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   int f = j + col_offset, l = j + col_offset;
@@ -1380,7 +1374,7 @@ __device__ inline double2 hpcp_negate(double2 u) { return Sc<double2>::scale(-1.
 // T = double2: the runs, the slots, base and bound count (re, im) pairs; every scalar of the chain is real, so isr_merge<double2>
 // scales and adds part by part and keeps an entry where either part is not zero; d = (1, 0).
 template <typename T, int KC>
-__global__ __launch_bounds__(256) void k_hpcp_update(int n, HpcpRuns A, HpcpRuns B, HpcpRuns C, HpcpRuns W, int col_offset, double s2, int al,
+__global__ __launch_bounds__(256) void k_hpcp_update(int n, SlabRuns A, SlabRuns B, SlabRuns C, SlabRuns W, int col_offset, double s2, int al,
                                                      const int64_t* __restrict__ base, IsrOut o1, IsrOut o2, int64_t bound,
                                                      double* __restrict__ part, unsigned long long* __restrict__ stat) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
@@ -1472,7 +1466,7 @@ template <typename T>
 bool hpcp_traces_run(const DevMat& DDH, const DevMat& D2DH, int32_t col_offset, double out2[2]) {
   const int n = DDH.cols;
   DevBuf<double> part((size_t)2 * n);
-  hipLaunchKernelGGL(k_hpcp_traces<T>, dim3(cdiv(n, 256)), dim3(256), 0, stream(), n, hpcp_runs(DDH), hpcp_runs(D2DH), col_offset, part.p);
+  hipLaunchKernelGGL(k_hpcp_traces<T>, dim3(cdiv(n, 256)), dim3(256), 0, stream(), n, slab_runs(DDH), slab_runs(D2DH), col_offset, part.p);
   fetch_pair_sums(part, n, out2);
   return true;
 }
@@ -1494,10 +1488,10 @@ bool hpcp_update_run(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH, do
   // (the operands' slots, and per column the diagonal's slot and the pads of a hull -- with room for diagonals away from their runs)
   const int64_t bound = fa.slots + fb.slots + fc.slots + 6LL * al * n;
   FreshSlabs fs(n, 2, bound, cplx, true);
-  const HpcpRuns ra = hpcp_runs(D1), rb = hpcp_runs(DDH), rc = hpcp_runs(D2DH);
+  const SlabRuns ra = slab_runs(D1), rb = slab_runs(DDH), rc = slab_runs(D2DH);
   hipLaunchKernelGGL(k_hpcp_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, rc, n, col_offset, al, fs.span.p);
   fs.scan();
-  hipLaunchKernelGGL((k_hpcp_update<T, KC>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, rc, hpcp_runs(WH), col_offset,
+  hipLaunchKernelGGL((k_hpcp_update<T, KC>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, rc, slab_runs(WH), col_offset,
                      -1.0 * 2.0 * sigma, al, fs.base.p, fs.out(0), fs.out(1), bound, fs.part.p, fs.stat.p);
   DevMat R[2];
   double e = 0.0;
@@ -1541,7 +1535,7 @@ bool slab_hpcp_update_c(const DevMat& D1, const DevMat& DDH, const DevMat& D2DH,
 // next branch -- and the first is the dot's terms in another fixed order.
 namespace {
 // the aligned hull of the two runs, per column (nothing where both are empty)
-__global__ void k_saf_span(HpcpRuns A, HpcpRuns B, int n, int al, int32_t* __restrict__ span) {
+__global__ void k_saf_span(SlabRuns A, SlabRuns B, int n, int al, int32_t* __restrict__ span) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   int f = INT_MAX, l = -1;
@@ -1565,7 +1559,7 @@ constexpr int SAF_KC_C = 2;
 // part by part and keep an entry where either part is not zero; the dot's term is Re conj(o) wh (hpcp_term) and the diagonal's
 // the real part, as k_sa_dot_trace_c reads them.
 template <typename T, int KC>
-__global__ __launch_bounds__(256) void k_saf_update(int n, HpcpRuns A, HpcpRuns B, HpcpRuns W, int col_offset, double sa, double sb, int al,
+__global__ __launch_bounds__(256) void k_saf_update(int n, SlabRuns A, SlabRuns B, SlabRuns W, int col_offset, double sa, double sb, int al,
                                                     const int64_t* __restrict__ base, IsrOut o1, int64_t bound, double* __restrict__ part,
                                                     unsigned long long* __restrict__ stat) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
@@ -1633,7 +1627,7 @@ __global__ __launch_bounds__(256) void k_saf_update(int n, HpcpRuns A, HpcpRuns 
 }
 // One wave per column of A = the new X: part[2 j] = sum over the rows both runs hold of x wh (lane-strided, then a wave sum),
 // part[2 j + 1] = X's diagonal entry as k_sa_diag reads it.  Writes nothing else.
-__global__ __launch_bounds__(256) void k_saf_dot_trace(int n, HpcpRuns A, HpcpRuns W, int col_offset, double* __restrict__ part) {
+__global__ __launch_bounds__(256) void k_saf_dot_trace(int n, SlabRuns A, SlabRuns W, int col_offset, double* __restrict__ part) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= n) return;
   const int lane = lane_id();
@@ -1680,10 +1674,10 @@ bool saf_update_run(const DevMat& X, const DevMat& X2, double a, double b, const
   // (the operands' slots and per column the pads of a hull)
   const int64_t bound = fa.slots + fb.slots + 4LL * al * n;
   FreshSlabs fs(n, 1, bound, cplx, true);
-  const HpcpRuns ra = hpcp_runs(X), rb = hpcp_runs(X2);
+  const SlabRuns ra = slab_runs(X), rb = slab_runs(X2);
   hipLaunchKernelGGL(k_saf_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), ra, rb, n, al, fs.span.p);
   fs.scan();
-  hipLaunchKernelGGL((k_saf_update<T, KC>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, hpcp_runs(WH), col_offset, a, b,
+  hipLaunchKernelGGL((k_saf_update<T, KC>), dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, ra, rb, slab_runs(WH), col_offset, a, b,
                      al, fs.base.p, fs.out(0), bound, fs.part.p, fs.stat.p);
   DevMat R;
   double sums[2] = {0.0, 0.0};
@@ -1709,7 +1703,7 @@ bool slab_saf_dot_trace(const DevMat& X, const DevMat& WH, int32_t col_offset, d
   if (!hpcp_operand(X) || !saf_wh_ok(WH) || X.cols != WH.cols || X.rows != WH.rows) return false;
   const int n = X.cols;
   DevBuf<double> part((size_t)2 * n);
-  hipLaunchKernelGGL(k_saf_dot_trace, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, hpcp_runs(X), hpcp_runs(WH), col_offset, part.p);
+  hipLaunchKernelGGL(k_saf_dot_trace, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, slab_runs(X), slab_runs(WH), col_offset, part.p);
   double sums[2] = {0.0, 0.0};
   fetch_pair_sums(part, n, sums);
   *dot = sums[0];

@@ -24,14 +24,7 @@
 // (the hull of W, K0, K1 is not bounded by their slots) or a slot beyond the output buffer -- nothing is written for that column.
 #include <hip/hip_runtime.h>
 
-#include <climits>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
-#include "device_util.hpp"
-#include "kernels.hpp"
+#include "slab_columns.hpp"
 
 namespace ntp {
 
@@ -40,25 +33,6 @@ int slab_wom_heun_register_rows() { return 512; }
 namespace {
 constexpr int WOM_KC = 8;   // chunks of 64 rows a column may span to be held in registers: 4 operands x 8 doubles per lane
 static_assert(WOM_KC * WAVE == 512, "slab_wom_heun_register_rows() names the register path's bound");
-
-struct WomRuns {   // one operand in slab form
-  const int32_t* first;
-  const int32_t* last;
-  const int64_t* off;
-  const double* val;
-};
-WomRuns wom_runs(const DevMat& M) { return WomRuns{M.slab->first.p, M.slab->last.p, M.slab->off.p, M.slab->val.p}; }
-
-struct WomCol {   // one column of an operand: p[r] is row r for f <= r <= l (an empty column: f = INT_MAX, l = -1)
-  const double* p;
-  int f, l;
-};
-__device__ inline WomCol wom_col(const WomRuns& R, int j) {
-  const int f = R.first[j], l = R.last[j];
-  if (l < f) return WomCol{R.val, INT_MAX, -1};
-  return WomCol{R.val + (R.off[j] - f), f, l};
-}
-__device__ inline double wom_at(const WomCol& c, int r) { return (r >= c.f && r <= c.l) ? c.p[r] : 0.0; }
 
 // one row of B <- alpha A + B at thr (k_sa_axpby with beta = 1: B's value is read as it is); amax / bmax: the operands' last rows
 // (-1: empty).  Returns the kept value, 0.0 for a row that is dropped or absent; *zk |= 1 when a kept value is exactly zero
@@ -74,29 +48,19 @@ __device__ inline double wom_link(double alpha, double a, double b, int r, int a
   return keep ? o : 0.0;
 }
 
-__global__ void k_wom_span(WomRuns W, WomRuns K0, WomRuns K1, int n, int al, int32_t* __restrict__ span) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  int f = INT_MAX, l = -1;
-  if (W.last[j] >= W.first[j]) { f = min(f, W.first[j]); l = max(l, W.last[j]); }
-  if (K0.last[j] >= K0.first[j]) { f = min(f, K0.first[j]); l = max(l, K0.last[j]); }
-  if (K1.last[j] >= K1.first[j]) { f = min(f, K1.first[j]); l = max(l, K1.last[j]); }
-  span[j] = l >= 0 ? (l / al + 1) * al - f / al * al : 0;
-}
-
 // the three sweeps of one column.  CACHED: the hull [b0, b1) of the four runs has at most WOM_KC * 64 rows and sits in registers,
 // every load requested before the first sweep; otherwise each sweep reads the runs it needs again.
 template <bool CACHED>
-__device__ inline void wom_column(int j, int lane, const WomCol& cw, const WomCol& ck0, const WomCol& ck1, const WomCol& cr1, int a0, int a1, int b0,
-                                  int b1, double c, double thr, double* __restrict__ dst, int32_t* __restrict__ ofirst,
-                                  int32_t* __restrict__ olast, int32_t* __restrict__ ocount, int64_t* __restrict__ ooff, int64_t slot,
-                                  double* __restrict__ cs1, double* __restrict__ cs2, unsigned long long* __restrict__ stat) {
+__device__ inline void wom_column(int j, int lane, const SlabCol<double>& cw, const SlabCol<double>& ck0, const SlabCol<double>& ck1,
+                                  const SlabCol<double>& cr1, int a0, int a1, int b0, int b1, double c, double thr, double* __restrict__ dst,
+                                  const IsrOut& o1, int64_t slot, double* __restrict__ cs1, double* __restrict__ cs2,
+                                  unsigned long long* __restrict__ stat) {
   double w[WOM_KC], k0[WOM_KC], k1[WOM_KC], r1[WOM_KC];
   if (CACHED) {
 #pragma unroll
     for (int k = 0; k < WOM_KC; ++k) {
       const int r = b0 + k * WAVE + lane;
-      w[k] = wom_at(cw, r); k0[k] = wom_at(ck0, r); k1[k] = wom_at(ck1, r); r1[k] = wom_at(cr1, r);
+      w[k] = slab_at(cw, r); k0[k] = slab_at(ck0, r); k1[k] = slab_at(ck1, r); r1[k] = slab_at(cr1, r);
     }
   }
   int zk = 0;
@@ -110,36 +74,33 @@ __device__ inline void wom_column(int j, int lane, const WomCol& cw, const WomCo
 #pragma unroll
     for (int k = 0; k < WOM_KC; ++k) s1(b0 + k * WAVE + lane, w[k], k0[k]);
   } else {
-    for (int r = b0 + lane; r < b1; r += WAVE) s1(r, wom_at(cw, r), wom_at(ck0, r));
+    for (int r = b0 + lane; r < b1; r += WAVE) s1(r, slab_at(cw, r), slab_at(ck0, r));
   }
   if (__ballot(zk != 0)) {   // (a kept zero of M1: its extent is not what compressed columns would carry on -- refused)
     if (lane == 0) {
       atomicOr(stat, 1ull);
-      ofirst[j] = INT_MAX; olast[j] = -1; ocount[j] = 0; ooff[j] = slot; cs1[j] = 0.0; cs2[j] = 0.0;
+      slab_empty_column(o1, j, slot);
+      cs1[j] = 0.0; cs2[j] = 0.0;
     }
     return;
   }
   e1 = wave_max_i32(e1);
   // sweep 2: RK2 = M1 + c K1 (IncrementMatrix(K1, RK2, c, thr): A = K1, B = M1), written with its extent and count
-  int cnt = 0, kf = INT_MAX, kl = -1;
+  KeptExtent kept;
   auto s2 = [&](int r, double vw, double vk0, double vk1) {
     const double m1 = wom_link(c, vk0, vw, r, ck0.l, cw.l, thr, &zk);
     const double o = wom_link(c, vk1, m1, r, ck1.l, e1, thr, &zk);
     if (r >= a0 && r < a1) dst[r] = o;
-    const bool keep = o != 0.0;
-    cnt += keep ? 1 : 0;
-    kf = min(kf, keep ? r : INT_MAX);
-    kl = max(kl, keep ? r : -1);
+    kept.note(o != 0.0, r);
   };
   if (CACHED) {
 #pragma unroll
     for (int k = 0; k < WOM_KC; ++k) s2(b0 + k * WAVE + lane, w[k], k0[k], k1[k]);
   } else {
-    for (int r = b0 + lane; r < b1; r += WAVE) s2(r, wom_at(cw, r), wom_at(ck0, r), wom_at(ck1, r));
+    for (int r = b0 + lane; r < b1; r += WAVE) s2(r, slab_at(cw, r), slab_at(ck0, r), slab_at(ck1, r));
   }
-  cnt = (int)wave_sum_i64(cnt);
-  kf = wave_min_i32(kf);
-  kl = wave_max_i32(kl);
+  kept.reduce();
+  const int kl = kept.kl;
   // sweep 3: D1 = RK1 - RK2 (A = RK2, B = RK1) and D2 = RK2 - W (A = W, B = RK2): sums of moduli per lane residue, first kept rows
   double p1 = 0.0, p2 = 0.0;
   int f1 = INT_MAX, f2 = INT_MAX;
@@ -157,7 +118,7 @@ __device__ inline void wom_column(int j, int lane, const WomCol& cw, const WomCo
 #pragma unroll
     for (int k = 0; k < WOM_KC; ++k) s3(b0 + k * WAVE + lane, w[k], k0[k], k1[k], r1[k]);
   } else {
-    for (int r = b0 + lane; r < b1; r += WAVE) s3(r, wom_at(cw, r), wom_at(ck0, r), wom_at(ck1, r), wom_at(cr1, r));
+    for (int r = b0 + lane; r < b1; r += WAVE) s3(r, slab_at(cw, r), slab_at(ck0, r), slab_at(ck1, r), slab_at(cr1, r));
   }
   f1 = wave_min_i32(f1);
   f2 = wave_min_i32(f2);
@@ -167,8 +128,7 @@ __device__ inline void wom_column(int j, int lane, const WomCol& cw, const WomCo
   p2 = wave_sum_f64(__shfl(p2, (lane + rot2) & (WAVE - 1), WAVE));
   if (__ballot(zk != 0) && lane == 0) atomicOr(stat, 1ull);
   if (lane == 0) {
-    ofirst[j] = kf; olast[j] = kl; ocount[j] = cnt;
-    ooff[j] = slot + (cnt ? kf - a0 : 0);
+    kept.store(o1, j, slot, a0);
     cs1[j] = p1;
     cs2[j] = p2;
   }
@@ -176,61 +136,50 @@ __device__ inline void wom_column(int j, int lane, const WomCol& cw, const WomCo
 
 // One wave per column.  base[j]: the slot of RK2's column (the aligned hull [a0, a1) of W, K0, K1, every row of it written: pads
 // and dropped rows zero); cs1 / cs2: the column sums of |D1| / |D2|
-__global__ __launch_bounds__(256) void k_wom_heun(int n, WomRuns W, WomRuns K0, WomRuns K1, WomRuns R1, double c, double thr, int al,
-                                                  const int64_t* __restrict__ base, double* __restrict__ out, int32_t* __restrict__ ofirst,
-                                                  int32_t* __restrict__ olast, int32_t* __restrict__ ocount, int64_t* __restrict__ ooff,
-                                                  int64_t bound, double* __restrict__ cs1, double* __restrict__ cs2,
-                                                  unsigned long long* __restrict__ stat) {
+__global__ __launch_bounds__(256) void k_wom_heun(int n, SlabRuns W, SlabRuns K0, SlabRuns K1, SlabRuns R1, double c, double thr, int al,
+                                                  const int64_t* __restrict__ base, IsrOut o1, int64_t bound, double* __restrict__ cs1,
+                                                  double* __restrict__ cs2, unsigned long long* __restrict__ stat) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= n) return;
   const int lane = lane_id();
-  const WomCol cw = wom_col(W, j), ck0 = wom_col(K0, j), ck1 = wom_col(K1, j), cr1 = wom_col(R1, j);
+  const SlabCol<double> wk[3] = {slab_col<double>(W, j), slab_col<double>(K0, j), slab_col<double>(K1, j)}, cr1 = slab_col<double>(R1, j);
+  const SlabCol<double> &cw = wk[0], &ck0 = wk[1], &ck1 = wk[2];
   const int64_t slot = base[j];
-  int f = INT_MAX, l = -1, own = 0;   // the hull of the three merged runs, and the rows their own aligned slots hold
-  if (cw.l >= 0) { f = min(f, cw.f); l = max(l, cw.l); own += (cw.l / al + 1) * al - cw.f / al * al; }
-  if (ck0.l >= 0) { f = min(f, ck0.f); l = max(l, ck0.l); own += (ck0.l / al + 1) * al - ck0.f / al * al; }
-  if (ck1.l >= 0) { f = min(f, ck1.f); l = max(l, ck1.l); own += (ck1.l / al + 1) * al - ck1.f / al * al; }
-  const int a0 = l >= 0 ? f / al * al : 0, a1 = l >= 0 ? (l / al + 1) * al : 0;
+  const SlabHull h(wk, al);   // (of the three merged runs: RK1 joins the sweeps' hull below)
+  const int a0 = h.a0, a1 = h.a1;
   // (runs far apart: their hull is not bounded by the three slots and the pads between them -- refused per column)
-  if (a1 - a0 > own + 3 * al || slot + (int64_t)(a1 - a0) > bound) {
+  if (h.apart(3, al) || slot + (int64_t)(a1 - a0) > bound) {
     if (lane == 0) {
-      ofirst[j] = INT_MAX; olast[j] = -1; ocount[j] = 0; ooff[j] = slot; cs1[j] = 0.0; cs2[j] = 0.0;
+      slab_empty_column(o1, j, slot);
+      cs1[j] = 0.0; cs2[j] = 0.0;
       atomicOr(stat, 2ull);
     }
     return;
   }
   // the sweeps' hull takes RK1 in too (D1's rows); rows of it outside [a0, a1) hold no entry of RK2
   const int b0 = cr1.l >= 0 ? min(a0, cr1.f / al * al) : a0, b1 = cr1.l >= 0 ? max(a1, (cr1.l / al + 1) * al) : a1;
-  double* __restrict__ dst = out + (slot - a0);
+  double* __restrict__ dst = static_cast<double*>(o1.val) + (slot - a0);
   if (b1 - b0 <= WOM_KC * WAVE)
-    wom_column<true>(j, lane, cw, ck0, ck1, cr1, a0, a1, b0, b1, c, thr, dst, ofirst, olast, ocount, ooff, slot, cs1, cs2, stat);
+    wom_column<true>(j, lane, cw, ck0, ck1, cr1, a0, a1, b0, b1, c, thr, dst, o1, slot, cs1, cs2, stat);
   else
-    wom_column<false>(j, lane, cw, ck0, ck1, cr1, a0, a1, b0, b1, c, thr, dst, ofirst, olast, ocount, ooff, slot, cs1, cs2, stat);
-}
-
-// sum of the entry counts of the columns (integers: any order gives the same total); out zeroed by the caller
-__global__ __launch_bounds__(256) void k_wom_count_sum(const int32_t* __restrict__ v, int n, unsigned long long* __restrict__ out) {
-  long long s = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) s += v[i];
-  s = wave_sum_i64(s);
-  if (lane_id() == 0 && s) atomicAdd(out, (unsigned long long)s);
+    wom_column<false>(j, lane, cw, ck0, ck1, cr1, a0, a1, b0, b1, c, thr, dst, o1, slot, cs1, cs2, stat);
 }
 
 // both dots of the canonical step, one wave per column: k_sa_dot's loop (from the later first row to the earlier last row of a
 // pair, lane-strided, then the wave butterfly) on (X, W) into part1 and on (W, XA) into part2, as the (x, 0) pairs of its sum
-__device__ inline double wom_pair_dot(const WomCol& a, const WomCol& b, int lane) {
+__device__ inline double wom_pair_dot(const SlabCol<double>& a, const SlabCol<double>& b, int lane) {
   const int f = max(a.f, b.f), l = min(a.l, b.l);
   double s = 0.0;
   if (l >= f)
     for (int r = f + lane; r <= l; r += WAVE) s = __dadd_rn(s, __dmul_rn(a.p[r], b.p[r]));
   return wave_sum_f64(s);
 }
-__global__ __launch_bounds__(256) void k_wom_c_dots(int n, WomRuns X, WomRuns W, WomRuns XA, double* __restrict__ part1,
+__global__ __launch_bounds__(256) void k_wom_c_dots(int n, SlabRuns X, SlabRuns W, SlabRuns XA, double* __restrict__ part1,
                                                     double* __restrict__ part2) {
   const int j = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
   if (j >= n) return;
   const int lane = lane_id();
-  const WomCol cx = wom_col(X, j), cw = wom_col(W, j), ca = wom_col(XA, j);
+  const SlabCol<double> cx = slab_col<double>(X, j), cw = slab_col<double>(W, j), ca = slab_col<double>(XA, j);
   const double d1 = wom_pair_dot(cx, cw, lane), d2 = wom_pair_dot(cw, ca, lane);
   if (lane == 0) {
     part1[2 * (size_t)j] = d1; part1[2 * (size_t)j + 1] = 0.0;
@@ -238,16 +187,13 @@ __global__ __launch_bounds__(256) void k_wom_c_dots(int n, WomRuns X, WomRuns W,
   }
 }
 
-// what the passes read: a real, unlabelled, zero-free slab form that is no view (square, or a column panel in a panel session)
-bool wom_operand(const DevMat& M) {
-  return M.expanded() && !M.cplx && (M.rows == M.cols || slab_panels_ok()) && !M.slab->labelled() && !M.slab->origin && M.zero_free == 1;
-}
 }  // namespace
 
 bool slab_wom_heun(const DevMat& W, const DevMat& K0, const DevMat& K1, const DevMat& RK1, double h, double thr, DevMat& Out, double* err,
                    double* err2) {
   const double c = h * 0.5;
-  if (!wom_operand(W) || !wom_operand(K0) || !wom_operand(K1) || !wom_operand(RK1)) return false;
+  for (const DevMat* M : {&W, &K0, &K1, &RK1})
+    if (!slab_merge_operand(*M, false)) return false;
   if (W.cols != K0.cols || W.cols != K1.cols || W.cols != RK1.cols || W.rows != K0.rows || W.rows != K1.rows || W.rows != RK1.rows || W.cols == 0)
     return false;
   if (!std::isfinite(h) || !std::isfinite(thr) || c == 0.0) return false;
@@ -258,42 +204,20 @@ bool slab_wom_heun(const DevMat& W, const DevMat& K0, const DevMat& K1, const De
     if (al % std::max(1, f->row_pad) != 0) return false;
   // (the operands' slots and per column the pads of a hull: what k_wom_heun's per-column rule admits)
   const int64_t bound = fw.slots + f0.slots + f1.slots + 10LL * al * n;
-  std::unique_ptr<SlabForm> fo(new SlabForm());
-  fo->first.alloc((size_t)n); fo->last.alloc((size_t)n); fo->count.alloc((size_t)n); fo->off.alloc((size_t)n + 1);
-  fo->val.alloc((size_t)bound + kIndexSlack);
-  DevBuf<int32_t> span((size_t)n);
-  DevBuf<int64_t> base((size_t)n + 1);
-  DevBuf<unsigned long long> stat(2);   // [0] the kernel's flags, [1] the kept entries
+  FreshSlabs fs(n, 1, bound, false, false);
+  fs.why[0] = " a kept value is exactly zero";
+  fs.why[1] = " runs far apart";
   DevBuf<double> cs1((size_t)n), cs2((size_t)n), res(4);
-  stat.zero();
-  const WomRuns rw = wom_runs(W), r0 = wom_runs(K0), r1 = wom_runs(K1), rr = wom_runs(RK1);
-  hipLaunchKernelGGL(k_wom_span, dim3(cdiv(n, 256)), dim3(256), 0, stream(), rw, r0, r1, n, al, span.p);
-  scan_i32_async(span.p, base.p, (int64_t)n);
-  hipLaunchKernelGGL(k_wom_heun, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, rw, r0, r1, rr, c, thr, al, base.p, fo->val.p,
-                     fo->first.p, fo->last.p, fo->count.p, fo->off.p, bound, cs1.p, cs2.p, stat.p);
-  hipLaunchKernelGGL(k_wom_count_sum, dim3(std::max(1, std::min(256, cdiv(n, 1024)))), dim3(256), 0, stream(), fo->count.p, n, stat.p + 1);
+  const SlabRuns rw = slab_runs(W), r0 = slab_runs(K0), r1 = slab_runs(K1), rr = slab_runs(RK1);
+  hull_slots(SlabIn<3>{{rw, r0, r1}}, n, al, fs);
+  hipLaunchKernelGGL(k_wom_heun, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, rw, r0, r1, rr, c, thr, al, fs.base.p, fs.out(0), bound,
+                     cs1.p, cs2.p, fs.stat.p);
   reduce_max_async(cs1.p, (int64_t)n, res.p);       // (slab_norm's maximum: exact in any grouping)
   reduce_max_async(cs2.p, (int64_t)n, res.p + 2);
-  int64_t slots = 0;
-  unsigned long long hs[2] = {0, 0};
   double hr[4] = {0.0, 0.0, 0.0, 0.0};
-  {
-    ScalarFetch ft;
-    ft.add(stat.p, 2, hs);
-    ft.add(base.p + n, 1, &slots);
-    ft.add(res.p, 4, hr);
-    ft.run();
-  }
-  if (hs[0] != 0) {   // (the caller takes the vocabulary calls)
-    if (std::getenv("NTPOLY_AMD_DEBUG_SPGEMM"))
-      std::fprintf(stderr, "[wom heun] refused:%s%s\n", (hs[0] & 1ull) ? " a kept value is exactly zero" : "", (hs[0] & 2ull) ? " runs far apart" : "");
-    return false;
-  }
-  fo->row_pad = al;
-  fo->slots = slots;
+  fs.also_fetch(res.p, 4, hr);
   DevMat R;
-  R.rows = W.rows; R.cols = n; R.cplx = false; R.nnz = (int64_t)hs[1]; R.zero_free = 1;
-  R.slab = std::move(fo);
+  if (!fs.finish("wom heun", W.rows, al, &R)) return false;
   Out = std::move(R);
   *err = hr[1];
   *err2 = hr[3];
@@ -306,7 +230,7 @@ bool slab_wom_c_dots(const DevMat& X, const DevMat& W, const DevMat& XA, double 
   if (!ok(X) || !ok(W) || !ok(XA) || X.cols != W.cols || X.cols != XA.cols || X.cols == 0) return false;
   const int n = X.cols;
   DevBuf<double> part1((size_t)2 * n), part2((size_t)2 * n), res(4);
-  hipLaunchKernelGGL(k_wom_c_dots, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, wom_runs(X), wom_runs(W), wom_runs(XA), part1.p,
+  hipLaunchKernelGGL(k_wom_c_dots, dim3(cdiv((int64_t)n * WAVE, 256)), dim3(256), 0, stream(), n, slab_runs(X), slab_runs(W), slab_runs(XA), part1.p,
                      part2.p);
   reduce_sum_pairs_async(part1.p, n, res.p);       // (slab_dot's two-level sum)
   reduce_sum_pairs_async(part2.p, n, res.p + 2);
